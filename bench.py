@@ -11,14 +11,19 @@ generated token ids are gathered with ONE RCCL all-gather issued by librdx itsel
 step -- the only collective on the path; torch.distributed (a gloo group on the host) carries the 128-byte RCCL id, the barrier and
 the max-over-ranks clock.
 
-`python bench.py --gpus N` without a launcher (no RANK / WORLD_SIZE in the environment) starts the N ranks itself: it re-executes
-under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one process per GPU, LOCAL_RANK -> device)
-and fails loudly when fewer than N GPUs are visible. Launched by torch.distributed.run directly (the driver's form) it reads
+`python bench.py --gpus N` without a launcher (no RANK / WORLD_SIZE in the environment) starts the N ranks itself: it runs
+`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` as a child (one process per GPU, LOCAL_RANK -> device)
+and exits with its status; it fails loudly when fewer than N GPUs are visible. Launched by torch.distributed.run directly (the driver's form) it reads
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment; WORLD_SIZE must equal --gpus.
 
-Rank 0 prints ONE JSON line of < 4 KB (round 6: compact_line() -- the contract's fields, `roofline` / `cpu_baseline` with scalars only, every sub-run as
-`<key>_value` / `_decode_ms` / `_frac` scalars, every parity leg as {ok, same, n, worst, bar}) and writes the full record described below to
-bench_detail.json beside this script (RDX_BENCH_DETAIL overrides the path). `value` = reports/s of the whole job with inputs resident in HBM. The full record:
+A plain run (`--gpus N --steps K --warmup W`) does only what the headline needs: set up, W warm-up steps, K timed steps, the outputs of the
+last timed step if `--dump-outputs DIR` is given (DIR/tokens.npy: the gathered greedy token ids, DIR/qformer_out.npy: rank 0's Q-Former output,
+both float32), and ONE JSON line with the contract's fields. `value` = reports/s of the whole job with inputs resident in HBM, `ms_per_step` = the
+milliseconds one timed step took (the max over ranks).
+
+`--full` adds everything else below. Rank 0 then prints ONE JSON line of < 4 KB (round 6: compact_line() -- the contract's fields, `roofline` /
+`cpu_baseline` with scalars only, every sub-run as `<key>_value` / `_decode_ms` / `_frac` scalars, every parity leg as {ok, same, n, worst, bar}) and
+writes the full record described below to bench_detail.json beside this script (RDX_BENCH_DETAIL overrides the path). The full record:
   roofline     bound "hbm": the kernel rocprofv3 ranks first in the decode loop -- at batch <= 2 the chained down(l) -> QKV(l+1)
                launch `decode_chain_k` (profiles/r03_bench_b1_kernel_stats.md), at batch 3-32 the gate/up SwiGLU `xstat32_k`:
                algorithmic bytes per launch / its average launch duration measured live with HIP events on the library's stream
@@ -67,7 +72,13 @@ def parse(argv=None):
     ap.add_argument("--no-b64", action="store_true", help="skip the 64-reports-per-GPU sub-run of a batch-1 bench")
     ap.add_argument("--no-f16", action="store_true", help="skip the fp16 (the reference's dtype) timed run of a batch-1 bf16 bench (value_f16)")
     ap.add_argument("--no-enc256", action="store_true", help="skip the batch-256 image-encode timing (enc_b256)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true", help="also the per-phase / roofline detail, the sub-runs, the token fixture check, the CPU oracle "
+                    "baseline and its parity legs, and bench_detail.json (the --no-* options select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy (float32)")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -550,6 +561,15 @@ def fixture_check(dtype, B, fp8, tokens_row0):
     return {"key": key, "tokens": tokens_row0, "expected": want, "ok": list(want) == list(tokens_row0)}
 
 
+def write_outputs(path, **arrays):
+    """--dump-outputs: each array as float32 path/<name>.npy. What the timed path returns is small (token ids int32[B x ranks, N],
+    exact in float32 below 2^24; Q-Former output f32[B, 32, 768]): 13 MB at the 128 rows one context holds, so nothing is sampled."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.detach().float().cpu().numpy())
+
+
 def cpu_baseline_pointer():
     """N > 1 lines: the CPU oracle is timed on rank 0 at N = 1 only (contract); multi-rank lines carry the committed N = 1 figure of this
     build so that SCALE records are self-contained."""
@@ -571,9 +591,11 @@ def spawn_command(n, port, argv):
 
 
 def spawn_ranks(args):
-    """`python bench.py --gpus N` with no launcher in the environment: become `torch.distributed.run` with N local ranks (one process per
-    GPU). The reference has no inference launcher to mirror (its only one is the training DDP of model/lavis/common/dist_utils.py:57-91)."""
+    """`python bench.py --gpus N` with no launcher in the environment: run `torch.distributed.run` with N local ranks (one process per
+    GPU) as a child and exit with its status. A child, not an exec: device_count() may already have initialised the HIP runtime here.
+    The reference has no inference launcher to mirror (its only one is the training DDP of model/lavis/common/dist_utils.py:57-91)."""
     import socket
+    import subprocess
     n = args.gpus
     vis = n if STUB else torch.cuda.device_count()
     if vis < n:
@@ -589,7 +611,8 @@ def spawn_ranks(args):
     cmd = spawn_command(n, port, sys.argv[1:])
     print("bench.py: no launcher in the environment, starting %d ranks: %s" % (n, " ".join(cmd)), file=sys.stderr)
     sys.stdout.flush(); sys.stderr.flush()
-    os.execvpe(sys.executable, cmd, env)
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)          # killed by signal S: the shell's 128 + S
 
 
 def resolve_gpus(args, env):
@@ -634,13 +657,18 @@ def compact_line(res, detail_name):
     """The ONE JSON line of stdout, under 4 KB (round 6, VERDICT r5 "weak" 10: the round-5 line was 15 KB, the driver keeps 8 KB of stdout, so the
     configs[2] / configs[4] sub-runs never reached its record): the contract's fields in full, `roofline` and `cpu_baseline` with scalars only, every
     sub-run as `<key>_value` / `_ms_per_step` / `_decode_ms` / `_frac` scalars, every parity leg as {ok, same, n, worst, bar}. Everything else -- kernel
-    names, prose, per-phase tables, token fixtures, divergence notes -- is in the detail file written beside it (`detail`)."""
-    roof = res["roofline"]
+    names, prose, per-phase tables, token fixtures, divergence notes -- is in the detail file written beside it (`detail`).
+    A plain run's record (no --full) holds the timed run alone: its line is the contract's fields and that run's own figures."""
     out = {k: res[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                                "dtype", "data")}
     cfg = res["config"]
     out["config"] = {"workload": cfg["workload"][:150], "per_gpu_batch": cfg["per_gpu_batch"], "global_batch": cfg["global_batch"],
                      "prompt_len": cfg["prompt_len"], "new_tokens": cfg["new_tokens"], "parallelism": cfg["parallelism"]}
+    if "roofline" not in res:
+        out.update(tokens_per_s=_sig(res["tokens_per_s"]), rccl_ranks=res["rccl_ranks"], per_rank_ms_per_step=_sig(res["per_rank_ms_per_step"], 12),
+                   collective=(res.get("collective") or "")[:70], build_hash=res.get("build_hash"))
+        return out
+    roof = res["roofline"]
     r = {"bound": roof["bound"], "kernel": roof["kernel"].split(" (")[0], "achieved": _sig(roof["achieved"]), "peak": roof["peak"], "unit": roof["unit"],
          "frac": _sig(roof["frac"]), "traffic": roof["traffic"], "bytes_per_launch": roof["bytes_per_launch"], "us_per_launch": _sig(roof["us_per_launch"]),
          "decode_avg_step_ms": _sig(roof["decode_avg_step_ms"]), "decode_avg_frac": _sig(roof["decode_avg_frac"]), "prefill_ms": _sig(roof["prefill_ms"]),
@@ -699,7 +727,7 @@ def main():
     args = parse()
     resolve_gpus(args, os.environ)
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
-        spawn_ranks(args)                          # does not return
+        spawn_ranks(args)                          # exits with the launcher's status
     # ONE JSON line on stdout, whatever native libraries print: RCCL writes its version banner to fd 1 at communicator bring-up. fd 1 is
     # pointed at stderr for the whole run and the result line goes to the saved descriptor.
     sys.stdout.flush()
@@ -736,11 +764,12 @@ def main():
     max_len = (T + N + 64 + 31) // 32 * 32
     use_graph = not args.no_graph
     host_dev = lambda e: e.device if (dist is not None and dist.get_backend() == "nccl") else "cpu"      # noqa: E731
-    want_oracle = world == 1 and not args.no_cpu_baseline and not STUB
+    want_oracle = args.full and world == 1 and not args.no_cpu_baseline and not STUB
 
-    def timed_run(B, fp8, steps, warmup, keep_engine=False, dtype=None):
+    def timed_run(B, fp8, steps, warmup, keep_engine=False, dtype=None, dump=False):
         """One engine per rank (full weight replica), RCCL communicator inside librdx, `steps` timed steps between barriers, the MAX of
-        the per-rank clocks. Every rank calls this (collectives inside); rank 0 also gets the per-phase detail."""
+        the per-rank clocks. Every rank calls this (collectives inside); rank 0 also writes the last step's outputs (dump and
+        --dump-outputs) and, with --full, gets the per-phase detail."""
         dtype = dtype or args.dtype
         eng = Engine(cfg, dtype=dtype, device=local_rank, max_batch=B, max_len=max_len, lora=True, weights_fp8=fp8)
         eng.load_weights(synth_getter(cfg, eng.device, lora=True))
@@ -765,7 +794,9 @@ def main():
         assert out.shape[0] == B * world and out.shape[1] == N, f"gathered token matrix {tuple(out.shape)}, expected {(B * world, N)}"
         r = {"B": B, "fp8": fp8, "dtype": dtype, "steps": steps, "warmup": warmup, "elapsed": elapsed, "per_rank_ms": per_rank_ms, "comm_world": eng.comm_world,
              "comm_note": comm_note, "tokens_row0": [int(t) for t in out[rank * B, :8].tolist()]}
-        if rank == 0:
+        if rank == 0 and dump and args.dump_outputs:
+            write_outputs(args.dump_outputs, tokens=out, qformer_out=out_q)      # before anything else runs on the engine's kept buffers
+        if rank == 0 and args.full:
             fp8_was, dt_was = args.fp8, args.dtype
             args.fp8, args.dtype = fp8, dtype
             r["enc_ms"], r["roof"] = measure_detail(eng, cfg, args, B, T, N, img, ids, out_q, elapsed / steps * 1e3, use_graph)
@@ -842,23 +873,23 @@ def main():
                 "encoder_ms_per_img": ms, "images_per_s": 1e3 / ms, "encode_tflops": tf, "encode_frac": tf / MFMA_PEAK_TFLOPS, "peak_tflops": MFMA_PEAK_TFLOPS}
 
     B = args.batch
-    main_r = timed_run(B, args.fp8, args.steps, args.warmup, keep_engine=(B == 1 and want_oracle))
+    main_r = timed_run(B, args.fp8, args.steps, args.warmup, keep_engine=(B == 1 and want_oracle), dump=True)
     subs = {}
     k2 = max(2, min(args.steps, 3))
-    if B == 1 and not args.fp8 and not args.no_b32:
+    if args.full and B == 1 and not args.fp8 and not args.no_b32:
         # BASELINE configs[2] (one GPU) / configs[3] (8 GPUs: global batch 256, one all-gather of int32[32,256] per rank) in the same job
         # and JSON line: batch 32 per GPU, KV cache in HBM, hipGraph-captured decode step
         subs["b32"] = (timed_run(32, False, k2, 1, keep_engine=want_oracle),
                        f"configs[{2 if world == 1 else 3}]: per-GPU batch 32 (global {32 * world}), same pipeline, "
                        "hipGraph-captured decode step" + (", RCCL all-gather of the token ids" if world > 1 else ""))
-    if B == 1 and not args.fp8 and not args.no_fp8:
+    if args.full and B == 1 and not args.fp8 and not args.no_fp8:
         # BASELINE configs[4] per-GPU load: fp8 e4m3 decoder weights + per-row scale, LoRA epilogue, batch 32 per GPU
         subs["fp8_b32"] = (timed_run(32, True, k2, 1, keep_engine=want_oracle),
                            f"configs[4]: fp8 e4m3 decoder GEMM weights + per-row scale + un-merged LoRA epilogue, per-GPU "
                            f"batch 32 (global {32 * world}); no reference fp8 path exists -- its oracle is the reference math on the "
                            "same fake-quantised operands (cpu_baseline.parity_fp8 / tests/test_gpu_parity.py), i.e. unpinnable against the reference itself; "
                            "cpu_baseline.fp8_vs_unquantised says what it costs against the un-quantised oracle")
-    if B == 1 and not args.fp8 and not args.no_b64 and not STUB and world == 1:        # one rank only: the N > 1 run stays lean (its per-GPU loads are b32 / fp8_b32)
+    if args.full and B == 1 and not args.fp8 and not args.no_b64 and not STUB and world == 1:        # one rank only: the N > 1 run stays lean (its per-GPU loads are b32 / fp8_b32)
         # round 5: 64 reports per GPU (33-64 decoder rows: the row-block family) -- not a BASELINE configuration (those stop at 32 per GPU): what the
         # 288 GB of HBM buy when the 13.2 GB weight stream of a decode step is amortised over twice the reports
         subs["b64"] = (timed_run(64, False, 2, 1), f"per-GPU batch 64 (global {64 * world}): beyond BASELINE configs[2]/[3]'s 32 per GPU, same pipeline, hipGraph step")
@@ -867,13 +898,13 @@ def main():
             subs["fp8_b128"] = (timed_run(128, True, 2, 1), f"per-GPU batch 128 (global {128 * world}) with the configs[4] weight path: fp8 x fp8 kernels per 32-row block "
                                                             "(row by row the arithmetic of fp8_b32: tests/test_gpu_parity.py::test_fp8_row_blocks_equal_the_32_row_kernels_row_by_row)")
     f16_r = None
-    if B == 1 and not args.fp8 and args.dtype != "f16" and world == 1 and not args.no_f16 and not STUB:
+    if args.full and B == 1 and not args.fp8 and args.dtype != "f16" and world == 1 and not args.no_f16 and not STUB:
         # the reference's dtype, in which token identity with the CPU path actually holds (parity_f16): the same configs[1] workload timed in fp16
         f16_r = timed_run(1, False, k2, 1, keep_engine=want_oracle, dtype="f16")
 
-    if rank == 0:
-        r, roof = main_r, main_r["roof"]
-        res = {
+    def line_head(r):
+        """The headline of the timed run: the contract's fields and what that run alone gives."""
+        return {
             "metric": "reports_per_sec (448px CXR encode + 160-tok prefill + 256-tok greedy decode)",
             "value": args.steps * B * world / r["elapsed"], "unit": "reports/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -885,12 +916,22 @@ def main():
                                    + (", fp8 e4m3 decoder weights + per-row scale [configs[4] weight path]" if args.fp8 else "") + ")",
                        "per_gpu_batch": B, "global_batch": B * world, "prompt_len": T, "new_tokens": N,
                        "parallelism": f"dp{world}", "weights": "random-init (deterministic generator)"},
-            "encoder_ms_per_img": r["enc_ms"],
             "tokens_per_s": args.steps * B * world * N / r["elapsed"],
             "rccl_ranks": r["comm_world"], "per_rank_ms_per_step": r["per_rank_ms"],
             "collective": ("rdx_allgather_tokens (ncclAllGather inside librdx), int32[%d,%d] per rank per step" % (B, N)) if r["comm_world"] else r["comm_note"],
-            "roofline": roof, "token_check": r["token_check"],
         }
+
+    if rank == 0 and not args.full:
+        from radialog_amd import _lib
+        res = line_head(main_r)
+        res["build_hash"] = "stub" if STUB else _lib.build_hash()
+        sys.stdout.flush()
+        os.write(out_fd, (json.dumps(compact_line(res, None), separators=(",", ":")) + "\n").encode())
+        rc = 0
+    elif rank == 0:
+        r, roof = main_r, main_r["roof"]
+        res = line_head(r)
+        res.update(encoder_ms_per_img=r["enc_ms"], roofline=roof, token_check=r["token_check"])
         if args.dtype == "bf16" and not args.fp8:
             res["dtype_note"] = ("bf16 is the THROUGHPUT dtype: against the CPU oracle its greedy tokens flip at near-ties (cpu_baseline.parity: teacher-forced "
                                  "argmax identity, first flip, margin); token identity with the reference's CPU path holds in the reference's own dtype, fp16 -- "

@@ -25,7 +25,7 @@ def _run(n, extra=()):
 
 
 def test_bench_gpus2_emits_one_line_with_the_multi_rank_fields():
-    d, err = _run(2)
+    d, err = _run(2, ("--full",))
     assert "starting 2 ranks" in err                                   # bench.py became its own launcher
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak"
     assert d["config"]["parallelism"] == "dp2" and d["config"]["global_batch"] == 2
@@ -62,3 +62,21 @@ def test_bench_stub_single_rank_under_the_launcher():
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip()][-1])
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and len(d["per_rank_ms_per_step"]) == 1 and "b32_value" not in d
+
+
+def test_plain_run_is_the_timed_steps_alone_and_dumps_the_last_steps_outputs(tmp_path):
+    """Without --full a run is set-up, warm-up, the timed steps and the headline: no sub-runs, no roofline, no oracle, no detail record.
+    --dump-outputs writes what the timed path returned in its last step (rank-major gathered token ids, rank 0's Q-Former output) as float32."""
+    import numpy as np
+    d, err = _run(2, ("--steps", "3", "--dump-outputs", str(tmp_path)))
+    assert "starting 2 ranks" in err
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 2 and d["unit"] == "reports/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "bf16" and abs(d["ms_per_step"] - max(d["per_rank_ms_per_step"])) < 1e-6
+    assert abs(d["value"] - 1000.0 / d["ms_per_step"] * d["config"]["global_batch"]) < 1e-3 * d["value"]
+    assert not {"roofline", "cpu_baseline", "parity", "detail", "encoder_ms_per_img", "tokens_ok"} & set(d)
+    assert not [k for k in d if k.startswith(("b32", "fp8_b32", "b64", "b128", "fp8_b128", "value_f16", "enc_b256"))]
+    assert sorted(os.listdir(tmp_path)) == ["qformer_out.npy", "tokens.npy"]
+    toks, q = np.load(tmp_path / "tokens.npy"), np.load(tmp_path / "qformer_out.npy")
+    assert toks.dtype == np.float32 and q.dtype == np.float32
+    assert toks.shape == (2, 256) and (toks[0] == 0).all() and (toks[1] == 1000).all()     # the stub names (rank, row): both ranks gathered
+    assert q.shape == (1, 32, 768)

@@ -26,7 +26,7 @@ if [ $what = all ] || [ $what = trace ]; then
   trace enc_b1 21 python $ROOT/tools/enc_only.py 1 20
   trace enc_b32 6 python $ROOT/tools/enc_only.py 32 5
   trace prefill_b1 11 python $ROOT/tools/prefill_only.py 1 160 10
-  trace bench_default 0 python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline
+  trace bench_default 0 python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
 fi
 if [ $what = all ] || [ $what = shapes ]; then
   python $ROOT/tools/pconv_check.py 32 auto > $OUT/pconv_shapes_b32.txt 2>&1

@@ -30,7 +30,7 @@ if [ $what = decode ]; then
   trace dec_b32 0 python $ROOT/tools/decode_only.py 32 256 1
 fi
 if [ $what = bench ]; then
-  trace bench_default 0 python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline
+  trace bench_default 0 python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
 fi
 if [ $what = pmc ]; then
   python -c "from radialog_amd import build; print(build.source_hash())" > $OUT/pmc_tree.txt      # the kernel sources these passes ran on (tools/pmc_to_json.py stamps it)

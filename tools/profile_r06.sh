@@ -23,6 +23,6 @@ if [ $what = decfp8 ]; then
   trace dec_fp8_b$2 0 python $ROOT/tools/decode_only.py $2 256 1 1
 fi
 if [ $what = bench ]; then
-  trace bench_default 0 python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline
+  trace bench_default 0 python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline
 fi
 du -sh $OUT

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/r05full
 mkdir -p $OUT
 ( time python -m pytest tests/ -x -q -m gpu --durations=12 ) > $OUT/pytest_gpu.log 2>&1; echo "rc $?" >> $OUT/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc $?" >> $OUT/smoke.log
-python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?" >> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?" >> $OUT/bench.err
 if [ "${1:-}" = prof ]; then
   timeout 600 bash tools/profile_r05.sh pmc > /dev/null 2>&1
   timeout 600 bash tools/profile_r05.sh bench > /dev/null 2>&1
