@@ -13,7 +13,7 @@ SOURCES = ["gemm.hip", "xstat32.hip", "xs16.hip", "gemm_dma.hip", "gemm8.hip", "
            "api.hip", "api_dispatch.hip", "api_encode.hip", "api_llama.hip", "api_comm.hip", "api_inspect.hip", "api_transform.hip"]
 HOOK_SOURCES = ["api_debug.hip"]
 HEADERS = ["rdx_common.h", "rdx_kernels.h", "rdx_ctx.h", "skinny_body.h", "attn_body.h", "handoff.h", os.path.join("..", "..", "include", "rdx.h"),
-           os.path.join("..", "..", "include", "rdx_hooks.h")]
+           os.path.join("..", "..", "include", "rdx_hooks.h"), os.path.join("..", "..", "include", "rdx_enc_hooks.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 

@@ -1,8 +1,9 @@
-// librdx_hooks.so: kernel-test, trace and microbenchmark hooks (include/rdx_hooks.h) -- NOT part of the product library. Built from this one
+// librdx_hooks.so: kernel-test, trace and microbenchmark hooks (include/rdx_hooks.h, and the encoder's: include/rdx_enc_hooks.h) -- NOT part of the product library. Built from this one
 // file and linked against librdx.so, whose context and launchers it drives; radialog_amd/_lib.py loads it only under RDX_DEBUG_HOOKS=1 (the
 // tests' conftest and the tools/ scripts set it). The product entry points, rdx_time included, are in librdx.so (include/rdx.h).
 #include "rdx_ctx.h"
 #include "../../include/rdx_hooks.h"
+#include "../../include/rdx_enc_hooks.h"
 
 // Debug: the stand-alone decode-attention kernel of layer `layer` at the current state, 8 timestamps of workgroup (0,0):
 // host[0..6] = after slot load, inputs ready, new token done, barrier 1, scores + barrier, softmax, PV + barrier; [7] = entry.
@@ -412,3 +413,147 @@ extern "C" int rdx_logits_test(rdx_ctx* c, const void* X, const float* W, int M,
     return 0;
 }
 
+
+// The image encoder's stem on caller data: img_prep_k, then (path 0) stem_pool_k row-major, (1) stem_pool_k fragment-packed with the encoder's
+// pad-row zeroing (run_stem_pool), unpacked here, or (2) the two-kernel path conv_gemm + maxpool_k. image fp32 [B][3][S][S]; W fp32 [stem][224] in
+// the (kh, kw 0..7, c 0..3) K order rdx_set_weight("v.conv1.w") takes, packed here as it packs it; out [B][S / 4][S / 4][stem] model dtype.
+// Path 1 also checks that the pad rows of the last packed tile (what every packed consumer reads as MFMA columns) are zero.
+extern "C" int rdx_stem_test(rdx_ctx* c, const float* image, const float* W, const float* bias, void* out, int B, int S, int stem, int path) {
+    if (!c || !image || !W || !bias || !out || B <= 0 || S < 16 || S % 4) return fail(c, -1, "rdx_stem_test: bad arguments (S %% 4 == 0, S >= 16)");
+    if (path < 0 || path > 2) return fail(c, -1, "rdx_stem_test: path 0 (fused, row-major), 1 (fused, packed) or 2 (conv_gemm + maxpool_k)");
+    if (path < 2 && !stem_pool_supported(stem)) return fail(c, -1, "rdx_stem_test: stem_pool_k has no instantiation for %d channels", stem);
+    if (path == 2 && stem % 16) return fail(c, -1, "rdx_stem_test: conv_gemm needs stem %% 16 == 0");
+    if (path == 1 && !c->zero16) return fail(c, -1, "rdx_stem_test: no zero line for the packed layout");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int dt = c->cfg.dtype, Hp = S + 6, Hc = S / 2, Ho = S / 4;
+    const long M = (long)B * Ho * Ho;
+    const int mt = (int)((M + 15) / 16);
+    const size_t wb = (size_t)stem * 224 * 2, ib = (size_t)B * Hp * Hp * 4 * 2;
+    const size_t tb = path == 1 ? (size_t)mt * 16 * stem * 2 : (path == 2 ? (size_t)B * Hc * Hc * stem * 2 : 0);
+    char* buf = nullptr;
+    HIPCHK(c, hipMalloc((void**)&buf, wb + ib + tb + 64));
+    GemmW w; w.N = stem; w.K = 224; w.Npad = stem; w.w = buf;
+    void* vin = buf + wb;
+    char* tmp = buf + wb + ib;
+    launch_pack_weight(dt, W, w.w, stem, 224, stem, nullptr, c->stream);
+    launch_img_prep(dt, image, vin, B, S, 3, Hp, Hp, c->stream);
+    struct WsScope { rdx_ctx* c; ~WsScope() { c->ws_ok = false; } } ws_scope{c};
+    c->ws_ok = true;
+    int rc = 0;
+    if (path == 0) rc = run_stem_pool(c, vin, w, bias, out, B, S, false);
+    else if (path == 1) {
+        (void)hipMemsetAsync(tmp, 0xff, tb, c->stream);              // what the buffer held before: NaN patterns, so that a missed pad row shows
+        rc = run_stem_pool(c, vin, w, bias, tmp, B, S, true);
+        if (!rc) launch_unpack_rows(dt, tmp, out, stem, (int)M, stem, c->stream);
+    } else {
+        conv_gemm(c, vin, w, bias, nullptr, tmp, B, Hp, Hp, 4, 7, 8, 2, 0, Hc, Hc, EPI_RELU);
+        launch_maxpool(dt, tmp, out, B, Hc, Hc, stem, c->stream);
+    }
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (!rc && e == hipSuccess && path == 1 && (M & 15)) {
+        std::vector<unsigned short> last((size_t)stem / 32 * 512);
+        for (int kc = 0; kc < stem / 32 && e == hipSuccess; ++kc)
+            e = hipMemcpy(last.data() + (size_t)kc * 512, tmp + ((size_t)kc * mt + (mt - 1)) * 1024, 1024, hipMemcpyDeviceToHost);
+        for (int kc = 0; kc < stem / 32 && !rc && e == hipSuccess; ++kc)
+            for (int lane = 0; lane < 64 && !rc; ++lane)
+                for (int j = 0; j < 8; ++j)
+                    if ((lane & 15) >= (int)(M & 15) && last[(size_t)kc * 512 + lane * 8 + j]) {
+                        rc = fail(c, -3, "rdx_stem_test: pad row %d of the last packed tile (channel chunk %d) is not zero", lane & 15, kc);
+                        break;
+                    }
+    }
+    hipFree(buf);
+    if (rc) return rc;
+    HIPCHK(c, e);
+    HIPCHK(c, hipGetLastError());
+    return take_unsupported(c);
+}
+
+// The encoder's normalisation / pooling kernels on caller data (X, emb, out model dtype; gamma, beta, out_f32 fp32; out_f32 nullable):
+//   op 0 layernorm_k          X [rows][H] -> out [rows][H] (+ out_f32);
+//   op 1 layernorm_ex_k       X rows `ldx` apart -> out rows `ldo` apart; emb (nullable) [aux][H] added as emb[row % aux];
+//   op 2 layernorm_packed_k   X [rows][H] packed here (pack_rows_k), normalised packed, unpacked into out [rows][H]; out_f32 [rows][H] by the kernel;
+//   op 3 scramble_layernorm_k X NHWC [rows = B][aux = P][H = C] -> out [B][P][C] (+ out_f32);
+//   op 4 avgpool_flatten_k    X [rows = B][aux = G][G][H = C] -> out [B][C][G / pool][G / pool] (gamma, beta, eps unused).
+extern "C" int rdx_norm_test(rdx_ctx* c, int op, const void* X, const float* gamma, const float* beta, const void* emb, void* out, float* out_f32,
+                             int rows, int H, long long ldx, long long ldo, int aux, int pool, float eps) {
+    if (!c || !X || !out || rows <= 0 || H <= 0) return fail(c, -1, "rdx_norm_test: bad arguments");
+    if (op != 4 && (!gamma || !beta)) return fail(c, -1, "rdx_norm_test: LayerNorm needs gamma and beta");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int dt = c->cfg.dtype;
+    hipStream_t s = c->stream;
+    char* tmp = nullptr;
+    switch (op) {
+    case 0: launch_layernorm(dt, X, gamma, beta, out, out_f32, rows, H, eps, s); break;
+    case 1:
+        if (ldx < H || ldo < H || (emb && aux <= 0)) return fail(c, -1, "rdx_norm_test: layernorm_ex needs ldx, ldo >= H and emb rows > 0");
+        launch_layernorm_ex(dt, X, (long)ldx, gamma, beta, emb, emb ? aux : 1, out, (long)ldo, rows, H, eps, s);
+        break;
+    case 2: {
+        if (!layernorm_packed_supported(H)) return fail(c, -1, "rdx_norm_test: layernorm_packed_k has no instantiation for H = %d", H);
+        const size_t pb = (size_t)(rows + 15) / 16 * 16 * H * 2;
+        HIPCHK(c, hipMalloc((void**)&tmp, 2 * pb));
+        launch_pack_rows(dt, X, H, tmp, rows, H, s);
+        launch_layernorm_packed(dt, tmp, gamma, beta, tmp + pb, out_f32, rows, H, eps, s);
+        launch_unpack_rows(dt, tmp + pb, out, H, rows, H, s);
+        break;
+    }
+    case 3:
+        if (aux <= 0) return fail(c, -1, "rdx_norm_test: scramble needs P > 0");
+        launch_scramble_layernorm(dt, X, gamma, beta, out, out_f32, rows, aux, H, eps, s);
+        break;
+    case 4:
+        if (aux <= 0 || pool <= 0 || aux / pool == 0) return fail(c, -1, "rdx_norm_test: avgpool needs G >= pool > 0");
+        launch_avgpool_flatten(dt, X, out, rows, aux, H, pool, s);
+        break;
+    default: return fail(c, -1, "rdx_norm_test: op 0..4");
+    }
+    hipError_t e = hipStreamSynchronize(s);
+    if (tmp) hipFree(tmp);
+    HIPCHK(c, e);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}
+
+// softmax(Q K^T / sqrt(D)) V through AttnArgs as the encoder / prefill callers fill it. strides[12] = element strides (batch, token, head) of Q, K, V, O;
+// key_mask (nullable) uint8 [B][km_bs], km_bs % 4 == 0 and >= Tk (the kernels read the mask as 32-bit words); o_packed: O is written fragment-packed
+// ([(h D + d) / 32][ceil(B Tq / 16)][64][8], row = b Tq + q) and unpacked here into out [B Tq][H D] (the O strides are then unused).
+// kernel 0 = production dispatch (launch_attention with the context's flash_min), 1 = attention_k, 2 = flash_prefill_k (only where
+// flash_prefill_supported holds: an error otherwise).
+extern "C" int rdx_attn_test(rdx_ctx* c, const void* Q, const void* K, const void* V, void* out, const long long* strides, int B, int H, int Tq,
+                             int Tk, int D, int causal, const uint8_t* key_mask, long long km_bs, int o_packed, int kernel) {
+    if (!c || !Q || !K || !V || !out || !strides || B <= 0 || H <= 0 || Tq <= 0 || Tk <= 0) return fail(c, -1, "rdx_attn_test: bad arguments");
+    if (!(D == 32 || D == 64 || D == 128)) return fail(c, -1, "rdx_attn_test: head dim 32, 64 or 128");
+    if (key_mask && (km_bs < Tk || km_bs % 4)) return fail(c, -1, "rdx_attn_test: key mask rows need km_bs >= Tk and km_bs %% 4 == 0");
+    if (kernel < 0 || kernel > 2) return fail(c, -1, "rdx_attn_test: kernel 0 (dispatch), 1 (attention_k) or 2 (flash_prefill_k)");
+    if ((size_t)16 * ((Tk + 31) & ~31) * 6 > 160 * 1024 && kernel != 2) return fail(c, -1, "rdx_attn_test: Tk = %d does not fit attention_k's LDS", Tk);
+    HIPCHK(c, hipSetDevice(c->device));
+    AttnArgs a;
+    memset(&a, 0, sizeof(a));
+    a.Q = Q; a.K = K; a.V = V;
+    a.q_bs = strides[0]; a.q_ts = strides[1]; a.q_hs = strides[2];
+    a.k_bs = strides[3]; a.k_ts = strides[4]; a.k_hs = strides[5];
+    a.v_bs = strides[6]; a.v_ts = strides[7]; a.v_hs = strides[8];
+    a.o_bs = strides[9]; a.o_ts = strides[10]; a.o_hs = strides[11];
+    a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.causal = causal;
+    a.key_mask = key_mask; a.km_bs = key_mask ? (long)km_bs : 0;
+    a.flash_min = kernel == 0 ? c->flash_min : (kernel == 2 ? 1 : 0);
+    if (kernel == 2 && !flash_prefill_supported(D, a))
+        return fail(c, -1, "rdx_attn_test: flash_prefill_k does not take this call (D 128, causal, key mask, 8-element strides)");
+    const long M = (long)B * Tq;
+    const int mt = (int)((M + 15) / 16);
+    char* tmp = nullptr;
+    if (o_packed) {
+        HIPCHK(c, hipMalloc((void**)&tmp, (size_t)mt * 16 * H * D * 2));
+        a.O = tmp; a.o_packed_mt = mt;
+    } else {
+        a.O = out;
+    }
+    launch_attention(c->cfg.dtype, D, a, c->stream);
+    if (o_packed) launch_unpack_rows(c->cfg.dtype, tmp, out, H * D, (int)M, H * D, c->stream);
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (tmp) hipFree(tmp);
+    HIPCHK(c, e);
+    HIPCHK(c, hipGetLastError());
+    return 0;
+}

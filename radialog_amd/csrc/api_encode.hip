@@ -36,6 +36,21 @@ static int ensure_enc_ws(rdx_ctx* c, int B) {
     return 0;
 }
 
+// conv1 + bn1 + relu + maxpool in one launch: the 224^2 x 64 stem output never goes to HBM (stem.hip). vin = the padded NHWC4 image of
+// img_prep_k; out = [B][S / 4][S / 4][W.N] row-major, or (packed) fragment-packed for pconv_k with the pad rows of its last 16-row tile zeroed
+int run_stem_pool(rdx_ctx* c, const void* vin, const GemmW& W, const float* bias, void* out, int B, int S, bool packed) {
+    const long rows0 = (long)B * (S / 4) * (S / 4);
+    const int mt0 = (int)((rows0 + 15) / 16);
+    if (packed && (rows0 & 15)) {
+        // the pad rows of the last 16-row tile are MFMA B columns of every consumer: zero them (once per chunk of 32 channels: that tile is
+        // one KiB of [C / 32][tiles][64][8]) instead of feeding whatever the buffer held (448 px has no pad rows, 488 px has)
+        for (int kc = 0; kc < W.N / 32; ++kc)
+            HIPCHK(c, hipMemsetAsync((char*)out + ((size_t)kc * mt0 + (mt0 - 1)) * 1024, 0, 1024, c->stream));
+    }
+    launch_stem_pool(c->cfg.dtype, vin, W.w, bias, out, B, S + 6, S / 2, S / 4, W.N, packed ? mt0 : 0, c->stream);
+    return 0;
+}
+
 static int encode_impl(rdx_ctx* c, const float* image, const float* previous, int Bimg, float* qformer_out, float* image_embeds,
                        float* cls_logits = nullptr) {
     if (!c) return -1;
@@ -86,16 +101,8 @@ static int encode_impl(rdx_ctx* c, const float* image, const float* previous, in
         if (!launch_pconv(dt, a, 1, 1, epi, rowout, s)) c->unsupported = "pconv: a 1 x 1 stride-1 convolution whose input and output row tilings differ";
     };
     if (stem_pool_supported(f.v_stem)) {
-        // conv1 + bn1 + relu + maxpool in one launch: the 224^2 x 64 stem output never goes to HBM (stem.hip)
-        const long rows0 = (long)B * (S_ / 4) * (S_ / 4);
-        if (packed && (rows0 & 15)) {
-            // the pad rows of the last 16-row tile are MFMA B columns of every consumer: zero them (once per chunk of 32 channels: that tile is
-            // one KiB of [C / 32][tiles][64][8]) instead of feeding whatever the buffer held (448 px has no pad rows, 488 px has)
-            const int mt0 = mtiles(rows0);
-            for (int kc = 0; kc < f.v_stem / 32; ++kc)
-                HIPCHK(c, hipMemsetAsync((char*)c->vbuf[1] + ((size_t)kc * mt0 + (mt0 - 1)) * 1024, 0, 1024, s));
-        }
-        launch_stem_pool(dt, c->vin, c->v_conv1.w, c->v_conv1_b, c->vbuf[1], B, Hp, Hc, S_ / 4, f.v_stem, packed ? mtiles(rows0) : 0, s);
+        rc = run_stem_pool(c, c->vin, c->v_conv1, c->v_conv1_b, c->vbuf[1], B, S_, packed);
+        if (rc) return rc;
     } else {
         conv_gemm(c, c->vin, c->v_conv1, c->v_conv1_b, nullptr, c->vbuf[0], B, Hp, Hp, 4, 7, 8, 2, 0, Hc, Hc, EPI_RELU);
         launch_maxpool(dt, c->vbuf[0], c->vbuf[1], B, Hc, Hc, f.v_stem, s);

@@ -181,6 +181,8 @@ void xs16_row(rdx_ctx* c, const void* xpacked, const GemmW& W, int B);     // dx
 void run_gemm(rdx_ctx* c, GemmArgs a, int epi);
 void conv_gemm(rdx_ctx* c, const void* X, const GemmW& W, const float* bias, const void* resid, void* out, int B,
                int Hin, int Win, int Cin, int KH, int KW, int stride, int pad, int Hout, int Wout, int epi);
+// the fused stem (stem.hip) as the encoder runs it, packed: with the pad-row zeroing of the fragment-packed output (api_encode.hip)
+int run_stem_pool(rdx_ctx* c, const void* vin, const GemmW& W, const float* bias, void* out, int B, int S, bool packed);
 int v_grid(const rdx_config& f);      // side of the trunk's output grid
 inline bool fp8_weights(const GemmW& W) { return W.w8 && W.scale && !W.w; }       // the engine's fp8 mode keeps no model-dtype copy
 int take_unsupported(rdx_ctx* c);     // nonzero (and rdx_last_error set) when a launch since the last call had no kernel for its shape

@@ -324,6 +324,74 @@ class RdxEngine:
                                                path, iters, C.byref(ms) if iters else None), "rdx_conv_test")
         return (out, ms.value) if iters else out
 
+    def stem_test(self, image, w, bias, path=0):
+        """The stem on its own (rdx_stem_test): image fp32 [B,3,S,S], w fp32 [stem,3,7,7] (torch layout, laid out here as the weight loader does),
+        bias fp32 [stem]; path 0 = fused stem_pool_k row-major, 1 = fused fragment-packed (unpacked), 2 = conv_gemm + maxpool_k. Returns
+        [B,S/4,S/4,stem] in the model dtype."""
+        B, _, S, _ = image.shape
+        stem = w.shape[0]
+        image = image.to(self.device, torch.float32).contiguous()
+        wk = W.stem_khwc4(w.float()).to(self.device)
+        b = bias.to(self.device, torch.float32).contiguous()
+        out = torch.empty(B, S // 4, S // 4, stem, dtype=self.tdtype, device=self.device)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_stem_test(self.ctx, _ptr(image), _ptr(wk), _ptr(b), _ptr(out), B, S, stem, path), "rdx_stem_test")
+        return out
+
+    def norm_test(self, op, x, gamma=None, beta=None, emb=None, out_rows_stride=None, want_f32=False, aux=0, pool=0, eps=1e-12):
+        """The encoder's LayerNorm / pooling kernels (rdx_norm_test). op 0 layernorm_k, 1 layernorm_ex_k (x [rows, ldx] with H = gamma's length,
+        output rows `out_rows_stride` apart, emb [aux, H] added as emb[row % aux]), 2 layernorm_packed_k, 3 scramble_layernorm_k (x [B, P, C]),
+        4 avgpool_flatten_k (x [B, G, G, C] -> [B, C * (G // pool) ** 2]). Returns (out, out_f32 or None); op 1 returns out as [rows, ldo]."""
+        x = x.to(self.device, self.tdtype).contiguous()
+        g = None if gamma is None else gamma.to(self.device, torch.float32).contiguous()
+        bt = None if beta is None else beta.to(self.device, torch.float32).contiguous()
+        e = None if emb is None else emb.to(self.device, self.tdtype).contiguous()
+        f32 = None
+        if op == 3:
+            B, P, H = x.shape
+            rows, aux, ldx, ldo = B, P, H, H
+            out = torch.empty(B, P, H, dtype=self.tdtype, device=self.device)
+        elif op == 4:
+            B, G, _, H = x.shape
+            rows, aux, ldx, ldo = B, G, H, H
+            out = torch.empty(B, H * (G // pool) ** 2, dtype=self.tdtype, device=self.device)
+        else:
+            rows, ldx = x.shape
+            H = g.numel()
+            ldo = out_rows_stride or H
+            out = torch.full((rows, ldo), float("nan"), dtype=self.tdtype, device=self.device)
+            if e is not None:
+                aux = e.shape[0]
+        if want_f32:
+            f32 = torch.empty(out.shape[:-1] + (H,) if op != 1 else (rows, H), dtype=torch.float32, device=self.device)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_norm_test(self.ctx, int(op), _ptr(x), _ptr(g), _ptr(bt), _ptr(e), _ptr(out), _ptr(f32), rows, H, ldx, ldo,
+                                               int(aux), int(pool), float(eps)), "rdx_norm_test")
+        return out, f32
+
+    def attn_test(self, q, k, v, causal=False, key_mask=None, o_packed=False, kernel=0):
+        """softmax(q k^T / sqrt(D)) v through the production attention kernels (rdx_attn_test). q [B,Tq,H,D], k / v [B,Tk,H,D] model-dtype views
+        with any strides whose last dim is contiguous (the kernels read 16-byte pieces); key_mask uint8 [B, >= Tk] (1 = attend), rows padded here
+        to a multiple of 4 bytes; kernel 0 = production dispatch, 1 = attention_k, 2 = flash_prefill_k. Returns [B,Tq,H,D]."""
+        B, Tq, H, D = q.shape
+        Tk = k.shape[1]
+        for t in (q, k, v):
+            assert t.device == self.device and t.dtype == self.tdtype and t.stride(3) == 1
+        out = torch.full((B, Tq, H, D), float("nan"), dtype=self.tdtype, device=self.device)
+        st = [q.stride(0), q.stride(1), q.stride(2), k.stride(0), k.stride(1), k.stride(2), v.stride(0), v.stride(1), v.stride(2),
+              out.stride(0), out.stride(1), out.stride(2)]
+        strides = torch.tensor(st, dtype=torch.int64)
+        km, km_bs = None, 0
+        if key_mask is not None:
+            km_bs = (max(key_mask.shape[1], Tk) + 3) // 4 * 4
+            km = torch.zeros(B, km_bs, dtype=torch.uint8)
+            km[:, :key_mask.shape[1]] = key_mask.to(torch.uint8).cpu()
+            km = km.to(self.device)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_attn_test(self.ctx, _ptr(q), _ptr(k), _ptr(v), _ptr(out), C.c_void_p(strides.data_ptr()), B, H, Tq, Tk, D,
+                                               int(causal), _ptr(km), km_bs, int(o_packed), int(kernel)), "rdx_attn_test")
+        return out
+
     def logits_test(self, x, w, n_valid=None, fp8=False):
         """(logits [M,N] model dtype, argmax int32[M]) of x @ w.T through the lm_head epilogue of the weight-streaming kernels."""
         import ctypes

@@ -42,13 +42,18 @@ def _khwc(w: torch.Tensor) -> torch.Tensor:
     return w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()
 
 
+def stem_khwc4(w: torch.Tensor) -> torch.Tensor:
+    """conv1 [stem, 3, 7, 7] -> [stem, 7 * 8 * 4] with K ordered (kh, kw, c), kw = 7 and c = 3 zero: the K layout of stem_pool_k (stem.hip)."""
+    w = F.pad(w.permute(0, 2, 3, 1), (0, 1, 0, 1))                                # [stem,7,8,4], zero kw=7 / c=3
+    return w.reshape(w.shape[0], 7 * 8 * 4).contiguous()
+
+
 def vision_items(get: Getter, v: VisionCfg, prefix: str = "visual_encoder.", with_ln: bool = True) -> Iterator[Item]:
     """`prefix` = attribute name of the ImageModel in the owning module: `visual_encoder.` in Blip2Qformer
     (blip2_qformer.py), `biovil_encoder.` in ChexpertClassifier (chexpert_model.py:10), which has no ln_vision."""
     P = prefix + "encoder.encoder."
     w, b = _bn_fold(get, get(P + "conv1.weight"), P + "bn1", v.bn_eps)           # [stem,3,7,7]
-    w = F.pad(w.permute(0, 2, 3, 1), (0, 1, 0, 1))                                # [stem,7,8,4], zero kw=7 / c=3
-    yield "v.conv1.w", w.reshape(v.stem, 7 * 8 * 4).contiguous(), RDX_W_GEMM
+    yield "v.conv1.w", stem_khwc4(w), RDX_W_GEMM
     yield "v.conv1.b", b.view(1, -1), RDX_W_F32
     for li, nblk in enumerate(v.blocks, start=1):
         for blk in range(nblk):

@@ -326,3 +326,125 @@ def test_findings_classifier_at_488px_matches_oracle():
         far = ref.abs() > 4 * tol * scale
         assert torch.equal((out > 0)[far], (ref > 0)[far])
         m._engine.close()
+
+
+# ----------------------------------------------------------------------------------------------------------------------------------------
+# the encoder at the batches the project runs: 256 (enc_b256, embed_dump's default), 32 (BASELINE configs[2]) and a ragged 33
+# ----------------------------------------------------------------------------------------------------------------------------------------
+_ORACLE_POS = [0, 3, 16, 127, 128, 201, 254, 255]       # where the 8 oracle images of full_enc_ref sit in the batch of 256
+_DUP = (4, 5, 6, 7)                                      # one image four times: the four phases of 196-row images against 16-row tiles
+_NOISE_POS = (9, 30)                                     # the distinct-channel noise images inside the batch-32 run
+
+
+@pytest.fixture(scope="module")
+def noise_enc_ref(full_vis_w):
+    """Two white-noise images with three DIFFERENT channels through the oracle (every synth_images input repeats one channel)."""
+    from oracle import ref_cpu
+    cfg, W = full_vis_w
+    img = torch.rand(2, 3, cfg.vision.img, cfg.vision.img, generator=torch.Generator().manual_seed(448))
+    with torch.no_grad():
+        ref_q, _ = ref_cpu.forward_image(img, W, cfg)
+    return img, ref_q
+
+
+def _production_batch(img8, S, device):
+    x = synth.synth_images(256, S, device=device, seed=101)
+    x[_DUP[1]:_DUP[-1] + 1] = x[_DUP[0]]
+    for j, p in enumerate(_ORACLE_POS):
+        x[p] = img8[j].to(device)
+    return x
+
+
+def _batch_invariance(run, x, tol, label):
+    """run(x) -> per-row output. Twice the same batch: bit-identical; the duplicates: bit-identical to each other (a row's arithmetic does not
+    depend on its neighbours within one launch); every row: within tol (relative L2) of the same image run alone at B = 1. Returns
+    (batch output, worst B = 1 distance).
+    The B = 1 encode is not the same arithmetic as the batched one -- one image's deep stages split K over the waves of a workgroup, the Q-Former's
+    32 rows run other tilings -- so the two differ by the rounding noise of two fp32-accumulating evaluations, about the size of either one's
+    distance from the oracle (measured: 2.8e-3 fp16 / 2.1e-2 bf16 at B = 256). The bar is ENC_TOL, half the per-image oracle bar."""
+    out = run(x)
+    assert torch.isfinite(out).all(), label
+    assert torch.equal(out, run(x)), f"{label}: the same batch twice gives different bits"
+    dups = [b for b in _DUP if b < x.shape[0]]
+    for b in dups[1:]:
+        assert torch.equal(out[b], out[dups[0]]), f"{label}: duplicate image at {b} differs from the one at {dups[0]}"
+    errs = [_rel_l2(out[b].cpu(), run(x[b:b + 1])[0].cpu()) for b in range(x.shape[0])]
+    worst = max(errs)
+    assert worst < tol, f"{label}: row {errs.index(worst)} is {worst:.3e} (rel-L2) from the same image encoded alone"
+    return out, worst
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+def test_full_size_encoder_at_production_batches(full_vis_w, full_enc_ref, noise_enc_ref, dtype):
+    """rdx_encode_image at B = 256 (the oracle's 8 images spread over the batch, incl. both ends and both sides of 128), B = 32 (configs[2];
+    with the two distinct-channel noise images inside) and B = 33 (a ragged last workgroup), packed trunk, 448 px: the oracle rows meet the
+    per-image bar, duplicates are bit-identical, every row is within ENC_TOL of its own B = 1 encode in the same (grown) context."""
+    from radialog_amd.engine import RdxEngine, synth_getter
+    cfg, W = full_vis_w
+    img8, ref_q, _ = full_enc_ref
+    nimg, nref = noise_enc_ref
+    tol = ENC_TOL[dtype]
+    eng = RdxEngine(cfg, dtype=dtype, device=0, llama=False)
+    eng.load_weights(synth_getter(cfg, eng.device), llama=False)
+    run = lambda x: eng.encode_image(x, want_image_embeds=False)[0]            # noqa: E731
+    x = _production_batch(img8, cfg.vision.img, eng.device)
+    q, worst = _batch_invariance(run, x, tol, f"{dtype} B=256")
+    errs = [_rel_l2(q[p].cpu(), ref_q[j]) for j, p in enumerate(_ORACLE_POS)]
+    print(f"encoder {dtype} B=256: oracle rows rel-L2 max {max(errs):.3e} (bar {2 * tol}); worst row vs B=1 {worst:.3e} (bar {tol})")
+    assert max(errs) < 2 * tol, errs
+    x32 = x[:32].clone()
+    for j, p in enumerate(_NOISE_POS):
+        x32[p] = nimg[j].to(eng.device)
+    q32, worst32 = _batch_invariance(run, x32, tol, f"{dtype} B=32")
+    q33, worst33 = _batch_invariance(run, x[:33].contiguous(), tol, f"{dtype} B=33")
+    n1 = run(nimg.to(eng.device))
+    en = [_rel_l2(n1[j].cpu(), nref[j]) for j in range(2)] + [_rel_l2(q32[p].cpu(), nref[j]) for j, p in enumerate(_NOISE_POS)]
+    print(f"encoder {dtype} B=32 / 33: worst row vs B=1 {worst32:.3e} / {worst33:.3e}; distinct-channel noise images vs oracle {max(en):.3e} (bar {tol})")
+    assert max(en) < tol, en
+    assert _rel_l2(q33[:32].cpu(), q[:32].cpu()) < tol and _rel_l2(q32[:9].cpu(), q[:9].cpu()) < tol
+    eng.close()
+
+
+def test_findings_classifier_at_488px_batch_17():
+    """rdx_classify_findings at B = 17, 488 px: ragged stem tiles and pad rows in every packed tensor (17 x 122^2 rows). Duplicates give
+    bit-identical logits; every row is within the classifier bar (4 x tol x max(1, |logit|)) of its B = 1 logits."""
+    from radialog_amd.chexpert_model import ChexpertClassifier
+    from radialog_amd.config import classifier_cfg
+    cfg = classifier_cfg()
+    W = synth.make_weights(synth.classifier_specs(cfg.vision, cfg.cls))
+    x = synth.synth_images(17, cfg.vision.img, seed=55, device="cuda")
+    x[_DUP[1]:_DUP[-1] + 1] = x[_DUP[0]]
+    for dtype, tol in (("f16", 5e-3), ("bf16", 3e-2)):
+        m = ChexpertClassifier(num_classes=cfg.cls.classes, cfg=cfg, dtype=dtype)
+        m.load_state_dict(W)
+        out = m(x).float()
+        assert torch.isfinite(out).all() and torch.equal(out, m(x).float())
+        for b in _DUP[1:]:
+            assert torch.equal(out[b], out[_DUP[0]]), f"{dtype}: duplicate at {b}"
+        worst = 0.0
+        for b in range(17):
+            one = m(x[b:b + 1]).float()[0]
+            e = float((out[b] - one).abs().max()) / float(one.abs().max().clamp_min(1.0))
+            worst = max(worst, e)
+            assert e < 4 * tol, f"{dtype}: row {b} differs from its B = 1 logits by {e:.3g} x scale"
+        print(f"findings classifier 488 px {dtype} B=17: worst row vs B=1 {worst:.3e} x logit scale (bar {4 * tol})")
+        m._engine.close()
+
+
+@pytest.mark.parametrize("dtype", ["f16", "bf16"])
+def test_two_image_mode_at_batch_16(full_vis_w, dtype):
+    """rdx_encode_image2 at B = 16 (a trunk batch of 32, the ViT pooler at 16 x 392 tokens): duplicates bit-identical, every row within
+    ENC_TOL of the same pair encoded alone."""
+    from radialog_amd.engine import RdxEngine, synth_getter
+    cfg, W = full_vis_w
+    eng = RdxEngine(cfg, dtype=dtype, device=0, llama=False)
+    eng.load_weights(synth_getter(cfg, eng.device), llama=False)
+    img = synth.synth_images(16, cfg.vision.img, seed=61, device=eng.device)
+    prev = synth.synth_images(16, cfg.vision.img, seed=62, device=eng.device)
+    img[_DUP[1]:_DUP[-1] + 1] = img[_DUP[0]]
+    prev[_DUP[1]:_DUP[-1] + 1] = prev[_DUP[0]]
+    pair = torch.cat([img, prev], 1)                 # rows carry both images through _batch_invariance's slicing
+    run = lambda xp: eng.encode_image(xp[:, :3].contiguous(), want_image_embeds=False, previous_image=xp[:, 3:].contiguous())[0]   # noqa: E731
+    _, worst = _batch_invariance(run, pair, ENC_TOL[dtype], f"two-image {dtype} B=16")
+    print(f"two-image mode {dtype} B=16: worst row vs B=1 {worst:.3e} (bar {ENC_TOL[dtype]})")
+    eng.close()

@@ -49,6 +49,29 @@ def test_hooks_live_in_their_own_library_and_need_the_switch(monkeypatch):
         fresh.rdx_gemm_test(None)
 
 
+def test_encoder_hooks_are_declared_bound_and_only_in_the_hooks_library(monkeypatch):
+    """The image encoder's kernel-test hooks (include/rdx_enc_hooks.h: rdx_stem_test, rdx_norm_test, rdx_attn_test) follow the rules of
+    rdx_hooks.h: header and binding table agree, librdx_hooks.so exports them and librdx.so does not, _lib binds them with their argtypes
+    under RDX_DEBUG_HOOKS=1 and replaces them with raising stubs without it."""
+    assert _declared_symbols("rdx_enc_hooks.h") == sorted(_lib.ENC_HOOK_SYMBOLS)
+    assert not set(_lib.ENC_HOOK_SYMBOLS) & set(_lib.SYMBOLS) and not set(_lib.ENC_HOOK_SYMBOLS) & set(_lib.HOOK_SYMBOLS)
+    lib = C.CDLL(_lib.LIB_PATH, mode=C.RTLD_GLOBAL)
+    hooks = C.CDLL(_lib.HOOKS_PATH, mode=C.RTLD_GLOBAL)
+    for name in _declared_symbols("rdx_enc_hooks.h"):
+        assert not hasattr(lib, name), f"librdx.so exports the test hook {name}"
+        assert hasattr(hooks, name), f"librdx_hooks.so does not export {name}"
+    bound = _lib.load()
+    for name, (res, args) in _lib.ENC_HOOK_SYMBOLS.items():
+        fn = getattr(bound, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    monkeypatch.setenv("RDX_DEBUG_HOOKS", "0")
+    fresh = C.CDLL(_lib.LIB_PATH, mode=C.RTLD_GLOBAL)
+    _lib.load_hooks(fresh)
+    for name in _lib.ENC_HOOK_SYMBOLS:
+        with pytest.raises(_lib.RdxLibraryError, match="RDX_DEBUG_HOOKS"):
+            getattr(fresh, name)(None)
+
+
 def test_config_struct_matches_header_field_count():
     text = open(os.path.join(REPO, "include", "rdx.h")).read()
     body = text[text.index("typedef struct rdx_config {"): text.index("} rdx_config;")]
