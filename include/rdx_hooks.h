@@ -17,7 +17,9 @@ int rdx_attn_trace(rdx_ctx* ctx, int layer, long long* host);
 int rdx_quant_test(rdx_ctx* ctx, const void* X, int M, int K, int groups, int mode, const void* norm_w, float eps, void* out8, float* scales);
 /* debug: per-workgroup timestamps of one stand-alone decode GEMV (what: 1 gate/up, 2 qkv, 4 down), host[tile*8 + 0..5]; the
  * persistent batch >= 3 kernels (xstat32.hip) write one record per WORKGROUP: entry, first trip's K loop done, first trip done, last
- * trip begins, its K loop done, end, [6] = trips, [7] = XCC id (tools/xs_trace.py) */
+ * trip begins, its K loop done, end, [6] = trips, [7] = XCC id (tools/xs_trace.py).
+ * what = 7: the chained down(layer) -> QKV(layer + 1) launch of the batch <= 2 step, in situ: runs ONE eager decode step (the state advances) and
+ * returns one record per workgroup of that launch (tools/chain_seam.py; slots: csrc/chain.hip chain_tile) */
 int rdx_gemv_trace(rdx_ctx* ctx, int what, int layer, long long* host, int max_tiles);
 
 /* one bare GEMM through the production kernels: out = epilogue(X . W^T); X/resid/norm_w/out model dtype, W [N][K] and

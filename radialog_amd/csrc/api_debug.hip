@@ -43,11 +43,34 @@ extern "C" int rdx_quant_test(rdx_ctx* c, const void* X, int M, int K, int group
 
 // Debug: one stand-alone decode GEMV (what = 1 gate/up, 2 qkv, 4 down, as in rdx_time) of `layer` with per-workgroup
 // timestamps: host[tile*8 + {0 entry, 1 weights issued, 2 activations staged, 3 K loop done, 4 all waves done, 5 end}].
+// what = 7: the chained down(layer) -> QKV(layer + 1) launch IN SITU (its hand-off counters are only valid inside a real step): ONE eager
+// decode step runs and advances the state; host[workgroup*8 + slot] with the slots of chain.hip (chain_tile; down_proj workgroups first, then the QKV workgroups).
 extern "C" int rdx_gemv_trace(rdx_ctx* c, int what, int layer, long long* host, int max_tiles) {
     if (!c || !c->finalized || c->cur_B <= 0 || !host) return fail(c, -1, "rdx_gemv_trace: run a prefill first");
     HIPCHK(c, hipSetDevice(c->device));
     const rdx_config& f = c->cfg;
     const int H = f.hidden, B = c->cur_B;
+    if (what == 7) {
+        if (layer < 0 || layer >= f.layers) return fail(c, -1, "rdx_gemv_trace(7): layer %d of %d", layer, f.layers);
+        if (c->cur_T + c->cur_steps + 1 > f.max_len || c->cur_T + c->cur_steps + 1 > f.max_pos)       // as rdx_time(7): bounded by the KV cache, not by max_new
+            return fail(c, -1, "rdx_gemv_trace(7): no room for one more decode step in the KV cache");
+        const int wgs = H / 16 + ((c->ll[0].wqkv.Npad + 15) / 16 + 3) / 4;      // down_proj tiles + QKV workgroups of 4 tiles
+        if (wgs > max_tiles) return fail(c, -1, "rdx_gemv_trace(7): need room for %d workgroups", wgs);
+        long long* dtr = nullptr;
+        const size_t bytes = (size_t)max_tiles * 8 * sizeof(long long);
+        HIPCHK(c, hipMalloc(&dtr, bytes));
+        HIPCHK(c, hipMemsetAsync(dtr, 0, bytes, c->stream));
+        c->chain_trace = dtr; c->chain_trace_layer = layer;
+        const bool chained = decode_step_launch(c, nullptr, nullptr, 0);
+        c->chain_trace = nullptr; c->chain_trace_layer = -1;
+        c->cur_steps = std::max(c->cur_steps + 1, c->cur_max_new);      // the state has moved: a new prefill comes first
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (e == hipSuccess) e = hipMemcpy(host, dtr, bytes, hipMemcpyDeviceToHost);
+        hipFree(dtr);
+        HIPCHK(c, e);
+        if (!chained) return fail(c, -1, "rdx_gemv_trace(7): the chained down -> QKV launch is not active in this configuration (batch > 2, RDX_CHAIN=0)");
+        return 0;
+    }
     const LlamaLayer& L = c->ll[layer];
     long long* dtr = nullptr;
     const size_t bytes = (size_t)max_tiles * 8 * sizeof(long long);

@@ -62,7 +62,7 @@ extern "C" int rdx_time(rdx_ctx* c, int what, int iters, float* ms_host) {
         for (hipEvent_t e : evs) hipEventDestroy(e);
         for (hipEvent_t e : nul) hipEventDestroy(e);
         hipEventDestroy(e0); hipEventDestroy(e1);
-        if (!chained || n == 0) return fail(c, -1, "rdx_time(7): the chained down -> QKV launch is not active in this configuration (batch > 2, RDX_CHAIN != 2)");
+        if (!chained || n == 0) return fail(c, -1, "rdx_time(7): the chained down -> QKV launch is not active in this configuration (batch > 2, RDX_CHAIN=0)");
         *ms_host = (float)(tot / (double)n);
         return 0;
     }

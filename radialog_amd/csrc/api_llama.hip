@@ -332,6 +332,7 @@ bool decode_step_launch(rdx_ctx* c, void* logits, const int* out_step, long step
             { GemmArgs a = gargs(c->dx, H, L.wgu, nullptr, c->dgu, f.inter, B); a.norm_w = L.mlp_norm; a.eps = f.rms_eps; skinny(c, a, EPI_SILU_MUL); }
             if (evs) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, s); evs->push_back(e); }
             ca.layer = l;
+            ca.trace = l == c->chain_trace_layer ? c->chain_trace : nullptr;
             launch_decode_chain(dt, ca, l + 1 < f.layers, s);
             if (evs) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, s); evs->push_back(e); }
             continue;

@@ -1,9 +1,14 @@
 // Chained decode launches of the batch-1/2 step (gfx950): units of consecutive decode layers run as ROLES of one launch, the dependency
-// between them is a counter hand-off (handoff.h) instead of a kernel boundary -- a consumer workgroup first puts two register batches
-// of ITS weight tile in flight, then waits until the producer role has published the activations, so HBM stays busy across the seam.
+// between them is a counter hand-off (handoff.h) instead of a kernel boundary -- a consumer workgroup first puts a ring of register
+// fragments of ITS weight tile in flight, then waits until the producer role has published the activations. What is in flight is all
+// that HBM moves during the hand-off, so the ring is sized to the hand-off, not to the main loop (profiles/r07_chain_seam.md).
 //
 //   decode_chain_k   down_proj(l) (+ residual)  ->  RMSNorm + QKV(l + 1): one launch per layer, one 1024-thread workgroup per CU
-//                    (two resident 16-wave workgroups per CU run every unit ~25 % slower, so the launch reserves > half of the LDS);
+//                    (two resident 16-wave workgroups per CU run every unit ~25 % slower, so the launch reserves > half of the LDS).
+//                    With one workgroup per CU a QKV workgroup becomes resident when a down_proj workgroup has retired; its dispatch and
+//                    first byte (~1.8 us) hide behind the wait for the LAST arrival (~3 us: poll 2 us behind the slowest down_proj tile),
+//                    then the row is loaded, normalised and staged (~2 us). A ring of 8 fragments per wave (25 MB over the chip, 4 us of
+//                    HBM time) left ~2 us of that with nothing in flight; the QKV role now holds 16 (half of a wave's K slice);
 //   attn_oproj16_k   decode attention (attn_body.h) -> o_proj (+ residual): 32 attention workgroups + 128 two-tile o_proj workgroups
 //                    whose whole K slice sits in registers while attention runs.
 // Payloads are written write-through (8-byte agent-scope stores) and read with agent-scope loads: no cache fences. Arithmetic,
@@ -34,10 +39,11 @@ struct ChainGemm {                                // one weight-streaming unit
 };
 
 template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false>
-__device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, const int ntiles, unsigned char* smem, WaitFn wait_inputs) {
+__device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, const int ntiles, unsigned char* smem, WaitFn wait_inputs,
+                                           long long* trace = nullptr) {
     typedef typename Vec8<T>::type V8;
     constexpr int WPS = CH_WAVES / SUB;           // waves per tile
-    // U chunks per register batch, two batches in flight: U = 4 keeps every role of the chained kernel <= 64 VGPRs
+    // U chunks per register batch, two batches in flight (a ring of 2 U fragments): 32 VGPRs at U = 4, 64 at U = 8; every role stays <= 128
     float* red = reinterpret_cast<float*>(smem);                        // [CH_WAVES][256]
     float* ssq = red + CH_WAVES * 256;                                  // [CH_WAVES][CH_MAXM]
     float* rstd_s = ssq + CH_WAVES * CH_MAXM;                           // [CH_MAXM] (+pad)
@@ -53,6 +59,11 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
     const T* X = reinterpret_cast<const T*>(a.X);
     const u4* wbase = reinterpret_cast<const u4*>(W8 ? a.W8 : a.W) + (size_t)tile_c * KC * 64 + lane;
     const int clast = min(max(c1 - 1, c0), KC - 1);
+    // debug timeline of this workgroup (rdx_gemv_trace 7; null in every product launch), 100 MHz ticks, wave 0: [0] entry, [5] first weight KiB
+    // back, [3] inputs ready, [6] first MFMA (row staged), [1] K loop done, [7] end; [2] = arrival, written by the down_proj role's caller
+    long long* trc = (trace && threadIdx.x == 0) ? trace : nullptr;
+#define CH_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
+    CH_T(0);
 
     // two register batches (A, B) in flight before anything else; the main loop ping-pongs between them (no register
     // rotation: a rotated pair makes the compiler wait for the batch it has just issued)
@@ -61,6 +72,10 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
     for (int u = 0; u < U; ++u) wa_[u] = ldg16_nt(wbase + (size_t)min(c0 + u, clast) * 64);
 #pragma unroll
     for (int u = 0; u < U; ++u) wb_[u] = ldg16_nt(wbase + (size_t)min(c0 + U + u, clast) * 64);
+    if (trace) {        // traced launches only: wave 0 watches its first KiB come back (it stalls here, which a product launch never does)
+        if (threadIdx.x < 64) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * U - 1) : "memory");
+        CH_T(5);
+    }
 
     // RESID_EARLY: the residual predates the launch (fused attention + o_proj) -> fetch it now, off the critical tail
     constexpr int QPT_E = EPI == EPI_SILU_MUL ? 2 : 4;
@@ -73,6 +88,7 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
     }
 
     wait_inputs();
+    CH_T(3);
 
     // activations: published write-through by other workgroups of this launch -> agent-scope 8-byte loads (L1 bypass),
     // each chunk loaded ONCE and kept in registers across the RMSNorm statistics
@@ -143,6 +159,7 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
     // the batch's last MFMA into a spare register, and the copy back waited vmcnt(0) on every trip
     const T* xrow = xs + (size_t)(r < a.M ? r : 0) * K + g * (W8 ? 16 : 8);
     v4f acc = (v4f){0.f, 0.f, 0.f, 0.f};
+    CH_T(6);
     // Main loop: loads are UNCONDITIONAL (addresses clamped into the slice) and no MFMA is guarded, so the compiler can
     // wait with counted vmcnt (one batch stays in flight); a conditional load anywhere in the loop makes it fall back
     // to vmcnt(0). At most one batch per wave is fetched in vain (same 1 KiB line as the slice's last chunk).
@@ -193,6 +210,7 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
     }
     consume(wa_, cb, true);
     consume(wb_, cb + U, true);
+    CH_T(1);
     // D[n_local = g*4+reg][m_local = r] -> red[wave][m_local*16 + n_local]
     *reinterpret_cast<float4*>(&red[wa * 256 + r * 16 + g * 4]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     __syncthreads();
@@ -242,27 +260,33 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
             if (ok) st8_agent(out + (size_t)m * a.ldo + t_o * 8 + q * 4, pk);
         }
     }
+    CH_T(7);
+#undef CH_T
 }
 
 // down_proj(l) then RMSNorm + QKV(l + 1): blocks [0, nwg_down) are down_proj tiles (one tile per workgroup, 16 waves split K; their
 // input predates the launch), blocks [nwg_down, +nwg_qkv) are QKV workgroups of the NEXT layer (4 tiles each, 4 waves per tile, the
-// normalised row staged once per workgroup) that wait for all down_proj tiles on the layer's sharded counter
+// normalised row staged once per workgroup) that wait for all down_proj tiles on the layer's sharded counter. The QKV role's ring is 16
+// fragments deep (U = 8; fp8 weights keep 8: 16 measured slower there): it is issued at entry and is what HBM carries while the
+// workgroup waits for the last arrival and stages the row. Same chunks in the same order per wave: the sums do not change by a bit.
 template <typename T, bool W8>
 __global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_k(ChainArgs ca) {
     extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
     const ChainLayer& L = ca.layers[ca.layer];
     int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
     const int H = ca.hidden, B = ca.B;
+    long long* trace = ca.trace ? ca.trace + (size_t)blockIdx.x * 8 : nullptr;
     if ((int)blockIdx.x < ca.nwg_down) {
         ChainGemm g = {ca.dgu, ca.inter, L.wdown, ca.dx, H, ca.dx, H, B, H, ca.inter, nullptr, 0.f, L.wdown8, L.sdown};
-        chain_tile<T, EPI_RESID, false, 1, 6, WaitSharded, 4, false, W8>(g, blockIdx.x, ca.nwg_down, msm, WaitSharded{ctr, 0, ca.err, ca.naps, nullptr});
+        chain_tile<T, EPI_RESID, false, 1, 6, WaitSharded, 4, false, W8>(g, blockIdx.x, ca.nwg_down, msm, WaitSharded{ctr, 0, ca.err, ca.naps, nullptr}, trace);
         publish_sc1(ctr, blockIdx.x);
+        if (trace && threadIdx.x == 0) trace[2] = (long long)__builtin_amdgcn_s_memrealtime();      // arrival
         return;
     }
     const ChainLayer& Ln = ca.layers[ca.layer + 1];
     ChainGemm g = {ca.dx, H, Ln.wqkv, nullptr, 0, ca.dqkv, ca.qkv_ld, B, ca.qkv_n, H, Ln.attn_norm, ca.eps, Ln.wqkv8, Ln.sqkv};
-    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, 4, false, W8>(g, blockIdx.x - ca.nwg_down, (ca.qkv_n + 15) / 16, msm,
-                                                                    WaitSharded{ctr, ca.nwg_down, ca.err, ca.naps, nullptr});
+    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, W8 ? 4 : 8, false, W8>(g, blockIdx.x - ca.nwg_down, (ca.qkv_n + 15) / 16, msm,
+                                                                             WaitSharded{ctr, ca.nwg_down, ca.err, ca.naps, nullptr}, trace);
 }
 
 // ---- decode attention + o_proj(+residual) in ONE launch, 16-wave workgroups -------------------------------------------------
@@ -316,7 +340,7 @@ void launch_decode_chain(int dtype, ChainArgs ca, bool with_next_qkv, hipStream_
     const int nwg_qkv = with_next_qkv ? ((ca.qkv_n + 15) / 16 + 3) / 4 : 0;
     const int kmax = ca.inter > ca.hidden ? ca.inter : ca.hidden;
     const size_t sm_gemm = (size_t)(CH_WAVES * 256 + CH_WAVES * CH_MAXM + 16) * 4 + (size_t)ca.B * kmax * 2;
-    // ONE workgroup per CU: the register budget alone (62 VGPRs) would admit two, so reserve more than half of the LDS
+    // ONE workgroup per CU: the register budget alone (<= 128 VGPRs) would admit two, so reserve more than half of the LDS
     const size_t smem = sm_gemm > (size_t)84 * 1024 ? sm_gemm : (size_t)84 * 1024;
     dim3 grid(ca.nwg_down + nwg_qkv), block(CH_THREADS);
     RDX_DISPATCH_T(dtype, T, {

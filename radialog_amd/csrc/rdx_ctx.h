@@ -100,6 +100,7 @@ struct rdx_ctx {
                                      // per layer); RDX_XS16=0 at create / rdx_set_option("xs16", 0): the 32-row family of xstat32.hip (7 launches; A/B leg of the tests)
     bool prompt_blk = true;          // one prompt's K = 4096 projections on xstat32_k<.., BLK> (RDX_PBLK=0 / rdx_set_option("prompt_blk", 0): wstat_k, the A/B leg)
     int chain_naps = 1;              // poll back-off of the chained launch (x s_sleep(8) between polls)
+    long long* chain_trace = nullptr; int chain_trace_layer = -1;     // rdx_gemv_trace(7): device timeline buffer of ONE chained launch of the next step
     GemmW cls_fc1, cls_fc2; const float *cls_fc1_b = nullptr, *cls_fc2_b = nullptr;   // findings classifier head
     void *cls_pooled = nullptr, *cls_h = nullptr, *cls_out = nullptr;
     void* zero16 = nullptr;          // 16 zero bytes: source of padding taps in the DMA conv gather

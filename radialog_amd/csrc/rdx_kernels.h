@@ -202,6 +202,7 @@ struct ChainArgs {
     int* err;
     int naps;                        // poll back-off (x s_sleep(8) between polls)
     int nwg_down;                    // filled by the launcher
+    long long* trace;                // debug: [workgroup][8] timestamps (100 MHz ticks) of one launch, slots in chain.hip; null in every product launch
 };
 bool chain_supported(const LlamaDims& d, int inter, int B);
 size_t chain_ctr_ints(int layers);
