@@ -69,6 +69,7 @@ extern "C" int rdx_create(rdx_ctx** out, int device_id, const rdx_config* cfg) {
     { const char* e = getenv("RDX_FLASH_MIN"); if (e) c->flash_min = atoi(e); }
     { const char* e = getenv("RDX_XS16"); if (e) c->xs16 = atoi(e) != 0; }
     { const char* e = getenv("RDX_PBLK"); if (e) c->prompt_blk = atoi(e) != 0; }
+    { const char* e = getenv("RDX_BLK_DOWN"); c->blk_down = !(e && atoi(e) == 0); }
     { const char* e = getenv("RDX_PCONV_KSPLIT"); c->pconv_noks = e && atoi(e) == 0; }
     { const char* e = getenv("RDX_PCONV"); c->trunk_packed = !(e && atoi(e) == 0); }      // read once (A/B legs of the tests set it before rdx_create)
     if (hipMalloc(&c->zero16, 64) == hipSuccess) { hipMemset(c->zero16, 0, 64); c->allocs.push_back(c->zero16); } else c->zero16 = nullptr;

@@ -13,11 +13,7 @@ extern "C" int rdx_attn_trace(rdx_ctx* c, int layer, long long* host) {
     long long* dtr = nullptr;
     HIPCHK(c, hipMalloc(&dtr, 8 * sizeof(long long)));
     HIPCHK(c, hipMemsetAsync(dtr, 0, 8 * sizeof(long long), c->stream));
-    const LlamaLayer& L = c->ll[layer];
-    DecAttnArgs at;
-    at.d = c->ld; at.qkv = c->dqkv; at.lbq = L.lora_bq; at.lbv = L.lora_bv; at.cos_t = c->rope_cos; at.sin_t = c->rope_sin;
-    at.pos = c->d_pos; at.slot_b = c->d_slot; at.key_mask = c->key_mask; at.cur_rope = c->d_cur_rope;
-    at.kcache = kv_ptr(c, c->kcache, layer); at.vcache = kv_ptr(c, c->vcache, layer); at.out = c->datt;
+    DecAttnArgs at = dec_attn_args(c, layer);
     at.trace = dtr;
     launch_decode_attention(c->cfg.dtype, at, c->cur_B, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
@@ -76,10 +72,8 @@ extern "C" int rdx_gemv_trace(rdx_ctx* c, int what, int layer, long long* host, 
     const size_t bytes = (size_t)max_tiles * 8 * sizeof(long long);
     HIPCHK(c, hipMalloc(&dtr, bytes));
     HIPCHK(c, hipMemsetAsync(dtr, 0, bytes, c->stream));
-    GemmArgs a;
-    if (what == 1) { a = gargs(c->dx, H, L.wgu, nullptr, c->dgu, f.inter, B); a.norm_w = L.mlp_norm; a.eps = f.rms_eps; }
-    else if (what == 2) { a = gargs(c->dx, H, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); a.N = L.wqkv.Npad; a.norm_w = L.attn_norm; a.eps = f.rms_eps; }
-    else { a = gargs(c->dgu, f.inter, L.wdown, nullptr, c->dqkv, H, B); }
+    GemmArgs a = unit_args(c, &L, what == 1 ? UNIT_GATE_UP : what == 2 ? UNIT_QKV : UNIT_DOWN, B);
+    if (what != 1 && what != 2) { a.out = c->dqkv; a.resid = nullptr; a.ldr = 0; }      // down_proj alone: into a scratch buffer, no residual (dx stays as it is)
     if ((a.N + 15) / 16 > max_tiles) { hipFree(dtr); return fail(c, -1, "rdx_gemv_trace: need room for %d tiles", (a.N + 15) / 16); }
     a.trace = dtr;
     skinny(c, a, what == 1 ? EPI_SILU_MUL : EPI_NONE);

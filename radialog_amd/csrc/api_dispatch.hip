@@ -10,39 +10,116 @@ GemmArgs gargs(const void* X, int ldx, const GemmW& W, const float* bias, void* 
     return a;
 }
 
-// Skinny GEMM with an optional fused RMSNorm: fused when the activations fit the kernel's LDS staging path, otherwise
-// the rows are normalised once by rmsnorm_k into a scratch buffer (batch-32 decode).
-// The RMSNorm of a projection whose rows do not fit the GEMV's LDS stage runs as its own launch in front of it; returns the
-// arguments of the GEMM proper (activations = c->dxn)
+// ---- the decode step's units: one definition each (rdx_ctx.h) ----
+DecAttnArgs dec_attn_args(rdx_ctx* c, int layer) {
+    const LlamaLayer& L = c->ll[layer];
+    DecAttnArgs at;
+    at.d = c->ld; at.qkv = c->dqkv; at.lbq = L.lora_bq; at.lbv = L.lora_bv; at.cos_t = c->rope_cos; at.sin_t = c->rope_sin;
+    at.pos = c->d_pos; at.slot_b = c->d_slot; at.key_mask = c->key_mask; at.cur_rope = c->d_cur_rope;
+    at.kcache = kv_ptr(c, c->kcache, layer); at.vcache = kv_ptr(c, c->vcache, layer); at.out = c->datt;
+    return at;
+}
+
+AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer) {
+    const rdx_config& f = c->cfg;
+    const int H = f.hidden;
+    AttnArgs at;
+    memset(&at, 0, sizeof(at));
+    at.Q = c->pq; at.q_bs = (long)T * H; at.q_ts = H; at.q_hs = 128;
+    at.K = kv_ptr(c, c->kcache, layer); at.V = kv_ptr(c, c->vcache, layer);
+    at.k_bs = at.v_bs = (long)f.heads * f.max_len * 128; at.k_ts = at.v_ts = 128; at.k_hs = at.v_hs = (long)f.max_len * 128;
+    at.O = c->patt; at.o_bs = (long)T * H; at.o_ts = H; at.o_hs = 128;
+    at.B = B; at.H = f.heads; at.Tq = T; at.Tk = keep + T; at.causal = 1; at.k_perm = c->ld.k_perm; at.key_mask = c->key_mask; at.km_bs = f.max_len;
+    at.flash_min = c->flash_min;
+    return at;
+}
+
+GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
+    const rdx_config& f = c->cfg;
+    const int H = f.hidden;
+    GemmArgs a;
+    switch (u) {
+    case UNIT_QKV: a = gargs(c->dx, H, L->wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); a.N = L->wqkv.Npad; a.norm_w = L->attn_norm; break;
+    case UNIT_O: a = gargs(c->datt, H, L->wo, nullptr, c->dx, H, B); a.resid = c->dx; a.ldr = H; break;
+    case UNIT_GATE_UP: a = gargs(c->dx, H, L->wgu, nullptr, c->dgu, f.inter, B); a.norm_w = L->mlp_norm; break;
+    case UNIT_DOWN: a = gargs(c->dgu, f.inter, L->wdown, nullptr, c->dx, H, B); a.resid = c->dx; a.ldr = H; break;
+    default:
+        a = gargs(c->dx, H, c->lm_head, nullptr, nullptr, f.vocab, B);
+        a.N = c->lm_head.Npad; a.n_valid = f.vocab; a.norm_w = c->final_norm; a.part_val = c->part_val; a.part_idx = c->part_idx;
+    }
+    if (a.norm_w) a.eps = f.rms_eps;
+    return a;
+}
+
+GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
+    GemmArgs a = unit_args(c, L, u, B);
+    if (u == UNIT_GATE_UP) a.out_packed = 1;
+    if (u == UNIT_O || u == UNIT_DOWN) a.xpacked = 1;
+    return a;
+}
+
+GemmArgs blk_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
+    GemmArgs a = unit_args(c, L, u, B);
+    a.xpacked = 3; a.mtiles = (B + 15) / 16; a.out_packed = u == UNIT_GATE_UP ? 3 : 0;
+    return a;
+}
+
+GemmArgs blk8_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
+    GemmArgs a = unit_args(c, L, u, B);
+    a.xpacked = (u == UNIT_O || u == UNIT_DOWN) ? 2 : 4; a.mtiles = (B + 15) / 16; a.out_packed = u == UNIT_GATE_UP ? 2 : 0;     // out 2: the 64-deep order, one 32-row block per 32 rows
+    a.xscale = c->dxs; a.xgroups = 1;
+    return a;
+}
+
+GemmArgs ksplit_args(GemmArgs a) {
+    a.xpacked = (a.W8 && a.wscale) ? 2 : 1;
+    return a;
+}
+
+GemmArgs prenormed(rdx_ctx* c, GemmArgs a) {
+    a.X = c->dxn; a.ldx = a.K; a.norm_w = nullptr;
+    return a;
+}
+
+GemmArgs norm_in_front(rdx_ctx* c, GemmArgs a) {
+    const int dt = c->cfg.dtype;
+    void* x = const_cast<void*>(a.X);
+    // a K-split projection before this unit left its residual epilogue to this RMSNorm: x += T(sum of slabs)
+    const int pend = (x == c->dx) ? c->pend_groups : 0;
+    if (pend) c->pend_groups = 0;
+    const float* slab = pend ? c->kslab : nullptr;
+    if (a.xpacked == 4 && a.mtiles) launch_rmsnorm_blk_fp8(dt, x, a.norm_w, c->dxn, c->dxs, a.M, a.mtiles, a.eps, slab, pend, c->stream);
+    else if (a.xpacked == 4) launch_rmsnorm_packed32_fp8(dt, x, a.norm_w, c->dxn, c->dxs, a.M, a.K, a.eps, slab, pend, c->stream);
+    else if (a.xpacked == 3 && pend) launch_rmsnorm_packed_slab(dt, x, a.norm_w, c->dxn, a.M, a.mtiles, a.eps, slab, pend, c->stream);
+    else if (a.xpacked == 3) launch_rmsnorm_packed(dt, x, a.norm_w, c->dxn, a.M, a.mtiles, a.K, a.eps, c->stream);
+    else if (a.xpacked || pend) launch_rmsnorm_packed32(dt, x, a.norm_w, c->dxn, a.M, a.K, a.eps, a.xpacked, slab, pend, c->stream);
+    else launch_rmsnorm(dt, x, a.norm_w, c->dxn, a.M, a.K, a.eps, c->stream);
+    return prenormed(c, a);
+}
+
+DecFamily decode_family(rdx_ctx* c, int B) {
+    if (B > 32) return !blk64_ok(c, B) ? DEC_UNSUPPORTED : blk64_fp8(c) ? DEC_BLK8 : DEC_BLK;
+    // batch <= 2: down(l) -> QKV(l+1) chained inside one launch by the fence-free hand-off, attention + o_proj in the fused launch
+    if (c->chain_mlp && c->fuse_attn_oproj && chain_supported(c->ld, c->cfg.inter, B) && attn_oproj16_supported(c->ld, c->cfg.hidden, c->cfg.hidden, B))
+        return DEC_CHAINED;
+    return xs16_ok(c, B) ? DEC_XS16 : DEC_GENERIC;
+}
+
+// Skinny GEMM with an optional fused RMSNorm: fused when the activations fit the GEMV's LDS stage; otherwise the RMSNorm runs as its own launch
+// in front of it (norm_in_front). Returns the arguments of the GEMM proper (activations = c->dxn)
 GemmArgs skinny_prenorm(rdx_ctx* c, GemmArgs a, int epi) {
     // (batch 3-4 rows would fit the GEMV's LDS stage with the norm fused, but the activation-stationary kernel behind a
     // stand-alone RMSNorm is faster there too: gate/up 41.7 -> 31 + 5 us at batch 4)
-    bool standalone = a.norm_w && !skinny_fits_lds(a.M, a.K);
-    if (a.norm_w && !standalone && a.M >= xs_min_rows() && c->kslab) {
-        GemmArgs t = a;
-        t.X = c->dxn; t.ldx = a.K; t.norm_w = nullptr;
-        standalone = xstat32_supported(t, epi);
+    if (!a.norm_w) return a;
+    const bool xs = xstat32_supported(prenormed(c, a), epi);
+    if (skinny_fits_lds(a.M, a.K) && !(a.M >= xs_min_rows() && c->kslab && xs)) return a;
+    if (xs && a.W8 && a.wscale) {
+        // fp8 weights: the normalised rows are quantised to e4m3 (one scale per row) in the consumer's 64-deep fragment order: fp8 x fp8 MFMA
+        a.xpacked = 4; a.xscale = c->dxs; a.xgroups = 1;
+    } else if (xs) {
+        a.xpacked = 1;       // the normalised rows go straight into the consumer's register-fragment order
     }
-    if (standalone) {
-        const void* x = a.X; const void* nw = a.norm_w;
-        a.X = c->dxn; a.ldx = a.K; a.norm_w = nullptr;
-        // a K-split projection before this one left its residual epilogue to this RMSNorm (xsplit32_k): x += T(sum of slabs)
-        const int pend = (x == c->dx) ? c->pend_groups : 0;
-        if (pend) c->pend_groups = 0;
-        if (xstat32_supported(a, epi) && a.W8 && a.wscale) {
-            // fp8 weights: the normalised rows are quantised to e4m3 (one scale per row) in the consumer's 64-deep fragment order: fp8 x fp8 MFMA
-            a.xpacked = 4; a.xscale = c->dxs; a.xgroups = 1;
-            launch_rmsnorm_packed32_fp8(c->cfg.dtype, const_cast<void*>(x), nw, c->dxn, c->dxs, a.M, a.K, a.eps, pend ? c->kslab : nullptr, pend, c->stream);
-        } else if (xstat32_supported(a, epi)) {       // the normalised rows go straight into the consumer's register-fragment order
-            a.xpacked = 1;
-            launch_rmsnorm_packed32(c->cfg.dtype, const_cast<void*>(x), nw, c->dxn, a.M, a.K, a.eps, a.xpacked, pend ? c->kslab : nullptr, pend, c->stream);
-        } else if (pend) {
-            launch_rmsnorm_packed32(c->cfg.dtype, const_cast<void*>(x), nw, c->dxn, a.M, a.K, a.eps, 0, c->kslab, pend, c->stream);
-        } else {
-            launch_rmsnorm(c->cfg.dtype, x, nw, c->dxn, a.M, a.K, a.eps, c->stream);
-        }
-    }
-    return a;
+    return norm_in_front(c, a);
 }
 
 void skinny(rdx_ctx* c, GemmArgs a, int epi) {
@@ -73,87 +150,51 @@ int take_unsupported(rdx_ctx* c) {
 // K-split over 4 workgroups per tile (xsplit32_k), its residual epilogue deferred to the next RMSNorm
 bool down_split_ok(rdx_ctx* c, const LlamaLayer& L, int B) {
     if (B < xs_min_rows() || !c->kslab) return false;
-    GemmArgs gu = gargs(c->dxn, c->cfg.hidden, L.wgu, nullptr, c->dgu, c->cfg.inter, B);
-    if (!xstat32_supported(gu, EPI_SILU_MUL)) return false;
-    GemmArgs dn = gargs(c->dgu, c->cfg.inter, L.wdown, nullptr, c->dx, c->cfg.hidden, B);
-    dn.xpacked = (dn.W8 && dn.wscale) ? 2 : 1;       // fp8 weights: the 64-deep fragment order
-    return xsplit32_groups(dn) > 0;
+    if (!xstat32_supported(prenormed(c, unit_args(c, &L, UNIT_GATE_UP, B)), EPI_SILU_MUL)) return false;
+    return xsplit32_groups(ksplit_args(unit_args(c, &L, UNIT_DOWN, B))) > 0;
 }
 
 // A K-split projection (o_proj, down_proj at batch 3-32): its fp32 slabs stay pending for the stand-alone RMSNorm of the
-// projection that follows (skinny_prenorm), which adds them, rounds and applies the residual.
-void launch_ksplit(rdx_ctx* c, const GemmArgs& a_in) {
-    const GemmArgs& a = a_in;        // (fp8 weights: every K-group workgroup quantises its range of the activations to e4m3 -- fp8 x fp8)
+// projection that follows (norm_in_front), which adds them, rounds and applies the residual.
+// (fp8 weights: W8A16 since round 6 -- the e4m3 weight fragments are expanded in registers and multiply the producer's model-dtype activation
+// fragments; RDX_FP8_SPLIT_A8=1 is the earlier form whose workgroups quantise their K range of the activations: xstat32.hip fp8_split_a8)
+void launch_ksplit(rdx_ctx* c, const GemmArgs& a) {
     launch_xsplit32(c->cfg.dtype, a, c->kslab, c->stream);
     c->pend_groups = xsplit32_groups(a);
 }
 
 void launch_down(rdx_ctx* c, const LlamaLayer& L, int B, bool split) {
-    const rdx_config& f = c->cfg;
-    GemmArgs a = gargs(c->dgu, f.inter, L.wdown, nullptr, c->dx, f.hidden, B);
-    a.resid = c->dx; a.ldr = f.hidden;
-    if (split) {
-        a.xpacked = (a.W8 && a.wscale) ? 2 : 1;
-        launch_ksplit(c, a);
-    } else {
-        skinny(c, a, EPI_RESID);
-    }
+    const GemmArgs a = unit_args(c, &L, UNIT_DOWN, B);
+    if (split) launch_ksplit(c, ksplit_args(a));
+    else skinny(c, a, EPI_RESID);
 }
 
 // 33-128 rows (round 5; VERDICT r4 "missing" 3): the decoder's rows as NB = ceil(rows / 32) blocks of 32. Every K = 4096 projection runs activation-stationary per block,
 // the two block workgroups of a tile walker on one XCD (xstat32_k<.., BLK>: a weight fragment comes from HBM once, from that L2 once more); o_proj is
-// un-split (final rows: no slabs), down_proj (K = 11008) takes the prompt's weight-stationary kernel; the RMSNorms write the fragment-packed
-// [k / 32][row tiles][lane][8] the consumers read. Model-dtype weights only.
+// un-split (final rows: no slabs), down_proj (K = 11008) K-split into fp32 slabs (or, RDX_BLK_DOWN=0, on the prompt's weight-stationary kernel); the RMSNorms write the
+// fragment-packed [k / 32][row tiles][lane][8] the consumers read. fp8 weights (blk64_fp8) take the 32-row fp8 kernels per row block instead.
 bool blk64_fp8(rdx_ctx* c) { return !c->ll.empty() && fp8_weights(c->ll[0].wqkv); }
 
 bool blk64_ok(rdx_ctx* c, int B) {
-    if (B <= 32 || B > RDX_MAX_ROWS || c->ll.empty()) return false;
-    const rdx_config& f = c->cfg;
-    const LlamaLayer& L = c->ll[0];
-    const int mtl = (B + 15) / 16;
+    if (B <= 32 || B > RDX_MAX_ROWS || c->ll.empty() || c->cfg.hidden != 4096) return false;
+    const LlamaLayer* L = &c->ll[0];
     if (blk64_fp8(c)) {
-        // fp8 x fp8 (round 5): the 32-row fp8 kernels per row block -- e4m3 blocks + xscale for QKV / gate-up / lm_head, o_proj and down_proj K-split with
-        // the workgroup's own quantisation of its K range (xsplit32_k<.., A8, BLK>), slabs combined by the next RMSNorm
-        auto p8 = [&](GemmArgs a, int xp, int outp) { a.xpacked = xp; a.mtiles = mtl; a.out_packed = outp; a.xscale = c->dxs; a.xgroups = 1; return a; };
-        GemmArgs q = gargs(c->dxn, f.hidden, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); q.N = L.wqkv.Npad;
-        GemmArgs o = gargs(c->datt, f.hidden, L.wo, nullptr, c->dx, f.hidden, B);
-        GemmArgs gu = gargs(c->dxn, f.hidden, L.wgu, nullptr, c->dgu, f.inter, B);
-        GemmArgs d = gargs(c->dgu, f.inter, L.wdown, nullptr, c->dx, f.hidden, B);
-        GemmArgs lm = gargs(c->dxn, f.hidden, c->lm_head, nullptr, nullptr, f.vocab, B); lm.N = c->lm_head.Npad;
-        return f.hidden == 4096 && c->kslab && c->dxs && xstat_blk8_supported(p8(q, 4, 0), EPI_NONE) && xsplit_blk8_groups(p8(o, 2, 0)) == 2 &&
-               xstat_blk8_supported(p8(gu, 4, 2), EPI_SILU_MUL) && xsplit_blk8_groups(p8(d, 2, 0)) == 4 && xstat_blk8_supported(p8(lm, 4, 0), EPI_LOGITS);
+        // fp8 weights (round 5): the 32-row fp8 kernels per row block -- e4m3 blocks + xscale for QKV / gate-up / lm_head (fp8 x fp8); o_proj and down_proj K-split
+        // over model-dtype activation blocks (xsplit32_k<.., BLK>: W8A16 since round 6, xstat32.hip fp8_split_a8), slabs combined by the next RMSNorm
+        return c->kslab && c->dxs && xstat_blk8_supported(prenormed(c, blk8_unit(c, L, UNIT_QKV, B)), EPI_NONE) && xsplit_blk8_groups(blk8_unit(c, L, UNIT_O, B)) == 2 &&
+               xstat_blk8_supported(prenormed(c, blk8_unit(c, L, UNIT_GATE_UP, B)), EPI_SILU_MUL) && xsplit_blk8_groups(blk8_unit(c, L, UNIT_DOWN, B)) == 4 &&
+               xstat_blk8_supported(prenormed(c, blk8_unit(c, L, UNIT_LM_HEAD, B)), EPI_LOGITS);
     }
-    auto pk = [&](GemmArgs a, int outp) { a.xpacked = 3; a.mtiles = mtl; a.out_packed = outp; return a; };
-    GemmArgs q = gargs(c->dxn, f.hidden, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); q.N = L.wqkv.Npad;
-    GemmArgs o = gargs(c->datt, f.hidden, L.wo, nullptr, c->dx, f.hidden, B); o.resid = c->dx; o.ldr = f.hidden;
-    GemmArgs gu = gargs(c->dxn, f.hidden, L.wgu, nullptr, c->dgu, f.inter, B);
-    GemmArgs d = gargs(c->dgu, f.inter, L.wdown, nullptr, c->dx, f.hidden, B); d.resid = c->dx; d.ldr = f.hidden;
-    GemmArgs lm = gargs(c->dxn, f.hidden, c->lm_head, nullptr, nullptr, f.vocab, B); lm.N = c->lm_head.Npad;
-    return f.hidden == 4096 && xstat_blk_supported(pk(q, 0), EPI_NONE) && xstat_blk_supported(pk(o, 0), EPI_RESID) &&
-           xstat_blk_supported(pk(gu, 3), EPI_SILU_MUL) && wstat_supported(pk(d, 0), EPI_RESID) && xstat_blk_supported(pk(lm, 0), EPI_LOGITS);
+    return xstat_blk_supported(prenormed(c, blk_unit(c, L, UNIT_QKV, B)), EPI_NONE) && xstat_blk_supported(blk_unit(c, L, UNIT_O, B), EPI_RESID) &&
+           xstat_blk_supported(prenormed(c, blk_unit(c, L, UNIT_GATE_UP, B)), EPI_SILU_MUL) && wstat_supported(blk_unit(c, L, UNIT_DOWN, B), EPI_RESID) &&
+           xstat_blk_supported(prenormed(c, blk_unit(c, L, UNIT_LM_HEAD, B)), EPI_LOGITS);
 }
 
 bool xs16_ok(rdx_ctx* c, int B) {
     if (!c->xs16 || !xs16_rows_ok(B) || c->ll.empty()) return false;
-    const rdx_config& f = c->cfg;
-    const LlamaLayer& L = c->ll[0];
-    GemmArgs q = gargs(c->dx, f.hidden, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); q.N = L.wqkv.Npad; q.norm_w = L.attn_norm;
-    GemmArgs gu = gargs(c->dx, f.hidden, L.wgu, nullptr, c->dgu, f.inter, B); gu.norm_w = L.mlp_norm;
-    GemmArgs lm = gargs(c->dx, f.hidden, c->lm_head, nullptr, nullptr, f.vocab, B); lm.N = c->lm_head.Npad; lm.norm_w = c->final_norm;
-    GemmArgs o = gargs(c->datt, f.hidden, L.wo, nullptr, c->dx, f.hidden, B); o.resid = c->dx; o.ldr = f.hidden; o.xpacked = 1;
-    GemmArgs d = gargs(c->dgu, f.inter, L.wdown, nullptr, c->dx, f.hidden, B); d.resid = c->dx; d.ldr = f.hidden; d.xpacked = 1;
-    return xstat16_supported(q, EPI_NONE) && xstat16_supported(gu, EPI_SILU_MUL) && xstat16_supported(lm, EPI_LOGITS) && xrow16_supported(o) &&
-           xrow16_supported(d);
-}
-
-void xs16_proj(rdx_ctx* c, GemmArgs a, int epi) {
-    launch_xstat16(c->cfg.dtype, a, epi, c->stream);
-}
-
-void xs16_row(rdx_ctx* c, const void* xpacked, const GemmW& W, int B) {
-    GemmArgs a = gargs(xpacked, W.K, W, nullptr, c->dx, c->cfg.hidden, B);
-    a.resid = c->dx; a.ldr = c->cfg.hidden; a.xpacked = 1;
-    launch_xrow16(c->cfg.dtype, a, c->stream);
+    const LlamaLayer* L = &c->ll[0];
+    return xstat16_supported(xs16_unit(c, L, UNIT_QKV, B), EPI_NONE) && xstat16_supported(xs16_unit(c, L, UNIT_GATE_UP, B), EPI_SILU_MUL) &&
+           xstat16_supported(xs16_unit(c, L, UNIT_LM_HEAD, B), EPI_LOGITS) && xrow16_supported(xs16_unit(c, L, UNIT_O, B)) && xrow16_supported(xs16_unit(c, L, UNIT_DOWN, B));
 }
 
 void run_gemm(rdx_ctx* c, GemmArgs a, int epi) {

@@ -25,14 +25,17 @@ extern "C" int rdx_time(rdx_ctx* c, int what, int iters, float* ms_host) {
     if (!ms_host || iters <= 0) return fail(c, -1, "rdx_time: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     const rdx_config& f = c->cfg;
-    const int dt = f.dtype, H = f.hidden, B = c->cur_B;
+    const int dt = f.dtype, B = c->cur_B;
     const bool same_layer = what >= 10;   // what = 10 + k: unit k on layer 0 only (weights stay cache resident)
     if (same_layer) what -= 10;
-    if (B > 32 && what >= 1 && what <= 5) return fail(c, -1, "rdx_time: the per-projection units time the <= 32-row kernel families; at %d rows use unit 0 (step) or 6 (attention)", B);
+    const DecFamily fam = decode_family(c, B);
+    const bool proj = what >= 1 && what <= 5;         // the per-projection units: 1 gate/up, 2 QKV, 3 o_proj, 4 down_proj, 5 lm_head (6: decode attention)
+    if (proj && (fam == DEC_BLK || fam == DEC_BLK8 || fam == DEC_UNSUPPORTED)) return fail(c, -1, "rdx_time: the per-projection units time the <= 32-row kernel families; at %d rows use unit 0 (step) or 6 (attention)", B);
     hipEvent_t e0, e1;
     HIPCHK(c, hipEventCreate(&e0));
     HIPCHK(c, hipEventCreate(&e1));
     int launches = 0;
+    bool x16 = false;
     if (what == 7) {
         // the chained down(l) -> QKV(l+1) launch (decode_chain_k, batch <= 2), IN SITU: `iters` eager decode steps with an event pair
         // around each of its launches (the hand-off counters are only valid inside a real step, so it cannot be looped alone)
@@ -80,78 +83,41 @@ extern "C" int rdx_time(rdx_ctx* c, int what, int iters, float* ms_host) {
         launches = iters;
         c->cur_steps = std::max(c->cur_steps, c->cur_max_new);
     } else {
-        // projections whose RMSNorm is a launch of its own (rows beyond the GEMV's LDS stage: batch > 4): normalise once,
-        // outside the timed region, and time the GEMM launches alone
-        int xpk = -1;
-        GemmArgs pn;
-        auto pre = [&](GemmArgs a, int epi) {
-            if (xpk < 0) { pn = skinny_prenorm(c, a, epi); xpk = pn.norm_w ? 0 : (pn.X == c->dxn ? 1 + pn.xpacked : 0); }
-            if (xpk > 0) { a.X = c->dxn; a.ldx = a.K; a.norm_w = nullptr; a.xpacked = xpk - 1; a.xscale = pn.xscale; a.xgroups = pn.xgroups; }
-            return a;
-        };
+        if (!proj && what != 6) { hipEventDestroy(e0); hipEventDestroy(e1); return fail(c, -1, "rdx_time: unknown unit %d", what); }
+        // Every unit's arguments come from the builders the step launches from (api_dispatch.hip). What the timers change on purpose:
+        //  - o_proj / down_proj write to dqkv, so that repeated launches do not grow dx, and (outside xs16, whose xrow16_k needs one) add no residual;
+        //  - a projection whose RMSNorm is a launch of its own (skinny_prenorm: rows beyond the GEMV's LDS stage, or the 32-row kernels from 3 rows) is
+        //    normalised once, outside the timed region, and the GEMM launches are timed alone.
+        const DecUnit u = what == 1 ? UNIT_GATE_UP : what == 2 ? UNIT_QKV : what == 3 ? UNIT_O : what == 4 ? UNIT_DOWN : UNIT_LM_HEAD;
+        const int epi = what == 1 ? EPI_SILU_MUL : what == 5 ? EPI_LOGITS : EPI_NONE;
+        const bool resid_unit = u == UNIT_O || u == UNIT_DOWN;
         // batch 3-16 decodes on xs16.hip (norm-prologue xstat16_k, un-split xrow16_k): time THOSE kernels, not the 32-row family the step never launches there
-        const bool x16 = what >= 1 && what <= 5 && xs16_ok(c, B);
-        if (x16) {
-            HIPCHK(c, hipEventRecord(e0, c->stream));
-            for (int i = 0; i < iters; ++i) {
-                for (int l = 0; l < (what == 5 ? 1 : f.layers); ++l) {
-                    const LlamaLayer& L = c->ll[same_layer ? 0 : l];
-                    if (what == 1) { GemmArgs a = gargs(c->dx, H, L.wgu, nullptr, c->dgu, f.inter, B); a.norm_w = L.mlp_norm; a.eps = f.rms_eps; a.out_packed = 1; xs16_proj(c, a, EPI_SILU_MUL); }
-                    else if (what == 2) { GemmArgs a = gargs(c->dx, H, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); a.N = L.wqkv.Npad; a.norm_w = L.attn_norm; a.eps = f.rms_eps; xs16_proj(c, a, EPI_NONE); }
-                    else if (what == 5) { GemmArgs a = gargs(c->dx, H, c->lm_head, nullptr, nullptr, f.vocab, B); a.N = c->lm_head.Npad; a.n_valid = f.vocab; a.norm_w = c->final_norm; a.eps = f.rms_eps;
-                                          a.part_val = c->part_val; a.part_idx = c->part_idx; xs16_proj(c, a, EPI_LOGITS); }
-                    else {      // 3: o_proj, 4: down_proj -- xrow16_k with the residual epilogue, written to a scratch buffer so that repeated launches do not grow dx
-                        const GemmW& W = what == 3 ? L.wo : L.wdown;
-                        GemmArgs a = gargs(what == 3 ? c->datt : c->dgu, W.K, W, nullptr, c->dqkv, H, B); a.resid = c->dx; a.ldr = H; a.xpacked = 1;
-                        launch_xrow16(f.dtype, a, c->stream);
-                    }
-                    ++launches;
-                }
-            }
-            HIPCHK(c, hipEventRecord(e1, c->stream));
-            HIPCHK(c, hipEventSynchronize(e1));
-            float ms16 = 0.f;
-            HIPCHK(c, hipEventElapsedTime(&ms16, e0, e1));
-            hipEventDestroy(e0); hipEventDestroy(e1);
-            *ms_host = ms16 / (float)launches;
-            return take_unsupported(c);
-        }
-        if (what == 1) { GemmArgs a = gargs(c->dx, H, c->ll[0].wgu, nullptr, c->dgu, f.inter, B); a.norm_w = c->ll[0].mlp_norm; a.eps = f.rms_eps; pre(a, EPI_SILU_MUL); }
-        if (what == 2) { GemmArgs a = gargs(c->dx, H, c->ll[0].wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); a.N = c->ll[0].wqkv.Npad; a.norm_w = c->ll[0].attn_norm; a.eps = f.rms_eps; pre(a, EPI_NONE); }
-        if (what == 5) { GemmArgs a = gargs(c->dx, H, c->lm_head, nullptr, nullptr, f.vocab, B); a.N = c->lm_head.Npad; a.n_valid = f.vocab; a.norm_w = c->final_norm; a.eps = f.rms_eps; pre(a, EPI_LOGITS); }
+        x16 = proj && fam == DEC_XS16;
+        GemmArgs pn;
+        bool hoisted = false;
+        if (proj && !x16 && !resid_unit) { pn = skinny_prenorm(c, unit_args(c, &c->ll[0], u, B), epi); hoisted = !pn.norm_w; }
         HIPCHK(c, hipEventRecord(e0, c->stream));
         for (int i = 0; i < iters; ++i) {
-            if (what == 5) {
-                GemmArgs a = gargs(c->dx, H, c->lm_head, nullptr, nullptr, f.vocab, B);
-                a.N = c->lm_head.Npad; a.n_valid = f.vocab; a.norm_w = c->final_norm; a.eps = f.rms_eps;
-                a.part_val = c->part_val; a.part_idx = c->part_idx;
-                launch_skinny_gemm(f.dtype, pre(a, EPI_LOGITS), EPI_LOGITS, c->stream);
-                ++launches;
-                continue;
-            }
-            for (int l = 0; l < f.layers; ++l) {
-                const LlamaLayer& L = c->ll[same_layer ? 0 : l];
-                if (what == 1) { GemmArgs a = gargs(c->dx, H, L.wgu, nullptr, c->dgu, f.inter, B); a.norm_w = L.mlp_norm; a.eps = f.rms_eps; launch_skinny_gemm(f.dtype, pre(a, EPI_SILU_MUL), EPI_SILU_MUL, c->stream); }
-                else if (what == 2) { GemmArgs a = gargs(c->dx, H, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); a.N = L.wqkv.Npad; a.norm_w = L.attn_norm; a.eps = f.rms_eps; launch_skinny_gemm(f.dtype, pre(a, EPI_NONE), EPI_NONE, c->stream); }
-                else if (what == 3) {
-                    GemmArgs a = gargs(c->datt, H, L.wo, nullptr, c->dqkv, H, B);
-                    GemmArgs ap = a; ap.xpacked = (a.W8 && a.wscale) ? 2 : 1;
-                    if (B >= xs_min_rows() && c->kslab && xsplit32_groups(ap)) launch_xsplit32(f.dtype, ap, c->kslab, c->stream);
+            for (int l = 0; l < (what == 5 ? 1 : f.layers); ++l, ++launches) {
+                const int li = same_layer ? 0 : l;
+                const LlamaLayer* L = &c->ll[li];
+                if (what == 6) {        // decode attention at the current slot (re-appends the same KV row: idempotent)
+                    launch_decode_attention(dt, dec_attn_args(c, li), B, c->stream);
+                } else if (x16) {
+                    GemmArgs a = xs16_unit(c, L, u, B);
+                    if (resid_unit) { a.out = c->dqkv; launch_xrow16(dt, a, c->stream); }
+                    else launch_xstat16(dt, a, epi, c->stream);
+                } else if (resid_unit) {
+                    GemmArgs a = unit_args(c, L, u, B);
+                    a.out = c->dqkv; a.resid = nullptr; a.ldr = 0;
+                    const bool split = u == UNIT_O ? B >= xs_min_rows() && c->kslab && xsplit32_groups(ksplit_args(a)) : down_split_ok(c, *L, B);
+                    if (split) launch_xsplit32(dt, ksplit_args(a), c->kslab, c->stream);
                     else skinny(c, a, EPI_NONE);
+                } else {
+                    GemmArgs a = unit_args(c, L, u, B);
+                    if (hoisted) { a = prenormed(c, a); a.xpacked = pn.xpacked; a.xscale = pn.xscale; a.xgroups = pn.xgroups; }
+                    launch_skinny_gemm(dt, a, epi, c->stream);
                 }
-                else if (what == 4) {
-                    if (down_split_ok(c, L, B)) { GemmArgs a = gargs(c->dgu, f.inter, L.wdown, nullptr, c->dqkv, H, B); a.xpacked = (a.W8 && a.wscale) ? 2 : 1; launch_xsplit32(f.dtype, a, c->kslab, c->stream); }
-                    else { GemmArgs a = gargs(c->dgu, f.inter, L.wdown, nullptr, c->dqkv, H, B); skinny(c, a, EPI_NONE); }
-                }
-                else if (what == 6) {   // decode attention at the current slot (re-appends the same KV row: idempotent)
-                    DecAttnArgs at;
-                    at.d = c->ld; at.qkv = c->dqkv; at.lbq = L.lora_bq; at.lbv = L.lora_bv; at.cos_t = c->rope_cos; at.sin_t = c->rope_sin;
-                    at.pos = c->d_pos; at.slot_b = c->d_slot; at.key_mask = c->key_mask; at.cur_rope = c->d_cur_rope;
-                    at.kcache = kv_ptr(c, c->kcache, same_layer ? 0 : l); at.vcache = kv_ptr(c, c->vcache, same_layer ? 0 : l); at.out = c->datt;
-                    launch_decode_attention(dt, at, B, c->stream);
-                }
-                else return fail(c, -1, "rdx_time: unknown unit %d", what);
-                ++launches;
             }
         }
         HIPCHK(c, hipEventRecord(e1, c->stream));
@@ -161,5 +127,5 @@ extern "C" int rdx_time(rdx_ctx* c, int what, int iters, float* ms_host) {
     HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
     hipEventDestroy(e0); hipEventDestroy(e1);
     *ms_host = ms / (float)launches;
-    return 0;
+    return x16 ? take_unsupported(c) : 0;
 }

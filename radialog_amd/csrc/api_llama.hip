@@ -25,34 +25,22 @@ static int ensure_prefill_ws(rdx_ctx* c, size_t rows) {
     return 0;
 }
 
+static const char* const k_need_blk = "more than 32 decoder rows need hidden 4096 / inter 11008 (the row-block family)";
+
 static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, const int* out_step, long step_stride,
                                int advance) {
     const rdx_config& f = c->cfg;
-    GemmArgs a = gargs(x, f.hidden, c->lm_head, nullptr, logits, f.vocab, B);
-    a.N = c->lm_head.Npad; a.n_valid = f.vocab;
-    a.norm_w = c->final_norm; a.eps = f.rms_eps;
-    a.part_val = c->part_val; a.part_idx = c->part_idx;
-    a.out_step = out_step; a.out_step_stride = step_stride;
-    if (B > 32) {
-        // 33-128 rows: final RMSNorm into the fragment-packed row tiles, lm_head in two row blocks (xstat32_k<EPI_LOGITS, BLK>)
-        if (!blk64_ok(c, B)) { c->unsupported = "more than 32 decoder rows need hidden 4096 / inter 11008 (the row-block family)"; return; }
-        const int mtl = (B + 15) / 16;
-        const int pend = (x == c->dx) ? c->pend_groups : 0;       // the last layer's K-split down_proj left its slabs (and the residual add) to this norm
-        if (blk64_fp8(c)) {
-            if (pend) c->pend_groups = 0;
-            launch_rmsnorm_blk_fp8(f.dtype, const_cast<void*>(x), c->final_norm, c->dxn, c->dxs, B, mtl, f.rms_eps, pend ? c->kslab : nullptr, pend, c->stream);
-            a.X = c->dxn; a.norm_w = nullptr; a.xpacked = 4; a.mtiles = mtl; a.xscale = c->dxs; a.xgroups = 1;
-            launch_xstat_blk8(f.dtype, a, EPI_LOGITS, c->stream);
-        }
-        else if (pend) { c->pend_groups = 0; launch_rmsnorm_packed_slab(f.dtype, c->dx, c->final_norm, c->dxn, B, mtl, f.rms_eps, c->kslab, pend, c->stream); }
-        else launch_rmsnorm_packed(f.dtype, x, c->final_norm, c->dxn, B, mtl, f.hidden, f.rms_eps, c->stream);
-        if (!blk64_fp8(c)) {
-            a.X = c->dxn; a.norm_w = nullptr; a.xpacked = 3; a.mtiles = mtl;
-            launch_xstat_blk(f.dtype, a, EPI_LOGITS, c->stream);
-        }
+    auto lm = [&](GemmArgs a) { a.X = x; a.out = logits; a.out_step = out_step; a.out_step_stride = step_stride; return a; };
+    switch (decode_family(c, B)) {
+    case DEC_UNSUPPORTED: c->unsupported = k_need_blk; return;
+    // 33-128 rows: final RMSNorm into the fragment-packed row tiles (after the last layer it also folds in the K-split down_proj's slabs), lm_head in row blocks
+    case DEC_BLK: launch_xstat_blk(f.dtype, norm_in_front(c, lm(blk_unit(c, nullptr, UNIT_LM_HEAD, B))), EPI_LOGITS, c->stream); break;
+    case DEC_BLK8: launch_xstat_blk8(f.dtype, norm_in_front(c, lm(blk8_unit(c, nullptr, UNIT_LM_HEAD, B))), EPI_LOGITS, c->stream); break;
+    case DEC_XS16:       // batch 3-16 decode: the final RMSNorm is the kernel's prologue (the prompt's last rows, in datt, go the generic way)
+        if (x == c->dx) { launch_xstat16(f.dtype, lm(xs16_unit(c, nullptr, UNIT_LM_HEAD, B)), EPI_LOGITS, c->stream); break; }
+        [[fallthrough]];
+    default: skinny(c, lm(unit_args(c, nullptr, UNIT_LM_HEAD, B)), EPI_LOGITS);
     }
-    else if (x == c->dx && xs16_ok(c, B)) xs16_proj(c, a, EPI_LOGITS);        // batch 3-16 decode: the final RMSNorm is the kernel's prologue
-    else skinny(c, a, EPI_LOGITS);
     launch_greedy_step(f.dtype, c->part_val, c->part_idx, c->n_vtiles, B, c->cur_eos, c->cur_pad, c->cur_max_new,
                        c->cur_tokens, c->d_unf, advance ? c->d_pos : nullptr, advance ? c->d_slot : nullptr, c->d_step,
                        c->embed, f.vocab, c->dx, f.hidden, c->d_pos, c->rope_cos, c->rope_sin, c->d_cur_rope,
@@ -122,14 +110,7 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
             launch_rmsnorm_fp8(dt, c->px, L.attn_norm, c->pxq, c->pxs, (int)M, H, f.rms_eps, s);
             g8(L.wqkv, H, 1, c->pqkv, c->ld.qkv_ld, nullptr, EPI_NONE);
             launch_rope_kv_prefill(dt, c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq, kc, vc, B, T, keep, s);
-            AttnArgs at;
-            memset(&at, 0, sizeof(at));
-            at.Q = c->pq; at.q_bs = (long)T * H; at.q_ts = H; at.q_hs = 128;
-            at.K = kc; at.V = vc; at.k_bs = at.v_bs = (long)f.heads * f.max_len * 128; at.k_ts = at.v_ts = 128; at.k_hs = at.v_hs = (long)f.max_len * 128;
-            at.O = c->patt; at.o_bs = (long)T * H; at.o_ts = H; at.o_hs = 128;
-            at.B = B; at.H = f.heads; at.Tq = T; at.Tk = keep + T; at.causal = 1; at.k_perm = c->ld.k_perm; at.key_mask = c->key_mask; at.km_bs = f.max_len;
-            at.flash_min = c->flash_min;
-            launch_attention(dt, 128, at, s);
+            launch_attention(dt, 128, prefill_attn_args(c, B, T, keep, l), s);
             launch_quant_rows(dt, c->patt, H, c->pxq, c->pxs, (int)M, H, 2, s);
             g8(L.wo, H, 2, c->px, H, c->px, EPI_RESID);
             launch_rmsnorm_fp8(dt, c->px, L.mlp_norm, c->pxq, c->pxs, (int)M, H, f.rms_eps, s);
@@ -175,14 +156,8 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
         // new K/V rows land behind the kept slots
         launch_rope_kv_prefill(dt, c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq,
                                kc, vc, B, T, keep, s);
-        AttnArgs at;
-        memset(&at, 0, sizeof(at));
-        at.Q = c->pq; at.q_bs = (long)T * H; at.q_ts = H; at.q_hs = 128;
-        at.K = kc; at.V = vc; at.k_bs = at.v_bs = (long)f.heads * f.max_len * 128; at.k_ts = at.v_ts = 128; at.k_hs = at.v_hs = (long)f.max_len * 128;
-        at.O = c->patt; at.o_bs = (long)T * H; at.o_ts = H; at.o_hs = 128;
-        at.B = B; at.H = f.heads; at.Tq = T; at.Tk = keep + T; at.causal = 1; at.k_perm = c->ld.k_perm; at.key_mask = c->key_mask; at.km_bs = f.max_len;
+        AttnArgs at = prefill_attn_args(c, B, T, keep, l);
         at.o_packed_mt = ws ? mtl : 0;
-        at.flash_min = c->flash_min;
         launch_attention(dt, 128, at, s);
         { GemmArgs a = gargs(c->patt, H, L.wo, nullptr, c->px, H, (int)M); a.resid = c->px; a.ldr = H; prompt_gemm(a, EPI_RESID, false); }
         if (ws) launch_rmsnorm_packed(dt, c->px, L.mlp_norm, c->pxn, (int)M, mtl, H, f.rms_eps, s);
@@ -215,136 +190,135 @@ extern "C" int rdx_prefill_append(rdx_ctx* c, const int32_t* ids_tail, int B, in
 
 static int decode_loop(rdx_ctx* c, int B, int max_new, int eos_id, void* scores, int* n_steps_host, int use_graph);
 
-bool decode_step_launch(rdx_ctx* c, void* logits, const int* out_step, long step_stride, std::vector<hipEvent_t>* evs) {
-    const rdx_config& f = c->cfg;
-    const int dt = f.dtype, H = f.hidden, B = c->cur_B;
+// ---- the decode step: one layer loop per kernel family (decode_family), every unit's arguments from the builders of api_dispatch.hip ----
+// 33-128 rows, model-dtype weights (api_dispatch.hip blk64_ok): 7 launches per layer
+static void step_blk(rdx_ctx* c, int B) {
+    const int dt = c->cfg.dtype;
     hipStream_t s = c->stream;
-    // the hand-off counter shards of the fused launches are cleared by greedy_step_k at the end of the previous step
-    // (and of the prefill): a memset node at the head of the step graph was observed to race with the first producers
-    // batch <= 2: down(l) -> QKV(l+1) chained inside one launch by the fence-free hand-off, attention + o_proj in the fused launch
-    const bool chain = c->chain_mlp && c->fuse_attn_oproj && chain_supported(c->ld, f.inter, B) &&
-                       attn_oproj16_supported(c->ld, f.hidden, f.hidden, B);
-    ChainArgs ca;
-    if (chain) {
-        memset(&ca, 0, sizeof(ca));
-        ca.layers = c->d_clayers; ca.hidden = H; ca.inter = f.inter; ca.qkv_n = c->ll[0].wqkv.Npad; ca.qkv_ld = c->ld.qkv_ld; ca.B = B; ca.eps = f.rms_eps;
-        ca.dx = c->dx; ca.dqkv = c->dqkv; ca.dgu = c->dgu; ca.ctr = c->d_cctr; ca.err = c->d_err; ca.naps = c->chain_naps;
-        const LlamaLayer& L0 = c->ll[0];        // fp8 weights: the chained roles stream the e4m3 bytes too
-        ca.w8 = (L0.wqkv.w8 && L0.wdown.w8 && f.hidden % 64 == 0 && f.inter % 64 == 0) ? 1 : 0;
+    for (int l = 0; l < c->cfg.layers; ++l) {
+        const LlamaLayer* L = &c->ll[l];
+        launch_xstat_blk(dt, norm_in_front(c, blk_unit(c, L, UNIT_QKV, B)), EPI_NONE, s);
+        DecAttnArgs at = dec_attn_args(c, l);
+        at.out_packed = 1; at.out_mt = (B + 15) / 16;
+        launch_decode_attention(dt, at, B, s);
+        launch_xstat_blk(dt, blk_unit(c, L, UNIT_O, B), EPI_RESID, s);
+        launch_xstat_blk(dt, norm_in_front(c, blk_unit(c, L, UNIT_GATE_UP, B)), EPI_SILU_MUL, s);
+        // down_proj: K-split over 4 workgroups per tile into fp32 slabs, combined (+ residual) by the next RMSNorm (xsplit32_k<.., BLK>: 21 us against
+        // 29.5 us for the prompt's weight-stationary kernel at 64 rows); RDX_BLK_DOWN=0: wstat_k, the A/B leg
+        const GemmArgs d = blk_unit(c, L, UNIT_DOWN, B);
+        if (c->blk_down && xsplit_blk_supported(d)) { launch_xsplit_blk(dt, d, c->kslab, s); c->pend_groups = 4; }
+        else launch_wstat(dt, d, EPI_RESID, s);
     }
-    if (B > 32) {
-        // 33-128 rows: the row-block family (api_dispatch.hip blk64_ok): 7 launches per layer, no K-split slabs
-        if (!blk64_ok(c, B)) { c->unsupported = "more than 32 decoder rows need hidden 4096 / inter 11008 (the row-block family)"; return false; }
-        const int mtl = (B + 15) / 16;
-        if (blk64_fp8(c)) {
-            // fp8 x fp8: the 32-row fp8 kernels per row block (api_dispatch.hip blk64_ok); both residual projections K-split, their slabs + residual left to the next RMSNorm
-            auto p8 = [&](GemmArgs a, int xp, int outp) { a.xpacked = xp; a.mtiles = mtl; a.out_packed = outp; a.xscale = c->dxs; a.xgroups = 1; return a; };
-            for (int l = 0; l < f.layers; ++l) {
-                const LlamaLayer& L = c->ll[l];
-                { const int pend = c->pend_groups; c->pend_groups = 0;
-                  launch_rmsnorm_blk_fp8(dt, c->dx, L.attn_norm, c->dxn, c->dxs, B, mtl, f.rms_eps, pend ? c->kslab : nullptr, pend, s); }
-                { GemmArgs a = gargs(c->dxn, H, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); a.N = L.wqkv.Npad; launch_xstat_blk8(dt, p8(a, 4, 0), EPI_NONE, s); }
-                DecAttnArgs at;
-                at.d = c->ld; at.qkv = c->dqkv; at.lbq = L.lora_bq; at.lbv = L.lora_bv; at.cos_t = c->rope_cos; at.sin_t = c->rope_sin;
-                at.pos = c->d_pos; at.slot_b = c->d_slot; at.key_mask = c->key_mask; at.cur_rope = c->d_cur_rope;
-                at.kcache = kv_ptr(c, c->kcache, l); at.vcache = kv_ptr(c, c->vcache, l); at.out = c->datt;
-                at.out_packed = 2;                       // the 64-deep order, one 32-row block per 32 rows
-                launch_decode_attention(dt, at, B, s);
-                { GemmArgs a = gargs(c->datt, H, L.wo, nullptr, c->dx, H, B); launch_xsplit_blk8(dt, p8(a, 2, 0), c->kslab, s); }
-                launch_rmsnorm_blk_fp8(dt, c->dx, L.mlp_norm, c->dxn, c->dxs, B, mtl, f.rms_eps, c->kslab, 2, s);
-                { GemmArgs a = gargs(c->dxn, H, L.wgu, nullptr, c->dgu, f.inter, B); launch_xstat_blk8(dt, p8(a, 4, 2), EPI_SILU_MUL, s); }
-                { GemmArgs a = gargs(c->dgu, f.inter, L.wdown, nullptr, c->dx, H, B); launch_xsplit_blk8(dt, p8(a, 2, 0), c->kslab, s); c->pend_groups = 4; }
-            }
-            lm_head_and_greedy(c, c->dx, B, logits, out_step, step_stride, /*advance=*/1);
-            return false;
-        }
-        auto pk = [&](GemmArgs a, int outp) { a.xpacked = 3; a.mtiles = mtl; a.out_packed = outp; return a; };
-        for (int l = 0; l < f.layers; ++l) {
-            const LlamaLayer& L = c->ll[l];
-            if (c->pend_groups) { launch_rmsnorm_packed_slab(dt, c->dx, L.attn_norm, c->dxn, B, mtl, f.rms_eps, c->kslab, c->pend_groups, s); c->pend_groups = 0; }
-            else launch_rmsnorm_packed(dt, c->dx, L.attn_norm, c->dxn, B, mtl, H, f.rms_eps, s);
-            { GemmArgs a = gargs(c->dxn, H, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); a.N = L.wqkv.Npad; launch_xstat_blk(dt, pk(a, 0), EPI_NONE, s); }
-            DecAttnArgs at;
-            at.d = c->ld; at.qkv = c->dqkv; at.lbq = L.lora_bq; at.lbv = L.lora_bv; at.cos_t = c->rope_cos; at.sin_t = c->rope_sin;
-            at.pos = c->d_pos; at.slot_b = c->d_slot; at.key_mask = c->key_mask; at.cur_rope = c->d_cur_rope;
-            at.kcache = kv_ptr(c, c->kcache, l); at.vcache = kv_ptr(c, c->vcache, l); at.out = c->datt;
-            at.out_packed = 1; at.out_mt = mtl;
-            launch_decode_attention(dt, at, B, s);
-            { GemmArgs a = gargs(c->datt, H, L.wo, nullptr, c->dx, H, B); a.resid = c->dx; a.ldr = H; launch_xstat_blk(dt, pk(a, 0), EPI_RESID, s); }
-            launch_rmsnorm_packed(dt, c->dx, L.mlp_norm, c->dxn, B, mtl, H, f.rms_eps, s);
-            { GemmArgs a = gargs(c->dxn, H, L.wgu, nullptr, c->dgu, f.inter, B); launch_xstat_blk(dt, pk(a, 3), EPI_SILU_MUL, s); }
-            // down_proj: K-split over 4 workgroups per tile into fp32 slabs, combined (+ residual) by the next RMSNorm (xsplit32_k<.., BLK>: 21 us against
-            // 29.5 us for the prompt's weight-stationary kernel at 64 rows); RDX_BLK_DOWN=0: wstat_k, the A/B leg
-            { GemmArgs a = gargs(c->dgu, f.inter, L.wdown, nullptr, c->dx, H, B); a.resid = c->dx; a.ldr = H; a = pk(a, 0);
-              static const bool split_down = !(getenv("RDX_BLK_DOWN") && atoi(getenv("RDX_BLK_DOWN")) == 0);
-              if (split_down && xsplit_blk_supported(a)) { launch_xsplit_blk(dt, a, c->kslab, s); c->pend_groups = 4; }
-              else launch_wstat(dt, a, EPI_RESID, s); }
-        }
-        lm_head_and_greedy(c, c->dx, B, logits, out_step, step_stride, /*advance=*/1);
-        return false;
+}
+
+// 33-128 rows, fp8 weights: the 32-row fp8 kernels per row block (api_dispatch.hip blk64_ok); both residual projections K-split, their slabs + residual left to
+// the next RMSNorm
+static void step_blk8(rdx_ctx* c, int B) {
+    const int dt = c->cfg.dtype;
+    hipStream_t s = c->stream;
+    auto ksplit = [&](const GemmArgs& a) { launch_xsplit_blk8(dt, a, c->kslab, s); c->pend_groups = xsplit_blk8_groups(a); };
+    for (int l = 0; l < c->cfg.layers; ++l) {
+        const LlamaLayer* L = &c->ll[l];
+        launch_xstat_blk8(dt, norm_in_front(c, blk8_unit(c, L, UNIT_QKV, B)), EPI_NONE, s);
+        DecAttnArgs at = dec_attn_args(c, l);
+        at.out_packed = 2;                       // the 64-deep order, one 32-row block per 32 rows
+        launch_decode_attention(dt, at, B, s);
+        ksplit(blk8_unit(c, L, UNIT_O, B));
+        launch_xstat_blk8(dt, norm_in_front(c, blk8_unit(c, L, UNIT_GATE_UP, B)), EPI_SILU_MUL, s);
+        ksplit(blk8_unit(c, L, UNIT_DOWN, B));
     }
-    if (!chain && xs16_ok(c, B)) {
-        // batch 3-16 (xs16.hip): five launches per layer -- QKV with the RMSNorm as its prologue, attention (output fragment-packed), o_proj with the
-        // residual epilogue, gate/up with the RMSNorm prologue (SwiGLU output fragment-packed), down_proj with the residual epilogue
-        for (int l = 0; l < f.layers; ++l) {
-            const LlamaLayer& L = c->ll[l];
-            { GemmArgs a = gargs(c->dx, H, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); a.N = L.wqkv.Npad; a.norm_w = L.attn_norm; a.eps = f.rms_eps;
-              xs16_proj(c, a, EPI_NONE); }
-            DecAttnArgs at;
-            at.d = c->ld; at.qkv = c->dqkv; at.lbq = L.lora_bq; at.lbv = L.lora_bv; at.cos_t = c->rope_cos; at.sin_t = c->rope_sin;
-            at.pos = c->d_pos; at.slot_b = c->d_slot; at.key_mask = c->key_mask; at.cur_rope = c->d_cur_rope;
-            at.kcache = kv_ptr(c, c->kcache, l); at.vcache = kv_ptr(c, c->vcache, l); at.out = c->datt;
-            at.out_packed = 1;
-            launch_decode_attention(dt, at, B, s);
-            xs16_row(c, c->datt, L.wo, B);
-            { GemmArgs a = gargs(c->dx, H, L.wgu, nullptr, c->dgu, f.inter, B); a.norm_w = L.mlp_norm; a.eps = f.rms_eps; a.out_packed = 1;
-              xs16_proj(c, a, EPI_SILU_MUL); }
-            xs16_row(c, c->dgu, L.wdown, B);
-        }
-        lm_head_and_greedy(c, c->dx, B, logits, out_step, step_stride, /*advance=*/1);
-        return false;
+}
+
+// batch 3-16 (xs16.hip): five launches per layer -- QKV with the RMSNorm as its prologue, attention (output fragment-packed), o_proj with the
+// residual epilogue, gate/up with the RMSNorm prologue (SwiGLU output fragment-packed), down_proj with the residual epilogue
+static void step_xs16(rdx_ctx* c, int B) {
+    const int dt = c->cfg.dtype;
+    hipStream_t s = c->stream;
+    for (int l = 0; l < c->cfg.layers; ++l) {
+        const LlamaLayer* L = &c->ll[l];
+        launch_xstat16(dt, xs16_unit(c, L, UNIT_QKV, B), EPI_NONE, s);
+        DecAttnArgs at = dec_attn_args(c, l);
+        at.out_packed = 1;
+        launch_decode_attention(dt, at, B, s);
+        launch_xrow16(dt, xs16_unit(c, L, UNIT_O, B), s);
+        launch_xstat16(dt, xs16_unit(c, L, UNIT_GATE_UP, B), EPI_SILU_MUL, s);
+        launch_xrow16(dt, xs16_unit(c, L, UNIT_DOWN, B), s);
     }
-    for (int l = 0; l < f.layers; ++l) {
+}
+
+// attention + o_proj of the chained and the generic family: ONE fused launch where it exists (batch <= 2, RDX_FUSE_AO), else two
+static void attn_oproj(rdx_ctx* c, int l, int B) {
+    const int dt = c->cfg.dtype;
+    const LlamaLayer& L = c->ll[l];
+    DecAttnArgs at = dec_attn_args(c, l);
+    const GemmArgs ao = unit_args(c, &L, UNIT_O, B);
+    if (c->fuse_attn_oproj && attn_oproj16_supported(c->ld, L.wo.N, L.wo.K, B)) {
+        launch_attn_oproj16(dt, at, ao, B, c->d_ctr + (size_t)l * 256, c->d_err, c->stream);
+        return;
+    }
+    // batch 3-32: attention writes its output fragment-packed and o_proj runs K-split over two workgroups per tile,
+    // its residual epilogue folded into the RMSNorm in front of gate/up (xsplit32_k)
+    const GemmArgs ap = ksplit_args(ao);
+    const int kg = (B >= xs_min_rows() && c->kslab) ? xsplit32_groups(ap) : 0;
+    at.out_packed = kg > 0 ? ap.xpacked : 0;
+    launch_decode_attention(dt, at, B, c->stream);
+    if (kg) launch_ksplit(c, ap);
+    else skinny(c, ao, EPI_RESID);
+}
+
+// the GEMV family (batch 1-2 without the chained launch, and every shape the activation-stationary kernels refuse) and, from 3 rows, the 32-row
+// xstat32 / xsplit32 kernels behind stand-alone RMSNorms: skinny() picks per projection
+static void step_generic(rdx_ctx* c, int B) {
+    for (int l = 0; l < c->cfg.layers; ++l) {
         const LlamaLayer& L = c->ll[l];
-        if (!chain || l == 0) {
-            GemmArgs a = gargs(c->dx, H, L.wqkv, nullptr, c->dqkv, c->ld.qkv_ld, B); a.N = L.wqkv.Npad; a.norm_w = L.attn_norm; a.eps = f.rms_eps;
-            skinny(c, a, EPI_NONE);
-        }
-        DecAttnArgs at;
-        at.d = c->ld; at.qkv = c->dqkv; at.lbq = L.lora_bq; at.lbv = L.lora_bv; at.cos_t = c->rope_cos; at.sin_t = c->rope_sin;
-        at.pos = c->d_pos; at.slot_b = c->d_slot; at.key_mask = c->key_mask; at.cur_rope = c->d_cur_rope;
-        at.kcache = kv_ptr(c, c->kcache, l); at.vcache = kv_ptr(c, c->vcache, l); at.out = c->datt;
-        GemmArgs ao = gargs(c->datt, H, L.wo, nullptr, c->dx, H, B);
-        ao.resid = c->dx; ao.ldr = H;
-        if (c->fuse_attn_oproj && attn_oproj16_supported(c->ld, L.wo.N, L.wo.K, B)) {
-            launch_attn_oproj16(dt, at, ao, B, c->d_ctr + (size_t)l * 256, c->d_err, s);
-        } else {
-            // batch 3-32: attention writes its output fragment-packed and o_proj runs K-split over two workgroups per tile,
-            // its residual epilogue folded into the RMSNorm in front of gate/up (xsplit32_k)
-            GemmArgs ap = ao; ap.xpacked = (ao.W8 && ao.wscale) ? 2 : 1;
-            const int kg = (B >= xs_min_rows() && c->kslab) ? xsplit32_groups(ap) : 0;
-            at.out_packed = kg > 0 ? ap.xpacked : 0;
-            launch_decode_attention(dt, at, B, s);
-            if (kg) launch_ksplit(c, ap);
-            else skinny(c, ao, EPI_RESID);
-        }
-        if (chain) {          // gate/up stand-alone, then down(l) -> QKV(l+1) chained
-            { GemmArgs a = gargs(c->dx, H, L.wgu, nullptr, c->dgu, f.inter, B); a.norm_w = L.mlp_norm; a.eps = f.rms_eps; skinny(c, a, EPI_SILU_MUL); }
-            if (evs) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, s); evs->push_back(e); }
-            ca.layer = l;
-            ca.trace = l == c->chain_trace_layer ? c->chain_trace : nullptr;
-            launch_decode_chain(dt, ca, l + 1 < f.layers, s);
-            if (evs) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, s); evs->push_back(e); }
-            continue;
-        }
+        skinny(c, unit_args(c, &L, UNIT_QKV, B), EPI_NONE);
+        attn_oproj(c, l, B);
         const bool split = down_split_ok(c, L, B);
-        { GemmArgs a = gargs(c->dx, H, L.wgu, nullptr, c->dgu, f.inter, B); a.norm_w = L.mlp_norm; a.eps = f.rms_eps;
-          a.out_packed = split ? ((L.wdown.w8 && L.wdown.scale) ? 2 : 1) : 0;
-          skinny(c, a, EPI_SILU_MUL); }
+        GemmArgs gu = unit_args(c, &L, UNIT_GATE_UP, B);
+        gu.out_packed = split ? ksplit_args(unit_args(c, &L, UNIT_DOWN, B)).xpacked : 0;         // down_proj's K-split reads the SwiGLU output fragment-packed
+        skinny(c, gu, EPI_SILU_MUL);
         launch_down(c, L, B, split);
     }
+}
+
+// batch <= 2: QKV of layer 0 and every gate/up stand-alone, attention + o_proj fused, down(l) -> QKV(l+1) chained inside one launch by the fence-free hand-off.
+// The hand-off counter shards of the fused launches are cleared by greedy_step_k at the end of the previous step (and of the prefill): a memset node at the
+// head of the step graph was observed to race with the first producers. evs: an event pair around every chained launch (rdx_time 7).
+static void step_chained(rdx_ctx* c, int B, std::vector<hipEvent_t>* evs) {
+    const rdx_config& f = c->cfg;
+    hipStream_t s = c->stream;
+    ChainArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.layers = c->d_clayers; ca.hidden = f.hidden; ca.inter = f.inter; ca.qkv_n = c->ll[0].wqkv.Npad; ca.qkv_ld = c->ld.qkv_ld; ca.B = B; ca.eps = f.rms_eps;
+    ca.dx = c->dx; ca.dqkv = c->dqkv; ca.dgu = c->dgu; ca.ctr = c->d_cctr; ca.err = c->d_err; ca.naps = c->chain_naps;
+    const LlamaLayer& L0 = c->ll[0];        // fp8 weights: the chained roles stream the e4m3 bytes too
+    ca.w8 = (L0.wqkv.w8 && L0.wdown.w8 && f.hidden % 64 == 0 && f.inter % 64 == 0) ? 1 : 0;
+    auto mark = [&] { if (evs) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, s); evs->push_back(e); } };
+    skinny(c, unit_args(c, &L0, UNIT_QKV, B), EPI_NONE);
+    for (int l = 0; l < f.layers; ++l) {
+        attn_oproj(c, l, B);
+        skinny(c, unit_args(c, &c->ll[l], UNIT_GATE_UP, B), EPI_SILU_MUL);
+        mark();
+        ca.layer = l;
+        ca.trace = l == c->chain_trace_layer ? c->chain_trace : nullptr;
+        launch_decode_chain(f.dtype, ca, l + 1 < f.layers, s);
+        mark();
+    }
+}
+
+bool decode_step_launch(rdx_ctx* c, void* logits, const int* out_step, long step_stride, std::vector<hipEvent_t>* evs) {
+    const int B = c->cur_B;
+    const DecFamily fam = decode_family(c, B);
+    switch (fam) {
+    case DEC_UNSUPPORTED: c->unsupported = k_need_blk; return false;
+    case DEC_BLK: step_blk(c, B); break;
+    case DEC_BLK8: step_blk8(c, B); break;
+    case DEC_XS16: step_xs16(c, B); break;
+    case DEC_CHAINED: step_chained(c, B, evs); break;
+    case DEC_GENERIC: step_generic(c, B); break;
+    }
     lm_head_and_greedy(c, c->dx, B, logits, out_step, step_stride, /*advance=*/1);
-    return chain;
+    return fam == DEC_CHAINED;
 }
 
 extern "C" int rdx_decode_step(rdx_ctx* c, void* logits) {

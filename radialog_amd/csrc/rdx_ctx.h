@@ -19,7 +19,7 @@
 using namespace rdx;
 
 // decoder rows per context: batch 1-2 chained launches, 3-16 xs16.hip, 3-32 xstat32.hip, 33-128 the row-block family (NB = ceil(rows / 32) row blocks per
-// tile walker sharing an XCD's L2: xstat32_k / xsplit32_k<.., BLK>; fp8 weights: the 32-row fp8 x fp8 kernels per block). 128 rows x 512 slots of KV = 68 GB of the 288.
+// tile walker sharing an XCD's L2: xstat32_k / xsplit32_k<.., BLK>; fp8 weights: the 32-row fp8 kernels per block). 128 rows x 512 slots of KV = 68 GB of the 288.
 constexpr int RDX_MAX_ROWS = 128;
 
 struct GemmW { void* w = nullptr; int N = 0, K = 0, Npad = 0; void* w8 = nullptr; float* scale = nullptr; };   // w8/scale: fp8 copy
@@ -99,6 +99,7 @@ struct rdx_ctx {
     bool xs16 = true;                // batch 3-16 decode on the one-row-tile family (xs16.hip: norm-prologue projections + un-split o_proj / down, 5 launches
                                      // per layer); RDX_XS16=0 at create / rdx_set_option("xs16", 0): the 32-row family of xstat32.hip (7 launches; A/B leg of the tests)
     bool prompt_blk = true;          // one prompt's K = 4096 projections on xstat32_k<.., BLK> (RDX_PBLK=0 / rdx_set_option("prompt_blk", 0): wstat_k, the A/B leg)
+    bool blk_down = true;            // 33-128 rows, model-dtype weights: down_proj K-split into fp32 slabs (xsplit32_k<.., BLK>); RDX_BLK_DOWN=0 at create: wstat_k, the A/B leg
     int chain_naps = 1;              // poll back-off of the chained launch (x s_sleep(8) between polls)
     long long* chain_trace = nullptr; int chain_trace_layer = -1;     // rdx_gemv_trace(7): device timeline buffer of ONE chained launch of the next step
     GemmW cls_fc1, cls_fc2; const float *cls_fc1_b = nullptr, *cls_fc2_b = nullptr;   // findings classifier head
@@ -170,15 +171,32 @@ inline void dfree(rdx_ctx* c, P*& p) {
 GemmArgs gargs(const void* X, int ldx, const GemmW& W, const float* bias, void* out, int ldo, int M);
 GemmArgs skinny_prenorm(rdx_ctx* c, GemmArgs a, int epi);
 void skinny(rdx_ctx* c, GemmArgs a, int epi);
-bool down_split_ok(rdx_ctx* c, const LlamaLayer& L, int B);
 void launch_ksplit(rdx_ctx* c, const GemmArgs& a);
+// ---- the decode step's units (api_dispatch.hip): ONE definition of each unit's arguments for the step (api_llama.hip), the probes, the timers (rdx_time) and the trace hooks ----
+enum DecUnit { UNIT_QKV, UNIT_O, UNIT_GATE_UP, UNIT_DOWN, UNIT_LM_HEAD };
+// the kernel family the step takes at B rows: batch <= 2 chained (both switches on), generic (GEMV; from 3 rows the 32-row xstat32 / xsplit32 kernels), 3-16 rows
+// xs16.hip, 33-128 rows the row blocks in the model dtype or with fp8 weights
+enum DecFamily { DEC_UNSUPPORTED, DEC_CHAINED, DEC_GENERIC, DEC_XS16, DEC_BLK, DEC_BLK8 };
+DecFamily decode_family(rdx_ctx* c, int B);
+DecAttnArgs dec_attn_args(rdx_ctx* c, int layer);                                  // decode attention; callers set out_packed / out_mt / trace
+AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer);         // T prompt tokens behind `keep` cached ones; callers set o_packed_mt
+// a unit in its base form: row-major activations, the RMSNorm in front of QKV / gate-up / lm_head as the kernel's prologue (norm_w), the residual of o_proj /
+// down_proj as its epilogue. L may be null for UNIT_LM_HEAD, whose callers set X (when not dx), out and out_step.
+GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);
+// ... and in the layout of a family (what its probe checks IS what its step function launches):
+GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);      // one row tile: gate/up writes, o_proj / down_proj read the fragment-packed block
+GemmArgs blk_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);       // row blocks: fragment-packed row tiles of 16 in and (gate/up) out
+GemmArgs blk8_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);      // ... fp8 weights: e4m3 blocks + xscale in; 64-deep model-dtype blocks into the K-split o_proj / down_proj
+GemmArgs ksplit_args(GemmArgs a);                  // o_proj / down_proj K-split at 3-32 rows: X is the fragment-packed 32-row block (fp8 weights: 64-deep)
+GemmArgs prenormed(rdx_ctx* c, GemmArgs a);        // the unit's RMSNorm is a launch of its own: the kernel reads the normalised rows from dxn
+// The RMSNorm in front of a unit whose kernel does not fuse it: a.X normalised by a.norm_w into dxn, in the layout a.xpacked / a.mtiles name. Slabs that a K-split
+// projection left pending on dx are folded in (dx += T(sum of slabs)) and pend_groups is cleared. Returns prenormed(c, a), the arguments of the GEMM proper.
+GemmArgs norm_in_front(rdx_ctx* c, GemmArgs a);
+bool down_split_ok(rdx_ctx* c, const LlamaLayer& L, int B);
 void launch_down(rdx_ctx* c, const LlamaLayer& L, int B, bool split);
-// batch 3-16, model-dtype weights, hidden 4096: the decode step's projections on xs16.hip (no stand-alone RMSNorm, no K-split slabs)
-bool blk64_ok(rdx_ctx* c, int B);      // 33-128 rows: the row-block decode family (model-dtype weights, or fp8 x fp8: blk64_fp8)
-bool blk64_fp8(rdx_ctx* c);            // ... its fp8 x fp8 form is the one in use (e4m3 decoder weights)
-bool xs16_ok(rdx_ctx* c, int B);
-void xs16_proj(rdx_ctx* c, GemmArgs a, int epi);          // a.norm_w set, a.X = the row-major residual stream
-void xs16_row(rdx_ctx* c, const void* xpacked, const GemmW& W, int B);     // dx += T(xpacked . W^T), in place
+bool blk64_ok(rdx_ctx* c, int B);      // 33-128 rows: the row-block decode family (model-dtype weights, or fp8 weights: blk64_fp8)
+bool blk64_fp8(rdx_ctx* c);            // ... its fp8 form is the one in use (e4m3 decoder weights)
+bool xs16_ok(rdx_ctx* c, int B);       // batch 3-16, model-dtype weights, hidden 4096: the step's projections on xs16.hip (no stand-alone RMSNorm, no K-split slabs)
 void run_gemm(rdx_ctx* c, GemmArgs a, int epi);
 void conv_gemm(rdx_ctx* c, const void* X, const GemmW& W, const float* bias, const void* resid, void* out, int B,
                int Hin, int Win, int Cin, int KH, int KW, int stride, int pad, int Hout, int Wout, int epi);
