@@ -104,6 +104,18 @@ ENC_HOOK_SYMBOLS = {
     "rdx_attn_test": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_longlong, C.c_int, C.c_int]),
 }
 
+# include/rdx_dec_hooks.h: the decoder's 3-16-row and row-block GEMM kernel-test hooks, also in librdx_hooks.so (csrc/api_dec_hooks.hip)
+_F = C.c_float
+DEC_HOOK_SYMBOLS = {
+    "rdx_xstat16_test": (C.c_int, [_P, _P, _P, _F, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "rdx_xrow16_test": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
+    "rdx_xstat_blk_test": (C.c_int, [_P, _P, _P, _F, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P]),
+    "rdx_xsplit_blk_test": (C.c_int, [_P, _P, _P, _P, _P, _F, C.c_int, C.c_int, _P, _P]),
+    "rdx_xstat_blk8_test": (C.c_int, [_P, _P, _P, _F, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "rdx_xsplit_blk8_test": (C.c_int, [_P, _P, _P, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+}
+ALL_HOOK_SYMBOLS = {**HOOK_SYMBOLS, **ENC_HOOK_SYMBOLS, **DEC_HOOK_SYMBOLS}
+
 _lib = None
 _hooks = None
 
@@ -114,18 +126,18 @@ def hooks_enabled() -> bool:
 
 def _missing_hook(name):
     def raiser(*_a, **_k):
-        raise RdxLibraryError(f"{name} is a kernel-test hook of librdx_hooks.so (include/rdx_hooks.h, rdx_enc_hooks.h), not part of the product library: "
+        raise RdxLibraryError(f"{name} is a kernel-test hook of librdx_hooks.so (include/rdx_hooks.h, rdx_enc_hooks.h, rdx_dec_hooks.h), not part of the product library: "
                               "set RDX_DEBUG_HOOKS=1 before radialog_amd is loaded (tests/conftest.py and the tools/ scripts do)")
     return raiser
 
 
 def load_hooks(lib):
-    """Bind the hooks of include/rdx_hooks.h and include/rdx_enc_hooks.h onto `lib` (the ctypes handle the engine calls through). Under
+    """Bind the hooks of include/rdx_hooks.h, rdx_enc_hooks.h and rdx_dec_hooks.h onto `lib` (the ctypes handle the engine calls through). Under
     RDX_DEBUG_HOOKS=1 they come from librdx_hooks.so (or from an RDX_LIB_PATH build that links them in: tools/sanitize_host.sh); otherwise every
     hook raises."""
     global _hooks
     if not hooks_enabled():
-        for name in {**HOOK_SYMBOLS, **ENC_HOOK_SYMBOLS}:
+        for name in ALL_HOOK_SYMBOLS:
             setattr(lib, name, _missing_hook(name))
         return
     src = lib
@@ -142,7 +154,7 @@ def load_hooks(lib):
         except OSError as e:
             raise RdxLibraryError(f"cannot load {HOOKS_PATH}: {e}") from e
         _hooks = src
-    for name, (res, args) in {**HOOK_SYMBOLS, **ENC_HOOK_SYMBOLS}.items():
+    for name, (res, args) in ALL_HOOK_SYMBOLS.items():
         try:
             fn = getattr(src, name)
         except AttributeError as e:

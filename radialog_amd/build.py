@@ -1,6 +1,6 @@
 """Build librdx.so (HIP C++, gfx950) in-tree with hipcc. No torch extension machinery: the library is a plain
 C-ABI shared object loaded with ctypes (radialog_amd/_lib.py). The kernel-test / trace / microbenchmark hooks (include/rdx_hooks.h,
-csrc/api_debug.hip) go into a second library, librdx_hooks.so, linked against librdx.so: the product library does not carry them."""
+rdx_enc_hooks.h, rdx_dec_hooks.h; csrc/api_debug.hip, csrc/api_dec_hooks.hip) go into a second library, librdx_hooks.so, linked against librdx.so: the product library does not carry them."""
 import os
 import subprocess
 import sys
@@ -11,9 +11,9 @@ OUT = os.path.join(HERE, "librdx.so")
 OUT_HOOKS = os.path.join(HERE, "librdx_hooks.so")
 SOURCES = ["gemm.hip", "xstat32.hip", "xs16.hip", "gemm_dma.hip", "gemm8.hip", "attn.hip", "flash.hip", "chain.hip", "elem.hip", "beam.hip", "conv1x1.hip", "wsgemm.hip", "stem.hip", "wstat.hip", "pconv.hip",
            "api.hip", "api_dispatch.hip", "api_encode.hip", "api_llama.hip", "api_comm.hip", "api_inspect.hip", "api_transform.hip"]
-HOOK_SOURCES = ["api_debug.hip"]
+HOOK_SOURCES = ["api_debug.hip", "api_dec_hooks.hip"]
 HEADERS = ["rdx_common.h", "rdx_kernels.h", "rdx_ctx.h", "skinny_body.h", "attn_body.h", "handoff.h", os.path.join("..", "..", "include", "rdx.h"),
-           os.path.join("..", "..", "include", "rdx_hooks.h"), os.path.join("..", "..", "include", "rdx_enc_hooks.h")]
+           os.path.join("..", "..", "include", "rdx_hooks.h"), os.path.join("..", "..", "include", "rdx_enc_hooks.h"), os.path.join("..", "..", "include", "rdx_dec_hooks.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 
 

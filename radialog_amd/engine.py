@@ -406,6 +406,106 @@ class RdxEngine:
                                                  ctypes.cast(am, ctypes.c_void_p), int(fp8)), "rdx_logits_test")
         return out, torch.tensor(list(am), dtype=torch.int32)
 
+    # -- the decoder's 3-16-row / row-block GEMM kernels alone (include/rdx_dec_hooks.h). Inputs may be device tensors (used as they are, so one
+    #    weight serves many calls); every output is pre-filled with NaN so that "not written" can be asserted ---------------------------------
+    def _dev(self, t, dtype=None):
+        return None if t is None else t.to(self.device, dtype or self.tdtype).contiguous()
+
+    def _nan(self, *shape, dtype=None):
+        return torch.full(shape, float("nan"), dtype=dtype or self.tdtype, device=self.device)
+
+    def xstat16_test(self, x, norm_w, w, epi=0, eps=1e-6, n_valid=None, ldo=None, out_packed=0):
+        """xstat16_k (rdx_xstat16_test): x [M, 4096], norm_w [4096], w fp32 [N, 4096]. Returns out [M, ldo] (epi 4: N / 2 columns), the raw packed
+        block [N / 64, 2, 64, 8] for out_packed 1, or (logits, argmax int32[M]) for epi 5."""
+        import ctypes
+        M, N = x.shape[0], w.shape[0]
+        x, nw, w = self._dev(x), self._dev(norm_w), self._dev(w, torch.float32)
+        cols = N // 2 if epi == 4 else N
+        ldo = ldo or cols
+        out = self._nan(N // 64, 2, 64, 8) if out_packed else self._nan(M + 2, ldo)
+        am = (ctypes.c_int32 * M)()
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_xstat16_test(self.ctx, _ptr(x), _ptr(nw), eps, _ptr(w), M, N, epi, N if n_valid is None else n_valid, _ptr(out),
+                                                  ldo, out_packed, ctypes.cast(am, ctypes.c_void_p)), "rdx_xstat16_test")
+        return (out, torch.tensor(list(am), dtype=torch.int32)) if epi == 5 else out
+
+    def xrow16_test(self, x, w, resid, M=None, ldo=None):
+        """xrow16_k (rdx_xrow16_test): out [M + 2, ldo] = resid [M, N] + T(x w^T). x [M, K] row-major, or (4-d) the packed block [K / 32, 2, 64, 8]
+        with M given."""
+        packed = x.dim() == 4
+        M = M if packed else x.shape[0]
+        N, K = w.shape
+        x, w, r = self._dev(x), self._dev(w, torch.float32), self._dev(resid)
+        ldo = ldo or N
+        out = self._nan(M + 2, ldo)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_xrow16_test(self.ctx, _ptr(x), int(packed), _ptr(w), _ptr(r), M, N, K, _ptr(out), ldo), "rdx_xrow16_test")
+        return out
+
+    def xstat_blk_test(self, x, norm_w, w, epi=0, resid=None, eps=1e-6, n_valid=None, ldo=None, out_packed=0, want_xp=False):
+        """launch_rmsnorm_packed + the row-block xstat32_k (rdx_xstat_blk_test): x [M, 4096], norm_w [4096] or None, w fp32 [N, 4096]. Returns
+        (out, xp, argmax): out [M + 2, ldo] or the raw packed block [N / 64, mtiles, 64, 8] (out_packed 3); xp the norm's raw packed output
+        [128, mtiles, 64, 8] (want_xp); argmax int32[M] (epi 5)."""
+        import ctypes
+        M, N = x.shape[0], w.shape[0]
+        mtl = (M + 15) // 16
+        x, nw, w, r = self._dev(x), self._dev(norm_w), self._dev(w, torch.float32), self._dev(resid)
+        ldo = ldo or (N // 2 if epi == 4 else N)
+        out = self._nan(N // 64, mtl, 64, 8) if out_packed else self._nan(M + 2, ldo)
+        xp = self._nan(128, mtl, 64, 8) if want_xp else None
+        am = (ctypes.c_int32 * M)()
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_xstat_blk_test(self.ctx, _ptr(x), _ptr(nw), eps, _ptr(w), _ptr(r), M, N, epi, N if n_valid is None else n_valid,
+                                                    _ptr(out), ldo, out_packed, _ptr(xp), ctypes.cast(am, ctypes.c_void_p)), "rdx_xstat_blk_test")
+        return out, xp, (torch.tensor(list(am), dtype=torch.int32) if epi == 5 else None)
+
+    def xsplit_blk_test(self, x, w, resid=None, norm_w=None, eps=1e-6):
+        """launch_rmsnorm_packed (re-layout) + the row-block xsplit32_k [+ launch_rmsnorm_packed_slab] (rdx_xsplit_blk_test): x [M, 11008], w fp32
+        [N, 11008]. Returns (slabs fp32 [4, 16 mtiles, N], updated residual rows [M, 4096] or None, raw packed norm [128, mtiles, 64, 8] or None)."""
+        M, N = x.shape[0], w.shape[0]
+        mtl = (M + 15) // 16
+        x, w, nw = self._dev(x), self._dev(w, torch.float32), self._dev(norm_w)
+        slab = self._nan(4, 16 * mtl, N, dtype=torch.float32)
+        r = None if resid is None else self._dev(resid).clone()
+        xn = None if resid is None else self._nan(128, mtl, 64, 8)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_xsplit_blk_test(self.ctx, _ptr(x), _ptr(w), _ptr(r), _ptr(nw), eps, M, N, _ptr(slab), _ptr(xn)), "rdx_xsplit_blk_test")
+        return slab, r, xn
+
+    def xstat_blk8_test(self, x, norm_w, w, epi=0, eps=1e-6, n_valid=None, ldo=None, out_packed=0):
+        """launch_rmsnorm_blk_fp8 + the fp8 row-block xstat32_k (rdx_xstat_blk8_test): x [M, 4096], norm_w [4096], w fp32 [N, 4096] (quantised to e4m3
+        by the production packer). Returns (out, x8 uint8 [NB, 32 * 4096], xscale fp32 [32 NB], argmax or None); out [M + 2, ldo] or, out_packed 2,
+        the raw blocks [NB, 32 * N / 2]."""
+        import ctypes
+        M, N = x.shape[0], w.shape[0]
+        NB = (M + 31) // 32
+        x, nw, w = self._dev(x), self._dev(norm_w), self._dev(w, torch.float32)
+        ldo = ldo or (N // 2 if epi == 4 else N)
+        out = self._nan(NB, 32 * (N // 2)) if out_packed else self._nan(M + 2, ldo)
+        x8 = torch.full((NB, 32 * 4096), 0xff, dtype=torch.uint8, device=self.device)
+        xs = self._nan(32 * NB, dtype=torch.float32)
+        am = (ctypes.c_int32 * M)()
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_xstat_blk8_test(self.ctx, _ptr(x), _ptr(nw), eps, _ptr(w), M, N, epi, N if n_valid is None else n_valid, _ptr(out), ldo,
+                                                     out_packed, _ptr(x8), _ptr(xs), ctypes.cast(am, ctypes.c_void_p)), "rdx_xstat_blk8_test")
+        return out, x8, xs, (torch.tensor(list(am), dtype=torch.int32) if epi == 5 else None)
+
+    def xsplit_blk8_test(self, x, w, resid=None, norm_w=None, eps=1e-6):
+        """launch_rmsnorm_packed32 (pack 2 re-layout per 32-row block) + the fp8 row-block xsplit32_k [+ launch_rmsnorm_blk_fp8 with the slabs]
+        (rdx_xsplit_blk8_test): x [M, K], w fp32 [N, K], K 4096 / 11008. Returns (slabs fp32 [groups, 32 NB, N], updated residual rows or None)."""
+        M, K = x.shape
+        N = w.shape[0]
+        NB = (M + 31) // 32
+        x, w, nw = self._dev(x), self._dev(w, torch.float32), self._dev(norm_w)
+        slab = self._nan(4 if K == 11008 else 2, 32 * NB, N, dtype=torch.float32)
+        r = None if resid is None else self._dev(resid).clone()
+        x8 = None if resid is None else torch.empty(NB, 32 * 4096, dtype=torch.uint8, device=self.device)
+        xs = None if resid is None else self._nan(32 * NB, dtype=torch.float32)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_xsplit_blk8_test(self.ctx, _ptr(x), _ptr(w), _ptr(r), _ptr(nw), eps, M, N, K, _ptr(slab), _ptr(x8), _ptr(xs)),
+              "rdx_xsplit_blk8_test")
+        return slab, r
+
     def classify_findings(self, image: torch.Tensor) -> torch.Tensor:
         """ChexpertClassifier.forward: float32[B,3,S,S] on the device -> float32[B,classes] logits."""
         image = image.to(self.device, torch.float32).contiguous()

@@ -72,6 +72,33 @@ def test_encoder_hooks_are_declared_bound_and_only_in_the_hooks_library(monkeypa
             getattr(fresh, name)(None)
 
 
+def test_decoder_hooks_are_declared_bound_and_only_in_the_hooks_library(monkeypatch):
+    """The decoder's GEMM kernel-test hooks (include/rdx_dec_hooks.h: rdx_xstat16_test, rdx_xrow16_test, rdx_xstat_blk_test, rdx_xsplit_blk_test and
+    the fp8 pair) follow the rules of rdx_hooks.h: header and binding table agree and share no name with the other tables, librdx_hooks.so exports
+    them and librdx.so does not, _lib binds them with their argtypes under RDX_DEBUG_HOOKS=1 and replaces them with raising stubs without it; the
+    source they are built from is part of the build and of the source hash."""
+    from radialog_amd import build
+    assert _declared_symbols("rdx_dec_hooks.h") == sorted(_lib.DEC_HOOK_SYMBOLS)
+    others = set(_lib.SYMBOLS) | set(_lib.HOOK_SYMBOLS) | set(_lib.ENC_HOOK_SYMBOLS)
+    assert not set(_lib.DEC_HOOK_SYMBOLS) & others and len(_lib.ALL_HOOK_SYMBOLS) == len(_lib.HOOK_SYMBOLS) + len(_lib.ENC_HOOK_SYMBOLS) + len(_lib.DEC_HOOK_SYMBOLS)
+    assert "api_dec_hooks.hip" in build.HOOK_SOURCES and "api_dec_hooks.hip" not in build.SOURCES
+    lib = C.CDLL(_lib.LIB_PATH, mode=C.RTLD_GLOBAL)
+    hooks = C.CDLL(_lib.HOOKS_PATH, mode=C.RTLD_GLOBAL)
+    for name in _declared_symbols("rdx_dec_hooks.h"):
+        assert not hasattr(lib, name), f"librdx.so exports the test hook {name}"
+        assert hasattr(hooks, name), f"librdx_hooks.so does not export {name}"
+    bound = _lib.load()
+    for name, (res, args) in _lib.DEC_HOOK_SYMBOLS.items():
+        fn = getattr(bound, name)
+        assert fn.restype is res and list(fn.argtypes) == args, name
+    monkeypatch.setenv("RDX_DEBUG_HOOKS", "0")
+    fresh = C.CDLL(_lib.LIB_PATH, mode=C.RTLD_GLOBAL)
+    _lib.load_hooks(fresh)
+    for name in _lib.DEC_HOOK_SYMBOLS:
+        with pytest.raises(_lib.RdxLibraryError, match="RDX_DEBUG_HOOKS"):
+            getattr(fresh, name)(None)
+
+
 def test_config_struct_matches_header_field_count():
     text = open(os.path.join(REPO, "include", "rdx.h")).read()
     body = text[text.index("typedef struct rdx_config {"): text.index("} rdx_config;")]
