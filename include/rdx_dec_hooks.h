@@ -20,33 +20,40 @@ int rdx_xstat16_test(rdx_ctx* ctx, const void* X, const void* norm_w, float eps,
                      int ldo, int out_packed, int32_t* argmax_host);
 
 /* launch_xrow16: out [M][ldo] = resid [M][N] + T(X W^T), K % 32 == 0, K >= 512, N % 16 == 0. x_packed 0: X [M][K] row-major, re-laid into the packed
- * 32-row block by launch_rmsnorm_packed32 without a norm weight; x_packed 1: X already is that block [K / 32][2][64][8] (rdx_xstat16_test's
+ * 32-row block by launch_rmsnorm without a norm weight; x_packed 1: X already is that block [K / 32][2][64][8] (rdx_xstat16_test's
  * out_packed 1 output: the production gate/up -> down_proj seam). */
 int rdx_xrow16_test(rdx_ctx* ctx, const void* X, int x_packed, const float* W, const void* resid, int M, int N, int K, void* out, int ldo);
 
-/* launch_rmsnorm_packed (norm_w nullable: re-layout only) + launch_xstat_blk: X [M][4096], M <= 192, N >= 2048. epi 0 / 3 / 5: out [M][ldo]
+/* launch_rmsnorm into the row tiles (norm_w nullable: re-layout only) + launch_xstat_blk: X [M][4096], M <= 192, N >= 2048. epi 0 / 3 / 5: out [M][ldo]
  * (3: resid [M][N]); epi 4, out_packed 0: out [M][ldo]; out_packed 3: out = the packed block [N / 64][mtiles][64][8] (N % 64 == 0), mtiles =
  * ceil(M / 16). xp_out (nullable): the norm's packed output [128][mtiles][64][8]. */
 int rdx_xstat_blk_test(rdx_ctx* ctx, const void* X, const void* norm_w, float eps, const float* W, const void* resid, int M, int N, int epi,
                        int n_valid, void* out, int ldo, int out_packed, void* xp_out, int32_t* argmax_host);
 
-/* launch_rmsnorm_packed (re-layout of X [M][11008]) + launch_xsplit_blk [+ launch_rmsnorm_packed_slab]. slab_out (nullable) fp32 [4][16 mtiles][N]:
+/* launch_rmsnorm (re-layout of X [M][11008]) + launch_xsplit_blk [+ launch_rmsnorm with the slabs]. slab_out (nullable) fp32 [4][16 mtiles][N]:
  * the K groups' partial sums. With x_resid: N == 4096, x_resid [M][4096] += T(sum of the slabs) in place, and xn_out = the packed RMSNorm
  * (norm_w [4096]) of the updated rows, [128][mtiles][64][8]. x_resid, norm_w and xn_out go together. */
 int rdx_xsplit_blk_test(rdx_ctx* ctx, const void* X, const float* W, void* x_resid, const void* norm_w, float eps, int M, int N, float* slab_out,
                         void* xn_out);
 
-/* fp8: launch_rmsnorm_blk_fp8 (norm_w [4096] required) + launch_xstat_blk8 on e4m3 weights packed here: X [M][4096], 33 <= M <= 128. epi 0 / 5: out
+/* fp8: launch_rmsnorm into e4m3 blocks (norm_w [4096] required) + launch_xstat_blk8 on e4m3 weights packed here: X [M][4096], 33 <= M <= 128. epi 0 / 5: out
  * [M][ldo]; epi 4: out [M][ldo], or out_packed 2: NB = ceil(M / 32) packed 32-row blocks in the 64-deep order, 32 (N / 2) elements each (N % 128 == 0).
  * x8_out (nullable) NB x 32 x 4096 e4m3 bytes and xscale_out (nullable) fp32 [32 NB]: what the norm wrote. */
 int rdx_xstat_blk8_test(rdx_ctx* ctx, const void* X, const void* norm_w, float eps, const float* W, int M, int N, int epi, int n_valid, void* out,
                         int ldo, int out_packed, void* x8_out, float* xscale_out, int32_t* argmax_host);
 
-/* fp8: launch_rmsnorm_packed32 (pack 2, no weight: re-layout of every 32-row block of X [M][K]) + launch_xsplit_blk8 [+ launch_rmsnorm_blk_fp8 with
- * the slabs], K 4096 (2 groups) or 11008 (4). slab_out (nullable) fp32 [groups][32 NB][N]. With x_resid (N == 4096): updated in place, and x8_out /
+/* fp8: launch_rmsnorm (64-deep order, no weight: re-layout of every 32-row block of X [M][K]) + launch_xsplit_blk8 [+ launch_rmsnorm into e4m3 blocks
+ * with the slabs], K 4096 (2 groups) or 11008 (4). slab_out (nullable) fp32 [groups][32 NB][N]. With x_resid (N == 4096): updated in place, and x8_out /
  * xscale_out = the e4m3 blocks and scales of its RMSNorm. x_resid, norm_w, x8_out and xscale_out go together. */
 int rdx_xsplit_blk8_test(rdx_ctx* ctx, const void* X, const float* W, void* x_resid, const void* norm_w, float eps, int M, int N, int K,
                          float* slab_out, void* x8_out, float* xscale_out);
+
+/* launch_rmsnorm alone (elem.hip): x [rows][H], norm_w [H] or null (re-layout only), layout 0-5 = the activation orders of ActLayout (csrc/rdx_kernels.h: 0
+ * row-major, 1 the 32-row block, 2 its 64-deep order, 3 mtiles row tiles, 4 e4m3 blocks in the 64-deep order + xscale, 5 e4m3 row-major + xscale). slab
+ * (nullable) fp32 [groups][rows the layout holds][H]: x += T(sum of the slabs) in place first. out (out_bytes) and xscale (nullable, xscale_n floats) are
+ * filled with 0xff bytes, then written by the norm. A combination without a kernel is an error and launches nothing. */
+int rdx_rmsnorm_test(rdx_ctx* ctx, void* x, const void* norm_w, float eps, int rows, int H, int layout, int mtiles, const float* slab, int groups, void* out,
+                     long long out_bytes, float* xscale, int xscale_n);
 
 #ifdef __cplusplus
 }

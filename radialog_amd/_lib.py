@@ -113,6 +113,7 @@ DEC_HOOK_SYMBOLS = {
     "rdx_xsplit_blk_test": (C.c_int, [_P, _P, _P, _P, _P, _F, C.c_int, C.c_int, _P, _P]),
     "rdx_xstat_blk8_test": (C.c_int, [_P, _P, _P, _F, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_xsplit_blk8_test": (C.c_int, [_P, _P, _P, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rdx_rmsnorm_test": (C.c_int, [_P, _P, _P, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong, _P, C.c_int]),
 }
 ALL_HOOK_SYMBOLS = {**HOOK_SYMBOLS, **ENC_HOOK_SYMBOLS, **DEC_HOOK_SYMBOLS}
 

@@ -24,17 +24,17 @@ extern "C" int rdx_attn_trace(rdx_ctx* c, int layer, long long* host) {
 }
 
 // Test hook: the fp8 path's activation quantisers on caller data. mode 0 = quant_rows_k (rows of X [M][K] -> e4m3 bytes [M][K] + scales [M][groups]),
-// mode 1 = RMSNorm -> e4m3 (rmsnorm4096_k / rmsnorm_k <T, 5>: bytes [M][K] + one scale per row; norm_w [K] in the model dtype, groups ignored).
+// mode 1 = RMSNorm -> e4m3 (ACT_ROWS_E4M3: bytes [M][K] + one scale per row; norm_w [K] in the model dtype, groups ignored).
 extern "C" int rdx_quant_test(rdx_ctx* c, const void* X, int M, int K, int groups, int mode, const void* norm_w, float eps, void* out8, float* scales) {
     if (!c || !X || !out8 || !scales || M <= 0 || K <= 0 || K % 128) return fail(c, -1, "rdx_quant_test: bad arguments (K %% 128 == 0)");
     if (mode == 0 && (groups < 1 || groups > 4)) return fail(c, -1, "rdx_quant_test: 1..4 K groups");
     if (mode == 1 && !norm_w) return fail(c, -1, "rdx_quant_test: mode 1 needs the norm weight");
     HIPCHK(c, hipSetDevice(c->device));
     if (mode == 0) launch_quant_rows(c->cfg.dtype, X, K, out8, scales, M, K, groups, c->stream);
-    else launch_rmsnorm_fp8(c->cfg.dtype, X, norm_w, out8, scales, M, K, eps, c->stream);
+    else run_rmsnorm(c, NormArgs{const_cast<void*>(X), norm_w, out8, scales, M, K, eps, ACT_ROWS_E4M3, 0, nullptr, 0});
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    return 0;
+    return take_unsupported(c);
 }
 
 // Debug: one stand-alone decode GEMV (what = 1 gate/up, 2 qkv, 4 down, as in rdx_time) of `layer` with per-workgroup
@@ -117,7 +117,7 @@ extern "C" int rdx_kernel_bench(rdx_ctx* c, int rows, int N, int K, int H, int k
         else {
             GemmArgs a = gargs(buf, K, w, bias, out, N, (int)M); a.resid = need_res ? res : nullptr; a.ldr = N; a.trace = dtr;
             if (kb_wstat) {       // RDX_KB_WSTAT=1: the single prompt's weight-stationary kernel on (zero) fragment-packed activations
-                a.xpacked = 3; a.mtiles = (int)((M + 15) / 16); a.bias = nullptr;
+                a.xpacked = ACT_TILES32; a.mtiles = (int)((M + 15) / 16); a.bias = nullptr;
                 if (wstat_supported(a, epi)) { launch_wstat(c->cfg.dtype, a, epi, c->stream); return; }
             }
             run_gemm(c, a, epi);
@@ -238,8 +238,8 @@ static int fp8_block_for_test(rdx_ctx* c, GemmArgs& a, int epi, char** tmp) {
     if (!xstat32_supported(t, epi)) return 0;
     HIPCHK(c, hipMalloc((void**)tmp, (size_t)32 * a.K + 32 * sizeof(float)));
     float* xs = (float*)(*tmp + (size_t)32 * a.K);
-    launch_rmsnorm_packed32_fp8(c->cfg.dtype, const_cast<void*>(a.X), a.norm_w, *tmp, xs, a.M, a.K, a.eps, nullptr, 0, c->stream);
-    a.X = *tmp; a.ldx = a.K; a.xpacked = 4; a.xscale = xs; a.xgroups = 1; a.norm_w = nullptr;
+    run_rmsnorm(c, NormArgs{const_cast<void*>(a.X), a.norm_w, *tmp, xs, a.M, a.K, a.eps, ACT_BLK64_E4M3, 0, nullptr, 0});
+    a.X = *tmp; a.ldx = a.K; a.xpacked = ACT_BLK64_E4M3; a.xscale = xs; a.xgroups = 1; a.norm_w = nullptr;
     return 0;
 }
 
@@ -264,7 +264,7 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
         char* tmp = nullptr;
         if (hipMalloc((void**)&tmp, (size_t)M * K + (size_t)M * 4 * sizeof(float)) != hipSuccess) { hipFree(wp); return fail(c, -2, "rdx_gemm_test: out of device memory"); }
         float* xs = (float*)(tmp + (size_t)M * K);
-        if (norm_w) launch_rmsnorm_fp8(c->cfg.dtype, X, norm_w, tmp, xs, M, K, eps, c->stream);
+        if (norm_w) run_rmsnorm(c, NormArgs{const_cast<void*>(X), norm_w, tmp, xs, M, K, eps, ACT_ROWS_E4M3, 0, nullptr, 0});
         else launch_quant_rows(c->cfg.dtype, X, K, tmp, xs, M, K, G, c->stream);
         GemmArgs a = gargs(tmp, K, w, nullptr, out, epi == EPI_SILU_MUL ? N / 2 : N, M);
         a.resid = resid; a.ldr = N; a.xscale = xs; a.xgroups = G;
@@ -274,6 +274,7 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
         hipError_t se = hipStreamSynchronize(c->stream);
         hipFree(wp); hipFree(tmp);
         if (rc) return rc;
+        if (int urc = take_unsupported(c)) return urc;
         HIPCHK(c, se);
         HIPCHK(c, hipGetLastError());
         return 0;
@@ -307,30 +308,30 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
         char* tmp = nullptr;
         const size_t xb = (size_t)32 * K * 2, sb = (size_t)4 * 32 * N * 4;
         if (hipMalloc((void**)&tmp, 2 * xb + sb) != hipSuccess) { hipFree(wp); return fail(c, -2, "rdx_gemm_test: out of device memory"); }
-        launch_rmsnorm_packed32(c->cfg.dtype, const_cast<void*>(X), nullptr, tmp, M, K, eps, split8 ? 2 : 1, nullptr, 0, c->stream);   // w = null: re-layout only
-        a.X = tmp; a.xpacked = split8 ? 2 : 1; a.norm_w = nullptr;
+        a.X = tmp; a.xpacked = split8 ? ACT_BLK64 : ACT_BLK32; a.norm_w = nullptr;
+        run_rmsnorm(c, NormArgs{const_cast<void*>(X), nullptr, tmp, nullptr, M, K, eps, a.xpacked, 0, nullptr, 0});   // w = null: re-layout only
         const int kg = xsplit32_groups(a);
         if (!kg) { hipFree(wp); hipFree(tmp); return fail(c, -1, "rdx_gemm_test: shape not supported by xsplit32_k"); }
         launch_xsplit32(c->cfg.dtype, a, (float*)(tmp + 2 * xb), c->stream);
         HIPCHK(c, hipMemcpyAsync(out, resid, (size_t)M * N * 2, hipMemcpyDeviceToDevice, c->stream));
-        launch_rmsnorm_packed32(c->cfg.dtype, out, nullptr, tmp + xb, M, N, eps, 0, (const float*)(tmp + 2 * xb), kg, c->stream);
+        run_rmsnorm(c, NormArgs{out, nullptr, tmp + xb, nullptr, M, N, eps, ACT_ROWS, 0, (const float*)(tmp + 2 * xb), kg});
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipGetLastError());
         hipFree(wp); hipFree(tmp);
-        return 0;
+        return take_unsupported(c);
     }
     if (force == 8) {         // the single prompt's weight-stationary kernel (wstat.hip): RMSNorm / re-layout into the fragment-packed order, then the GEMM
         const int mtl = (M + 15) / 16;
         char* tmp = nullptr;
         HIPCHK(c, hipMalloc((void**)&tmp, (size_t)mtl * 16 * K * 2));
-        launch_rmsnorm_packed(c->cfg.dtype, X, norm_w, tmp, M, mtl, K, eps, c->stream);        // norm_w == null: re-layout only
-        a.X = tmp; a.xpacked = 3; a.mtiles = mtl; a.norm_w = nullptr;
+        run_rmsnorm(c, NormArgs{const_cast<void*>(X), norm_w, tmp, nullptr, M, K, eps, ACT_TILES32, mtl, nullptr, 0});        // norm_w == null: re-layout only
+        a.X = tmp; a.xpacked = ACT_TILES32; a.mtiles = mtl; a.norm_w = nullptr;
         if (!wstat_supported(a, epi)) { hipFree(wp); hipFree(tmp); return fail(c, -1, "rdx_gemm_test: shape not supported by wstat_k"); }
         launch_wstat(c->cfg.dtype, a, epi, c->stream);
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipGetLastError());
         hipFree(wp); hipFree(tmp);
-        return 0;
+        return take_unsupported(c);
     }
     if (force == 7) {         // the encoder's many-row kernel (wsgemm.hip), tile shape via RDX_WS_CFG
         ConvGeom cg0;
@@ -363,7 +364,7 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
     } else {
         if (a.norm_w) {
             HIPCHK(c, hipMalloc(&xn, (size_t)M * K * 2));
-            launch_rmsnorm(c->cfg.dtype, X, norm_w, xn, M, K, eps, c->stream);
+            run_rmsnorm(c, NormArgs{const_cast<void*>(X), norm_w, xn, nullptr, M, K, eps, ACT_ROWS, 0, nullptr, 0});
             a.X = xn; a.norm_w = nullptr;
         }
         ConvGeom cg;
@@ -379,7 +380,7 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
     HIPCHK(c, hipGetLastError());
     hipFree(wp);
     if (xn) hipFree(xn);
-    return 0;
+    return take_unsupported(c);
 }
 
 // the lm_head epilogue (logits + per-tile argmax partials) of the weight-streaming kernels on a bare GEMM: what the decode

@@ -1,5 +1,5 @@
-// librdx_hooks.so, second unit: the decoder's 3-16-row and row-block GEMM kernels on caller data (include/rdx_dec_hooks.h;
-// tests/test_gpu_decoder_gemms.py). Every hook packs the caller's fp32 weight with the production packer, allocates its own temporaries (the test
+// librdx_hooks.so, second unit: the decoder's 3-16-row and row-block GEMM kernels and its RMSNorm on caller data (include/rdx_dec_hooks.h;
+// tests/test_gpu_decoder_gemms.py, tests/test_gpu_rmsnorm.py). Every hook packs the caller's fp32 weight with the production packer, allocates its own temporaries (the test
 // engines have no decoder: c->kslab / c->dxs / c->dxn do not exist), asks the production *_supported predicate BEFORE anything is launched on the
 // caller's outputs, and calls the production launch_* functions unchanged. Temporaries the kernels only partly write are filled with 0xff bytes
 // (NaN in both model dtypes and in fp32) first.
@@ -40,14 +40,19 @@ int reduce_partials(rdx_ctx* c, const GemmArgs& a, int32_t* argmax_host) {
 bool epi_args_ok(int epi, int N, int n_valid, int ldo, int out_packed, const void* resid, const int32_t* argmax_host) {
     if (epi == EPI_LOGITS && (!argmax_host || n_valid <= 0 || n_valid > N)) return false;
     if (epi == EPI_RESID && !resid) return false;
-    if (epi == EPI_SILU_MUL && out_packed) return true;
+    if (epi == EPI_SILU_MUL && out_packed != ACT_ROWS) return true;
     return ldo >= (epi == EPI_SILU_MUL ? N / 2 : N);
 }
 
 int finish(rdx_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    return 0;
+    return take_unsupported(c);       // a norm combination without a kernel (run_rmsnorm)
+}
+
+// the hooks' RMSNorm / re-layout launches: no slabs unless given
+NormArgs nargs(const void* x, const void* w, void* out, float* xscale, int rows, int H, float eps, ActLayout layout, int mtiles) {
+    return NormArgs{const_cast<void*>(x), w, out, xscale, rows, H, eps, layout, mtiles, nullptr, 0};
 }
 
 }  // namespace
@@ -55,7 +60,7 @@ int finish(rdx_ctx* c) {
 extern "C" int rdx_xstat16_test(rdx_ctx* c, const void* X, const void* norm_w, float eps, const float* W, int M, int N, int epi, int n_valid, void* out,
                                 int ldo, int out_packed, int32_t* argmax_host) {
     if (!c || !X || !norm_w || !W || !out || M <= 0 || N <= 0 || N % 16) return fail(c, -1, "rdx_xstat16_test: bad arguments (N %% 16 == 0)");
-    if (!epi_args_ok(epi, N, n_valid, ldo, out_packed, nullptr, argmax_host) || (out_packed && (out_packed != 1 || epi != EPI_SILU_MUL || N % 64)))
+    if (!epi_args_ok(epi, N, n_valid, ldo, out_packed, nullptr, argmax_host) || (out_packed != ACT_ROWS && (out_packed != ACT_BLK32 || epi != EPI_SILU_MUL || N % 64)))
         return fail(c, -1, "rdx_xstat16_test: epilogue arguments (ldo, n_valid, argmax_host; out_packed 1 with SwiGLU and N %% 64 == 0 only)");
     HIPCHK(c, hipSetDevice(c->device));
     const int K = 4096, nt = N / 16;
@@ -66,7 +71,7 @@ extern "C" int rdx_xstat16_test(rdx_ctx* c, const void* X, const void* norm_w, f
     int* pi = (int*)b.get((size_t)M * nt * 4);
     if (!w.w || !pv || !pi) return fail(c, -2, "rdx_xstat16_test: out of device memory");
     GemmArgs a = gargs(X, K, w, nullptr, out, ldo, M);
-    a.norm_w = norm_w; a.eps = eps; a.out_packed = out_packed;
+    a.norm_w = norm_w; a.eps = eps; a.out_packed = (ActLayout)out_packed;
     if (epi == EPI_LOGITS) { a.n_valid = n_valid; a.part_val = pv; a.part_idx = pi; }
     if (!xstat16_supported(a, epi)) return fail(c, -1, "rdx_xstat16_test: %d x %d (epilogue %d) is not a shape of xstat16_k", M, N, epi);
     launch_pack_weight(c->cfg.dtype, W, w.w, N, K, N, nullptr, c->stream);
@@ -84,10 +89,10 @@ extern "C" int rdx_xrow16_test(rdx_ctx* c, const void* X, int x_packed, const fl
     void* xp = x_packed ? nullptr : b.get((size_t)32 * K * 2);
     if (!w.w || (!x_packed && !xp)) return fail(c, -2, "rdx_xrow16_test: out of device memory");
     GemmArgs a = gargs(x_packed ? X : xp, K, w, nullptr, out, ldo, M);
-    a.resid = resid; a.ldr = N; a.xpacked = 1;
+    a.resid = resid; a.ldr = N; a.xpacked = ACT_BLK32;
     if (!xrow16_supported(a)) return fail(c, -1, "rdx_xrow16_test: %d x %d x %d is not a shape of xrow16_k", M, N, K);
     launch_pack_weight(c->cfg.dtype, W, w.w, N, K, N, nullptr, c->stream);
-    if (!x_packed) launch_rmsnorm_packed32(c->cfg.dtype, const_cast<void*>(X), nullptr, xp, M, K, 0.f, 1, nullptr, 0, c->stream);      // w = null: re-layout only
+    if (!x_packed) run_rmsnorm(c, nargs(X, nullptr, xp, nullptr, M, K, 0.f, ACT_BLK32, 0));      // w = null: re-layout only
     launch_xrow16(c->cfg.dtype, a, c->stream);
     return finish(c);
 }
@@ -95,7 +100,7 @@ extern "C" int rdx_xrow16_test(rdx_ctx* c, const void* X, int x_packed, const fl
 extern "C" int rdx_xstat_blk_test(rdx_ctx* c, const void* X, const void* norm_w, float eps, const float* W, const void* resid, int M, int N, int epi,
                                   int n_valid, void* out, int ldo, int out_packed, void* xp_out, int32_t* argmax_host) {
     if (!c || !X || !W || !out || M <= 0 || M > 192 || N <= 0 || N % 16) return fail(c, -1, "rdx_xstat_blk_test: bad arguments (M <= 192, N %% 16 == 0)");
-    if (!epi_args_ok(epi, N, n_valid, ldo, out_packed, resid, argmax_host) || (out_packed && (out_packed != 3 || epi != EPI_SILU_MUL || N % 64)))
+    if (!epi_args_ok(epi, N, n_valid, ldo, out_packed, resid, argmax_host) || (out_packed != ACT_ROWS && (out_packed != ACT_TILES32 || epi != EPI_SILU_MUL || N % 64)))
         return fail(c, -1, "rdx_xstat_blk_test: epilogue arguments (ldo, resid, n_valid, argmax_host; out_packed 3 with SwiGLU and N %% 64 == 0 only)");
     HIPCHK(c, hipSetDevice(c->device));
     const int K = 4096, nt = N / 16, mtl = (M + 15) / 16;
@@ -108,13 +113,13 @@ extern "C" int rdx_xstat_blk_test(rdx_ctx* c, const void* X, const void* norm_w,
     int* pi = (int*)b.get((size_t)M * nt * 4);
     if (!w.w || !xp || !pv || !pi) return fail(c, -2, "rdx_xstat_blk_test: out of device memory");
     GemmArgs a = gargs(xp, K, w, nullptr, out, ldo, M);
-    a.xpacked = 3; a.mtiles = mtl; a.out_packed = out_packed;
+    a.xpacked = ACT_TILES32; a.mtiles = mtl; a.out_packed = (ActLayout)out_packed;
     if (epi == EPI_RESID) { a.resid = resid; a.ldr = N; }
     if (epi == EPI_LOGITS) { a.n_valid = n_valid; a.part_val = pv; a.part_idx = pi; }
     if (!xstat_blk_supported(a, epi)) return fail(c, -1, "rdx_xstat_blk_test: %d x %d (epilogue %d) is not a shape of the row-block xstat32_k", M, N, epi);
     launch_pack_weight(c->cfg.dtype, W, w.w, N, K, N, nullptr, c->stream);
     HIPCHK(c, hipMemsetAsync(xp, 0xff, xpb, c->stream));
-    launch_rmsnorm_packed(c->cfg.dtype, X, norm_w, xp, M, mtl, K, eps, c->stream);
+    run_rmsnorm(c, nargs(X, norm_w, xp, nullptr, M, K, eps, ACT_TILES32, mtl));
     launch_xstat_blk(c->cfg.dtype, a, epi, c->stream);
     if (xp_out) HIPCHK(c, hipMemcpyAsync(xp_out, xp, xpb, hipMemcpyDeviceToDevice, c->stream));
     if (int rc = finish(c)) return rc;
@@ -125,7 +130,7 @@ extern "C" int rdx_xsplit_blk_test(rdx_ctx* c, const void* X, const float* W, vo
                                    void* xn_out) {
     if (!c || !X || !W || M <= 0 || M > 192 || N <= 0 || N % 16 || (!slab_out && !x_resid)) return fail(c, -1, "rdx_xsplit_blk_test: bad arguments");
     if ((x_resid != nullptr) != (xn_out != nullptr) || (x_resid && (!norm_w || N != 4096)))
-        return fail(c, -1, "rdx_xsplit_blk_test: the slab combine (x_resid, norm_w, xn_out together) is launch_rmsnorm_packed_slab: N = 4096 only");
+        return fail(c, -1, "rdx_xsplit_blk_test: the slab combine (x_resid, norm_w, xn_out together) is the 4096-wide RMSNorm: N = 4096 only");
     HIPCHK(c, hipSetDevice(c->device));
     const int K = 11008, mtl = (M + 15) / 16, groups = 4;
     const size_t xpb = (size_t)mtl * 16 * K * 2, sb = (size_t)groups * 16 * mtl * N * 4;
@@ -136,22 +141,22 @@ extern "C" int rdx_xsplit_blk_test(rdx_ctx* c, const void* X, const float* W, vo
     float* slab = (float*)b.get(sb);
     if (!w.w || !xp || !slab) return fail(c, -2, "rdx_xsplit_blk_test: out of device memory");
     GemmArgs a = gargs(xp, K, w, nullptr, nullptr, N, M);
-    a.xpacked = 3; a.mtiles = mtl;
+    a.xpacked = ACT_TILES32; a.mtiles = mtl;
     if (!xsplit_blk_supported(a)) return fail(c, -1, "rdx_xsplit_blk_test: %d x %d is not a shape of the row-block xsplit32_k", M, N);
     launch_pack_weight(c->cfg.dtype, W, w.w, N, K, N, nullptr, c->stream);
     HIPCHK(c, hipMemsetAsync(xp, 0xff, xpb, c->stream));
     HIPCHK(c, hipMemsetAsync(slab, 0xff, sb, c->stream));
-    launch_rmsnorm_packed(c->cfg.dtype, X, nullptr, xp, M, mtl, K, eps, c->stream);       // w = null: re-layout only
+    run_rmsnorm(c, nargs(X, nullptr, xp, nullptr, M, K, eps, ACT_TILES32, mtl));       // w = null: re-layout only
     launch_xsplit_blk(c->cfg.dtype, a, slab, c->stream);
     if (slab_out) HIPCHK(c, hipMemcpyAsync(slab_out, slab, sb, hipMemcpyDeviceToDevice, c->stream));
-    if (x_resid) launch_rmsnorm_packed_slab(c->cfg.dtype, x_resid, norm_w, xn_out, M, mtl, eps, slab, groups, c->stream);
+    if (x_resid) run_rmsnorm(c, NormArgs{x_resid, norm_w, xn_out, nullptr, M, N, eps, ACT_TILES32, mtl, slab, groups});
     return finish(c);
 }
 
 extern "C" int rdx_xstat_blk8_test(rdx_ctx* c, const void* X, const void* norm_w, float eps, const float* W, int M, int N, int epi, int n_valid, void* out,
                                    int ldo, int out_packed, void* x8_out, float* xscale_out, int32_t* argmax_host) {
     if (!c || !X || !norm_w || !W || !out || M <= 0 || M > 128 || N <= 0 || N % 16) return fail(c, -1, "rdx_xstat_blk8_test: bad arguments (norm_w, M <= 128, N %% 16 == 0)");
-    if (!epi_args_ok(epi, N, n_valid, ldo, out_packed, nullptr, argmax_host) || (out_packed && (out_packed != 2 || epi != EPI_SILU_MUL || N % 128)))
+    if (!epi_args_ok(epi, N, n_valid, ldo, out_packed, nullptr, argmax_host) || (out_packed != ACT_ROWS && (out_packed != ACT_BLK64 || epi != EPI_SILU_MUL || N % 128)))
         return fail(c, -1, "rdx_xstat_blk8_test: epilogue arguments (ldo, n_valid, argmax_host; out_packed 2 with SwiGLU and N %% 128 == 0 only)");
     HIPCHK(c, hipSetDevice(c->device));
     const int K = 4096, nt = N / 16, mtl = (M + 15) / 16, NB = (mtl + 1) / 2;
@@ -166,11 +171,11 @@ extern "C" int rdx_xstat_blk8_test(rdx_ctx* c, const void* X, const void* norm_w
     int* pi = (int*)b.get((size_t)M * nt * 4);
     if (!w.w8 || !w.scale || !x8 || !xs || !pv || !pi) return fail(c, -2, "rdx_xstat_blk8_test: out of device memory");
     GemmArgs a = gargs(x8, K, w, nullptr, out, ldo, M);
-    a.xpacked = 4; a.xscale = xs; a.xgroups = 1; a.mtiles = mtl; a.out_packed = out_packed;
+    a.xpacked = ACT_BLK64_E4M3; a.xscale = xs; a.xgroups = 1; a.mtiles = mtl; a.out_packed = (ActLayout)out_packed;
     if (epi == EPI_LOGITS) { a.n_valid = n_valid; a.part_val = pv; a.part_idx = pi; }
     if (!xstat_blk8_supported(a, epi)) return fail(c, -1, "rdx_xstat_blk8_test: %d x %d (epilogue %d) is not a shape of the fp8 row-block xstat32_k", M, N, epi);
     launch_pack_weight_fp8(c->cfg.dtype, W, w.w8, w.scale, nullptr, N, K, N, c->stream);
-    launch_rmsnorm_blk_fp8(c->cfg.dtype, const_cast<void*>(X), norm_w, x8, xs, M, mtl, eps, nullptr, 0, c->stream);
+    run_rmsnorm(c, nargs(X, norm_w, x8, xs, M, K, eps, ACT_BLK64_E4M3, mtl));
     launch_xstat_blk8(c->cfg.dtype, a, epi, c->stream);
     if (x8_out) HIPCHK(c, hipMemcpyAsync(x8_out, x8, x8b, hipMemcpyDeviceToDevice, c->stream));
     if (xscale_out) HIPCHK(c, hipMemcpyAsync(xscale_out, xs, (size_t)NB * 32 * 4, hipMemcpyDeviceToDevice, c->stream));
@@ -183,7 +188,7 @@ extern "C" int rdx_xsplit_blk8_test(rdx_ctx* c, const void* X, const float* W, v
     if (!c || !X || !W || M <= 0 || M > 128 || N <= 0 || N % 16 || !(K == 4096 || K == 11008) || (!slab_out && !x_resid))
         return fail(c, -1, "rdx_xsplit_blk8_test: bad arguments (M <= 128, N %% 16 == 0, K 4096 or 11008)");
     if ((x_resid != nullptr) != (x8_out != nullptr) || (x_resid != nullptr) != (xscale_out != nullptr) || (x_resid && (!norm_w || N != 4096)))
-        return fail(c, -1, "rdx_xsplit_blk8_test: the slab combine (x_resid, norm_w, x8_out, xscale_out together) is launch_rmsnorm_blk_fp8: N = 4096 only");
+        return fail(c, -1, "rdx_xsplit_blk8_test: the slab combine (x_resid, norm_w, x8_out, xscale_out together) is the 4096-wide RMSNorm: N = 4096 only");
     HIPCHK(c, hipSetDevice(c->device));
     const int mtl = (M + 15) / 16, NB = (mtl + 1) / 2;
     const size_t xpb = (size_t)NB * 32 * K * 2;
@@ -194,7 +199,7 @@ extern "C" int rdx_xsplit_blk8_test(rdx_ctx* c, const void* X, const float* W, v
     char* xp = (char*)b.get(xpb);
     if (!w.w8 || !w.scale || !xp) return fail(c, -2, "rdx_xsplit_blk8_test: out of device memory");
     GemmArgs a = gargs(xp, K, w, nullptr, nullptr, N, M);
-    a.xpacked = 2; a.mtiles = mtl;
+    a.xpacked = ACT_BLK64; a.mtiles = mtl;
     const int groups = xsplit_blk8_groups(a);
     if (!groups) return fail(c, -1, "rdx_xsplit_blk8_test: %d x %d x %d is not a shape of the fp8 row-block xsplit32_k", M, N, K);
     const size_t sb = (size_t)groups * 32 * NB * N * 4;
@@ -202,11 +207,20 @@ extern "C" int rdx_xsplit_blk8_test(rdx_ctx* c, const void* X, const float* W, v
     if (!slab) return fail(c, -2, "rdx_xsplit_blk8_test: out of device memory");
     launch_pack_weight_fp8(c->cfg.dtype, W, w.w8, w.scale, nullptr, N, K, N, c->stream);
     HIPCHK(c, hipMemsetAsync(slab, 0xff, sb, c->stream));
-    for (int blk = 0; blk < NB; ++blk)      // every 32-row block in the 64-deep order of the fp8 kernels, rows past M zero: the re-layout launch of rdx_gemm_test force 6
-        launch_rmsnorm_packed32(c->cfg.dtype, (char*)const_cast<void*>(X) + (size_t)blk * 32 * K * 2, nullptr, xp + (size_t)blk * 32 * K * 2,
-                                std::min(32, M - 32 * blk), K, eps, 2, nullptr, 0, c->stream);
+    for (int blk = 0; blk < NB; ++blk)      // every 32-row block in the 64-deep order of the fp8 kernels, rows past M zero: the re-layout launch of rdx_gemm_test's fp8 K-split mode
+        run_rmsnorm(c, nargs((const char*)X + (size_t)blk * 32 * K * 2, nullptr, xp + (size_t)blk * 32 * K * 2, nullptr, std::min(32, M - 32 * blk), K, eps, ACT_BLK64, 0));
     launch_xsplit_blk8(c->cfg.dtype, a, slab, c->stream);
     if (slab_out) HIPCHK(c, hipMemcpyAsync(slab_out, slab, sb, hipMemcpyDeviceToDevice, c->stream));
-    if (x_resid) launch_rmsnorm_blk_fp8(c->cfg.dtype, x_resid, norm_w, x8_out, xscale_out, M, mtl, eps, slab, groups, c->stream);
+    if (x_resid) run_rmsnorm(c, NormArgs{x_resid, norm_w, x8_out, xscale_out, M, N, eps, ACT_BLK64_E4M3, mtl, slab, groups});
+    return finish(c);
+}
+
+extern "C" int rdx_rmsnorm_test(rdx_ctx* c, void* x, const void* w, float eps, int rows, int H, int layout, int mtiles, const float* slab, int groups, void* out,
+                                long long out_bytes, float* xscale, int xscale_n) {
+    if (!c || !x || !out || out_bytes <= 0 || (xscale && xscale_n <= 0)) return fail(c, -1, "rdx_rmsnorm_test: bad arguments");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemsetAsync(out, 0xff, (size_t)out_bytes, c->stream));
+    if (xscale) HIPCHK(c, hipMemsetAsync(xscale, 0xff, (size_t)xscale_n * 4, c->stream));
+    run_rmsnorm(c, NormArgs{x, w, out, xscale, rows, H, eps, (ActLayout)layout, mtiles, slab, groups});
     return finish(c);
 }

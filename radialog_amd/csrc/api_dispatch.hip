@@ -53,26 +53,26 @@ GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
 
 GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     GemmArgs a = unit_args(c, L, u, B);
-    if (u == UNIT_GATE_UP) a.out_packed = 1;
-    if (u == UNIT_O || u == UNIT_DOWN) a.xpacked = 1;
+    if (u == UNIT_GATE_UP) a.out_packed = ACT_BLK32;
+    if (u == UNIT_O || u == UNIT_DOWN) a.xpacked = ACT_BLK32;
     return a;
 }
 
 GemmArgs blk_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     GemmArgs a = unit_args(c, L, u, B);
-    a.xpacked = 3; a.mtiles = (B + 15) / 16; a.out_packed = u == UNIT_GATE_UP ? 3 : 0;
+    a.xpacked = ACT_TILES32; a.mtiles = (B + 15) / 16; a.out_packed = u == UNIT_GATE_UP ? ACT_TILES32 : ACT_ROWS;
     return a;
 }
 
 GemmArgs blk8_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     GemmArgs a = unit_args(c, L, u, B);
-    a.xpacked = (u == UNIT_O || u == UNIT_DOWN) ? 2 : 4; a.mtiles = (B + 15) / 16; a.out_packed = u == UNIT_GATE_UP ? 2 : 0;     // out 2: the 64-deep order, one 32-row block per 32 rows
+    a.xpacked = (u == UNIT_O || u == UNIT_DOWN) ? ACT_BLK64 : ACT_BLK64_E4M3; a.mtiles = (B + 15) / 16; a.out_packed = u == UNIT_GATE_UP ? ACT_BLK64 : ACT_ROWS;
     a.xscale = c->dxs; a.xgroups = 1;
     return a;
 }
 
 GemmArgs ksplit_args(GemmArgs a) {
-    a.xpacked = (a.W8 && a.wscale) ? 2 : 1;
+    a.xpacked = (a.W8 && a.wscale) ? ACT_BLK64 : ACT_BLK32;
     return a;
 }
 
@@ -81,19 +81,19 @@ GemmArgs prenormed(rdx_ctx* c, GemmArgs a) {
     return a;
 }
 
+void run_rmsnorm(rdx_ctx* c, const NormArgs& n) {
+    if (launch_rmsnorm(c->cfg.dtype, n, c->stream)) return;
+    char buf[200];
+    snprintf(buf, sizeof(buf), "RMSNorm: no kernel for %d x %d rows into layout %d (%d row tiles, %d slab groups%s)", n.rows, n.H, (int)n.layout, n.mtiles,
+             n.slab ? n.groups : 0, n.w ? "" : ", no weight");
+    c->unsupported = buf;
+}
+
 GemmArgs norm_in_front(rdx_ctx* c, GemmArgs a) {
-    const int dt = c->cfg.dtype;
-    void* x = const_cast<void*>(a.X);
     // a K-split projection before this unit left its residual epilogue to this RMSNorm: x += T(sum of slabs)
-    const int pend = (x == c->dx) ? c->pend_groups : 0;
+    const int pend = (a.X == c->dx) ? c->pend_groups : 0;
     if (pend) c->pend_groups = 0;
-    const float* slab = pend ? c->kslab : nullptr;
-    if (a.xpacked == 4 && a.mtiles) launch_rmsnorm_blk_fp8(dt, x, a.norm_w, c->dxn, c->dxs, a.M, a.mtiles, a.eps, slab, pend, c->stream);
-    else if (a.xpacked == 4) launch_rmsnorm_packed32_fp8(dt, x, a.norm_w, c->dxn, c->dxs, a.M, a.K, a.eps, slab, pend, c->stream);
-    else if (a.xpacked == 3 && pend) launch_rmsnorm_packed_slab(dt, x, a.norm_w, c->dxn, a.M, a.mtiles, a.eps, slab, pend, c->stream);
-    else if (a.xpacked == 3) launch_rmsnorm_packed(dt, x, a.norm_w, c->dxn, a.M, a.mtiles, a.K, a.eps, c->stream);
-    else if (a.xpacked || pend) launch_rmsnorm_packed32(dt, x, a.norm_w, c->dxn, a.M, a.K, a.eps, a.xpacked, slab, pend, c->stream);
-    else launch_rmsnorm(dt, x, a.norm_w, c->dxn, a.M, a.K, a.eps, c->stream);
+    run_rmsnorm(c, NormArgs{const_cast<void*>(a.X), a.norm_w, c->dxn, c->dxs, a.M, a.K, a.eps, a.xpacked, a.mtiles, pend ? c->kslab : nullptr, pend});
     return prenormed(c, a);
 }
 
@@ -115,9 +115,9 @@ GemmArgs skinny_prenorm(rdx_ctx* c, GemmArgs a, int epi) {
     if (skinny_fits_lds(a.M, a.K) && !(a.M >= xs_min_rows() && c->kslab && xs)) return a;
     if (xs && a.W8 && a.wscale) {
         // fp8 weights: the normalised rows are quantised to e4m3 (one scale per row) in the consumer's 64-deep fragment order: fp8 x fp8 MFMA
-        a.xpacked = 4; a.xscale = c->dxs; a.xgroups = 1;
+        a.xpacked = ACT_BLK64_E4M3; a.xscale = c->dxs; a.xgroups = 1;
     } else if (xs) {
-        a.xpacked = 1;       // the normalised rows go straight into the consumer's register-fragment order
+        a.xpacked = ACT_BLK32;       // the normalised rows go straight into the consumer's register-fragment order
     }
     return norm_in_front(c, a);
 }
@@ -128,7 +128,7 @@ void skinny(rdx_ctx* c, GemmArgs a, int epi) {
         // fp8-only weights: the kernels that read e4m3 are the batch <= 2 GEMV with LDS-staged activations (expanded in registers) and, from
         // batch 3, the activation-stationary fp8 x fp8 kernel (K = 4096, many tiles). Anything else has no kernel in this mode.
         const bool gemv8 = skinny_fits_lds(a.M, a.K) && a.K % 64 == 0 && a.M < xs_min_rows();
-        const bool xs8 = a.xpacked == 4 && xstat32_supported(a, epi);
+        const bool xs8 = a.xpacked == ACT_BLK64_E4M3 && xstat32_supported(a, epi);
         if (!gemv8 && !xs8) {
             char buf[200];
             snprintf(buf, sizeof(buf), "fp8 weights: no kernel for a %d x %d x %d projection at this batch (batch <= 2: M K <= 16 Ki; batch 3-32: K = 4096)", a.M, a.N, a.K);

@@ -92,6 +92,10 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
     launch_embed_splice(dt, ids, c->d_img_pos, c->embed, f.vocab, c->pimg, 32, c->px, B, T, H, qformer_embs ? 1 : 0, s);
 
     const bool fp8 = fp8_weights(c->ll[0].wqkv);
+    // the RMSNorm of the residual stream px in the layout the projection behind it reads; `pend` slab groups of a K-split down_proj are folded in first
+    auto prompt_norm = [&](const void* w, void* out, ActLayout layout, int mtiles, int pend) {
+        run_rmsnorm(c, NormArgs{c->px, w, out, c->pxs, (int)M, H, f.rms_eps, layout, mtiles, pend ? c->pslab : nullptr, pend});
+    };
     if (B > 32 && !blk64_ok(c, B)) return fail(c, -8, "rdx_prefill: more than 32 rows per context need the Vicuna-7B widths (hidden 4096, inter 11008: the row-block decode family)");
     if (fp8) {
         // fp8 weights (BASELINE configs[4]): every projection of the prompt is an fp8 x fp8 MFMA GEMM (gemm8.hip) over e4m3 activations with one
@@ -107,13 +111,13 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
                 if (!gemm8_supported(a, epi)) { c->unsupported = "fp8 weights: prefill projection shape not supported by gemm8 (N % 16, K % 64)"; return; }
                 launch_gemm8(dt, a, epi, s);
             };
-            launch_rmsnorm_fp8(dt, c->px, L.attn_norm, c->pxq, c->pxs, (int)M, H, f.rms_eps, s);
+            prompt_norm(L.attn_norm, c->pxq, ACT_ROWS_E4M3, 0, 0);
             g8(L.wqkv, H, 1, c->pqkv, c->ld.qkv_ld, nullptr, EPI_NONE);
             launch_rope_kv_prefill(dt, c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq, kc, vc, B, T, keep, s);
             launch_attention(dt, 128, prefill_attn_args(c, B, T, keep, l), s);
             launch_quant_rows(dt, c->patt, H, c->pxq, c->pxs, (int)M, H, 2, s);
             g8(L.wo, H, 2, c->px, H, c->px, EPI_RESID);
-            launch_rmsnorm_fp8(dt, c->px, L.mlp_norm, c->pxq, c->pxs, (int)M, H, f.rms_eps, s);
+            prompt_norm(L.mlp_norm, c->pxq, ACT_ROWS_E4M3, 0, 0);
             g8(L.wgu, H, 1, c->pgu, f.inter, nullptr, EPI_SILU_MUL);
             launch_quant_rows(dt, c->pgu, f.inter, c->pxq, c->pxs, (int)M, f.inter, 4, s);
             g8(L.wdown, f.inter, 4, c->px, H, c->px, EPI_RESID);
@@ -129,13 +133,13 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
     constexpr int ws_minpad = 24;
     bool ws = (int)M > 32 && (int)M <= ws_maxm && (int)((M + 127) / 128 * 128 - M) >= ws_minpad;
     if (ws) {
-        GemmArgs p = gargs(c->pxn, H, c->ll[0].wqkv, nullptr, c->pqkv, c->ld.qkv_ld, (int)M); p.xpacked = 3; p.mtiles = mtl;
-        GemmArgs d = gargs(c->pgu, f.inter, c->ll[0].wdown, nullptr, c->px, H, (int)M); d.xpacked = 3; d.mtiles = mtl;
+        GemmArgs p = gargs(c->pxn, H, c->ll[0].wqkv, nullptr, c->pqkv, c->ld.qkv_ld, (int)M); p.xpacked = ACT_TILES32; p.mtiles = mtl;
+        GemmArgs d = gargs(c->pgu, f.inter, c->ll[0].wdown, nullptr, c->px, H, (int)M); d.xpacked = ACT_TILES32; d.mtiles = mtl;
         ws = wstat_supported(p, EPI_NONE) && wstat_supported(d, EPI_RESID);
     }
     auto prompt_gemm = [&](GemmArgs a, int epi, bool packed_out) {
         if (!ws) { run_gemm(c, a, epi); return; }
-        a.xpacked = 3; a.mtiles = mtl; a.out_packed = packed_out ? 3 : 0;
+        a.xpacked = ACT_TILES32; a.mtiles = mtl; a.out_packed = packed_out ? ACT_TILES32 : ACT_ROWS;
         // round 5: up to 192 rows the K = 4096 projections run activation-stationary in row blocks of 32 whose workgroups share an XCD's L2
         // (xstat32_k<.., BLK>: the weights cross each CU once per row block instead of the activations once per 32 columns); down_proj
         // (K = 11008) and longer prompts keep the weight-stationary kernel
@@ -145,13 +149,13 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
     // round 5: down_proj of a prompt of <= 128 rows (<= 4 row blocks: 160 rows measured 55.9 us against wstat_k 49.5; 64 rows 3.96 -> 3.69 ms per prefill) K-split over 4 workgroups per tile into fp32 slabs (xsplit32_k<.., BLK>), combined (+ residual) by the next
     // layer's RMSNorm -- after the last layer by one more norm launch whose packed output nobody reads
     int pend = 0;
+    const ActLayout xl = ws ? ACT_TILES32 : ACT_ROWS;       // what the norms write and the projections read
     for (int l = 0; l < f.layers; ++l) {
         const LlamaLayer& L = c->ll[l];
         void* kc = kv_ptr(c, c->kcache, l);
         void* vc = kv_ptr(c, c->vcache, l);
-        if (ws && pend) { launch_rmsnorm_packed_slab(dt, c->px, L.attn_norm, c->pxn, (int)M, mtl, f.rms_eps, c->pslab, pend, s); pend = 0; }
-        else if (ws) launch_rmsnorm_packed(dt, c->px, L.attn_norm, c->pxn, (int)M, mtl, H, f.rms_eps, s);
-        else launch_rmsnorm(dt, c->px, L.attn_norm, c->pxn, (int)M, H, f.rms_eps, s);
+        prompt_norm(L.attn_norm, c->pxn, xl, mtl, pend);
+        pend = 0;
         { GemmArgs a = gargs(c->pxn, H, L.wqkv, nullptr, c->pqkv, c->ld.qkv_ld, (int)M); a.N = L.wqkv.Npad; prompt_gemm(a, EPI_NONE, false); }
         // new K/V rows land behind the kept slots
         launch_rope_kv_prefill(dt, c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq,
@@ -160,15 +164,14 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
         at.o_packed_mt = ws ? mtl : 0;
         launch_attention(dt, 128, at, s);
         { GemmArgs a = gargs(c->patt, H, L.wo, nullptr, c->px, H, (int)M); a.resid = c->px; a.ldr = H; prompt_gemm(a, EPI_RESID, false); }
-        if (ws) launch_rmsnorm_packed(dt, c->px, L.mlp_norm, c->pxn, (int)M, mtl, H, f.rms_eps, s);
-        else launch_rmsnorm(dt, c->px, L.mlp_norm, c->pxn, (int)M, H, f.rms_eps, s);
+        prompt_norm(L.mlp_norm, c->pxn, xl, mtl, 0);
         { GemmArgs a = gargs(c->pxn, H, L.wgu, nullptr, c->pgu, f.inter, (int)M); prompt_gemm(a, EPI_SILU_MUL, true); }
         { GemmArgs a = gargs(c->pgu, f.inter, L.wdown, nullptr, c->px, H, (int)M); a.resid = c->px; a.ldr = H;
-          GemmArgs b = a; b.xpacked = 3; b.mtiles = mtl;
+          GemmArgs b = a; b.xpacked = ACT_TILES32; b.mtiles = mtl;
           if (ws && c->prompt_blk && M <= 128 && xsplit_blk_supported(b)) { launch_xsplit_blk(dt, b, c->pslab, s); pend = 4; }
           else prompt_gemm(a, EPI_RESID, false); }
     }
-    if (pend) launch_rmsnorm_packed_slab(dt, c->px, c->ll[0].attn_norm, c->pxn, (int)M, mtl, f.rms_eps, c->pslab, pend, s);
+    if (pend) prompt_norm(c->ll[0].attn_norm, c->pxn, xl, mtl, pend);
     }
     launch_gather_last(dt, c->px, c->datt, B, T, H, s);      // datt doubles as the [B][H] last-position buffer
     lm_head_and_greedy(c, c->datt, B, logits, nullptr, 0, /*advance=*/0);
@@ -199,7 +202,7 @@ static void step_blk(rdx_ctx* c, int B) {
         const LlamaLayer* L = &c->ll[l];
         launch_xstat_blk(dt, norm_in_front(c, blk_unit(c, L, UNIT_QKV, B)), EPI_NONE, s);
         DecAttnArgs at = dec_attn_args(c, l);
-        at.out_packed = 1; at.out_mt = (B + 15) / 16;
+        at.out_packed = ACT_TILES32; at.out_mt = (B + 15) / 16;
         launch_decode_attention(dt, at, B, s);
         launch_xstat_blk(dt, blk_unit(c, L, UNIT_O, B), EPI_RESID, s);
         launch_xstat_blk(dt, norm_in_front(c, blk_unit(c, L, UNIT_GATE_UP, B)), EPI_SILU_MUL, s);
@@ -221,7 +224,7 @@ static void step_blk8(rdx_ctx* c, int B) {
         const LlamaLayer* L = &c->ll[l];
         launch_xstat_blk8(dt, norm_in_front(c, blk8_unit(c, L, UNIT_QKV, B)), EPI_NONE, s);
         DecAttnArgs at = dec_attn_args(c, l);
-        at.out_packed = 2;                       // the 64-deep order, one 32-row block per 32 rows
+        at.out_packed = ACT_BLK64;
         launch_decode_attention(dt, at, B, s);
         ksplit(blk8_unit(c, L, UNIT_O, B));
         launch_xstat_blk8(dt, norm_in_front(c, blk8_unit(c, L, UNIT_GATE_UP, B)), EPI_SILU_MUL, s);
@@ -238,7 +241,7 @@ static void step_xs16(rdx_ctx* c, int B) {
         const LlamaLayer* L = &c->ll[l];
         launch_xstat16(dt, xs16_unit(c, L, UNIT_QKV, B), EPI_NONE, s);
         DecAttnArgs at = dec_attn_args(c, l);
-        at.out_packed = 1;
+        at.out_packed = ACT_BLK32;
         launch_decode_attention(dt, at, B, s);
         launch_xrow16(dt, xs16_unit(c, L, UNIT_O, B), s);
         launch_xstat16(dt, xs16_unit(c, L, UNIT_GATE_UP, B), EPI_SILU_MUL, s);
@@ -260,7 +263,7 @@ static void attn_oproj(rdx_ctx* c, int l, int B) {
     // its residual epilogue folded into the RMSNorm in front of gate/up (xsplit32_k)
     const GemmArgs ap = ksplit_args(ao);
     const int kg = (B >= xs_min_rows() && c->kslab) ? xsplit32_groups(ap) : 0;
-    at.out_packed = kg > 0 ? ap.xpacked : 0;
+    at.out_packed = kg > 0 ? ap.xpacked : ACT_ROWS;
     launch_decode_attention(dt, at, B, c->stream);
     if (kg) launch_ksplit(c, ap);
     else skinny(c, ao, EPI_RESID);
@@ -275,7 +278,7 @@ static void step_generic(rdx_ctx* c, int B) {
         attn_oproj(c, l, B);
         const bool split = down_split_ok(c, L, B);
         GemmArgs gu = unit_args(c, &L, UNIT_GATE_UP, B);
-        gu.out_packed = split ? ksplit_args(unit_args(c, &L, UNIT_DOWN, B)).xpacked : 0;         // down_proj's K-split reads the SwiGLU output fragment-packed
+        gu.out_packed = split ? ksplit_args(unit_args(c, &L, UNIT_DOWN, B)).xpacked : ACT_ROWS;         // down_proj's K-split reads the SwiGLU output fragment-packed
         skinny(c, gu, EPI_SILU_MUL);
         launch_down(c, L, B, split);
     }

@@ -7,12 +7,6 @@ namespace rdx {
 
 // ---- e4m3 activation quantisation of the fp8 path (gemm8.hip, xstat32.hip): q = RNE_e4m3(x * (448 / absmax)), scale = absmax / 448 ----------
 // (the arithmetic of pack_weight_fp8_k and of the oracle's fake quantisation: an all-zero range gets scale 1)
-// where the 8 fp8 bytes of elements i .. i + 8 of row `row` go. PACK 5: row-major [rows][H]. PACK 4: the 32-row block in the 64-deep fragment
-// order xstat32_k<W8, A8> reads, [chunk j = i / 64][row tile mt][lane (g = (i % 64) / 16, r = row % 16)][16 bytes], this piece's half i & 8
-template <int PACK> __device__ __forceinline__ unsigned char* dst8(unsigned char* out8, size_t row, int i, int H) {
-    if (PACK == 5) return out8 + row * H + i;
-    return out8 + ((size_t)(((i >> 6) * 2 + (int)(row >> 4)) * 64 + ((i & 63) >> 4) * 16 + (int)(row & 15)) << 4) + (i & 8);
-}
 
 // Row-wise e4m3 quantisation of model-dtype activations [rows][K] (row stride ldx) into row-major bytes [rows][K] + scales [rows][G]:
 // K group q = 128-deep blocks [NB q / G, NB (q + 1) / G), NB = K / 128 (G <= 4; K % 128 == 0), one absmax / 448 scale per (row, group). One
@@ -56,39 +50,35 @@ void launch_quant_rows(int dtype, const void* x, long ldx, void* out8, float* xs
 }
 
 // ---- LlamaRMSNorm (modeling_llama_imgemb.py:85-93): fp32 statistics, (x*rstd).to(T), then weight*h in T ---------------
-// PACK != 0 (batch-32 decode, consumer xstat32_k): the output is written in the MFMA B-operand fragment order of the 32-row
-// block, [fragment f][row tile mt][lane (g, r)][8], so that a wave's activation fragment is one contiguous KiB. A thread's 8
-// elements k = i .. i + 8 of row m are exactly one lane's piece: PACK 1 (32-deep fragments): f = i / 32, g = (i % 32) / 8;
-// PACK 2 (the fp8 weights' 64-deep chunks): f = 2 (i / 64) + (i % 16) / 8, g = (i % 64) / 16. Rows >= n_rows are zero-filled.
-// PACK 3 (one prompt's prefill, consumer wstat_k): the PACK 1 order over `groups` row tiles instead of 2 (no slabs on that path).
-// PACK 4 / 5 (fp8 path): the normalised row is quantised to e4m3 with ONE absmax / 448 scale (xscale[row]); 5 = row-major bytes (prefill,
-// gemm8.hip), 4 = the 32-row block in the 64-deep fragment order (batch 3-32 decode, xstat32_k<W8, A8>); rows >= n_rows are zero bytes, scale 1.
-template <typename T, int PACK>
-__global__ __launch_bounds__(256) void rmsnorm_k(const T* x, const T* __restrict__ w, T* __restrict__ out,
-                                                 int H, float eps, int n_rows, const float* __restrict__ slab, int groups, T* xw,
-                                                 float* __restrict__ xscale = nullptr) {
+// One workgroup per row of the output layout L (ActLayout, rdx_kernels.h; act_offset): rows >= n_rows are its zero padding. The e4m3 layouts quantise
+// the normalised row with ONE absmax / 448 scale (xscale[row]). slab: the pending K-split partials [groups][srows][H] are added into x first (written back).
+template <ActLayout L> constexpr bool norm_e4m3 = L == ACT_BLK64_E4M3 || L == ACT_ROWS_E4M3;
+template <typename T, ActLayout L> __device__ __forceinline__ void norm_store(T* out, size_t row, int k, int mtl, int H, typename Vec8<T>::type v, float inv) {
+    if (norm_e4m3<L>) *reinterpret_cast<u2*>(reinterpret_cast<unsigned char*>(out) + act_offset(L, row, k, mtl, H)) = quant8<T>(v, inv);
+    else stg16(out + act_offset(L, row, k, mtl, H), as_u4<T>(v));
+}
+template <typename T, ActLayout L> __device__ __forceinline__ void norm_store_zero(T* out, size_t row, int k, int mtl, int H) {
+    if (norm_e4m3<L>) *reinterpret_cast<u2*>(reinterpret_cast<unsigned char*>(out) + act_offset(L, row, k, mtl, H)) = (u2){0u, 0u};
+    else stg16(out + act_offset(L, row, k, mtl, H), (u4){0u, 0u, 0u, 0u});
+}
+
+// any H, w nullable (re-layout only: the test hooks), any number of slab groups; one 32-row block of slabs (rmsnorm_supported)
+template <typename T, ActLayout L>
+__global__ __launch_bounds__(256) void rmsnorm_k(T* x, const T* __restrict__ w, T* __restrict__ out, int H, float eps, int n_rows,
+                                                 const float* __restrict__ slab, int groups, float* __restrict__ xscale, int mtl) {
     typedef typename Vec8<T>::type V8;
     __shared__ float red[32];
     const size_t row = blockIdx.x;
-    auto dst = [&](int i) -> T* {
-        if (PACK == 0) return out + row * H + i;
-        const int f = PACK != 2 ? (i >> 5) : (2 * (i >> 6) + ((i & 15) >> 3)), g = PACK != 2 ? ((i & 31) >> 3) : ((i & 63) >> 4);
-        return out + ((size_t)((f * (PACK == 3 ? groups : 2) + (int)(row >> 4)) * 64 + g * 16 + (int)(row & 15)) << 3);
-    };
-    if (PACK >= 4 && (int)row >= n_rows) {
-        for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8) *reinterpret_cast<u2*>(dst8<PACK == 4 ? 4 : 5>(reinterpret_cast<unsigned char*>(out), row, i, H)) = (u2){0u, 0u};
-        if (threadIdx.x == 0) xscale[row] = 1.0f;
+    if (L != ACT_ROWS && (int)row >= n_rows) {
+        for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8) norm_store_zero<T, L>(out, row, i, mtl, H);
+        if (norm_e4m3<L> && threadIdx.x == 0) xscale[row] = 1.0f;
         return;
     }
-    if (PACK && PACK < 4 && (int)row >= n_rows) {
-        for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8) stg16(dst(i), (u4){0u, 0u, 0u, 0u});
-        return;
-    }
-    const T* xr = x + row * H;
+    T* xr = x + row * H;
     float ss = 0.f;
     for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8) {
         V8 v = as_vec8<T>(ldg16(xr + i));
-        if (PACK != 3 && slab) {
+        if (slab) {
             // pending K-split projection (xsplit32_k): x[row] += T(sum of the groups' fp32 partials, fixed order) -- the residual
             // epilogue of o_proj / down_proj, done here at the launch boundary; the completed row is written back (same thread
             // re-reads it below)
@@ -101,7 +91,7 @@ __global__ __launch_bounds__(256) void rmsnorm_k(const T* x, const T* __restrict
             }
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[j] = fromf<T>(tof<T>(v[j]) + rnd<T>(acc[j]));
-            stg16(xw + row * H + i, as_u4<T>(v));
+            stg16(xr + i, as_u4<T>(v));
         }
 #pragma unroll
         for (int j = 0; j < 8; ++j) { const float f = tof<T>(v[j]); ss += f * f; }
@@ -110,63 +100,43 @@ __global__ __launch_bounds__(256) void rmsnorm_k(const T* x, const T* __restrict
     const float rs = rsqrtf(ss / (float)H + eps);
     auto normed = [&](int i) -> V8 {
         V8 v = as_vec8<T>(ldg16(xr + i));
-        if (!w) return v;                           // w == null: re-layout only (test hook)
+        if (!w) return v;
         V8 o;
         V8 wv = as_vec8<T>(ldg16(w + i));
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[j] = fromf<T>(tof<T>(wv[j]) * rnd<T>(tof<T>(v[j]) * rs));
         return o;
     };
-    if (PACK >= 4) {
+    float inv = 0.f;
+    if (norm_e4m3<L>) {
         float am = 0.f;
         for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8) am = fmaxf(am, amax8<T>(normed(i)));
         am = block_max(am, red);
-        float sc, inv;
+        float sc;
         fp8_scale(am, sc, inv);
         if (threadIdx.x == 0) xscale[row] = sc;
-        for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8)
-            *reinterpret_cast<u2*>(dst8<PACK == 4 ? 4 : 5>(reinterpret_cast<unsigned char*>(out), row, i, H)) = quant8<T>(normed(i), inv);
-        return;
     }
-    for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8) stg16(dst(i), as_u4<T>(normed(i)));
+    for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8) norm_store<T, L>(out, row, i, mtl, H, normed(i), inv);
 }
 
-
-
-void launch_rmsnorm_packed(int dtype, const void* x, const void* w, void* out, int rows, int mtiles, int H, float eps, hipStream_t s);
-
-// One-round-trip version for H = 4096 (decode at batch 3-32: two of these per layer sit on the step's critical path): a
+// One-round-trip version for H = 4096 (decode at batch 3-128: two of these per layer sit on the step's critical path): a
 // thread owns 2 x 8 elements, every load (row, slabs, norm weight) is issued up front, the row stays in registers between the
-// statistics and the scaling. Same arithmetic and rounding points as rmsnorm_k.
-template <typename T, int PACK>
-__global__ __launch_bounds__(256) void rmsnorm4096_k(const T* x, const T* __restrict__ w, T* __restrict__ out, float eps, int n_rows,
-                                                     const float* __restrict__ slab, int groups, T* xw, float* __restrict__ xscale = nullptr, int mtl = 0) {
-    // PACK 6 (round 5, 33-128 decoder rows): the PACK 3 order over `mtl` row tiles WITH the pending K-split slabs [groups][16 mtl][H] folded in first
-    // PACK 4 with mtl > 0 (fp8 at 33-128 rows): ceil(mtl / 2) blocks of 32 rows, block b = the PACK 4 e4m3 block at byte offset 32 H b; slabs [groups][32 blocks][H]
+// statistics and the scaling. Same arithmetic and rounding points as rmsnorm_k. Up to 4 slab groups; srows = the slabs' rows per group.
+template <typename T, ActLayout L>
+__global__ __launch_bounds__(256) void rmsnorm4096_k(T* x, const T* __restrict__ w, T* __restrict__ out, float eps, int n_rows,
+                                                     const float* __restrict__ slab, int groups, int srows, float* __restrict__ xscale, int mtl) {
     typedef typename Vec8<T>::type V8;
     constexpr int H = 4096;
     __shared__ float red[32];
     const size_t row = blockIdx.x;
-    auto dst = [&](int i) -> T* {
-        if (PACK == 0) return out + row * H + i;
-        const int f = PACK != 2 ? (i >> 5) : (2 * (i >> 6) + ((i & 15) >> 3)), g = PACK != 2 ? ((i & 31) >> 3) : ((i & 63) >> 4);
-        return out + ((size_t)((f * (PACK == 3 ? groups : PACK == 6 ? mtl : 2) + (int)(row >> 4)) * 64 + g * 16 + (int)(row & 15)) << 3);
-    };
     const int i0 = threadIdx.x * 8, i1 = i0 + 2048;
-    const size_t row8 = PACK == 4 ? (row & 31) : row;          // PACK 4: the row inside its 32-row e4m3 block ...
-    unsigned char* const o8 = reinterpret_cast<unsigned char*>(out) + (PACK == 4 ? (row >> 5) * (size_t)(32 * H) : (size_t)0);      // ... and the block
-    if ((PACK == 4 || PACK == 5) && (int)row >= n_rows) {
-        *reinterpret_cast<u2*>(dst8<PACK == 4 ? 4 : 5>(o8, row8, i0, H)) = (u2){0u, 0u};
-        *reinterpret_cast<u2*>(dst8<PACK == 4 ? 4 : 5>(o8, row8, i1, H)) = (u2){0u, 0u};
-        if (threadIdx.x == 0) xscale[row] = 1.0f;
+    if (L != ACT_ROWS && (int)row >= n_rows) {
+        norm_store_zero<T, L>(out, row, i0, mtl, H);
+        norm_store_zero<T, L>(out, row, i1, mtl, H);
+        if (norm_e4m3<L> && threadIdx.x == 0) xscale[row] = 1.0f;
         return;
     }
-    if (PACK && (PACK < 4 || PACK == 6) && (int)row >= n_rows) {
-        stg16(dst(i0), (u4){0u, 0u, 0u, 0u});
-        stg16(dst(i1), (u4){0u, 0u, 0u, 0u});
-        return;
-    }
-    const T* xr = x + row * H;
+    T* xr = x + row * H;
     V8 v[2] = {as_vec8<T>(ldg16(xr + i0)), as_vec8<T>(ldg16(xr + i1))};
     const V8 wv[2] = {as_vec8<T>(ldg16(w + i0)), as_vec8<T>(ldg16(w + i1))};
     if (slab) {
@@ -175,7 +145,7 @@ __global__ __launch_bounds__(256) void rmsnorm4096_k(const T* x, const T* __rest
         for (int gq = 0; gq < 4; ++gq)
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
-                const float* p = slab + ((size_t)min(gq, groups - 1) * (PACK == 6 ? 16 * mtl : (PACK == 4 && mtl) ? 32 * ((mtl + 1) >> 1) : 32) + row) * H + (k ? i1 : i0);
+                const float* p = slab + ((size_t)min(gq, groups - 1) * srows + row) * H + (k ? i1 : i0);
                 sp[gq][k][0] = *reinterpret_cast<const float4*>(p);
                 sp[gq][k][1] = *reinterpret_cast<const float4*>(p + 4);
             }
@@ -190,7 +160,7 @@ __global__ __launch_bounds__(256) void rmsnorm4096_k(const T* x, const T* __rest
                 }
 #pragma unroll
             for (int j = 0; j < 8; ++j) v[k][j] = fromf<T>(tof<T>(v[k][j]) + rnd<T>(acc[j]));
-            stg16(xw + row * H + (k ? i1 : i0), as_u4<T>(v[k]));
+            stg16(xr + (k ? i1 : i0), as_u4<T>(v[k]));
         }
     }
     float ss = 0.f;
@@ -205,91 +175,46 @@ __global__ __launch_bounds__(256) void rmsnorm4096_k(const T* x, const T* __rest
     for (int k = 0; k < 2; ++k)
 #pragma unroll
         for (int j = 0; j < 8; ++j) o[k][j] = fromf<T>(tof<T>(wv[k][j]) * rnd<T>(tof<T>(v[k][j]) * rs));
-    if (PACK == 4 || PACK == 5) {
+    float inv = 0.f;
+    if (norm_e4m3<L>) {
         const float am = block_max(fmaxf(amax8<T>(o[0]), amax8<T>(o[1])), red);
-        float sc, inv;
+        float sc;
         fp8_scale(am, sc, inv);
         if (threadIdx.x == 0) xscale[row] = sc;
-        *reinterpret_cast<u2*>(dst8<PACK == 4 ? 4 : 5>(o8, row8, i0, H)) = quant8<T>(o[0], inv);
-        *reinterpret_cast<u2*>(dst8<PACK == 4 ? 4 : 5>(o8, row8, i1, H)) = quant8<T>(o[1], inv);
-        return;
     }
-    stg16(dst(i0), as_u4<T>(o[0]));
-    stg16(dst(i1), as_u4<T>(o[1]));
+    norm_store<T, L>(out, row, i0, mtl, H, o[0], inv);
+    norm_store<T, L>(out, row, i1, mtl, H, o[1], inv);
 }
 
-void launch_rmsnorm_packed(int dtype, const void* x, const void* w, void* out, int rows, int mtiles, int H, float eps, hipStream_t s) {
-    if (H == 4096 && w) {       // one-round-trip kernel, PACK 3: `groups` carries the row tiles
-        RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm4096_k<T, 3>), dim3(mtiles * 16), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out, eps, rows,
-                                                    (const float*)nullptr, mtiles, (T*)nullptr));
-        return;
-    }
-    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm_k<T, 3>), dim3(mtiles * 16), dim3(256), 0, s, (const T*)x, (const T*)w,
-                                                (T*)out, H, eps, rows, (const float*)nullptr, mtiles, (T*)nullptr));
+// what the two kernels cover between them: rmsnorm_k holds one 32-row block of slabs and of e4m3 bytes
+static bool norm_4096(const NormArgs& n) { return n.H == 4096 && n.w && (!n.slab || n.groups <= 4); }
+static int norm_blocks(const NormArgs& n) { return n.layout == ACT_BLK64_E4M3 && n.mtiles > 2 ? (n.mtiles + 1) / 2 : 1; }
+
+bool rmsnorm_supported(const NormArgs& n) {
+    const bool e4m3 = n.layout == ACT_BLK64_E4M3 || n.layout == ACT_ROWS_E4M3, rowmajor = n.layout == ACT_ROWS || n.layout == ACT_ROWS_E4M3;
+    if (!n.x || !n.out || n.rows <= 0 || n.H <= 0 || n.H % (rowmajor ? 8 : (n.layout == ACT_BLK32 || n.layout == ACT_TILES32) ? 32 : 64) || (e4m3 && !n.xscale) || (n.slab && n.groups < 1)) return false;
+    if (n.layout < ACT_ROWS || n.layout > ACT_ROWS_E4M3 || (n.layout == ACT_TILES32 && n.mtiles < 1)) return false;
+    const int held = n.layout == ACT_TILES32 ? 16 * n.mtiles : 32 * norm_blocks(n);      // rows the packed orders hold; row-major slabs hold 32
+    if ((!rowmajor || n.slab) && n.rows > held) return false;
+    return norm_4096(n) || !((n.layout == ACT_TILES32 && n.slab) || norm_blocks(n) > 1);
 }
 
-// 33-128 decoder rows: x += T(sum of the `groups` pending K-split slabs [groups][16 mtiles][H]) (written back), then RMSNorm into the fragment-packed
-// [k / 32][mtiles][lane][8] the row-block kernels read. H = 4096.
-void launch_rmsnorm_packed_slab(int dtype, void* x, const void* w, void* out, int rows, int mtiles, float eps, const float* slab, int groups, hipStream_t s) {
-    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm4096_k<T, 6>), dim3(mtiles * 16), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out, eps, rows, slab, groups,
-                                                (T*)x, (float*)nullptr, mtiles));
-}
-
-void launch_rmsnorm(int dtype, const void* x, const void* w, void* out, int rows, int H, float eps, hipStream_t s) {
-    if (H == 4096 && w) {       // the one-round-trip kernel (row kept in registers between the statistics and the scaling): same elements per thread, same order
-        RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm4096_k<T, 0>), dim3(rows), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out, eps, rows,
-                                                    (const float*)nullptr, 0, (T*)nullptr));
-        return;
-    }
-    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm_k<T, 0>), dim3(rows), dim3(256), 0, s, (const T*)x, (const T*)w,
-                                                (T*)out, H, eps, rows, (const float*)nullptr, 0, (T*)nullptr));
-}
-
-// RMSNorm -> e4m3 row-major bytes [rows][H] + one scale per row (the fp8 path's prefill: input of the QKV / gate-up gemm8 launches)
-void launch_rmsnorm_fp8(int dtype, const void* x, const void* w, void* out8, float* xscale, int rows, int H, float eps, hipStream_t s) {
-    if (H == 4096 && w) {
-        RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm4096_k<T, 5>), dim3(rows), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out8, eps, rows,
-                                                    (const float*)nullptr, 0, (T*)nullptr, xscale));
-        return;
-    }
-    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm_k<T, 5>), dim3(rows), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out8, H, eps, rows,
-                                                (const float*)nullptr, 0, (T*)nullptr, xscale));
-}
-
-// ... and the batch 3-32 decode form: rows <= 32 into the fragment-packed 32-row fp8 block of xstat32_k<W8, A8> + xscale[32], with the pending
-// K-split slabs folded in first like launch_rmsnorm_packed32
-void launch_rmsnorm_packed32_fp8(int dtype, void* x, const void* w, void* out8, float* xscale, int rows, int H, float eps, const float* slab,
-                                 int groups, hipStream_t s) {
-    if (H == 4096 && w && groups <= 4) {
-        RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm4096_k<T, 4>), dim3(32), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out8, eps, rows, slab,
-                                                    groups, (T*)x, xscale));
-        return;
-    }
-    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm_k<T, 4>), dim3(32), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out8, H, eps, rows, slab,
-                                                groups, (T*)x, xscale));
-}
-
-// ... and fp8 at 33-128 rows: ceil(mtiles / 2) such 32-row e4m3 blocks at a block stride of 32 H bytes, xscale[32 blocks], slabs [groups][32 blocks][H]. H = 4096.
-void launch_rmsnorm_blk_fp8(int dtype, void* x, const void* w, void* out8, float* xscale, int rows, int mtiles, float eps, const float* slab, int groups, hipStream_t s) {
-    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((rmsnorm4096_k<T, 4>), dim3(32 * ((mtiles + 1) / 2)), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out8, eps, rows, slab,
-                                                groups, (T*)x, xscale, mtiles));
-}
-
-void launch_rmsnorm_packed32(int dtype, void* x, const void* w, void* out, int rows, int H, float eps, int pack, const float* slab,
-                             int groups, hipStream_t s) {
-    if (H == 4096 && w && groups <= 4) {
-        RDX_DISPATCH_T(dtype, T, {
-            if (pack == 2) hipLaunchKernelGGL((rmsnorm4096_k<T, 2>), dim3(32), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out, eps, rows, slab, groups, (T*)x);
-            else if (pack == 1) hipLaunchKernelGGL((rmsnorm4096_k<T, 1>), dim3(32), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out, eps, rows, slab, groups, (T*)x);
-            else hipLaunchKernelGGL((rmsnorm4096_k<T, 0>), dim3(rows), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out, eps, rows, slab, groups, (T*)x);
-        });
-        return;
-    }
-    RDX_DISPATCH_T(dtype, T, {
-        if (pack == 2) hipLaunchKernelGGL((rmsnorm_k<T, 2>), dim3(32), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out, H, eps, rows, slab, groups, (T*)x);
-        else if (pack == 1) hipLaunchKernelGGL((rmsnorm_k<T, 1>), dim3(32), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out, H, eps, rows, slab, groups, (T*)x);
-        else hipLaunchKernelGGL((rmsnorm_k<T, 0>), dim3(rows), dim3(256), 0, s, (const T*)x, (const T*)w, (T*)out, H, eps, rows, slab, groups, (T*)x);
-    });
+bool launch_rmsnorm(int dtype, const NormArgs& n, hipStream_t s) {
+    if (!rmsnorm_supported(n)) return false;
+    const int mtl = n.layout == ACT_TILES32 ? n.mtiles : 2 * norm_blocks(n);
+    const int held = n.layout == ACT_TILES32 ? 16 * mtl : 32 * norm_blocks(n);
+    const dim3 grid(n.layout == ACT_ROWS || n.layout == ACT_ROWS_E4M3 ? n.rows : held);
+    const bool k4096 = norm_4096(n);
+    const float* slab = n.slab;
+    const int groups = slab ? n.groups : 0;
+#define RDX_NORM(LAY)                                                                                                                                    \
+    case LAY:                                                                                                                                            \
+        if (k4096) hipLaunchKernelGGL((rmsnorm4096_k<T, LAY>), grid, dim3(256), 0, s, (T*)n.x, (const T*)n.w, (T*)n.out, n.eps, n.rows, slab, groups, held, n.xscale, mtl); \
+        else hipLaunchKernelGGL((rmsnorm_k<T, LAY>), grid, dim3(256), 0, s, (T*)n.x, (const T*)n.w, (T*)n.out, n.H, n.eps, n.rows, slab, groups, n.xscale, mtl);            \
+        break;
+    RDX_DISPATCH_T(dtype, T, switch (n.layout) { RDX_NORM(ACT_ROWS) RDX_NORM(ACT_BLK32) RDX_NORM(ACT_BLK64) RDX_NORM(ACT_TILES32) RDX_NORM(ACT_BLK64_E4M3) RDX_NORM(ACT_ROWS_E4M3) });
+#undef RDX_NORM
+    return true;
 }
 
 // ---- LayerNorm over the last dim (Q-Former post-LN, eps 1e-12; fp32 statistics, two-pass variance) -------------------

@@ -167,15 +167,15 @@ static void launch_skinny_T(const GemmArgs& a, int epi, hipStream_t s) {
         if (w8) { if (norm) launch_skinny_epi<T, 1, true, WV, true, true>(a, epi, s); else launch_skinny_epi<T, 1, false, WV, true, true>(a, epi, s); return; }
         if (norm) launch_skinny_epi<T, 1, true, WV, true>(a, epi, s); else launch_skinny_epi<T, 1, false, WV, true>(a, epi, s);
     } else if (a.M <= 16) {
-        launch_skinny_epi<T, 1, false, WV, false>(a, epi, s);     // caller pre-normalises (rmsnorm_k) when needed
+        launch_skinny_epi<T, 1, false, WV, false>(a, epi, s);     // caller pre-normalises (launch_rmsnorm) when needed
     } else {
         launch_skinny_epi<T, 2, false, WV, false>(a, epi, s);
     }
 }
 
 void launch_skinny_gemm(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
-    // (fp8 weights: only with the e4m3 activation block, xpacked 4 -- the batch >= 3 rule of the fp8 scheme; callers go through skinny())
-    if (xstat32_supported(a, epi) && (!(a.W8 && a.wscale) || (a.xpacked == 4 && a.xscale))) { launch_xstat32(dtype, a, epi, s); return; }
+    // (fp8 weights: only with the e4m3 activation block, ACT_BLK64_E4M3 -- the batch >= 3 rule of the fp8 scheme; callers go through skinny())
+    if (xstat32_supported(a, epi) && (!(a.W8 && a.wscale) || (a.xpacked == ACT_BLK64_E4M3 && a.xscale))) { launch_xstat32(dtype, a, epi, s); return; }
     RDX_DISPATCH_T(dtype, T, launch_skinny_T<T>(a, epi, s));
 }
 

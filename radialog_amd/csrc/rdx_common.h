@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <math.h>
+#include "rdx_kernels.h"
 
 namespace rdx {
 
@@ -167,6 +168,19 @@ __device__ __forceinline__ float silu(float x) { return x / (1.0f + expf(-x)); }
 __host__ __device__ __forceinline__ size_t kperm(int pos, int dim, int perm = 1) {
     return perm ? (size_t)(pos >> 4) * 2048 + (size_t)((((dim >> 5) * 64) + ((dim & 31) >> 3) * 16 + (pos & 15)) << 3)
                 : (size_t)pos * 128 + dim;
+}
+
+// Where the 8 elements (e4m3 layouts: bytes) k .. k + 8 of activation row `row` live in layout L, in elements (bytes) from the buffer's start: the
+// orders of ActLayout (rdx_kernels.h). k is a multiple of 8. Used by the RMSNorm kernels (elem.hip); the GEMM and attention kernels carry their own copies.
+__device__ __forceinline__ size_t act_offset(ActLayout L, size_t row, int k, int mtiles, int H) {
+    const int rt = (int)(row >> 4), r = (int)(row & 15);
+    switch (L) {
+    case ACT_BLK32: return (size_t)(((k >> 5) * 2 + rt) * 64 + ((k & 31) >> 3) * 16 + r) << 3;
+    case ACT_TILES32: return (size_t)(((k >> 5) * mtiles + rt) * 64 + ((k & 31) >> 3) * 16 + r) << 3;
+    case ACT_BLK64: return (size_t)(((2 * (k >> 6) + ((k & 15) >> 3)) * 2 + rt) * 64 + ((k & 63) >> 4) * 16 + r) << 3;
+    case ACT_BLK64_E4M3: return (row >> 5) * (size_t)(32 * H) + ((size_t)(((k >> 6) * 2 + (rt & 1)) * 64 + ((k & 63) >> 4) * 16 + r) << 4) + (k & 8);
+    default: return row * H + k;
+    }
 }
 
 // packed GEMM weight geometry: [n_tile16][k_chunk32][64 lanes][8 elems]; lane = (g<<4)|r holds

@@ -80,7 +80,7 @@ struct rdx_ctx {
     float* part_val = nullptr; int* part_idx = nullptr; int n_vtiles = 0;
     // decode-step activations ([max_batch] rows) and prefill activations (grown on demand)
     void *dx = nullptr, *dxn = nullptr, *dqkv = nullptr, *datt = nullptr, *dgu = nullptr;
-    float* dxs = nullptr;            // fp8 path, batch 3-128 decode: xscale[rows in 32-row blocks] of the e4m3 activation block(s) in dxn (rmsnorm4096_k<T, 4>)
+    float* dxs = nullptr;            // fp8 path, batch 3-128 decode: xscale[rows in 32-row blocks] of the e4m3 activation block(s) in dxn (ACT_BLK64_E4M3)
     void* pxq = nullptr; float* pxs = nullptr;   // fp8 path, prefill: e4m3 activations [rows][max(hidden, inter)] and their scales [rows][4]
     std::string unsupported;         // set by the dispatch when a shape has no kernel in the current mode (fp8 weights); reported by the entry points
     float* kslab = nullptr;          // batch 3-32 decode: fp32 partial slabs [<= 4 groups][32][hidden] of a K-split projection
@@ -192,6 +192,7 @@ GemmArgs prenormed(rdx_ctx* c, GemmArgs a);        // the unit's RMSNorm is a la
 // The RMSNorm in front of a unit whose kernel does not fuse it: a.X normalised by a.norm_w into dxn, in the layout a.xpacked / a.mtiles name. Slabs that a K-split
 // projection left pending on dx are folded in (dx += T(sum of slabs)) and pend_groups is cleared. Returns prenormed(c, a), the arguments of the GEMM proper.
 GemmArgs norm_in_front(rdx_ctx* c, GemmArgs a);
+void run_rmsnorm(rdx_ctx* c, const NormArgs& n);      // launch_rmsnorm; a combination without a kernel is reported through c->unsupported (take_unsupported)
 bool down_split_ok(rdx_ctx* c, const LlamaLayer& L, int B);
 void launch_down(rdx_ctx* c, const LlamaLayer& L, int B, bool split);
 bool blk64_ok(rdx_ctx* c, int B);      // 33-128 rows: the row-block decode family (model-dtype weights, or fp8 weights: blk64_fp8)

@@ -15,6 +15,20 @@ enum Epilogue {
     EPI_RESID_RELU = 6,  // tiled only: out = T(relu(resid + T(acc + bias)))   (Bottleneck tail)
 };
 
+// The memory orders of the decoder's activations, [rows][H] in the model dtype unless said otherwise. A "fragment" is what one MFMA B operand holds:
+// 64 lanes x 8 elements, lane = 16 g + r with r = row % 16; a thread's 8 consecutive elements k .. k + 8 of a row are exactly one lane's piece
+// (act_offset in rdx_common.h is this arithmetic). Rows past the real ones are zero.
+enum ActLayout : int {
+    ACT_ROWS = 0,        // row-major [rows][H]
+    ACT_BLK32 = 1,       // one 32-row block in 32-deep fragments, [k / 32][2 row tiles][lane][8], g = (k % 32) / 8: ACT_TILES32 at mtiles = 2
+    ACT_BLK64 = 2,       // the 32-row block in the fp8 weights' 64-deep order, [f = 2 (k / 64) + (k % 16) / 8][2][lane][8], g = (k % 64) / 16; beyond 32 rows
+                         // one such block per 32 rows at a stride of 32 H elements
+    ACT_TILES32 = 3,     // `mtiles` row tiles of 16 in 32-deep fragments, [k / 32][mtiles][lane][8]
+    ACT_BLK64_E4M3 = 4,  // e4m3 bytes + xscale[row] (absmax / 448): chunk k / 64 = [2 row tiles][lane, g = (k % 64) / 16][16 bytes], one 32-row block per 32
+                         // rows at a stride of 32 H bytes; pad rows have scale 1
+    ACT_ROWS_E4M3 = 5,   // e4m3 bytes row-major [rows][H] + xscale[row] (RMSNorm output only; the input of gemm8)
+};
+
 struct GemmArgs {
     const void* X; int ldx;          // activations [M][K], row stride in elements
     const void* W;                   // fragment-packed weights (see gemm.hip)
@@ -29,13 +43,12 @@ struct GemmArgs {
     // fp8 weights: e4m3 bytes in the 64-deep fragment order (gemm.hip) + one fp32 scale per output row; `W` is null in the engine (no
     // model-dtype copy exists: api_dispatch.hip refuses shapes without an fp8 kernel), only the kernel test hooks set both
     const void* W8; const float* wscale;
-    int out_packed;                  // xstat32_k, EPI_SILU_MUL: write the output fragment-packed (input of xsplit32_k)
-    int xpacked;                     // xstat32_k: X is the fragment-packed 32-row block written by launch_rmsnorm_packed32 (1 / 2);
-                                     // 3 (wstat_k): fragment-packed [k / 32][mtiles][lane][8] over `mtiles` row tiles of 16 (out_packed 3 alike)
-    int mtiles;
+    ActLayout out_packed;            // EPI_SILU_MUL: the order the output is written in (see ActLayout)
+    ActLayout xpacked;               // the order X is in (see ActLayout)
+    int mtiles;                      // row tiles of 16 of the packed orders
     int xdup_off;                    // experiments (RDX_XDUP=0): padding rows of a 32-row block load their own (zero / stale) lines instead of re-reading real rows
     // fp8 activations (W8A8: gemm8.hip, xstat32_k<.., A8>): X holds e4m3 bytes, xscale[row][xgroups] their absmax / 448 scales over `xgroups`
-    // equal K ranges (1 behind an RMSNorm, 2 o_proj, 4 down_proj); xpacked 4 = the 32-row block in the 64-deep fragment order
+    // equal K ranges (1 behind an RMSNorm, 2 o_proj, 4 down_proj); see ActLayout
     const float* xscale; int xgroups;
     long long* trace;                // debug: [tile][8] timestamps (100 MHz ticks) written by thread 0 of every workgroup (skinny_tile)
 };
@@ -96,16 +109,16 @@ void launch_skinny_gemm(int dtype, const GemmArgs& a, int epi, hipStream_t s);
 bool xstat32_supported(const GemmArgs& a, int epi);
 void launch_xstat32(int dtype, const GemmArgs& a, int epi, hipStream_t s);
 // K-split activation-stationary GEMM for the 256-tile projections at 16 < M <= 32: fp32 partial slabs [groups][32][N], combined
-// (+ residual, rounding) by the following RMSNorm (launch_rmsnorm_packed32 with `slab`). groups = 0: shape not supported
+// (+ residual, rounding) by the following RMSNorm (NormArgs::slab). groups = 0: shape not supported
 int xsplit32_groups(const GemmArgs& a);
 void launch_xsplit32(int dtype, const GemmArgs& a, float* slab, hipStream_t s);
 int xs_min_rows();        // smallest batch on the xstat32 / xsplit32 path (3)
-// one prompt's K = 4096 projections in row blocks of 32, the row blocks of a tile walker sharing an XCD's L2 (xstat32_k<.., BLK>): X xpacked 3
+// one prompt's K = 4096 projections in row blocks of 32, the row blocks of a tile walker sharing an XCD's L2 (xstat32_k<.., BLK>): X ACT_TILES32
 bool xstat_blk_supported(const GemmArgs& a, int epi);
 void launch_xstat_blk(int dtype, const GemmArgs& a, int epi, hipStream_t s);
 // batch 3-16 decode (xs16.hip): activation-stationary K = 4096 projection over ONE row tile with the RMSNorm as its prologue (a.norm_w: X is the
-// row-major residual stream; otherwise X is the fragment-packed 32-row block, xpacked 1), and the un-split o_proj / down_proj with the residual
-// epilogue (X fragment-packed, xpacked 1; resid / out row-major)
+// row-major residual stream; otherwise X is ACT_BLK32), and the un-split o_proj / down_proj with the residual
+// epilogue (X ACT_BLK32; resid / out row-major)
 bool xs16_rows_ok(int M);
 bool xstat16_supported(const GemmArgs& a, int epi);
 void launch_xstat16(int dtype, const GemmArgs& a, int epi, hipStream_t s);
@@ -128,21 +141,18 @@ void launch_conv1x1_stream(int dtype, const GemmArgs& a, const ConvGeom& cg, int
 
 // many-row GEMM / implicit-GEMM convolution with the weight slice in an LDS ring and the activation fragments fetched straight into
 // registers by the wave that owns the rows (wsgemm.hip): K % 64 == 0; convolutions need Cin % 64 == 0
-// weight-stationary GEMM for one prompt's prefill: activations fragment-packed (xpacked 3) and streamed past register-resident weights (wstat.hip)
+// weight-stationary GEMM for one prompt's prefill: activations ACT_TILES32 and streamed past register-resident weights (wstat.hip)
 bool wstat_supported(const GemmArgs& a, int epi);
 void launch_wstat(int dtype, const GemmArgs& a, int epi, hipStream_t s);
-void launch_rmsnorm_packed(int dtype, const void* x, const void* w, void* out, int rows, int mtiles, int H, float eps, hipStream_t s);
-void launch_rmsnorm_packed_slab(int dtype, void* x, const void* w, void* out, int rows, int mtiles, float eps, const float* slab, int groups, hipStream_t s);   // H = 4096
-// K-split down_proj / o_proj over 33-128 rows (xsplit32_k<.., BLK>): X xpacked 3 over a.mtiles row tiles, slabs [groups][16 mtiles][N]
+// K-split down_proj / o_proj over 33-128 rows (xsplit32_k<.., BLK>): X ACT_TILES32 over a.mtiles row tiles, slabs [groups][16 mtiles][N]
 bool xsplit_blk_supported(const GemmArgs& a);
 void launch_xsplit_blk(int dtype, const GemmArgs& a, float* slab, hipStream_t s);
-// ... and with fp8 weights (fp8 x fp8): every 32-row block keeps the layouts of the 32-row fp8 kernels at a block stride -- xstat: X = e4m3 blocks (xpacked 4, 32 K bytes
-// apart) + xscale[rows]; xsplit: X = model-dtype 64-deep blocks (xpacked 2, 32 K elements apart), slabs [groups][32 blocks][N], groups = 2 (K = 4096) or 4 (K = 11008)
+// ... and with fp8 weights (fp8 x fp8): every 32-row block keeps the layouts of the 32-row fp8 kernels at a block stride -- xstat: X = ACT_BLK64_E4M3 + xscale[rows];
+// xsplit: X = ACT_BLK64, slabs [groups][32 blocks][N], groups = 2 (K = 4096) or 4 (K = 11008)
 bool xstat_blk8_supported(const GemmArgs& a, int epi);
 void launch_xstat_blk8(int dtype, const GemmArgs& a, int epi, hipStream_t s);
 int xsplit_blk8_groups(const GemmArgs& a);
 void launch_xsplit_blk8(int dtype, const GemmArgs& a, float* slab, hipStream_t s);
-void launch_rmsnorm_blk_fp8(int dtype, void* x, const void* w, void* out8, float* xscale, int rows, int mtiles, float eps, const float* slab, int groups, hipStream_t s);
 bool wsgemm_supported(const GemmArgs& a, const ConvGeom& cg, int epi);
 void launch_wsgemm(int dtype, const GemmArgs& a, const ConvGeom& cg, int epi, const void* zero16, hipStream_t s);
 
@@ -182,8 +192,8 @@ struct DecAttnArgs {
     const uint8_t* key_mask;
     void *kcache, *vcache, *out;
     long long* trace = nullptr;      // debug: 8 timestamps (100 MHz ticks) of workgroup (b=0,h=0)
-    int out_packed = 0;              // stand-alone launches, batch 3-32: write `out` fragment-packed for xsplit32_k (attn_body.h)
-    int out_mt = 2;                  // row tiles of that packed block: 2 (the 32-row block), 3-4 for 33-128 rows ([k / 32][out_mt][lane][8], xpacked 3)
+    ActLayout out_packed = ACT_ROWS; // stand-alone launches, from 3 rows: the order `out` is written in for the projection behind it (ACT_BLK32 / ACT_BLK64 / ACT_TILES32)
+    int out_mt = 2;                  // ACT_TILES32: its row tiles
 };
 void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, hipStream_t s);
 // Chained decode launches of the batch <= 2 step (chain.hip): units run as roles of one launch, chained by a fence-free counter
@@ -214,19 +224,22 @@ void launch_decode_chain(int dtype, ChainArgs ca, bool with_next_qkv, hipStream_
 bool attn_oproj16_supported(const LlamaDims& d, int N, int K, int B);
 void launch_attn_oproj16(int dtype, const DecAttnArgs& a, const GemmArgs& g, int B, int* counter, int* err, hipStream_t s);
 
-void launch_rmsnorm(int dtype, const void* x, const void* w, void* out, int rows, int H, float eps, hipStream_t s);
+// LlamaRMSNorm of `rows` rows into any ActLayout (elem.hip). w null: re-layout only. slab: the fp32 partials [groups][slab rows][H] a K-split projection
+// left pending -- x[row] += T(sum over the groups, in order) first, written back to x; slab rows = the rows the layout holds (32 for ACT_ROWS, <= 32 rows).
+struct NormArgs {
+    void* x; const void* w;          // [rows][H]; weight [H] or null
+    void* out; float* xscale;        // the layout's buffer; the e4m3 layouts' scales [rows the layout holds]
+    int rows, H; float eps;
+    ActLayout layout; int mtiles;    // row tiles of 16 (ACT_TILES32; ACT_BLK64_E4M3: ceil(mtiles / 2) blocks, 0 = one). The one-block orders hold 32 rows
+    const float* slab; int groups;
+};
+bool rmsnorm_supported(const NormArgs& n);
+bool launch_rmsnorm(int dtype, const NormArgs& n, hipStream_t s);      // false: no kernel for this combination (rmsnorm_supported), nothing launched
 // fp8 path (BASELINE configs[4]): e4m3 activations with absmax / 448 scales -- see gemm8.hip for the scheme
 void launch_quant_rows(int dtype, const void* x, long ldx, void* out8, float* xscale, int rows, int K, int groups, hipStream_t s);
-void launch_rmsnorm_fp8(int dtype, const void* x, const void* w, void* out8, float* xscale, int rows, int H, float eps, hipStream_t s);
-void launch_rmsnorm_packed32_fp8(int dtype, void* x, const void* w, void* out8, float* xscale, int rows, int H, float eps, const float* slab,
-                                 int groups, hipStream_t s);
 // fp8 x fp8 MFMA GEMM over row-major e4m3 activations (any M; N % 16 == 0, K % 64 == 0): epilogues NONE / RESID / SILU_MUL
 bool gemm8_supported(const GemmArgs& a, int epi);
 void launch_gemm8(int dtype, const GemmArgs& a, int epi, hipStream_t s);
-// rows <= 32 normalised into the 32-row fragment-packed block xstat32_k reads (pack 1: 32-deep fragments, 2: fp8 64-deep order)
-// slab != null: the rows are first completed as x[row] = x[row] + T(sum over g < groups of slab[g][row][:]) (written back to x)
-void launch_rmsnorm_packed32(int dtype, void* x, const void* w, void* out, int rows, int H, float eps, int pack, const float* slab,
-                             int groups, hipStream_t s);
 void launch_layernorm(int dtype, const void* x, const float* gamma, const float* beta, void* out, float* out_f32,
                       int rows, int H, float eps, hipStream_t s);
 void launch_layernorm_ex(int dtype, const void* x, long ldx, const float* gamma, const float* beta, const void* emb, int emb_rows,

@@ -8,7 +8,7 @@
 // Here the WEIGHTS are stationary and read from HBM exactly once: a workgroup owns NT output tiles of 16 columns; wave w keeps their
 // MFMA A fragments for its K range (KC / WAVES chunks of 32) in registers (NT x CPW x 4 VGPRs: half the CU's register file at
 // NT = 2, K = 4096, 8 waves). The ACTIVATIONS stream past them, row tile by row tile, out of L2: they arrive fragment-packed
-// ([k / 32][row tile][lane][8] -- written so by rmsnorm_k<T, 3>, the attention kernel and this kernel's SwiGLU epilogue), so a wave's
+// ([k / 32][row tile][lane][8] -- written so by the RMSNorm (ACT_TILES32), the attention kernel and this kernel's SwiGLU epilogue), so a wave's
 // B fragment is one contiguous KiB, fetched through a register ring that is refilled one load per consumed fragment (issue order =
 // consume order, the waits stay counted). Per row tile a wave does NT x CPW MFMAs and drops its 16 x 16 fp32 partials in one of four
 // LDS buffers; there is NO workgroup barrier in the loop (LDS counters instead, see below): every wave adds the WAVES partials of the
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(WAVES * 64) void wstat_k(GemmArgs a) {
         } else if (EPI == EPI_SILU_MUL) {
             // columns 0-7 of a tile are gate rows, 8-15 the matching up rows: the partner sits 8 lanes away in the same DPP row
             const float u = dpp_mov<DPP_ROR8>(v);
-            if (a.out_packed) {
+            if (a.out_packed != ACT_ROWS) {
                 // fragment-packed for the down projection: this tile's 8 outputs k = 8 t .. + 8 of row m are one lane's 16-byte piece
                 // of fragment (k / 32, row tile); rows >= M are zero-filled
                 if (e_on && e_nl < 8 && e_t < ntiles)
@@ -181,11 +181,11 @@ __global__ __launch_bounds__(WAVES * 64) void wstat_k(GemmArgs a) {
 #undef WS_T
 }
 
-// shapes: activations fragment-packed in `mtiles` row tiles (xpacked 3), K % 32 == 0; K = 4096 -> 16 chunks per wave, K = 11008 -> 43 (the Vicuna-7B projections; other K keep the tile GEMMs)
+// shapes: activations fragment-packed in `mtiles` row tiles (ACT_TILES32), K % 32 == 0; K = 4096 -> 16 chunks per wave, K = 11008 -> 43 (the Vicuna-7B projections; other K keep the tile GEMMs)
 static int wstat_cfg(const GemmArgs& a, int epi) {
-    if (a.xpacked != 3 || a.mtiles <= 0 || a.M > a.mtiles * 16 || (a.K & 31) || a.norm_w) return 0;
+    if (a.xpacked != ACT_TILES32 || a.mtiles <= 0 || a.M > a.mtiles * 16 || (a.K & 31) || a.norm_w) return 0;
     if (epi != EPI_NONE && epi != EPI_RESID && epi != EPI_SILU_MUL) return 0;
-    if (epi != EPI_SILU_MUL && a.out_packed) return 0;
+    if (epi != EPI_SILU_MUL && a.out_packed != ACT_ROWS) return 0;
     const int KC = a.K >> 5;
     if (KC == 8 * 16) return 1;                 // K = 4096: 8 waves x 16 chunks
     if (KC == 8 * 43) return 2;                 // K = 11008: 8 waves x 43 chunks

@@ -157,7 +157,7 @@ __global__ __launch_bounds__(X16_THREADS) void xstat16_k(GemmArgs a) {
         } else if (EPI == EPI_SILU_MUL) {
             // rows 0-7 of a tile are gate, 8-15 the matching up rows: the partner sits 8 lanes away in the same DPP row
             const float u = dpp_mov<DPP_ROR8>(v);
-            if (a.out_packed) {
+            if (a.out_packed != ACT_ROWS) {
                 // the 32-row fragment-packed block xrow16_k reads (row tile 0 of [f = k / 32][mt][lane (g = (k % 32) / 8, r = m)][8]): this
                 // tile's 8 outputs k = 8 t_o .. + 8 of row m are one lane's 16-byte piece; rows >= M are zero-filled
                 if (e_nl < 8 && t_o < ntiles)
@@ -257,7 +257,7 @@ __global__ __launch_bounds__(XR_THREADS) void xrow16_k(GemmArgs a) {
 bool xs16_rows_ok(int M) { return M >= 3 && M <= 16; }
 
 bool xstat16_supported(const GemmArgs& a, int epi) {
-    return xs16_rows_ok(a.M) && a.K == X16_K && a.W && !a.W8 && (a.N + 15) / 16 >= 512 && a.norm_w && a.ldx % 8 == 0 && !a.xpacked &&
+    return xs16_rows_ok(a.M) && a.K == X16_K && a.W && !a.W8 && (a.N + 15) / 16 >= 512 && a.norm_w && a.ldx % 8 == 0 && a.xpacked == ACT_ROWS &&
            (epi == EPI_NONE || epi == EPI_SILU_MUL || epi == EPI_LOGITS);
 }
 
@@ -283,7 +283,7 @@ void launch_xstat16(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
 
 // X: the fragment-packed 32-row block (row tile 0 is read); resid / out row-major
 bool xrow16_supported(const GemmArgs& a) {
-    return xs16_rows_ok(a.M) && a.W && !a.W8 && a.K % 32 == 0 && a.K >= 32 * XR_WAVES && a.N % 16 == 0 && a.xpacked == 1 && a.resid && !a.bias && !a.norm_w;
+    return xs16_rows_ok(a.M) && a.W && !a.W8 && a.K % 32 == 0 && a.K >= 32 * XR_WAVES && a.N % 16 == 0 && a.xpacked == ACT_BLK32 && a.resid && !a.bias && !a.norm_w;
 }
 
 void launch_xrow16(int dtype, const GemmArgs& a, hipStream_t s) {

@@ -30,13 +30,13 @@ __device__ __forceinline__ v4f xs_mfma8(const u4& a, const u4& b, v4f c) {
     return __builtin_amdgcn_mfma_f32_16x16x32_fp8_fp8(a1, b1, c, 0, 0, 0);
 }
 
-// A8 (with W8): the activations arrive as e4m3 bytes in the 64-deep fragment order (xpacked 4, written by rmsnorm4096_k<T, 4> with one scale per
+// A8 (with W8): the activations arrive as e4m3 bytes in the 64-deep fragment order (ACT_BLK64_E4M3, written by the RMSNorm with one scale per
 // row): a piece is 16 bytes per lane like a weight piece, two fp8 MFMAs per pair, half the activation registers and half the start-up fetch;
 // the fp32 sum is scaled by wscale[n] * xscale[m] in the epilogue.
 // BLK (round 5: ONE prompt's prefill, M <= 192 rows): the rows are cut into blocks of 32 and every (tile walker, row block) pair is a workgroup of
 // its own -- the NB row-block workgroups of a walker sit on the SAME XCD (workgroup ids are dealt round-robin over the 8 XCDs: id % 8) and walk the
 // same tile sequence, so a weight fragment comes from HBM once and from that XCD's L2 NB - 1 times. X is the prompt's fragment-packed
-// [k / 32][mtiles][lane][8] (xpacked 3, what rmsnorm_k<T, 3> / attention_k / the SwiGLU epilogue write); row block mb reads row tiles 2 mb, 2 mb + 1.
+// [k / 32][mtiles][lane][8] (ACT_TILES32, what the RMSNorm / attention_k / the SwiGLU epilogue write); row block mb reads row tiles 2 mb, 2 mb + 1.
 // Where a fragment load of row tile `mt` reads when only `m` of the block's 32 rows are real (round 5): a fragment is 16 rows x 16 bytes per lane group, i.e. two 128-byte lines
 // of 8 rows each -- a lane whose row lies past the last line with a real row reads row `row % (8 ceil(m / 8))` instead (its MFMA column is never stored), so the lines of
 // padding rows are never requested: at 12 rows half of every activation block (the 256 workgroups of a launch pull 32-64 MB of them through the L2s), at 40 rows 3/4 of
@@ -101,7 +101,7 @@ __global__ __launch_bounds__(XS_THREADS) void xstat32_k(GemmArgs a) {
     const T* X = reinterpret_cast<const T*>(a.X);
     constexpr int NXF = A8 ? XS_CPW / 2 : XS_CPW;
     u4 xf[2][NXF];
-    const bool xp = a.xpacked != 0;          // fragment-packed by rmsnorm_k<T, PACK>: fragment (f, mt) is one contiguous KiB
+    const bool xp = a.xpacked != ACT_ROWS;   // fragment-packed by the RMSNorm: fragment (f, mt) is one contiguous KiB
     const int m_real = a.xdup_off ? 32 : min(32, a.M - 32 * mb);       // real rows of this 32-row block
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt) {
@@ -204,17 +204,17 @@ __global__ __launch_bounds__(XS_THREADS) void xstat32_k(GemmArgs a) {
             } else if (EPI == EPI_SILU_MUL) {
                 // rows 0-7 of a tile are gate, 8-15 the matching up rows: the partner sits 8 lanes away in the same DPP row
                 const float u = dpp_mov<DPP_ROR8>(v);
-                if (BLK && a.out_packed == 3) {
-                    // the prompt's fragment-packed [k / 32][mtiles][lane][8] (out_packed 3: what wstat_k / this kernel's BLK mode read)
+                if (BLK && a.out_packed == ACT_TILES32) {
+                    // the prompt's fragment-packed [k / 32][mtiles][lane][8] (ACT_TILES32: what wstat_k / this kernel's BLK mode read)
                     const int mtg = 2 * mb + e_mt;
                     if (e_nl < 8 && t_o < ntiles && mtg < a.mtiles)
                         out[((((size_t)(t_o >> 2) * a.mtiles + mtg) * 64 + (t_o & 3) * 16 + (e_idx >> 4)) << 3) + e_nl] =
                             e_m < a.M ? fromf<T>(swiglu<T>(v, u)) : fromf<T>(0.f);
-                } else if (a.out_packed) {
+                } else if (a.out_packed != ACT_ROWS) {
                     // fragment-packed [f = k / 32][mt][lane (g = (k % 32) / 8, r = m % 16)][8] for the K-split consumer (xsplit32_k):
                     // this tile's 8 outputs k = 8 t_o .. + 8 of row m are one lane's 16-byte piece; rows >= M are zero-filled
-                    // (out_packed 2, fp8 consumer: the 64-deep order -- piece t_o is fragment 2 (t_o / 8) + (t_o & 1), g = (t_o & 7) / 2)
-                    const int pf = a.out_packed == 2 ? 2 * (t_o >> 3) + (t_o & 1) : (t_o >> 2), pg = a.out_packed == 2 ? ((t_o & 7) >> 1) : (t_o & 3);
+                    // (ACT_BLK64, fp8 consumer: the 64-deep order -- piece t_o is fragment 2 (t_o / 8) + (t_o & 1), g = (t_o & 7) / 2)
+                    const int pf = a.out_packed == ACT_BLK64 ? 2 * (t_o >> 3) + (t_o & 1) : (t_o >> 2), pg = a.out_packed == ACT_BLK64 ? ((t_o & 7) >> 1) : (t_o & 3);
                     if (e_nl < 8 && t_o < ntiles)
                         out[(BLK ? (size_t)mb * 32 * (ntiles * 8) : (size_t)0) + ((size_t)((pf * 2 + e_mt) * 64 + pg * 16 + (e_idx >> 4)) << 3) + e_nl] =
                             e_m < a.M ? fromf<T>(swiglu<T>(v, u)) : fromf<T>(0.f);
@@ -258,11 +258,11 @@ __global__ __launch_bounds__(XS_THREADS) void xstat32_k(GemmArgs a) {
 // a tile: workgroup b is K group kg = b % KGN of tile slot b / KGN, its 8 waves hold the fragments of chunk range
 // [KC s / S, KC (s + 1) / S), s = 8 kg + wave, S = 8 KGN (<= CPW chunks: 10-11 for K = 11008, KGN = 4), and it walks the tiles
 // slot, slot + G / KGN, ... (4 trips of 88 KiB at G = 256). The activations must be fragment-packed (written by the producer's
-// epilogue: xstat32_k's SwiGLU, or rmsnorm_k<T, 1>). Output: the fp32 partial of every K group in its own slab [kg][32][N],
+// epilogue: xstat32_k's SwiGLU, or the RMSNorm into ACT_BLK32). Output: the fp32 partial of every K group in its own slab [kg][32][N],
 // plain stores, no in-launch reduction -- the next kernel on the stream is always the RMSNorm of the following projection, and
-// its prologue adds the slabs in kg order, rounds, adds the residual (rmsnorm_k with `slab`): the launch boundary is the sync.
+// its prologue adds the slabs in kg order, rounds, adds the residual (NormArgs::slab): the launch boundary is the sync.
 // fp8 weights (W8): KC counts 64-deep chunks, one 16-byte load feeds two MFMAs per row tile, the activations are packed in the
-// 64-deep order (PACK 2), the per-row scale is applied to the partial; two tiles per trip (TPI) keep 8-12 KiB per wave in flight.
+// 64-deep order (ACT_BLK64), the per-row scale is applied to the partial; two tiles per trip (TPI) keep 8-12 KiB per wave in flight.
 // (A variant that ran that RMSNorm as a tail of this launch -- write-through slabs, arrival counter, workgroups 0..31 finishing one
 // row each -- was measured 1.2 us slower per norm than the 5-us launch it replaced and made low-index workgroups wait on all others,
 // against the liveness rule of handoff.h; removed in round 2.)
@@ -326,7 +326,7 @@ __global__ __launch_bounds__(XS_THREADS) void xsplit32_k(GemmArgs a, float* __re
 #pragma unroll
         for (int j = 0; j < CPW * FPL; ++j) {
             const int f = (c0 + min(j / FPL, cnt - 1)) * FPL + (j % FPL);          // packed fragment index (32-deep, or 2 per 64-deep chunk)
-            // BLK: the row-tile order of the model-dtype path (xpacked 3), or -- fp8 -- block mb's own 32-row block in the 64-deep order (xpacked 2)
+            // BLK: the row-tile order of the model-dtype path (ACT_TILES32), or -- fp8 -- block mb's own 32-row block in the 64-deep order (ACT_BLK64)
             const u4 v = (BLK && !W8) ? ldg16(X + ((size_t)((f * a.mtiles + min(2 * mb + mts, a.mtiles - 1)) * 64 + ls) << 3))
                                       : ldg16(X + (BLK ? (size_t)mb * 32 * a.K : (size_t)0) + ((size_t)((f * 2 + mts) * 64 + ls) << 3));
             xf[mt][j] = (j / FPL) < cnt ? v : (u4){0u, 0u, 0u, 0u};
@@ -462,10 +462,10 @@ int xs_min_rows() {
     return 3;
 }
 
-// K groups for this shape (0 = not supported): needs fragment-packed activations (xpacked 1; 2 = the fp8 64-deep order)
+// K groups for this shape (0 = not supported): needs fragment-packed activations (ACT_BLK32; fp8 weights: ACT_BLK64)
 int xsplit32_groups(const GemmArgs& a) {
     const bool w8 = a.W8 && a.wscale;
-    if (!(a.M >= xs_min_rows() && a.M <= 32) || a.xpacked != (w8 ? 2 : 1) || a.norm_w || a.bias || (a.N + 15) / 16 < 128 || (a.N + 15) / 16 > 512) return 0;
+    if (!(a.M >= xs_min_rows() && a.M <= 32) || a.xpacked != (w8 ? ACT_BLK64 : ACT_BLK32) || a.norm_w || a.bias || (a.N + 15) / 16 < 128 || (a.N + 15) / 16 > 512) return 0;
     if (a.K == 11008) return 4;
     if (a.K == 4096) return 2;
     return 0;
@@ -492,11 +492,11 @@ void launch_xsplit32(int dtype, const GemmArgs& a_in, float* slab, hipStream_t s
     });
 }
 
-// fp8 x fp8 on row blocks (33-128 rows, round 5): X = per-block 32-row layouts at a block stride -- xstat: e4m3 blocks (xpacked 4) + xscale[rows];
-// xsplit: model-dtype 64-deep blocks (xpacked 2), each K-group workgroup quantises its range; slabs [groups][32 NB][N]
+// fp8 x fp8 on row blocks (33-128 rows, round 5): X = per-block 32-row layouts at a block stride -- xstat: e4m3 blocks (ACT_BLK64_E4M3) + xscale[rows];
+// xsplit: model-dtype 64-deep blocks (ACT_BLK64), each K-group workgroup quantises its range; slabs [groups][32 NB][N]
 bool xstat_blk8_supported(const GemmArgs& a, int epi) {
-    return a.xpacked == 4 && a.xscale && a.mtiles >= 3 && a.mtiles <= 8 && a.M <= a.mtiles * 16 && a.K == XS_K && a.W8 && a.wscale && !a.norm_w && !a.bias &&
-           (epi == EPI_NONE || epi == EPI_SILU_MUL || epi == EPI_LOGITS) && (a.out_packed == 0 || (a.out_packed == 2 && epi == EPI_SILU_MUL)) && (a.N + 15) / 16 >= 128;
+    return a.xpacked == ACT_BLK64_E4M3 && a.xscale && a.mtiles >= 3 && a.mtiles <= 8 && a.M <= a.mtiles * 16 && a.K == XS_K && a.W8 && a.wscale && !a.norm_w && !a.bias &&
+           (epi == EPI_NONE || epi == EPI_SILU_MUL || epi == EPI_LOGITS) && (a.out_packed == ACT_ROWS || (a.out_packed == ACT_BLK64 && epi == EPI_SILU_MUL)) && (a.N + 15) / 16 >= 128;
 }
 
 void launch_xstat_blk8(int dtype, const GemmArgs& a_in, int epi, hipStream_t s) {
@@ -510,7 +510,7 @@ void launch_xstat_blk8(int dtype, const GemmArgs& a_in, int epi, hipStream_t s) 
 }
 
 int xsplit_blk8_groups(const GemmArgs& a) {
-    if (a.xpacked != 2 || !a.W8 || !a.wscale || a.mtiles < 3 || a.mtiles > 8 || a.M > a.mtiles * 16 || a.norm_w || a.bias || (a.N + 15) / 16 < 128 || (a.N + 15) / 16 > 512) return 0;
+    if (a.xpacked != ACT_BLK64 || !a.W8 || !a.wscale || a.mtiles < 3 || a.mtiles > 8 || a.M > a.mtiles * 16 || a.norm_w || a.bias || (a.N + 15) / 16 < 128 || (a.N + 15) / 16 > 512) return 0;
     return a.K == 11008 ? 4 : a.K == 4096 ? 2 : 0;
 }
 
@@ -529,7 +529,7 @@ void launch_xsplit_blk8(int dtype, const GemmArgs& a_in, float* slab, hipStream_
 }
 
 bool xsplit_blk_supported(const GemmArgs& a) {
-    return a.xpacked == 3 && a.mtiles >= 3 && a.mtiles <= 12 && a.M <= a.mtiles * 16 && a.M > (a.mtiles - 1) * 16 && a.K == 11008 && a.W && !a.W8 && !a.norm_w && !a.bias &&
+    return a.xpacked == ACT_TILES32 && a.mtiles >= 3 && a.mtiles <= 12 && a.M <= a.mtiles * 16 && a.M > (a.mtiles - 1) * 16 && a.K == 11008 && a.W && !a.W8 && !a.norm_w && !a.bias &&
            (a.N + 15) / 16 >= 128 && (a.N + 15) / 16 <= 512;
 }
 
@@ -566,11 +566,11 @@ static void launch_xstat32_t(const GemmArgs& a, int epi, hipStream_t s) {
     }
 }
 
-// ONE prompt's projections (K = 4096) in row blocks of 32: see BLK above. X fragment-packed (xpacked 3, a.mtiles row tiles), epilogues NONE / RESID /
-// SILU_MUL (out_packed 3: the same packed order for the next projection). Every XCD runs 32 / NB walkers with NB = ceil(mtiles / 2) row blocks each.
+// ONE prompt's projections (K = 4096) in row blocks of 32: see BLK above. X fragment-packed (ACT_TILES32, a.mtiles row tiles), epilogues NONE / RESID /
+// SILU_MUL (out_packed ACT_TILES32: the same packed order for the next projection). Every XCD runs 32 / NB walkers with NB = ceil(mtiles / 2) row blocks each.
 bool xstat_blk_supported(const GemmArgs& a, int epi) {
-    return a.xpacked == 3 && a.mtiles >= 1 && a.mtiles <= 12 && a.M <= a.mtiles * 16 && a.M > (a.mtiles - 1) * 16 && a.K == XS_K && a.W && !a.W8 && !a.norm_w &&
-           !a.bias && (epi == EPI_NONE || epi == EPI_RESID || epi == EPI_SILU_MUL || epi == EPI_LOGITS) && (a.out_packed == 0 || (a.out_packed == 3 && epi == EPI_SILU_MUL)) &&
+    return a.xpacked == ACT_TILES32 && a.mtiles >= 1 && a.mtiles <= 12 && a.M <= a.mtiles * 16 && a.M > (a.mtiles - 1) * 16 && a.K == XS_K && a.W && !a.W8 && !a.norm_w &&
+           !a.bias && (epi == EPI_NONE || epi == EPI_RESID || epi == EPI_SILU_MUL || epi == EPI_LOGITS) && (a.out_packed == ACT_ROWS || (a.out_packed == ACT_TILES32 && epi == EPI_SILU_MUL)) &&
            (a.N + 15) / 16 >= 128;
 }
 
@@ -587,7 +587,7 @@ void launch_xstat_blk(int dtype, const GemmArgs& a_in, int epi, hipStream_t s) {
 
 void launch_xstat32(int dtype, const GemmArgs& a_in, int epi, hipStream_t s) {
     const GemmArgs a = xs_env(a_in);
-    const bool w8 = a.W8 && a.wscale;        // fp8 weights: the activations are the e4m3 block of rmsnorm4096_k<T, 4> (xpacked 4; launch_skinny_gemm checks)
+    const bool w8 = a.W8 && a.wscale;        // fp8 weights: the activations are the RMSNorm's e4m3 block (ACT_BLK64_E4M3; launch_skinny_gemm checks)
     RDX_DISPATCH_T(dtype, T, {
         if (w8) launch_xstat32_t<T, true, true>(a, epi, s);
         else launch_xstat32_t<T, false>(a, epi, s);

@@ -443,7 +443,7 @@ class RdxEngine:
         return out
 
     def xstat_blk_test(self, x, norm_w, w, epi=0, resid=None, eps=1e-6, n_valid=None, ldo=None, out_packed=0, want_xp=False):
-        """launch_rmsnorm_packed + the row-block xstat32_k (rdx_xstat_blk_test): x [M, 4096], norm_w [4096] or None, w fp32 [N, 4096]. Returns
+        """launch_rmsnorm into row tiles + the row-block xstat32_k (rdx_xstat_blk_test): x [M, 4096], norm_w [4096] or None, w fp32 [N, 4096]. Returns
         (out, xp, argmax): out [M + 2, ldo] or the raw packed block [N / 64, mtiles, 64, 8] (out_packed 3); xp the norm's raw packed output
         [128, mtiles, 64, 8] (want_xp); argmax int32[M] (epi 5)."""
         import ctypes
@@ -460,7 +460,7 @@ class RdxEngine:
         return out, xp, (torch.tensor(list(am), dtype=torch.int32) if epi == 5 else None)
 
     def xsplit_blk_test(self, x, w, resid=None, norm_w=None, eps=1e-6):
-        """launch_rmsnorm_packed (re-layout) + the row-block xsplit32_k [+ launch_rmsnorm_packed_slab] (rdx_xsplit_blk_test): x [M, 11008], w fp32
+        """launch_rmsnorm (re-layout) + the row-block xsplit32_k [+ launch_rmsnorm with the slabs] (rdx_xsplit_blk_test): x [M, 11008], w fp32
         [N, 11008]. Returns (slabs fp32 [4, 16 mtiles, N], updated residual rows [M, 4096] or None, raw packed norm [128, mtiles, 64, 8] or None)."""
         M, N = x.shape[0], w.shape[0]
         mtl = (M + 15) // 16
@@ -473,7 +473,7 @@ class RdxEngine:
         return slab, r, xn
 
     def xstat_blk8_test(self, x, norm_w, w, epi=0, eps=1e-6, n_valid=None, ldo=None, out_packed=0):
-        """launch_rmsnorm_blk_fp8 + the fp8 row-block xstat32_k (rdx_xstat_blk8_test): x [M, 4096], norm_w [4096], w fp32 [N, 4096] (quantised to e4m3
+        """launch_rmsnorm into e4m3 blocks + the fp8 row-block xstat32_k (rdx_xstat_blk8_test): x [M, 4096], norm_w [4096], w fp32 [N, 4096] (quantised to e4m3
         by the production packer). Returns (out, x8 uint8 [NB, 32 * 4096], xscale fp32 [32 NB], argmax or None); out [M + 2, ldo] or, out_packed 2,
         the raw blocks [NB, 32 * N / 2]."""
         import ctypes
@@ -491,7 +491,7 @@ class RdxEngine:
         return out, x8, xs, (torch.tensor(list(am), dtype=torch.int32) if epi == 5 else None)
 
     def xsplit_blk8_test(self, x, w, resid=None, norm_w=None, eps=1e-6):
-        """launch_rmsnorm_packed32 (pack 2 re-layout per 32-row block) + the fp8 row-block xsplit32_k [+ launch_rmsnorm_blk_fp8 with the slabs]
+        """launch_rmsnorm (64-deep re-layout per 32-row block) + the fp8 row-block xsplit32_k [+ launch_rmsnorm into e4m3 blocks with the slabs]
         (rdx_xsplit_blk8_test): x [M, K], w fp32 [N, K], K 4096 / 11008. Returns (slabs fp32 [groups, 32 NB, N], updated residual rows or None)."""
         M, K = x.shape
         N = w.shape[0]
@@ -505,6 +505,24 @@ class RdxEngine:
         check(self.ctx, self.lib.rdx_xsplit_blk8_test(self.ctx, _ptr(x), _ptr(w), _ptr(r), _ptr(nw), eps, M, N, K, _ptr(slab), _ptr(x8), _ptr(xs)),
               "rdx_xsplit_blk8_test")
         return slab, r
+
+    def rmsnorm_test(self, x, norm_w, layout, mtiles=0, slab=None, eps=1e-6, out_bytes=None, n_scales=0):
+        """launch_rmsnorm alone (rdx_rmsnorm_test): x [rows, H], norm_w [H] or None (re-layout only), layout 0-5 (ActLayout, csrc/rdx_kernels.h), slab fp32
+        [groups, rows the layout holds, H] or None. Returns (error message or None, raw output uint8 [out_bytes], scales fp32 [n_scales] or None, the
+        updated copy of x); output and scales are 0xff bytes wherever the norm wrote nothing -- everywhere after a refusal, which does not raise."""
+        rows, H = x.shape
+        x, nw = self._dev(x).clone(), self._dev(norm_w)
+        slab = self._dev(slab, torch.float32)
+        out = torch.zeros(out_bytes or rows * H * 2, dtype=torch.uint8, device=self.device)
+        xs = torch.zeros(n_scales, dtype=torch.float32, device=self.device) if n_scales else None
+        torch.cuda.synchronize(self.device)
+        rc = self.lib.rdx_rmsnorm_test(self.ctx, _ptr(x), _ptr(nw), eps, rows, H, layout, mtiles, _ptr(slab), 0 if slab is None else slab.shape[0], _ptr(out),
+                                       out.numel(), _ptr(xs), n_scales)
+        err = None
+        if rc != 0:
+            msg = self.lib.rdx_last_error(self.ctx)
+            err = msg.decode() if msg else "?"
+        return err, out, xs, x
 
     def classify_findings(self, image: torch.Tensor) -> torch.Tensor:
         """ChexpertClassifier.forward: float32[B,3,S,S] on the device -> float32[B,classes] logits."""

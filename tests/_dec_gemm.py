@@ -90,10 +90,17 @@ def pack_frag(rows, MT):
 
 def unpack_frag64(buf):
     """One 32-row block in the fp8 kernels' 64-deep order [f][2 row tiles][lane = 16 g + r][8], f = 2 (k / 64) + (k % 16) / 8, g = (k % 64) / 16
-    (xstat32.hip out_packed 2 / elem.hip PACK 2) -> rows [32, K]. buf: flat, 32 K elements."""
+    (ActLayout value 2, csrc/rdx_kernels.h) -> rows [32, K]. buf: flat, 32 K elements."""
     K = buf.numel() // 32
     b = buf.reshape(K // 64, 2, 2, 4, 16, 8)                    # [k / 64][h = (k % 16) / 8][mt][g][r][j]
     return b.permute(2, 4, 0, 3, 1, 5).reshape(32, K)           # row = 16 mt + r, k = 64 (k / 64) + 16 g + 8 h + j
+
+
+def unpack_frag64_e4m3(buf):
+    """The byte-order twin for the e4m3 block (ActLayout value 4): one 32-row block [k / 64][2 row tiles][lane = 16 g + r][16 bytes = k % 16],
+    g = (k % 64) / 16 -> codes [32, K]. buf: flat, 32 K bytes."""
+    K = buf.numel() // 32
+    return buf.reshape(K // 64, 2, 4, 16, 16).permute(1, 3, 0, 2, 4).reshape(32, K)
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------------------

@@ -184,7 +184,7 @@ def test_xstat16_swiglu_packed_and_the_seam_into_xrow16(eng):
 @pytest.mark.parametrize("N", [64, 4096])
 @pytest.mark.parametrize("Kx", [512, 544, 4096, 4128, 11008])
 def test_xrow16_matches_fp64(eng, Kx, N):
-    """launch_xrow16 behind the production re-layout (launch_rmsnorm_packed32 without a weight), residual epilogue, ldo = N + 8. 16 waves split
+    """launch_xrow16 behind the production re-layout (launch_rmsnorm into ACT_BLK32 without a weight), residual epilogue, ldo = N + 8. 16 waves split
     K / 32 chunks as [KC w / 16, KC (w + 1) / 16): 512 -> one chunk per wave (tail only, one MFMA); 544 -> 17 chunks, wave 15 gets two; 4096 ->
     exactly XR_U = 8 per wave (the main loop's condition cb + 8 < c1 fails at once: tail only, whole ring); 4128 -> 129 chunks, one wave gets 9
     (one trip of the main loop with clamped refills, then a tail of one); 11008 -> 344 chunks, 21 / 22 per wave. At <= 4, <= 8, <= 12 rows
@@ -239,12 +239,12 @@ def _blk_ref(dt, N, normed):
 @pytest.mark.parametrize("variant", ["none", "resid", "swiglu", "logits"])
 @pytest.mark.parametrize("N", [2048, 8208])
 def test_xstat_blk_matches_fp64(eng, N, variant):
-    """launch_rmsnorm_packed + launch_xstat_blk (xstat32_k<T, EPI, false, false, true>) at M = 20 .. 192. Grid 256 = 8 XCDs x 32 slots; NB =
+    """launch_rmsnorm into row tiles (ACT_TILES32) + launch_xstat_blk (xstat32_k<T, EPI, false, false, true>) at M = 20 .. 192. Grid 256 = 8 XCDs x 32 slots; NB =
     ceil(mtiles / 2) row blocks per walker, 32 / NB walkers per XCD (NB = 3, 5, 6 leave 2, 2, 2 slots idle: M = 80 / 88 / 160, 177, 192), G =
     8 (32 / NB) walkers over the N / 16 tiles (N = 2048: 128 tiles, the minimum, fewer tiles than walkers at NB = 1; 8208: 513, a ragged last
     round). An odd mtiles (M = 33, 48, 80, 100) makes the last block's second row tile a clamped re-read of the first (never stored); a ragged last
-    tile re-reads real rows (xs_src_lane). Variants: none / logits / swiglu behind the norm WITH a weight (rmsnorm4096_k<T, 3>), resid behind the
-    re-layout only (rmsnorm_k<T, 3>, no weight: rows keep their scales). swiglu: out_packed 0, and 3 where N % 64 == 0. Chain count 56. Row
+    tile re-reads real rows (xs_src_lane). Variants: none / logits / swiglu behind the norm WITH a weight (rmsnorm4096_k into ACT_TILES32), resid behind the
+    re-layout only (rmsnorm_k into ACT_TILES32, no weight: rows keep their scales). swiglu: out_packed 0, and 3 where N % 64 == 0. Chain count 56. Row
     independence holds across ALL row counts, not only equal mtiles: a row's fragments, its MFMA column and the reduction order do not depend on
     mtiles or on the row's block (columns of an MFMA are independent), so every call must reproduce the 192-row call's rows bit for bit."""
     dt = eng.dt
@@ -280,7 +280,7 @@ def test_xstat_blk_matches_fp64(eng, N, variant):
         assert torch.equal(o, full[:M]), f"row independence: the {M}-row call differs from the 192-row call"
         if variant == "none":                                     # the packing norm's own output: inside the rstd interval, pad rows zero
             rows = D.unpack_frag(xp.cpu()).double()
-            assert rows.shape == (16 * mtl, K) and bool(((rows[:M] >= lo[:M]) & (rows[:M] <= hi[:M])).all()), f"M = {M}: launch_rmsnorm_packed"
+            assert rows.shape == (16 * mtl, K) and bool(((rows[:M] >= lo[:M]) & (rows[:M] <= hi[:M])).all()), f"M = {M}: launch_rmsnorm into row tiles"
             assert float(rows[M:].abs().max() if M < 16 * mtl else 0.0) == 0.0, f"M = {M}: pad rows of the packed norm output are not zero"
         if variant == "swiglu" and N % 64 == 0:
             pk, _, _ = eng.xstat_blk_test(x[:M], nw, wd, epi=4, out_packed=3)
@@ -312,12 +312,12 @@ def test_xstat_blk_matches_fp64(eng, N, variant):
 
 @pytest.mark.parametrize("N", [2048, 4096])
 def test_xsplit_blk_slabs_and_the_slab_norm(eng, N):
-    """launch_rmsnorm_packed (re-layout of [M][11008]) + launch_xsplit_blk (xsplit32_k<T, 344, 4, false, 1, false, true>) at M = 33 .. 128: PS =
+    """launch_rmsnorm (re-layout of [M][11008] into ACT_TILES32) + launch_xsplit_blk (xsplit32_k<T, 344, 4, false, 1, false, true>) at M = 33 .. 128: PS =
     32 / NB slots per XCD hold PS / 4 tile walkers x 4 K groups (NB = 3: 10 slots -> 2 walkers, 2 + 2 idle), K group kg = chunks [86 kg, 86 kg + 86)
     = k in [2752 kg, 2752 kg + 2752) over 8 waves (10 / 11 chunks each), slabs [4][16 mtiles][N] with the PADDED row count as the plane stride.
     Each slab is held to the accumulation allowance alone against the fp64 partial product of its K range (c = 51; nothing is rounded), rows >= M
     of every plane keep their NaN. The combine x += T(s0 + s1 + s2 + s3) is exact fp32 arithmetic, redone here: it must meet the residual bar
-    (c = 55) and -- N = 4096, where launch_rmsnorm_packed_slab exists (rmsnorm4096_k<T, 6>, H = 4096 only) -- equal the kernel's updated rows
+    (c = 55) and -- N = 4096, where the slab fold into row tiles exists (rmsnorm4096_k, H = 4096 only) -- equal the kernel's updated rows
     bit for bit; the packed norm of those rows lies in the rstd interval of the kernel's own rows, pad rows zero."""
     dt = eng.dt
     KD = 11008
@@ -344,7 +344,7 @@ def test_xsplit_blk_slabs_and_the_slab_norm(eng, N):
         worst = max(worst, off)
         assert ok, f"M = {M}: the combined rows are {ex} ulp outside the residual interval"
         if N == 4096:
-            assert torch.equal(r2.cpu(), host), f"M = {M}: launch_rmsnorm_packed_slab's updated rows differ from x + T(s0 + s1 + s2 + s3)"
+            assert torch.equal(r2.cpu(), host), f"M = {M}: the slab-folding norm's updated rows differ from x + T(s0 + s1 + s2 + s3)"
             rows = D.unpack_frag(xnp.cpu()).double()
             _, _, lo, hi = D.rms_ref(host, nw, dt)
             assert bool(((rows[:M] >= lo) & (rows[:M] <= hi)).all()), f"M = {M}: the slab norm's packed output leaves the rstd interval"
@@ -369,8 +369,8 @@ def _windows(M):
 
 @pytest.mark.parametrize("epi", [0, 4])
 def test_xstat_blk8_is_the_32_row_arithmetic_bit_for_bit(eng, epi):
-    """README round 5: the fp8 row-block kernels are the 32-row arithmetic row by row. launch_rmsnorm_blk_fp8 + launch_xstat_blk8 at M = 40 (rows
-    0-31 and 8-39), 96 and 128 (block by block) against rdx_gemm_test force 4 (rmsnorm4096_k<T, 4> + xstat32_k<T, EPI, true, true>) on those 32
+    """README round 5: the fp8 row-block kernels are the 32-row arithmetic row by row. launch_rmsnorm into e4m3 blocks (ACT_BLK64_E4M3) + launch_xstat_blk8 at M = 40 (rows
+    0-31 and 8-39), 96 and 128 (block by block) against rdx_gemm_test force 4 (rmsnorm4096_k into ACT_BLK64_E4M3 + xstat32_k<T, EPI, true, true>) on those 32
     rows. N = 8192, not the row-block minimum of 2048: the 32-row kernel it is compared with takes >= 512 tiles only (xstat32_supported)."""
     dt = eng.dt
     N = 8192
@@ -388,7 +388,7 @@ def test_xstat_blk8_is_the_32_row_arithmetic_bit_for_bit(eng, epi):
 
 @pytest.mark.parametrize("Kx,N", [(4096, 2048), (4096, 4096), (11008, 2048), (11008, 4096)])
 def test_xsplit_blk8_is_the_32_row_arithmetic_bit_for_bit(eng, Kx, N):
-    """launch_xsplit_blk8 (W8A16 K-split, 2 / 4 groups) [+ launch_rmsnorm_blk_fp8 with the slabs] against rdx_gemm_test force 6 on every 32-row
+    """launch_xsplit_blk8 (W8A16 K-split, 2 / 4 groups) [+ launch_rmsnorm into e4m3 blocks with the slabs] against rdx_gemm_test force 6 on every 32-row
     window: the slabs combined here in the kernels' fp32 order, and -- N = 4096 -- the rows the slab norm updated. Plus the fake-quantised fp64
     reference at the tolerance of test_fp8_x_fp8_gemm_matches_fake_quantised_fp32 (groups 0: the activations are not quantised)."""
     from test_gpu_gemm import _fake_quant_e4m3, _ref
@@ -406,7 +406,7 @@ def test_xsplit_blk8_is_the_32_row_arithmetic_bit_for_bit(eng, Kx, N):
         assert slab.shape == (G, 32 * NB, N) and _isnan(slab[:, M:]), f"M = {M}: slab rows >= M were written"
         host = D.combine_slabs([slab[g, :M] for g in range(G)], resid[:M], dt)
         if N == 4096:
-            assert torch.equal(r2.cpu(), host), f"M = {M}: launch_rmsnorm_blk_fp8's updated rows differ from x + T(sum of slabs)"
+            assert torch.equal(r2.cpu(), host), f"M = {M}: the slab-folding norm's updated rows differ from x + T(sum of slabs)"
         for a in _windows(M):
             ref32 = eng.gemm_test(x[a:a + 32], wd, None, resid[a:a + 32], 3, None, EPS, 6).cpu()
             assert torch.equal(host[a:a + 32], ref32), f"M = {M}: rows {a}..{a + 31} differ from the 32-row K-split kernel's"
