@@ -33,6 +33,9 @@ def parse_args(argv=None):
     p.add_argument("--vicuna", default=None, help="local lmsys/vicuna-7b-v1.3 directory (weights + tokenizer)")
     p.add_argument("--lora_model", default=None, help="adapter dir (adapter_model.bin incl. img_proj_layer)")
     p.add_argument("--max_new_tokens", type=int, default=300)
+    p.add_argument("--repetition_penalty", type=float, default=1.0, help="greedy decode: divide / multiply the logits of tokens already in the sequence (1.0 = off)")
+    p.add_argument("--no_repeat_ngram_size", type=int, default=0, help="greedy decode: no n-gram of this size occurs twice (0 = off)")
+    p.add_argument("--min_new_tokens", type=int, default=0, help="greedy decode: no EOS before this many generated tokens (0 = off)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     p.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: decoder GEMMs in OCP e4m3 on the fp8 MFMA (weights_fp8=True)")
     p.add_argument("--synthetic", action="store_true", help="run on the deterministic random-init weights (no checkpoints are "
@@ -78,7 +81,7 @@ def init_chexpert_predictor(args):
     return m.set_weight_getter(synth_getter(m.cfg, torch.device("cuda", 0), lora=False)).eval().half()
 
 
-def get_response(blip_model, lang_model, tok, conv, image, findings, max_new_tokens=300):
+def get_response(blip_model, lang_model, tok, conv, image, findings, max_new_tokens=300, **rules):
     blip_model = blip_model.to(torch.device("cuda"))
     qformer_embs = blip_model.forward_image(image[None].to(torch.device("cuda")))[0].cpu().detach()
     blip_model = blip_model.to(torch.device("cpu"))
@@ -87,7 +90,7 @@ def get_response(blip_model, lang_model, tok, conv, image, findings, max_new_tok
     conv.append_message(conv.roles[1], None)
     inputs = tok(conv.get_prompt(), return_tensors="pt")
     out = lang_model.generate(input_ids=inputs["input_ids"], dicom=None, use_img=True, return_dict_in_generate=True,
-                              output_scores=True, max_new_tokens=max_new_tokens)
+                              output_scores=True, max_new_tokens=max_new_tokens, **rules)
     preds = tok.batch_decode(out.sequences, skip_special_tokens=True)
     new_pred = preds[0].split("ASSISTANT:")[-1]
     conv.messages.pop()
@@ -113,7 +116,9 @@ def main(argv=None):
         findings = init_chexpert_predictor(args).predict_findings(cp_image[None].half().cuda())[0]
         print("predicted findings:", findings or "(none)")
     findings = findings or "no finding"
-    pred, out = get_response(blip_model, lang_model, tok, new_conversation(), image, findings, args.max_new_tokens)
+    pred, out = get_response(blip_model, lang_model, tok, new_conversation(), image, findings, args.max_new_tokens,
+                             repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
+                             min_new_tokens=args.min_new_tokens)
     print(f"generated {out.sequences.shape[1]} ids, {len(out.scores)} steps")
     print("ASSISTANT:", pred[:400])
     lang_model.close()

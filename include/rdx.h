@@ -122,6 +122,23 @@ int rdx_decode_step(rdx_ctx* ctx, void* logits);
  * caller's forward(input_ids=[B,1], past_key_values) (modeling_llama_imgemb.py:705-836) -- teacher forcing, constrained decoding. */
 int rdx_decode_step_ids(rdx_ctx* ctx, const int32_t* ids, void* logits);
 
+/* Logits rules of the greedy search: transformers 4.28.1 `_get_logits_processor` as generate(repetition_penalty=, no_repeat_ngram_size=,
+ * min_new_tokens=) builds it, applied in that order to every step's logits row x (model dtype) before the argmax. The history of a row is what HF
+ * holds in input_ids: the prompt as passed (left pads and <IMG> ids included), then every token selected so far (the pad_id of a finished row too).
+ *   repetition_penalty p > 0 (1.0 = off): every DISTINCT token t of the history, once: x[t] = T(x[t] < 0 ? x[t] * p : x[t] / p), fp32 arithmetic with
+ *                an IEEE division, one round-to-nearest-even to the model dtype -- torch.where(score < 0, score * p, score / p), bit for bit
+ *   no_repeat_ngram_size n >= 0 (0 = off): with history length L >= n - 1, every j with hist[j .. j+n-2] == hist[L-n+1 .. L-1] and j + n - 1 < L
+ *                sets x[hist[j+n-1]] = -inf
+ *   min_new_tokens m >= 0 (0 = off): while the row has generated fewer than m tokens and eos_id >= 0, x[eos_id] = -inf
+ * The processed row is what `logits` / `scores` receive (HF's .scores), the token is its argmax (lowest index on ties), then the greedy rule as before.
+ * rdx_set_logits_rules sets the rules of the NEXT rdx_prefill / rdx_generate / rdx_decode_step* calls on this context; NULL or all-neutral
+ * (1.0, 0, 0) = off: launches, graph and outputs are exactly those of a context that never heard of rules. Returns -1 for p <= 0 or not finite,
+ * n < 0, m < 0. With rules on, rdx_decode_step_ids records the caller's ids in the history (not the token it replaced), and rdx_beam_search,
+ * rdx_prefill_append and rdx_generate_append return -1: beam search applies processors to log-softmax scores and reorders histories, append needs
+ * the history carried across calls. */
+typedef struct rdx_logits_rules { float repetition_penalty; int no_repeat_ngram_size; int min_new_tokens; } rdx_logits_rules;
+int rdx_set_logits_rules(rdx_ctx* ctx, const rdx_logits_rules* rules);
+
 /* Multi-turn re-prompting (test.py:440-674, demo.py:277-305: the reference re-runs the whole conversation each turn). The
  * next turn's prompt usually starts with the previous prompt + answer; its KV rows are still in the cache. These calls keep the
  * first keep_len cache slots of every row (keep_len <= cached positions = previous T + tokens consumed; the caller compares

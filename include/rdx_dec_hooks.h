@@ -55,6 +55,13 @@ int rdx_xsplit_blk8_test(rdx_ctx* ctx, const void* X, const float* W, void* x_re
 int rdx_rmsnorm_test(rdx_ctx* ctx, void* x, const void* norm_w, float eps, int rows, int H, int layout, int mtiles, const float* slab, int groups, void* out,
                      long long out_bytes, float* xscale, int xscale_n);
 
+/* select_step_k alone (elem.hip: the greedy step under logits rules): its penalty, ban and argmax part on caller data, without the decode-state tail.
+ * logits_inout [B][vocab] row-major model dtype (vocab may be odd: the rows then start at odd elements), processed in place; hist int32 [B][ld],
+ * hist_len [B] (0 .. ld), n_generated [B] (what min_new_tokens compares with), all device; tokens_out int32 [B] device: the argmax of each processed
+ * row, lowest index on ties. Works on any context (no weights involved). */
+int rdx_select_test(rdx_ctx* ctx, void* logits_inout, int B, int vocab, const int32_t* hist, const int32_t* hist_len, const int32_t* n_generated, int ld,
+                    const rdx_logits_rules* rules, int eos_id, int32_t* tokens_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,6 +29,11 @@ class RdxError(RuntimeError):
     pass
 
 
+class RdxLogitsRules(C.Structure):
+    """rdx_logits_rules (include/rdx.h): neutral = (1.0, 0, 0)."""
+    _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int), ("min_new_tokens", C.c_int)]
+
+
 class RdxConfig(C.Structure):
     _fields_ = [
         ("dtype", C.c_int),
@@ -70,6 +75,7 @@ SYMBOLS = {
     "rdx_prefill": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rdx_decode_step": (C.c_int, [_P, _P]),
     "rdx_decode_step_ids": (C.c_int, [_P, _P, _P]),
+    "rdx_set_logits_rules": (C.c_int, [_P, C.POINTER(RdxLogitsRules)]),
     "rdx_prefill_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rdx_generate_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
                                       C.POINTER(C.c_int), C.c_int]),
@@ -114,6 +120,7 @@ DEC_HOOK_SYMBOLS = {
     "rdx_xstat_blk8_test": (C.c_int, [_P, _P, _P, _F, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_xsplit_blk8_test": (C.c_int, [_P, _P, _P, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_rmsnorm_test": (C.c_int, [_P, _P, _P, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong, _P, C.c_int]),
+    "rdx_select_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, _P]),
 }
 ALL_HOOK_SYMBOLS = {**HOOK_SYMBOLS, **ENC_HOOK_SYMBOLS, **DEC_HOOK_SYMBOLS}
 

@@ -224,3 +224,20 @@ extern "C" int rdx_rmsnorm_test(rdx_ctx* c, void* x, const void* w, float eps, i
     run_rmsnorm(c, NormArgs{x, w, out, xscale, rows, H, eps, (ActLayout)layout, mtiles, slab, groups});
     return finish(c);
 }
+
+extern "C" int rdx_select_test(rdx_ctx* c, void* logits_inout, int B, int vocab, const int32_t* hist, const int32_t* hist_len, const int32_t* n_generated, int ld,
+                               const rdx_logits_rules* rules, int eos_id, int32_t* tokens_out) {
+    if (!c || !logits_inout || !hist || !hist_len || !n_generated || !rules || !tokens_out || B <= 0 || ld <= 0)
+        return fail(c, -1, "rdx_select_test: bad arguments");
+    if (!(rules->repetition_penalty > 0.f) || rules->no_repeat_ngram_size < 0 || rules->min_new_tokens < 0) return fail(c, -1, "rdx_select_test: bad rules");
+    if (!select_step_supported(vocab)) return fail(c, -1, "rdx_select_test: vocab %d exceeds the LDS bitmaps of select_step_k", vocab);
+    HIPCHK(c, hipSetDevice(c->device));
+    SelectArgs a;
+    a.logits = logits_inout; a.step_stride = 0; a.n_gen = n_generated;
+    a.penalty = rules->repetition_penalty; a.ngram = rules->no_repeat_ngram_size; a.min_new = rules->min_new_tokens; a.sel_out = tokens_out;
+    StepTail t = {};
+    t.vocab = vocab; t.eos_id = eos_id;
+    t.hist = const_cast<int32_t*>(hist); t.hist_len = const_cast<int32_t*>(hist_len); t.hist_ld = ld;       // read only: with sel_out set the tail does not run
+    launch_select_step(c->cfg.dtype, a, t, B, c->stream);
+    return finish(c);
+}

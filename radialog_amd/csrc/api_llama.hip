@@ -1,4 +1,6 @@
 // librdx C ABI, part 3: the Llama decoder -- prompt prefill, the hipGraph-captured greedy decode step, multi-turn append, beam search.
+#include <cmath>
+
 #include "rdx_ctx.h"
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -30,6 +32,8 @@ static const char* const k_need_blk = "more than 32 decoder rows need hidden 409
 static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, const int* out_step, long step_stride,
                                int advance) {
     const rdx_config& f = c->cfg;
+    // logits rules: the row select_step_k processes must exist, so without a caller buffer the lm_head writes into the context's own
+    if (c->rules_on && !logits) { logits = c->rule_logits; out_step = nullptr; }
     auto lm = [&](GemmArgs a) { a.X = x; a.out = logits; a.out_step = out_step; a.out_step_stride = step_stride; return a; };
     switch (decode_family(c, B)) {
     case DEC_UNSUPPORTED: c->unsupported = k_need_blk; return;
@@ -41,11 +45,55 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
         [[fallthrough]];
     default: skinny(c, lm(unit_args(c, nullptr, UNIT_LM_HEAD, B)), EPI_LOGITS);
     }
-    launch_greedy_step(f.dtype, c->part_val, c->part_idx, c->n_vtiles, B, c->cur_eos, c->cur_pad, c->cur_max_new,
-                       c->cur_tokens, c->d_unf, advance ? c->d_pos : nullptr, advance ? c->d_slot : nullptr, c->d_step,
-                       c->embed, f.vocab, c->dx, f.hidden, c->d_pos, c->rope_cos, c->rope_sin, c->d_cur_rope,
-                       (c->fuse_attn_oproj || c->chain_mlp) ? c->d_ctr : nullptr,
-                       f.layers * 256 + (c->chain_mlp ? (int)chain_ctr_ints(f.layers) : 0), c->stream);
+    StepTail t = {};
+    t.eos_id = c->cur_eos; t.pad_id = c->cur_pad; t.max_new = c->cur_max_new; t.out_tokens = c->cur_tokens; t.unfinished = c->d_unf;
+    t.pos = advance ? c->d_pos : nullptr; t.slot_b = advance ? c->d_slot : nullptr; t.step_b = c->d_step;
+    t.embed = c->embed; t.vocab = f.vocab; t.x_next = c->dx; t.H = f.hidden; t.pos_ro = c->d_pos; t.cos_t = c->rope_cos; t.sin_t = c->rope_sin;
+    t.cur_rope = c->d_cur_rope;
+    t.ctr_zero = (c->fuse_attn_oproj || c->chain_mlp) ? c->d_ctr : nullptr;
+    t.n_zero = f.layers * 256 + (c->chain_mlp ? (int)chain_ctr_ints(f.layers) : 0);
+    if (!c->rules_on) { launch_greedy_step(f.dtype, c->part_val, c->part_idx, c->n_vtiles, B, t, c->stream); return; }
+    // the row at the address the lm_head just wrote (a captured step with scores: both offset it by the step count, read from d_step before the tail advances it)
+    t.hist = c->d_hist; t.hist_len = c->d_hist_len; t.hist_ld = f.max_len;
+    SelectArgs sa;
+    sa.logits = logits; sa.step_stride = out_step ? step_stride : 0; sa.n_gen = c->d_step;
+    sa.penalty = c->rules.repetition_penalty; sa.ngram = c->rules.no_repeat_ngram_size; sa.min_new = c->rules.min_new_tokens; sa.sel_out = nullptr;
+    launch_select_step(f.dtype, sa, t, B, c->stream);
+}
+
+static const rdx_logits_rules k_neutral_rules = {1.0f, 0, 0};
+
+extern "C" int rdx_set_logits_rules(rdx_ctx* c, const rdx_logits_rules* rules) {
+    if (!c) return -1;
+    const rdx_logits_rules r = rules ? *rules : k_neutral_rules;
+    if (!(r.repetition_penalty > 0.f) || !std::isfinite(r.repetition_penalty))
+        return fail(c, -1, "rdx_set_logits_rules: repetition_penalty must be a finite float > 0 (1.0 = off)");
+    if (r.no_repeat_ngram_size < 0) return fail(c, -1, "rdx_set_logits_rules: no_repeat_ngram_size %d is negative (0 = off)", r.no_repeat_ngram_size);
+    if (r.min_new_tokens < 0) return fail(c, -1, "rdx_set_logits_rules: min_new_tokens %d is negative (0 = off)", r.min_new_tokens);
+    const bool on = r.repetition_penalty != 1.0f || r.no_repeat_ngram_size != 0 || r.min_new_tokens != 0;
+    if (on) {
+        if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_set_logits_rules: llama weights not finalized");
+        const rdx_config& f = c->cfg;
+        if (!select_step_supported(f.vocab)) return fail(c, -1, "rdx_set_logits_rules: vocab %d exceeds the LDS bitmaps of select_step_k", f.vocab);
+        HIPCHK(c, hipSetDevice(c->device));
+        // each buffer on its own: a call that failed half way leaves the rules off, and the next one allocates what is still missing
+        if (!c->d_hist) ALLOC(c, c->d_hist, (size_t)f.max_batch * f.max_len * sizeof(int));
+        if (!c->rule_logits) ALLOC(c, c->rule_logits, (size_t)f.max_batch * f.vocab * 2);
+        if (!c->d_hist_len) {
+            ALLOC(c, c->d_hist_len, (size_t)f.max_batch * sizeof(int));
+            HIPCHK(c, hipMemset(c->d_hist_len, 0, (size_t)f.max_batch * sizeof(int)));
+        }
+    }
+    if (on != c->rules_on) c->hist_ready = false;        // the history belongs to the prefill that filled it
+    c->rules = on ? r : k_neutral_rules;
+    c->rules_on = on;
+    return 0;
+}
+
+// a decode step under rules continues the history its prefill started
+static int rules_need_prefill(rdx_ctx* c, const char* who) {
+    if (c->rules_on && !c->hist_ready) return fail(c, -1, "%s: logits rules were set after the last prefill; run a new prefill first", who);
+    return 0;
 }
 
 // keep == 0: a fresh prompt. keep > 0: `T` further prompt tokens behind the first `keep` cache slots of the previous call(s)
@@ -83,6 +131,8 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
         launch_prep_prompt(ids, mask, B, T, 32000, pad_id, c->d_img_pos, c->d_pos_ids, c->key_mask, f.max_len, c->d_pos, c->d_slot,
                            c->d_step, c->d_unf, s);
     }
+    c->hist_ready = c->rules_on;
+    if (c->rules_on) launch_hist_init(ids, B, T, c->d_hist, c->d_hist_len, f.max_len, s);
     if (qformer_embs) {
         // a8: img_proj_layer on the model-dtype copy of the Q-Former output (".half()", modeling_llama_imgemb.py:576-579)
         launch_from_f32(dt, qformer_embs, c->pqe, (size_t)B * 32 * f.qformer_dim, s);
@@ -187,6 +237,7 @@ extern "C" int rdx_prefill(rdx_ctx* c, const int32_t* ids, const int32_t* mask, 
 extern "C" int rdx_prefill_append(rdx_ctx* c, const int32_t* ids_tail, int B, int T_tail, int keep_len, int max_new, int eos_id,
                                   int pad_id, int32_t* out_tokens, void* logits) {
     if (!c) return -1;
+    if (c->rules_on) return fail(c, -1, "rdx_prefill_append: not available under logits rules (the token history is not carried across calls); rdx_set_logits_rules(ctx, NULL) first");
     if (keep_len <= 0 || c->cur_B <= 0) return fail(c, -1, "rdx_prefill_append: no cached conversation to continue (keep_len %d)", keep_len);
     return prefill_impl(c, ids_tail, nullptr, B, T_tail, nullptr, keep_len, max_new, eos_id, pad_id, out_tokens, logits);
 }
@@ -332,6 +383,7 @@ extern "C" int rdx_decode_step(rdx_ctx* c, void* logits) {
         return fail(c, -1, "rdx_decode_step: all %d tokens of this prompt (max_new) have been generated; run a new prefill", c->cur_max_new);
     if (c->cur_T + c->cur_steps > c->cfg.max_len || c->cur_T + c->cur_steps > c->cfg.max_pos)
         return fail(c, -1, "rdx_decode_step: KV cache full (%d prompt + %d generated slots of %d)", c->cur_T, c->cur_steps, c->cfg.max_len);
+    if (int rrc = rules_need_prefill(c, "rdx_decode_step")) return rrc;
     HIPCHK(c, hipSetDevice(c->device));
     decode_step_launch(c, logits, nullptr, 0);
     ++c->cur_steps;
@@ -350,8 +402,10 @@ extern "C" int rdx_decode_step_ids(rdx_ctx* c, const int32_t* ids, void* logits)
         return fail(c, -1, "rdx_decode_step_ids: all %d tokens of this prompt (max_new) have been generated; run a new prefill", c->cur_max_new);
     if (c->cur_T + c->cur_steps > c->cfg.max_len || c->cur_T + c->cur_steps > c->cfg.max_pos)
         return fail(c, -1, "rdx_decode_step_ids: KV cache full (%d prompt + %d generated slots of %d)", c->cur_T, c->cur_steps, c->cfg.max_len);
+    if (int rrc = rules_need_prefill(c, "rdx_decode_step_ids")) return rrc;
     HIPCHK(c, hipSetDevice(c->device));
     launch_embed_rows(c->cfg.dtype, ids, c->embed, c->cfg.vocab, c->dx, c->cur_B, c->cfg.hidden, c->stream);
+    if (c->rules_on) launch_hist_set_last(ids, c->d_hist, c->d_hist_len, c->cfg.max_len, c->cur_B, c->stream);      // the caller's token is the history, not the one it replaces
     decode_step_launch(c, logits, nullptr, 0);
     ++c->cur_steps;
     HIPCHK(c, hipGetLastError());
@@ -362,6 +416,8 @@ int build_graph(rdx_ctx* c, void* scores, bool fixed) {
     const rdx_config& f = c->cfg;
     GraphKey k;
     k.B = c->cur_B; k.max_new = c->cur_max_new; k.eos = c->cur_eos; k.pad = c->cur_pad; k.tokens = c->cur_tokens; k.scores = scores; k.fixed = fixed;
+    k.rules = c->rules;
+    if (int rrc = rules_need_prefill(c, "decode step graph")) return rrc;
     if (c->graph && k == c->gkey) return 0;
     if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }
     hipGraph_t g = nullptr;
@@ -389,6 +445,7 @@ extern "C" int rdx_generate_append(rdx_ctx* c, const int32_t* ids_tail, int B, i
                                    int pad_id, int32_t* out_tokens, void* scores, int* n_steps_host, int use_graph) {
     if (!c) return -1;
     if (max_new <= 0) return fail(c, -1, "rdx_generate_append: max_new must be positive");
+    if (c->rules_on) return fail(c, -1, "rdx_generate_append: not available under logits rules (the token history is not carried across calls); rdx_set_logits_rules(ctx, NULL) first");
     int rc = rdx_prefill_append(c, ids_tail, B, T_tail, keep_len, max_new, eos_id, pad_id, out_tokens, scores);
     if (rc) return rc;
     return decode_loop(c, B, max_new, eos_id, scores, n_steps_host, use_graph);
@@ -480,6 +537,7 @@ extern "C" int rdx_beam_search(rdx_ctx* c, const int32_t* ids, const int32_t* ma
     if (!c) return -1;
     if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_beam_search: llama weights not finalized");
     const rdx_config& f = c->cfg;
+    if (c->rules_on) return fail(c, -1, "rdx_beam_search: not available under logits rules (beam search applies them to log-softmax scores and reorders histories); rdx_set_logits_rules(ctx, NULL) first");
     const int rows = groups * num_beams;
     if (groups <= 0 || num_beams < 2 || num_beams > RDX_MAX_BEAMS) return fail(c, -1, "rdx_beam_search: num_beams must be in [2, %d]", RDX_MAX_BEAMS);
     if (rows > f.max_batch) return fail(c, -1, "rdx_beam_search: batch %d x %d beams exceeds max_batch %d", groups, num_beams, f.max_batch);

@@ -545,27 +545,17 @@ void launch_gather_last(int dtype, const void* x, void* out, int B, int T_, int 
 // ---- greedy step (transformers 4.28.1 greedy_search rule) ----------------------------------------------------------------
 // next = argmax(logits) (lowest index wins ties); finished rows emit pad; a row finishes when it emits eos.
 // Also advances the per-row decode state and gathers the next input embedding, so the whole step stays on the device.
-template <typename T>
-__global__ __launch_bounds__(256) void greedy_step_k(const float* __restrict__ part_val, const int* __restrict__ part_idx,
-                                                     int n_tiles, int eos_id, int pad_id, int max_new, int* __restrict__ out_tokens,
-                                                     int* __restrict__ unfinished, int* __restrict__ pos, int* __restrict__ slot_b,
-                                                     int* __restrict__ step_b, const T* __restrict__ embed, int vocab,
-                                                     T* __restrict__ x_next, int H, const int* pos_ro,
-                                                     const T* __restrict__ cos_t, const T* __restrict__ sin_t, T* __restrict__ cur_rope,
-                                                     int* __restrict__ ctr_zero, int n_zero) {
+
+// hand-off counters of the NEXT decode step's fused launches: zeroed by the last kernel of this step
+__device__ __forceinline__ void zero_handoff_counters(int* __restrict__ ctr_zero, int n_zero) {
+    if (ctr_zero && blockIdx.x == 0) for (int i = threadIdx.x; i < n_zero; i += blockDim.x) ctr_zero[i] = 0;
+}
+
+// (value, index) argmax over the 256 threads of a workgroup, ties -> lowest index (torch.argmax): a fixed LDS tree, no float atomics, so the
+// same inputs give the same token. The result is valid in thread 0.
+__device__ __forceinline__ int block_argmax256(float bv, int bi) {
     __shared__ float sv[256];
     __shared__ int si[256];
-    __shared__ int tok_s, pos_s;
-    const int b = blockIdx.x;
-    // hand-off counters of the NEXT decode step's fused launches: zeroed here, by the last kernel of this step
-    if (ctr_zero && b == 0) for (int i = threadIdx.x; i < n_zero; i += blockDim.x) ctr_zero[i] = 0;
-    float bv = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = threadIdx.x; i < n_tiles; i += blockDim.x) {
-        const float v = part_val[(size_t)b * n_tiles + i];
-        const int ix = part_idx[(size_t)b * n_tiles + i];
-        if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
-    }
     sv[threadIdx.x] = bv; si[threadIdx.x] = bi;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -576,33 +566,144 @@ __global__ __launch_bounds__(256) void greedy_step_k(const float* __restrict__ p
         }
         __syncthreads();
     }
+    return si[0];
+}
+
+// What follows the selection of row b's token, shared by greedy_step_k and select_step_k: the EOS / pad rule, the per-row decode state, the token
+// history (select_step_k only: hist != null), the next input embedding and the cos | sin row of the next position. `tok` is read in thread 0.
+template <typename T>
+__device__ __forceinline__ void step_tail(const StepTail& t, int b, int tok) {
+    __shared__ int tok_s, pos_s;
     if (threadIdx.x == 0) {
-        int tok = si[0];
-        const int step = step_b[b];
-        if (eos_id >= 0) {
-            const int unf = unfinished[b];
-            tok = unf ? tok : pad_id;
-            if (tok == eos_id) unfinished[b] = 0;
+        const int step = t.step_b[b];
+        if (t.eos_id >= 0) {
+            const int unf = t.unfinished[b];
+            tok = unf ? tok : t.pad_id;
+            if (tok == t.eos_id) t.unfinished[b] = 0;
         }
-        if (step < max_new) out_tokens[(size_t)b * max_new + step] = tok;
-        step_b[b] = step + 1;
-        if (slot_b) slot_b[b] += 1;      // null on the prefill call: token 0 is consumed by the first decode step
-        int pcur = pos_ro ? pos_ro[b] : 0;
-        if (pos) { pcur = pos[b] + 1; pos[b] = pcur; }
+        if (step < t.max_new) t.out_tokens[(size_t)b * t.max_new + step] = tok;
+        t.step_b[b] = step + 1;
+        if (t.slot_b) t.slot_b[b] += 1;      // null on the prefill call: token 0 is consumed by the first decode step
+        int pcur = t.pos_ro ? t.pos_ro[b] : 0;
+        if (t.pos) { pcur = t.pos[b] + 1; t.pos[b] = pcur; }
+        if (t.hist) {                        // select_step_k: history index = cache slot index: T + max_new <= max_len bounds it; the check keeps a timing replay inside the row
+            const int L = t.hist_len[b];
+            if (L < t.hist_ld) { t.hist[(size_t)b * t.hist_ld + L] = tok; t.hist_len[b] = L + 1; }
+        }
         pos_s = pcur;
         tok_s = tok;
     }
     __syncthreads();
     int id = tok_s;
-    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
-    const T* src = embed + (size_t)id * H;
-    for (int i = threadIdx.x * 8; i < H; i += blockDim.x * 8) stg16(x_next + (size_t)b * H + i, ldg16(src + i));
+    id = id < 0 ? 0 : (id >= t.vocab ? t.vocab - 1 : id);
+    const T* src = (const T*)t.embed + (size_t)id * t.H;
+    T* x_next = (T*)t.x_next;
+    for (int i = threadIdx.x * 8; i < t.H; i += blockDim.x * 8) stg16(x_next + (size_t)b * t.H + i, ldg16(src + i));
     // cos | sin row of the position the NEXT decode step works at, so that decode attention needs no pos -> table load chain
-    if (cur_rope && threadIdx.x < 32) {
+    if (t.cur_rope && threadIdx.x < 32) {
         const int half = threadIdx.x >> 4, c8 = (threadIdx.x & 15) * 8;
-        const T* tab = half ? sin_t : cos_t;
-        stg16(cur_rope + (size_t)b * 256 + half * 128 + c8, ldg16(tab + (size_t)pos_s * 128 + c8));
+        const T* tab = (const T*)(half ? t.sin_t : t.cos_t);
+        stg16((T*)t.cur_rope + (size_t)b * 256 + half * 128 + c8, ldg16(tab + (size_t)pos_s * 128 + c8));
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void greedy_step_k(const float* __restrict__ part_val, const int* __restrict__ part_idx,
+                                                     int n_tiles, StepTail t) {
+    const int b = blockIdx.x;
+    zero_handoff_counters(t.ctr_zero, t.n_zero);
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < n_tiles; i += blockDim.x) {
+        const float v = part_val[(size_t)b * n_tiles + i];
+        const int ix = part_idx[(size_t)b * n_tiles + i];
+        if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
+    }
+    step_tail<T>(t, b, block_argmax256(bv, bi));
+}
+
+// ---- greedy step under logits rules (transformers 4.28.1 _get_logits_processor: repetition penalty -> n-gram ban -> min-new-tokens) ----------
+// One workgroup per batch row, behind the lm_head launch that wrote the row (plain loads). The row's history -- the prompt as passed, then every token
+// selected so far -- marks two LDS bitmaps over the vocabulary: `seen` (penalised once however often a token occurs) and `ban` (-inf). One pass
+// over the row applies both, writes the changed elements back in place (the processed row is what the caller's scores hold) and takes the
+// argmax of the processed values; no element is read after another thread wrote it. Then the tail of greedy_step_k.
+// The row starts at an odd element when vocab is odd (32001): scalar head up to the first 16-byte boundary, 16-byte pieces, scalar tail.
+__device__ __forceinline__ unsigned bits8(const unsigned* m, int i) {       // bits i .. i + 7 of a bitmap (i + 7 inside it)
+    const int w = i >> 5, sh = i & 31;
+    const unsigned long long lo = m[w], hi = sh > 24 ? m[w + 1] : 0u;
+    return (unsigned)(((hi << 32) | lo) >> sh) & 0xffu;
+}
+template <typename T>
+__device__ __forceinline__ T apply_rules(T v, bool seen, bool ban, float p) {
+    if (seen) {                          // torch.where(x < 0, x * p, x / p) on a model-dtype tensor: fp32 arithmetic, IEEE division, one RNE rounding
+        const float f = tof<T>(v);
+        v = fromf<T>(f < 0.f ? f * p : __fdiv_rn(f, p));
+    }
+    return ban ? fromf<T>(-INFINITY) : v;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void select_step_k(SelectArgs a, StepTail t) {
+    extern __shared__ unsigned sel_bits[];           // seen[W] | ban[W]
+    const int b = blockIdx.x, V = t.vocab, W = (V + 31) >> 5;
+    unsigned* seen = sel_bits;
+    unsigned* ban = sel_bits + W;
+    zero_handoff_counters(t.ctr_zero, t.n_zero);
+    for (int i = threadIdx.x; i < 2 * W; i += blockDim.x) sel_bits[i] = 0u;
+    __syncthreads();
+    const int L = min(t.hist_len[b], t.hist_ld), gen = a.n_gen[b], n = a.ngram;
+    const int* h = t.hist + (size_t)b * t.hist_ld;
+    if (a.penalty != 1.0f)
+        for (int j = threadIdx.x; j < L; j += blockDim.x) {
+            const int id = h[j];
+            if (id >= 0 && id < V) atomicOr(&seen[id >> 5], 1u << (id & 31));
+        }
+    if (n > 0 && L + 1 >= n)             // every earlier occurrence of the last n - 1 tokens bans the token that followed it
+        for (int j = threadIdx.x; j + n - 1 < L; j += blockDim.x) {
+            bool same = true;
+            for (int k = 0; k < n - 1 && same; ++k) same = h[j + k] == h[L - n + 1 + k];
+            const int id = h[j + n - 1];
+            if (same && id >= 0 && id < V) atomicOr(&ban[id >> 5], 1u << (id & 31));
+        }
+    if (threadIdx.x == 0 && a.min_new > 0 && t.eos_id >= 0 && t.eos_id < V && gen < a.min_new) atomicOr(&ban[t.eos_id >> 5], 1u << (t.eos_id & 31));
+    __syncthreads();
+
+    T* row = (T*)a.logits + (size_t)gen * a.step_stride + (size_t)b * V;
+    const float p = a.penalty;
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    auto one = [&](int i) {
+        const T v0 = row[i];
+        const bool s = (seen[i >> 5] >> (i & 31)) & 1u, x = (ban[i >> 5] >> (i & 31)) & 1u;
+        const T v1 = apply_rules<T>(v0, s, x, p);
+        if (s || x) row[i] = v1;
+        const float f = tof<T>(v1);
+        if (f > bv || (f == bv && i < bi)) { bv = f; bi = i; }
+    };
+    const int head = min(V, (int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 1));
+    const int nvec = (V - head) >> 3;
+    if ((int)threadIdx.x < head) one(threadIdx.x);
+    for (int i = head + nvec * 8 + threadIdx.x; i < V; i += blockDim.x) one(i);
+    for (int q = threadIdx.x; q < nvec; q += blockDim.x) {
+        const int i = head + q * 8;
+        typename Vec8<T>::type v = as_vec8<T>(ldg16(row + i));
+        const unsigned s = bits8(seen, i), x = bits8(ban, i);
+        if (s | x) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = apply_rules<T>(v[j], (s >> j) & 1u, (x >> j) & 1u, p);
+            stg16(row + i, as_u4<T>(v));
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float f = tof<T>(v[j]);
+            if (f > bv || (f == bv && i + j < bi)) { bv = f; bi = i + j; }
+        }
+    }
+    const int tok = block_argmax256(bv, bi);
+    if (a.sel_out) {                     // the kernel-test hook: the selection alone, no decode state behind it
+        if (threadIdx.x == 0) a.sel_out[b] = tok;
+        return;
+    }
+    step_tail<T>(t, b, tok);
 }
 // ---- avg_pool2d(pool) + NCHW flatten of the NHWC projector output (chexpert_model.py:17-18) ----------------------------
 template <typename T>
@@ -624,13 +725,35 @@ void launch_avgpool_flatten(int dtype, const void* in, void* out, int B, int G, 
     RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((avgpool_flatten_k<T>), dim3(blocks), dim3(256), 0, s, (const T*)in, (T*)out, B, G, C, pool));
 }
 
-void launch_greedy_step(int dtype, const float* part_val, const int* part_idx, int n_tiles, int B, int eos_id, int pad_id,
-                        int max_new, int* out_tokens, int* unfinished, int* pos, int* slot_b, int* step_b, const void* embed,
-                        int vocab, void* x_next, int H, const int* pos_ro, const void* cos_t, const void* sin_t, void* cur_rope,
-                        int* ctr_zero, int n_zero, hipStream_t s) {
-    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((greedy_step_k<T>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_tiles, eos_id,
-                                                pad_id, max_new, out_tokens, unfinished, pos, slot_b, step_b, (const T*)embed, vocab,
-                                                (T*)x_next, H, pos_ro, (const T*)cos_t, (const T*)sin_t, (T*)cur_rope, ctr_zero, n_zero));
+void launch_greedy_step(int dtype, const float* part_val, const int* part_idx, int n_tiles, int B, const StepTail& t, hipStream_t s) {
+    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((greedy_step_k<T>), dim3(B), dim3(256), 0, s, part_val, part_idx, n_tiles, t));
+}
+
+bool select_step_supported(int vocab) { return vocab > 0 && select_step_lds(vocab) <= 48 * 1024; }
+
+void launch_select_step(int dtype, const SelectArgs& a, const StepTail& t, int B, hipStream_t s) {
+    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((select_step_k<T>), dim3(B), dim3(256), select_step_lds(t.vocab), s, a, t));
+}
+
+// the caller's ids replace the token the previous step appended (rdx_decode_step_ids under logits rules)
+__global__ void hist_set_last_k(const int* __restrict__ ids, int* __restrict__ hist, const int* __restrict__ hist_len, int ld, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int L = hist_len[b];
+    if (L > 0 && L <= ld) hist[(size_t)b * ld + L - 1] = ids[b];
+}
+void launch_hist_set_last(const int* ids, int* hist, const int* hist_len, int ld, int B, hipStream_t s) {
+    hipLaunchKernelGGL(hist_set_last_k, dim3((B + 63) / 64), dim3(64), 0, s, ids, hist, hist_len, ld, B);
+}
+
+// the prompt becomes the rows' history: hist[b][0 .. T) = ids[b], hist_len[b] = T
+__global__ void hist_init_k(const int* __restrict__ ids, int T_, int* __restrict__ hist, int* __restrict__ hist_len, int ld) {
+    const int b = blockIdx.x;
+    for (int t = threadIdx.x; t < T_ && t < ld; t += blockDim.x) hist[(size_t)b * ld + t] = ids[(size_t)b * T_ + t];
+    if (threadIdx.x == 0) hist_len[b] = min(T_, ld);
+}
+void launch_hist_init(const int* ids, int B, int T_, int* hist, int* hist_len, int ld, hipStream_t s) {
+    hipLaunchKernelGGL(hist_init_k, dim3(B), dim3(256), 0, s, ids, T_, hist, hist_len, ld);
 }
 
 }  // namespace rdx

@@ -50,8 +50,11 @@ struct GraphKey {
     int B = -1, max_new = 0, eos = 0, pad = 0;
     const void* tokens = nullptr; const void* scores = nullptr;
     bool fixed = false;             // logits always to `scores` itself (beam search) instead of scores + step * stride
+    rdx_logits_rules rules = {1.0f, 0, 0};      // the captured step selects through select_step_k unless neutral
     bool operator==(const GraphKey& o) const {
-        return B == o.B && max_new == o.max_new && eos == o.eos && pad == o.pad && tokens == o.tokens && scores == o.scores && fixed == o.fixed;
+        return B == o.B && max_new == o.max_new && eos == o.eos && pad == o.pad && tokens == o.tokens && scores == o.scores && fixed == o.fixed &&
+               rules.repetition_penalty == o.rules.repetition_penalty && rules.no_repeat_ngram_size == o.rules.no_repeat_ngram_size &&
+               rules.min_new_tokens == o.rules.min_new_tokens;
     }
 };
 
@@ -114,6 +117,12 @@ struct rdx_ctx {
     bool ws_ok = false;              // set while the image encoder runs: its many-row GEMMs / convolutions may take wsgemm_k
     float* gemm_ws = nullptr; size_t gemm_ws_floats = 0;      // split-K slabs of gemm_dma_k
     GraphKey gkey;
+    // ---- logits rules of the greedy search (rdx_set_logits_rules); the buffers exist from the first active rule on ----
+    rdx_logits_rules rules = {1.0f, 0, 0};
+    bool hist_ready = false;                        // the last prefill ran under the current rules and filled the history
+    bool rules_on = false;                          // any rule differs from neutral: the step selects through select_step_k (elem.hip)
+    int *d_hist = nullptr, *d_hist_len = nullptr;   // [max_batch][max_len] token history (index = cache slot), [max_batch] its lengths
+    void* rule_logits = nullptr;                    // [max_batch][vocab]: where the lm_head writes when the caller passes no logits / scores buffer
 
     // ---- beam search workspaces (rdx_beam_search), sized on first use ----
     void* bm_logits = nullptr; float* bm_scores = nullptr; float* bm_cand_s = nullptr; int* bm_cand_i = nullptr;

@@ -263,13 +263,31 @@ void launch_prep_append(int B, int T_, int keep_len, int* img_pos, int* pos_ids,
 void launch_embed_splice(int dtype, const int* ids, const int* img_pos, const void* embed, int vocab, const void* img_emb,
                          int n_img, void* out, int B, int T, int H, int use_img, hipStream_t s);
 void launch_gather_last(int dtype, const void* x, void* out, int B, int T, int H, hipStream_t s);
-void launch_greedy_step(int dtype, const float* part_val, const int* part_idx, int n_tiles, int B, int eos_id, int pad_id,
-                        int max_new, int* out_tokens, int* unfinished, int* pos, int* slot_b, int* step_b,
-                        const void* embed, int vocab, void* x_next, int H, const int* pos_ro, const void* cos_t,
-                        const void* sin_t, void* cur_rope, int* ctr_zero, int n_zero, hipStream_t s);
-// pos_ro / cos_t / sin_t / cur_rope: after the update, copy the cos | sin table row of each row's position into
-// cur_rope [B][2][128] (pos_ro = the position array even when `pos` is null, i.e. not advanced).
-// ctr_zero / n_zero: hand-off counter words to clear for the next decode step (nullable).
+// What follows the selection of a row's token, for both greedy kernels (elem.hip: step_tail). pos / slot_b null: not advanced (the prefill call).
+// pos_ro / cos_t / sin_t / cur_rope: after the update, copy the cos | sin table row of each row's position into cur_rope [B][2][128] (pos_ro = the
+// position array even when `pos` is null). ctr_zero / n_zero: hand-off counter words to clear for the next decode step (nullable).
+// hist / hist_len / hist_ld: the token history [B][hist_ld] and its lengths, read and appended to by select_step_k only (greedy_step_k: null).
+struct StepTail {
+    int eos_id, pad_id, max_new, vocab, H, n_zero, hist_ld;
+    int *out_tokens, *unfinished, *pos, *slot_b, *step_b, *ctr_zero, *hist, *hist_len;
+    const int* pos_ro;
+    const void *embed, *cos_t, *sin_t;
+    void *x_next, *cur_rope;
+};
+void launch_greedy_step(int dtype, const float* part_val, const int* part_idx, int n_tiles, int B, const StepTail& t, hipStream_t s);
+// Greedy step under logits rules (select_step_k): repetition penalty, n-gram ban and min-new-tokens on row b of `logits` (model dtype, row-major
+// [B][vocab] at logits + n_gen[b] * step_stride elements), in place, then the argmax and the tail of launch_greedy_step.
+struct SelectArgs {
+    void* logits; long step_stride;
+    const int* n_gen;                      // [B] tokens generated so far (the step's d_step; also the score row of a captured step)
+    float penalty; int ngram, min_new;
+    int* sel_out;                          // kernel-test hook: [B] selected tokens; the tail (state advance, history append) does not run
+};
+inline size_t select_step_lds(int vocab) { return (size_t)2 * ((vocab + 31) / 32) * sizeof(unsigned); }     // two bitmaps over the vocabulary
+bool select_step_supported(int vocab);
+void launch_select_step(int dtype, const SelectArgs& a, const StepTail& t, int B, hipStream_t s);       // t.hist* = the rows' history
+void launch_hist_init(const int* ids, int B, int T, int* hist, int* hist_len, int ld, hipStream_t s);
+void launch_hist_set_last(const int* ids, int* hist, const int* hist_len, int ld, int B, hipStream_t s);
 
 // beam search (beam.hip)
 #define RDX_MAX_BEAMS 8

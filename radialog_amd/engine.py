@@ -6,6 +6,9 @@ all arithmetic of the hot path runs in librdx's HIP kernels. There is no eager/C
 from __future__ import annotations
 
 import ctypes as C
+import math
+import numbers
+from dataclasses import dataclass
 from typing import Callable, Dict, Optional
 
 import torch
@@ -21,6 +24,35 @@ _RDX_DT = {"f16": _lib.RDX_DTYPE_F16, "bf16": _lib.RDX_DTYPE_BF16}
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+@dataclass(frozen=True)
+class LogitsRules:
+    """The greedy search's logits rules (rdx_logits_rules, include/rdx.h): transformers' `repetition_penalty`, `no_repeat_ngram_size` and
+    `min_new_tokens`, applied in that order before the argmax. The defaults are neutral (= off). Raises ValueError on values HF refuses."""
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_new_tokens: int = 0
+
+    def __post_init__(self):
+        p, n, m = self.repetition_penalty, self.no_repeat_ngram_size, self.min_new_tokens
+        if isinstance(p, bool) or not isinstance(p, numbers.Real) or not math.isfinite(p) or not p > 0:
+            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {p}")
+        if isinstance(n, bool) or not isinstance(n, numbers.Integral) or n < 0:
+            raise ValueError(f"`no_repeat_ngram_size` has to be a non-negative integer, but is {n}")
+        if isinstance(m, bool) or not isinstance(m, numbers.Integral) or m < 0:
+            raise ValueError(f"`min_new_tokens` has to be a non-negative integer, but is {m}")
+
+    @property
+    def active(self) -> bool:
+        return float(self.repetition_penalty) != 1.0 or self.no_repeat_ngram_size != 0 or self.min_new_tokens != 0
+
+    @classmethod
+    def of(cls, rules) -> "LogitsRules":
+        """None, a LogitsRules or a (repetition_penalty, no_repeat_ngram_size, min_new_tokens) tuple."""
+        if rules is None:
+            return cls()
+        return rules if isinstance(rules, cls) else cls(*rules)
 
 
 class RdxEngine:
@@ -63,6 +95,7 @@ class RdxEngine:
             raise _lib.RdxError(f"rdx_create failed ({rcode}): {msg.decode() if msg else '?'}")
         self._finalized = False
         self._keep = {}
+        self._rules = LogitsRules()                  # what the context holds (set_logits_rules is the one place that changes it)
 
     # ------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -151,6 +184,31 @@ class RdxEngine:
         self.sync()
         return out, emb
 
+    def set_logits_rules(self, rules=None) -> LogitsRules:
+        """rdx_set_logits_rules: the rules of the next prefill / generate / decode_step calls; None or neutral = off (the plain greedy path)."""
+        r = LogitsRules.of(rules)
+        c = _lib.RdxLogitsRules(float(r.repetition_penalty), int(r.no_repeat_ngram_size), int(r.min_new_tokens)) if r.active else None
+        check(self.ctx, self.lib.rdx_set_logits_rules(self.ctx, None if c is None else C.byref(c)), "rdx_set_logits_rules")
+        self._rules = r
+        return r
+
+    def select_test(self, logits, hist, hist_len, n_generated, rules, eos_id=-1):
+        """select_step_k alone (rdx_select_test): logits [B, V] model dtype, hist int [B, ld], hist_len / n_generated int [B]. Returns (processed
+        logits [B, V], tokens int32 [B]); the caller's tensors are left as they are."""
+        B, V = logits.shape
+        r = LogitsRules.of(rules)
+        x = logits.to(self.device, self.tdtype).contiguous().clone()
+        h = hist.to(self.device, torch.int32).contiguous()
+        hl, ng = hist_len.to(self.device, torch.int32).contiguous(), n_generated.to(self.device, torch.int32).contiguous()
+        if h.shape[0] != B or hl.numel() != B or ng.numel() != B or int(hl.max()) > h.shape[1] or int(hl.min()) < 0:
+            raise ValueError("select_test: hist [B, ld], hist_len [B] in 0 .. ld, n_generated [B]")
+        out = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        c = _lib.RdxLogitsRules(float(r.repetition_penalty), int(r.no_repeat_ngram_size), int(r.min_new_tokens))
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_select_test(self.ctx, _ptr(x), B, V, _ptr(h), _ptr(hl), _ptr(ng), h.shape[1], C.byref(c), int(eos_id), _ptr(out)),
+              "rdx_select_test")
+        return x, out
+
     def _reusable_prefix(self, ids: torch.Tensor, qf, pad_id: int) -> int:
         """Number of leading cache slots of the previous generate(reuse_prefix=True) call that this prompt can keep: the
         longest token prefix all rows share with what was fed then (prompt + consumed answer tokens), provided the image
@@ -173,11 +231,15 @@ class RdxEngine:
 
     def generate(self, ids: torch.Tensor, qformer_embs: Optional[torch.Tensor], max_new: int, eos_id: int = 2,
                  pad_id: int = 0, mask: Optional[torch.Tensor] = None, output_scores: bool = False, use_graph: bool = True,
-                 reuse_prefix: bool = False):
+                 reuse_prefix: bool = False, logits_rules=None):
         """Greedy generation. Returns (tokens int32[B,n_steps], scores [n_steps,B,V] model dtype or None, n_steps).
         reuse_prefix: multi-turn conversations -- keep the KV rows of the token prefix this prompt shares with the previous
-        reuse_prefix call and prefill only the rest (rdx_generate_append); outputs are those of the full prompt."""
+        reuse_prefix call and prefill only the rest (rdx_generate_append); outputs are those of the full prompt.
+        logits_rules: LogitsRules or (repetition_penalty, no_repeat_ngram_size, min_new_tokens); the scores are then the processed ones
+        (HF's .scores). An active rule prefills the whole prompt: the token history is not carried across calls."""
         B, T = ids.shape
+        if self.set_logits_rules(logits_rules).active:
+            reuse_prefix = False
         ids32 = ids.to(device=self.device, dtype=torch.int32).contiguous()
         m32 = None if mask is None else mask.to(device=self.device, dtype=torch.int32).contiguous()
         qf = None if qformer_embs is None else qformer_embs.to(device=self.device, dtype=torch.float32).contiguous()
@@ -223,6 +285,7 @@ class RdxEngine:
         k = int(num_beams)
         rep = lambda t, dt: None if t is None else t.to(device=self.device, dtype=dt).repeat_interleave(k, dim=0).contiguous()   # noqa: E731
         ids32, m32, qf = rep(ids, torch.int32), rep(mask, torch.int32), rep(qformer_embs, torch.float32)
+        self.set_logits_rules(None)                  # rules are a greedy-search feature; a call that left some behind must not make this one fail
         toks = torch.zeros(B, max_new, dtype=torch.int32)
         lens = torch.zeros(B, dtype=torch.int32)
         seq_scores = torch.zeros(B, dtype=torch.float32)
@@ -236,8 +299,10 @@ class RdxEngine:
               "rdx_beam_search")
         return toks, lens, seq_scores, (None if sc is None else sc[: n.value]), n.value
 
-    def prefill(self, ids, qformer_embs, max_new, eos_id=2, pad_id=0, mask=None, want_logits=True):
+    def prefill(self, ids, qformer_embs, max_new, eos_id=2, pad_id=0, mask=None, want_logits=True, logits_rules=None):
+        """The prompt and token 0. logits_rules (as in generate) stay in force for the decode_step calls behind this prefill."""
         B, T = ids.shape
+        self.set_logits_rules(logits_rules)
         ids32 = ids.to(device=self.device, dtype=torch.int32).contiguous()
         m32 = None if mask is None else mask.to(device=self.device, dtype=torch.int32).contiguous()
         qf = None if qformer_embs is None else qformer_embs.to(device=self.device, dtype=torch.float32).contiguous()
@@ -251,9 +316,13 @@ class RdxEngine:
         self.sync()
         return toks, logits
 
-    def decode_step(self, want_logits=True, input_ids: Optional[torch.Tensor] = None):
-        """One decode step on the token the previous step selected, or on caller-supplied `input_ids` int[B] (rdx_decode_step_ids)."""
+    def decode_step(self, want_logits=True, input_ids: Optional[torch.Tensor] = None, logits_rules=None):
+        """One decode step on the token the previous step selected, or on caller-supplied `input_ids` int[B] (rdx_decode_step_ids).
+        logits_rules: None keeps the rules the context holds (those of the prefill, unless a generate / beam_search call came in between); rules
+        cannot be switched on behind a prefill that ran without any."""
         ids32, m32, qf, toks = self._keep["prefill"]
+        if logits_rules is not None and LogitsRules.of(logits_rules) != self._rules:
+            self.set_logits_rules(logits_rules)
         B = ids32.shape[0]
         logits = torch.empty(B, self.cfg.llama.vocab, dtype=self.tdtype, device=self.device) if want_logits else None
         if input_ids is None:

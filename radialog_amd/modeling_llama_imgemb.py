@@ -15,6 +15,7 @@ The image embeddings reach `generate` the way the reference passes them (modelin
 from __future__ import annotations
 
 import json
+import numbers
 import os
 import pickle
 from types import SimpleNamespace
@@ -213,11 +214,20 @@ class LlamaForCausalLM:
                  return_dict_in_generate: bool = False, output_scores: bool = False, max_new_tokens: int = 20,
                  attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1, do_sample: bool = False,
                  qformer_embs: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
-                 pad_token_id: Optional[int] = None, length_penalty: float = 1.0, early_stopping: bool = False, **_unused):
+                 pad_token_id: Optional[int] = None, length_penalty: float = 1.0, early_stopping: bool = False,
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, **_unused):
         if do_sample:
             raise NotImplementedError("sampling is not on the path: every reference call site decodes deterministically")
         if num_beams < 1:
             raise ValueError("`num_beams` has to be an integer strictly greater than 0")
+        from .engine import LogitsRules
+        # transformers builds RepetitionPenaltyLogitsProcessor, which takes a float only, when the value differs from 1.0: 1 (int) is "off" there too
+        if not isinstance(repetition_penalty, float) and not (isinstance(repetition_penalty, numbers.Real) and repetition_penalty == 1):
+            raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty}")
+        rules = LogitsRules(repetition_penalty, no_repeat_ngram_size, min_new_tokens)       # ValueError on what transformers refuses
+        if rules.active and num_beams > 1:
+            raise ValueError("repetition_penalty / no_repeat_ngram_size / min_new_tokens apply to greedy search only (num_beams=1): beam search "
+                             "under logits rules is not built")
         if input_ids.dim() != 2:
             raise ValueError("You have to specify decoder_input_ids of shape [batch, seq]")
         B, T = input_ids.shape
@@ -231,10 +241,12 @@ class LlamaForCausalLM:
             return self._beam_generate(input_ids, embs, num_beams, max_new_tokens, eos, pad, attention_mask, length_penalty,
                                        early_stopping, return_dict_in_generate, output_scores)
         # multi-turn chats (demo.py:277-305 re-sends the whole conversation every turn): with `reuse_prefix_kv` set on the model
-        # the KV rows of the token prefix shared with the previous call are kept and only the new turn is prefilled
+        # the KV rows of the token prefix shared with the previous call are kept and only the new turn is prefilled (not under an
+        # active logits rule: the token history is not carried across calls, the full prompt is prefilled)
         toks, scores, n = self._engine.generate(input_ids, embs, max_new=max_new_tokens, eos_id=eos, pad_id=pad,
                                                 mask=attention_mask, output_scores=output_scores,
-                                                reuse_prefix=bool(getattr(self, "reuse_prefix_kv", False)) and attention_mask is None)
+                                                reuse_prefix=bool(getattr(self, "reuse_prefix_kv", False)) and attention_mask is None,
+                                                logits_rules=rules)
         toks = toks[:, :n].to(torch.int64)
         # HF stops as soon as every row has emitted EOS; the engine polls every 4th step (api_llama.hip decode_loop), so trim the all-pad tail
         if eos >= 0 and n > 0:
