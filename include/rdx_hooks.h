@@ -19,7 +19,13 @@ int rdx_quant_test(rdx_ctx* ctx, const void* X, int M, int K, int groups, int mo
  * persistent batch >= 3 kernels (xstat32.hip) write one record per WORKGROUP: entry, first trip's K loop done, first trip done, last
  * trip begins, its K loop done, end, [6] = trips, [7] = XCC id (tools/xs_trace.py).
  * what = 7: the chained down(layer) -> QKV(layer + 1) launch of the batch <= 2 step, in situ: runs ONE eager decode step (the state advances) and
- * returns one record per workgroup of that launch (tools/chain_seam.py; slots: csrc/chain.hip chain_tile) */
+ * returns one record per workgroup of that launch (tools/chain_seam.py; slots: csrc/chain.hip chain_tile)
+ * what = 8 (RDX_TRACE_ATTN_OPROJ): the fused attention + o_proj launch of `layer` (batch <= 2), in situ in the same way: the heads * B attention
+ * workgroups first ([0] entry, [1] qkv row loaded, [2] scores done, [3] softmax done, [4] P.V reduced, [5] output stored (stores issued), [6] the
+ * stores acknowledged), then the o_proj workgroups with chain_tile's slots ([0] entry, [5] first weight KiB back, [3] inputs ready, [6] first MFMA,
+ * [1] K loop done, [7] end) (tools/attn_seam.py). An error when the fused launch is not active (batch > 2, RDX_FUSE_AO=0). */
+#define RDX_TRACE_CHAIN 7
+#define RDX_TRACE_ATTN_OPROJ 8
 int rdx_gemv_trace(rdx_ctx* ctx, int what, int layer, long long* host, int max_tiles);
 
 /* one bare GEMM through the production kernels: out = epilogue(X . W^T); X/resid/norm_w/out model dtype, W [N][K] and

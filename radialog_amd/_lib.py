@@ -103,6 +103,10 @@ HOOK_SYMBOLS = {
     "rdx_logits_test": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_int]),
 }
 
+# rdx_gemv_trace's in-situ `what` values (include/rdx_hooks.h: RDX_TRACE_CHAIN, RDX_TRACE_ATTN_OPROJ)
+TRACE_CHAIN = 7
+TRACE_ATTN_OPROJ = 8
+
 # include/rdx_enc_hooks.h: the image encoder's kernel-test hooks, also in librdx_hooks.so
 ENC_HOOK_SYMBOLS = {
     "rdx_stem_test": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),

@@ -253,11 +253,16 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
         HIPCHK(c, hipMemset(c->key_mask, 0, (size_t)B * f.max_len));
         ALLOC(c, c->d_img_pos, B * sizeof(int)); ALLOC(c, c->d_pos, B * sizeof(int)); ALLOC(c, c->d_slot, B * sizeof(int));
         ALLOC(c, c->d_step, B * sizeof(int)); ALLOC(c, c->d_unf, B * sizeof(int));
-        // hand-off counters (zero at the start of every step: greedy_step_k clears them): per layer 256 ints for the fused attention +
-        // o_proj launch (8 shards x one 64-byte line), then the chained down -> QKV launches' block (chain_ctr_ints)
-        ALLOC(c, c->d_ctr, ((size_t)f.layers * 256 + chain_ctr_ints(f.layers)) * sizeof(int)); ALLOC(c, c->d_err, sizeof(int));
-        HIPCHK(c, hipMemset(c->d_ctr, 0, ((size_t)f.layers * 256 + chain_ctr_ints(f.layers)) * sizeof(int)));
-        c->d_cctr = c->d_ctr + (size_t)f.layers * 256;
+        // hand-off counters of the chained down -> QKV launches (chain_ctr_ints; zero at the start of every step: greedy_step_k clears them)
+        ALLOC(c, c->d_ctr, chain_ctr_ints(f.layers) * sizeof(int)); ALLOC(c, c->d_err, sizeof(int));
+        HIPCHK(c, hipMemset(c->d_ctr, 0, chain_ctr_ints(f.layers) * sizeof(int)));
+        c->d_cctr = c->d_ctr;
+        // the fused attention + o_proj launch's data-tagged hand-off (handoff.h): ONE granule buffer [2][hidden] x 4 bytes for the whole model with its
+        // hint words behind it, and the step epoch the tags derive from -- zero now, never reset
+        ALLOC(c, c->d_gran, (size_t)2 * H * 4 + HO_HINT_INTS * sizeof(int)); ALLOC(c, c->d_epoch, sizeof(int));
+        HIPCHK(c, hipMemset(c->d_gran, 0, (size_t)2 * H * 4 + HO_HINT_INTS * sizeof(int)));
+        HIPCHK(c, hipMemset(c->d_epoch, 0, sizeof(int)));
+        c->d_hint = reinterpret_cast<int*>(reinterpret_cast<char*>(c->d_gran) + (size_t)2 * H * 4);
         HIPCHK(c, hipMemset(c->d_err, 0, sizeof(int)));
         {
             std::vector<ChainLayer> cl(f.layers);

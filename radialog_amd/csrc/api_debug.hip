@@ -41,30 +41,39 @@ extern "C" int rdx_quant_test(rdx_ctx* c, const void* X, int M, int K, int group
 // timestamps: host[tile*8 + {0 entry, 1 weights issued, 2 activations staged, 3 K loop done, 4 all waves done, 5 end}].
 // what = 7: the chained down(layer) -> QKV(layer + 1) launch IN SITU (its hand-off counters are only valid inside a real step): ONE eager
 // decode step runs and advances the state; host[workgroup*8 + slot] with the slots of chain.hip (chain_tile; down_proj workgroups first, then the QKV workgroups).
+// what = 8: the fused attention + o_proj launch of `layer` IN SITU, the same way: the heads * B attention workgroups first ([0] entry, [1] qkv row loaded,
+// [2] scores done, [3] softmax done, [4] P.V reduced, [5] output stored (stores issued), [6] arrival), then the o_proj workgroups (chain_tile's slots:
+// [0] entry, [5] first weight KiB back, [3] inputs ready, [6] first MFMA, [1] K loop done, [7] end).
 extern "C" int rdx_gemv_trace(rdx_ctx* c, int what, int layer, long long* host, int max_tiles) {
     if (!c || !c->finalized || c->cur_B <= 0 || !host) return fail(c, -1, "rdx_gemv_trace: run a prefill first");
     HIPCHK(c, hipSetDevice(c->device));
     const rdx_config& f = c->cfg;
     const int H = f.hidden, B = c->cur_B;
-    if (what == 7) {
-        if (layer < 0 || layer >= f.layers) return fail(c, -1, "rdx_gemv_trace(7): layer %d of %d", layer, f.layers);
+    if (what == 7 || what == 8) {
+        if (layer < 0 || layer >= f.layers) return fail(c, -1, "rdx_gemv_trace(%d): layer %d of %d", what, layer, f.layers);
         if (c->cur_T + c->cur_steps + 1 > f.max_len || c->cur_T + c->cur_steps + 1 > f.max_pos)       // as rdx_time(7): bounded by the KV cache, not by max_new
-            return fail(c, -1, "rdx_gemv_trace(7): no room for one more decode step in the KV cache");
-        const int wgs = H / 16 + ((c->ll[0].wqkv.Npad + 15) / 16 + 3) / 4;      // down_proj tiles + QKV workgroups of 4 tiles
-        if (wgs > max_tiles) return fail(c, -1, "rdx_gemv_trace(7): need room for %d workgroups", wgs);
+            return fail(c, -1, "rdx_gemv_trace(%d): no room for one more decode step in the KV cache", what);
+        const bool fused = c->fuse_attn_oproj && attn_oproj16_supported(c->ld, c->ll[layer].wo.N, c->ll[layer].wo.K, B);
+        if (what == 8 && !fused)
+            return fail(c, -1, "rdx_gemv_trace(8): the fused attention + o_proj launch is not active in this configuration (batch > 2, RDX_FUSE_AO=0)");
+        const int wgs = what == 7 ? H / 16 + ((c->ll[0].wqkv.Npad + 15) / 16 + 3) / 4      // down_proj tiles + QKV workgroups of 4 tiles
+                                  : f.heads * B + ((c->ll[layer].wo.N + 15) / 16 + 1) / 2;  // attention workgroups + o_proj workgroups of 2 tiles
+        if (wgs > max_tiles) return fail(c, -1, "rdx_gemv_trace(%d): need room for %d workgroups", what, wgs);
         long long* dtr = nullptr;
         const size_t bytes = (size_t)max_tiles * 8 * sizeof(long long);
         HIPCHK(c, hipMalloc(&dtr, bytes));
         HIPCHK(c, hipMemsetAsync(dtr, 0, bytes, c->stream));
-        c->chain_trace = dtr; c->chain_trace_layer = layer;
+        if (what == 7) { c->chain_trace = dtr; c->chain_trace_layer = layer; }
+        else { c->ao_trace = dtr; c->ao_trace_layer = layer; }
         const bool chained = decode_step_launch(c, nullptr, nullptr, 0);
         c->chain_trace = nullptr; c->chain_trace_layer = -1;
+        c->ao_trace = nullptr; c->ao_trace_layer = -1;
         c->cur_steps = std::max(c->cur_steps + 1, c->cur_max_new);      // the state has moved: a new prefill comes first
         hipError_t e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess) e = hipMemcpy(host, dtr, bytes, hipMemcpyDeviceToHost);
         hipFree(dtr);
         HIPCHK(c, e);
-        if (!chained) return fail(c, -1, "rdx_gemv_trace(7): the chained down -> QKV launch is not active in this configuration (batch > 2, RDX_CHAIN=0)");
+        if (what == 7 && !chained) return fail(c, -1, "rdx_gemv_trace(7): the chained down -> QKV launch is not active in this configuration (batch > 2, RDX_CHAIN=0)");
         return 0;
     }
     const LlamaLayer& L = c->ll[layer];

@@ -50,8 +50,9 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
     t.pos = advance ? c->d_pos : nullptr; t.slot_b = advance ? c->d_slot : nullptr; t.step_b = c->d_step;
     t.embed = c->embed; t.vocab = f.vocab; t.x_next = c->dx; t.H = f.hidden; t.pos_ro = c->d_pos; t.cos_t = c->rope_cos; t.sin_t = c->rope_sin;
     t.cur_rope = c->d_cur_rope;
-    t.ctr_zero = (c->fuse_attn_oproj || c->chain_mlp) ? c->d_ctr : nullptr;
-    t.n_zero = f.layers * 256 + (c->chain_mlp ? (int)chain_ctr_ints(f.layers) : 0);
+    t.ctr_zero = c->chain_mlp ? c->d_ctr : nullptr;
+    t.n_zero = (int)chain_ctr_ints(f.layers);
+    t.epoch = c->d_epoch;
     if (!c->rules_on) { launch_greedy_step(f.dtype, c->part_val, c->part_idx, c->n_vtiles, B, t, c->stream); return; }
     // the row at the address the lm_head just wrote (a captured step with scores: both offset it by the step count, read from d_step before the tail advances it)
     t.hist = c->d_hist; t.hist_len = c->d_hist_len; t.hist_ld = f.max_len;
@@ -307,7 +308,11 @@ static void attn_oproj(rdx_ctx* c, int l, int B) {
     DecAttnArgs at = dec_attn_args(c, l);
     const GemmArgs ao = unit_args(c, &L, UNIT_O, B);
     if (c->fuse_attn_oproj && attn_oproj16_supported(c->ld, L.wo.N, L.wo.K, B)) {
-        launch_attn_oproj16(dt, at, ao, B, c->d_ctr + (size_t)l * 256, c->d_err, c->stream);
+        at.trace = l == c->ao_trace_layer ? c->ao_trace : nullptr;
+        at.out = c->d_gran; at.epoch = c->d_epoch; at.layers = c->cfg.layers; at.layer = l;      // tagged granules instead of datt (handoff.h)
+        GemmArgs ag = ao;
+        ag.X = c->d_gran;
+        launch_attn_oproj16(dt, at, ag, B, c->d_hint, c->d_err, c->stream);
         return;
     }
     // batch 3-32: attention writes its output fragment-packed and o_proj runs K-split over two workgroups per tile,
@@ -336,8 +341,8 @@ static void step_generic(rdx_ctx* c, int B) {
 }
 
 // batch <= 2: QKV of layer 0 and every gate/up stand-alone, attention + o_proj fused, down(l) -> QKV(l+1) chained inside one launch by the fence-free hand-off.
-// The hand-off counter shards of the fused launches are cleared by greedy_step_k at the end of the previous step (and of the prefill): a memset node at the
-// head of the step graph was observed to race with the first producers. evs: an event pair around every chained launch (rdx_time 7).
+// The hand-off counter shards of the chained launches are cleared by greedy_step_k at the end of the previous step (and of the prefill): a memset node at the
+// head of the step graph was observed to race with the first producers. The fused launch's tagged granules need no clearing: step_tail bumps their epoch. evs: an event pair around every chained launch (rdx_time 7).
 static void step_chained(rdx_ctx* c, int B, std::vector<hipEvent_t>* evs) {
     const rdx_config& f = c->cfg;
     hipStream_t s = c->stream;

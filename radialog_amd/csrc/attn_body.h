@@ -48,7 +48,7 @@ template <> __device__ __forceinline__ float dot2<f16>(unsigned a, unsigned b, f
 
 template <typename T, int WAVES, bool DED = (WAVES == 8), typename WaitFn = NoWait, bool V_EARLY_ = !DED, int KG_ = 0, bool COH = false>
 __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, const int h, const int b, float* dsm,
-                                                      WaitFn wait_inputs = WaitFn()) {
+                                                      WaitFn wait_inputs = WaitFn(), const unsigned tag = 0u, int* hint = nullptr) {
     typedef typename Vec8<T>::type V8;
     constexpr int D = 128;
     // DED (register-tight launches): wave 0 is dedicated to the new token and holds no cache rows, so its register-hungry
@@ -82,7 +82,13 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
     T* vc = reinterpret_cast<T*>(a.vcache) + ((size_t)b * d.heads + h) * d.max_len * D;
     const uint8_t* km = a.key_mask + (size_t)b * d.max_len;
 
-    if (a.trace && h == 0 && b == 0 && tid == 0) a.trace[7] = (long long)__builtin_amdgcn_s_memrealtime();   // entry
+    // debug timeline (null in every product launch), 100 MHz ticks, thread 0. Stand-alone launches: workgroup (0, 0) alone, slots as rdx_attn_trace
+    // documents them. COH (the fused launch, rdx_gemv_trace 8): one record per workgroup at trace[(b heads + h) * 8]: [0] entry, [1] qkv row loaded (new
+    // token done), [2] scores done, [3] softmax done, [4] P.V reduced, [5] output stored (stores issued); [6] is the caller's
+    long long* trc = !(a.trace && tid == 0) ? nullptr : COH ? a.trace + ((size_t)b * d.heads + h) * 8 : (h == 0 && b == 0) ? a.trace : nullptr;
+#define ATT_T(i) do { constexpr int ts_ = COH ? ((i) == 7 ? 0 : (i) == 2 ? 1 : (i) == 4 ? 2 : (i) == 5 ? 3 : (i) == 6 ? 4 : (i) == 8 ? 5 : -1) : ((i) < 8 ? (i) : -1); \
+                      if (ts_ >= 0 && trc) trc[ts_] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
+    ATT_T(7);                                    // entry
     // ---- cache loads of this lane in flight first ------------------------------------------------------------------
     const int cw = DED ? w - 1 : w;              // cache-wave index (-1: the dedicated new-token wave)
     const bool owns_rows = !DED || w > 0;        // wave-uniform
@@ -151,8 +157,6 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
     }
     const int slot = a.slot_b[b];
     const int nk = slot + 1;
-    long long* trc = (a.trace && h == 0 && b == 0 && tid == 0) ? a.trace : nullptr;
-#define ATT_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
     ATT_T(0);
     wait_inputs();      // chained launches: the cache loads are already in flight; block until this step's qkv row is published
     ATT_T(1);
@@ -269,6 +273,8 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
     if (w == 0 && lane == 0) S[slot] = km_new ? rnd<T>(rnd<T>(s_new) / div) : -INFINITY;      // the new position itself
     __syncthreads();
     ATT_T(4);
+    // COH: the scores are finished, the output is about one round trip away -> open the consumers' sweep window (handoff.h; un-drained, a hint only)
+    if (COH && tid == 0) store_hint(hint, 0, tag);
 
     // ---- softmax statistics (fp32), recomputed by every wave -------------------------------------------------------
     float mx = -INFINITY;
@@ -364,16 +370,17 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
                            : a.out_packed != ACT_ROWS ? ((size_t)((pf * a.out_mt + (b >> 4)) * 64 + pg * 16 + (b & 15)) << 3) + (k & 7) : (size_t)b * H + k;
             reinterpret_cast<T*>(a.out)[o] = fromf<T>(v);
         }
-    } else if (tid < D / 4) {                                  // write-through 8-byte stores (4 dims per lane)
-        unsigned long long pk = 0ull;
+    } else if (tid < D / 2) {                                  // one tagged granule (2 dims) per lane: ONE aligned 8-byte write-through store, no drain, no signal
+        unsigned pk = 0u;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
+        for (int e = 0; e < 2; ++e) {
             float v = 0.f;
 #pragma unroll
-            for (int i = 0; i < WAVES; ++i) v += part[i * D + tid * 4 + e];
-            pk |= (unsigned long long)bits16<T>(fromf<T>(v)) << (16 * e);
+            for (int i = 0; i < WAVES; ++i) v += part[i * D + tid * 2 + e];
+            pk |= (unsigned)bits16<T>(fromf<T>(v)) << (16 * e);
         }
-        st8_agent(reinterpret_cast<T*>(a.out) + (size_t)b * H + h * D + tid * 4, pk);
+        store_granule(a.out, (((size_t)b * H + h * D) >> 1) + tid, pk, tag);
+        ATT_T(8);
     }
 #undef ATT_T
 }

@@ -10,7 +10,10 @@
 //                    then the row is loaded, normalised and staged (~2 us). A ring of 8 fragments per wave (25 MB over the chip, 4 us of
 //                    HBM time) left ~2 us of that with nothing in flight; the QKV role now holds 16 (half of a wave's K slice);
 //   attn_oproj16_k   decode attention (attn_body.h) -> o_proj (+ residual): 32 attention workgroups + 128 two-tile o_proj workgroups
-//                    whose whole K slice sits in registers while attention runs.
+//                    whose whole K slice sits in registers while attention runs. Its hand-off is DATA-TAGGED (handoff.h: WaitTagged): the
+//                    attention output travels as 8-byte {two elements, tag} granules in one buffer shared by all layers, the producer neither
+//                    drains nor signals, the consumer re-reads its own granules until the tags match and stages them; a hint word per head,
+//                    stored when the scores are finished, opens the sweep (profiles/r08_attn_oproj_handoff.md: 13.5 -> 12.6 us per launch).
 // Payloads are written write-through (8-byte agent-scope stores) and read with agent-scope loads: no cache fences. Arithmetic,
 // rounding points and the fixed-order LDS reduction are those of skinny_body.h (same oracle parity).
 // Liveness: a workgroup only waits on counters fed by lower-indexed workgroups; spins are bounded (handoff.h).
@@ -88,18 +91,24 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
     }
 
     wait_inputs();
-    CH_T(3);
+    if (!WaitFn::TAGGED) CH_T(3);
 
     // activations: published write-through by other workgroups of this launch -> agent-scope 8-byte loads (L1 bypass),
     // each chunk loaded ONCE and kept in registers across the RMSNorm statistics
     // XL = chunks of 4 elements per thread: M*K/4 <= XL*1024 (checked by chain_supported)
     const int K4 = K >> 2, total4 = a.M * K4;
     unsigned long long xr[XL];
+    if constexpr (WaitFn::TAGGED) {              // tagged granules (handoff.h): the loads are the wait; same chunks in the same registers
+        wait_inputs.template sweep<XL>(xr, a.X, a.ldx, K4, total4, CH_THREADS);
+        if (trace) __syncthreads();              // traced launches only: "inputs ready" = EVERY wave has its granules (a product launch meets at the staging barrier below)
+        CH_T(3);
+    } else {
 #pragma unroll
-    for (int i = 0; i < XL; ++i) {
-        const int c = threadIdx.x + i * CH_THREADS;
-        xr[i] = 0ull;
-        if (c < total4) { const int m = c / K4, k4 = c - m * K4; xr[i] = ld8_agent(X + (size_t)m * a.ldx + (size_t)k4 * 4); }
+        for (int i = 0; i < XL; ++i) {
+            const int c = threadIdx.x + i * CH_THREADS;
+            xr[i] = 0ull;
+            if (c < total4) { const int m = c / K4, k4 = c - m * K4; xr[i] = ld8_agent(X + (size_t)m * a.ldx + (size_t)k4 * 4); }
+        }
     }
     if (NORM) {
         float ss[CH_MAXM];
@@ -291,18 +300,26 @@ __global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_k(ChainArgs ca) {
 
 // ---- decode attention + o_proj(+residual) in ONE launch, 16-wave workgroups -------------------------------------------------
 // Workgroups [0, heads*B): attention exactly as the stand-alone latency kernel (wave 0 = new token, 15 cache waves),
-// output stored write-through. Workgroups [heads*B, +ntiles/2): two o_proj tiles each (8 waves per tile), whose WHOLE
-// K slice (16 chunks per wave) goes in flight at entry and sits in registers while attention runs; then the fence-free
-// hand-off (handoff.h) and ~2 us of work. heads*B + ntiles/2 <= 256 workgroups of <= 128 VGPRs: all resident, one per CU.
+// output stored write-through as tagged granules. Workgroups [heads*B, +ntiles/2): two o_proj tiles each (8 waves per tile), whose WHOLE
+// K slice (16 chunks per wave) goes in flight at entry and sits in registers while attention runs; then the data-tagged
+// hand-off (handoff.h: hint poll, granule sweep straight into the LDS staging) and ~2 us of work. heads*B + ntiles/2 <= 256 workgroups
+// of <= 128 VGPRs: all resident, one per CU.
 template <typename T, bool W8>
-__global__ __launch_bounds__(CH_THREADS, 4) void attn_oproj16_k(DecAttnArgs at, ChainGemm g, int n_attn, int ntiles, int* counter, int* err) {
+__global__ __launch_bounds__(CH_THREADS, 4) void attn_oproj16_k(DecAttnArgs at, ChainGemm g, int n_attn, int ntiles, int* hint, int* err) {
     extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
+    // debug timeline (rdx_gemv_trace 8; null in every product launch): one 8-slot record per workgroup, attention's slots in attn_body.h
+    // ([6] = its stores acknowledged, written here: only a traced launch drains them), o_proj's those of chain_tile
+    long long* trace = at.trace ? at.trace + (size_t)blockIdx.x * 8 : nullptr;
+    const unsigned tag = handoff_tag(*at.epoch, at.layers, at.layer);
     if ((int)blockIdx.x < n_attn) {
         const int b = blockIdx.x / at.d.heads, h = blockIdx.x - b * at.d.heads;
-        decode_attention_body<T, CH_WAVES, true, NoWait, true, 0, true>(at, h, b, reinterpret_cast<float*>(msm));
-        publish_sc1(counter, blockIdx.x);
+        decode_attention_body<T, CH_WAVES, true, NoWait, true, 0, true>(at, h, b, reinterpret_cast<float*>(msm), NoWait(), tag, hint + blockIdx.x);
+        if (trace && threadIdx.x == 0) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            trace[6] = (long long)__builtin_amdgcn_s_memrealtime();
+        }
     } else {
-        chain_tile<T, EPI_RESID, false, 2, 2, WaitSharded, W8 ? 4 : 8, true, W8>(g, blockIdx.x - n_attn, ntiles, msm, WaitSharded{counter, n_attn, err, 1, nullptr});
+        chain_tile<T, EPI_RESID, false, 2, 2, WaitTagged, W8 ? 4 : 8, true, W8>(g, blockIdx.x - n_attn, ntiles, msm, WaitTagged{hint, n_attn, tag, err}, trace);
     }
 }
 
@@ -312,17 +329,18 @@ bool attn_oproj16_supported(const LlamaDims& d, int N, int K, int B) {
            d.heads * B + (ntiles + 1) / 2 <= 256;
 }
 
-void launch_attn_oproj16(int dtype, const DecAttnArgs& a, const GemmArgs& ga, int B, int* counter, int* err, hipStream_t s) {
+void launch_attn_oproj16(int dtype, const DecAttnArgs& a, const GemmArgs& ga, int B, int* hint, int* err, hipStream_t s) {
     const int n_attn = a.d.heads * B, ntiles = (ga.N + 15) / 16;
     const bool w8 = ga.W8 && ga.wscale && ga.K % 64 == 0;
+    // a.out = ga.X = the granule buffer: [B][K] elements as 8-byte {pair, tag} granules
     ChainGemm g = {ga.X, ga.ldx, ga.W, ga.resid, ga.ldr, ga.out, ga.ldo, ga.M, ga.N, ga.K, nullptr, 0.f, ga.W8, ga.wscale};
     const size_t sm_gemm = (size_t)(CH_WAVES * 256 + CH_WAVES * CH_MAXM + 16) * 4 + (size_t)B * ga.K * 2;
     const size_t sm_att = decode_attention_smem_floats(CH_WAVES, a.d.max_len) * sizeof(float);
     const size_t smem = sm_gemm > sm_att ? sm_gemm : sm_att;
     dim3 grid(n_attn + (ntiles + 1) / 2), block(CH_THREADS);
     RDX_DISPATCH_T(dtype, T, {
-        if (w8) hipLaunchKernelGGL((attn_oproj16_k<T, true>), grid, block, smem, s, a, g, n_attn, ntiles, counter, err);
-        else hipLaunchKernelGGL((attn_oproj16_k<T, false>), grid, block, smem, s, a, g, n_attn, ntiles, counter, err);
+        if (w8) hipLaunchKernelGGL((attn_oproj16_k<T, true>), grid, block, smem, s, a, g, n_attn, ntiles, hint, err);
+        else hipLaunchKernelGGL((attn_oproj16_k<T, false>), grid, block, smem, s, a, g, n_attn, ntiles, hint, err);
     });
 }
 

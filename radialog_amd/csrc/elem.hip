@@ -583,6 +583,7 @@ __device__ __forceinline__ void step_tail(const StepTail& t, int b, int tok) {
         }
         if (step < t.max_new) t.out_tokens[(size_t)b * t.max_new + step] = tok;
         t.step_b[b] = step + 1;
+        if (b == 0 && t.epoch) *reinterpret_cast<unsigned*>(t.epoch) += 1u;      // a step has run: the next fused launches' tags differ from every one so far (handoff.h)
         if (t.slot_b) t.slot_b[b] += 1;      // null on the prefill call: token 0 is consumed by the first decode step
         int pcur = t.pos_ro ? t.pos_ro[b] : 0;
         if (t.pos) { pcur = t.pos[b] + 1; t.pos[b] = pcur; }

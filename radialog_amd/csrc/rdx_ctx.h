@@ -105,12 +105,14 @@ struct rdx_ctx {
     bool blk_down = true;            // 33-128 rows, model-dtype weights: down_proj K-split into fp32 slabs (xsplit32_k<.., BLK>); RDX_BLK_DOWN=0 at create: wstat_k, the A/B leg
     int chain_naps = 1;              // poll back-off of the chained launch (x s_sleep(8) between polls)
     long long* chain_trace = nullptr; int chain_trace_layer = -1;     // rdx_gemv_trace(7): device timeline buffer of ONE chained launch of the next step
+    long long* ao_trace = nullptr; int ao_trace_layer = -1;           // rdx_gemv_trace(8): the same for ONE fused attention + o_proj launch
     GemmW cls_fc1, cls_fc2; const float *cls_fc1_b = nullptr, *cls_fc2_b = nullptr;   // findings classifier head
     void *cls_pooled = nullptr, *cls_h = nullptr, *cls_out = nullptr;
     void* zero16 = nullptr;          // 16 zero bytes: source of padding taps in the DMA conv gather
     void* d_cur_rope = nullptr;      // [B][2][128] cos | sin row of each row's current position (written by greedy_step_k)
     ChainLayer* d_clayers = nullptr; int* d_cctr = nullptr;
-    int *d_ctr = nullptr, *d_err = nullptr;   // per-layer hand-off counters of the fused launch, sticky error flag
+    int *d_ctr = nullptr, *d_err = nullptr;   // hand-off counters of the chained launches (= d_cctr), sticky error flag
+    void* d_gran = nullptr; int *d_hint = nullptr, *d_epoch = nullptr;   // fused attention + o_proj launch: tagged-granule buffer [2][hidden] x 4 B, hint words, step epoch (handoff.h)
     int flash_min = 512;             // batched causal prefill attention: flash_prefill_k from this many workgroups (RDX_FLASH_MIN at create / rdx_set_option)
     bool pconv_noks = false;         // RDX_PCONV_KSPLIT=0 at create: pconv_k never splits K inside a workgroup (A/B)
     bool trunk_packed = true;        // the ResNet trunk (and the Q-Former GEMMs) on fragment-packed activations (pconv.hip); RDX_PCONV=0 at create: the row-major kernels

@@ -191,9 +191,12 @@ struct DecAttnArgs {
     const int *pos, *slot_b;
     const uint8_t* key_mask;
     void *kcache, *vcache, *out;
-    long long* trace = nullptr;      // debug: 8 timestamps (100 MHz ticks) of workgroup (b=0,h=0)
+    long long* trace = nullptr;      // debug: 8 timestamps (100 MHz ticks) of workgroup (b=0,h=0); the fused launch: [workgroup][8] (attn_body.h, chain.hip)
     ActLayout out_packed = ACT_ROWS; // stand-alone launches, from 3 rows: the order `out` is written in for the projection behind it (ACT_BLK32 / ACT_BLK64 / ACT_TILES32)
     int out_mt = 2;                  // ACT_TILES32: its row tiles
+    // the fused attention + o_proj launch only: `out` is the tagged-granule buffer (handoff.h), tag = handoff_tag(*epoch, layers, layer)
+    const int* epoch = nullptr;
+    int layers = 0, layer = 0;
 };
 void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, hipStream_t s);
 // Chained decode launches of the batch <= 2 step (chain.hip): units run as roles of one launch, chained by a fence-free counter
@@ -219,10 +222,11 @@ size_t chain_ctr_ints(int layers);
 // down_proj(l) (+ residual) -> RMSNorm + QKV(l + 1) in ONE launch, one workgroup per CU; with_next_qkv = false for the last layer
 void launch_decode_chain(int dtype, ChainArgs ca, bool with_next_qkv, hipStream_t s);
 // decode attention + o_proj (+ residual) in ONE launch of 16-wave workgroups: fast attention body, two o_proj tiles per workgroup with
-// their whole K slice in registers, fence-free hand-off. `counter` = 128 ints (8 shards), zero at launch; `err` is set to 1 if a wait
-// ever times out (never hangs).
+// their whole K slice in registers, data-tagged hand-off (handoff.h): a.out = g.X = the granule buffer ([2][hidden] x 4 bytes, one for the whole
+// model, never zeroed after creation), `hint` = HO_HINT_INTS words behind it; `err` is set to 1 if a wait ever times out (never hangs).
+constexpr int HO_HINT_INTS = 128;
 bool attn_oproj16_supported(const LlamaDims& d, int N, int K, int B);
-void launch_attn_oproj16(int dtype, const DecAttnArgs& a, const GemmArgs& g, int B, int* counter, int* err, hipStream_t s);
+void launch_attn_oproj16(int dtype, const DecAttnArgs& a, const GemmArgs& g, int B, int* hint, int* err, hipStream_t s);
 
 // LlamaRMSNorm of `rows` rows into any ActLayout (elem.hip). w null: re-layout only. slab: the fp32 partials [groups][slab rows][H] a K-split projection
 // left pending -- x[row] += T(sum over the groups, in order) first, written back to x; slab rows = the rows the layout holds (32 for ACT_ROWS, <= 32 rows).
@@ -266,10 +270,11 @@ void launch_gather_last(int dtype, const void* x, void* out, int B, int T, int H
 // What follows the selection of a row's token, for both greedy kernels (elem.hip: step_tail). pos / slot_b null: not advanced (the prefill call).
 // pos_ro / cos_t / sin_t / cur_rope: after the update, copy the cos | sin table row of each row's position into cur_rope [B][2][128] (pos_ro = the
 // position array even when `pos` is null). ctr_zero / n_zero: hand-off counter words to clear for the next decode step (nullable).
+// epoch (nullable): the step counter the tagged hand-off derives its tags from (handoff.h), incremented by thread 0 of block 0.
 // hist / hist_len / hist_ld: the token history [B][hist_ld] and its lengths, read and appended to by select_step_k only (greedy_step_k: null).
 struct StepTail {
     int eos_id, pad_id, max_new, vocab, H, n_zero, hist_ld;
-    int *out_tokens, *unfinished, *pos, *slot_b, *step_b, *ctr_zero, *hist, *hist_len;
+    int *out_tokens, *unfinished, *pos, *slot_b, *step_b, *ctr_zero, *hist, *hist_len, *epoch;
     const int* pos_ro;
     const void *embed, *cos_t, *sin_t;
     void *x_next, *cur_rope;

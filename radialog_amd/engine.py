@@ -661,7 +661,8 @@ class RdxEngine:
 
     def gemv_trace(self, what: int, layer: int, max_tiles: int = 2048):
         """Debug: per-workgroup timestamps [tiles, 8] of one stand-alone decode GEMV (1 gate/up, 2 qkv, 4 down); what = 7: of the chained
-        down(layer) -> QKV(layer + 1) launch inside ONE real eager decode step (advances the state; batch <= 2)."""
+        down(layer) -> QKV(layer + 1) launch inside ONE real eager decode step (advances the state; batch <= 2); what = 8 (_lib.TRACE_ATTN_OPROJ): of the
+        fused attention + o_proj launch of `layer`, the same way (attention workgroups first; slots in include/rdx_hooks.h)."""
         buf = torch.zeros(max_tiles, 8, dtype=torch.int64)
         check(self.ctx, self.lib.rdx_gemv_trace(self.ctx, what, layer, buf.data_ptr(), max_tiles), "rdx_gemv_trace")
         return buf
