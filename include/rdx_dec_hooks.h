@@ -1,5 +1,5 @@
-/* rdx_dec_hooks.h -- the decoder's 3-16-row (xs16.hip) and row-block (xstat32.hip, BLK) GEMM kernels one launch at a time on caller data
- * (tests/test_gpu_decoder_gemms.py). Like the hooks of rdx_hooks.h they live in radialog_amd/librdx_hooks.so (radialog_amd/csrc/api_dec_hooks.hip,
+/* rdx_dec_hooks.h -- the decoder's 3-16-row (xs16.hip) and row-block (xstat32.hip, BLK) GEMM kernels, its RMSNorm, decode attention and the prompt's RoPE / KV
+ * write one launch at a time on caller data (tests/test_gpu_decoder_gemms.py, test_gpu_rmsnorm.py, test_gpu_decode_attn.py). Like the hooks of rdx_hooks.h they live in radialog_amd/librdx_hooks.so (radialog_amd/csrc/api_dec_hooks.hip,
  * linked against librdx.so), never in the product library, and radialog_amd/_lib.py binds them (DEC_HOOK_SYMBOLS) only under RDX_DEBUG_HOOKS=1.
  * Each hook packs the fp32 weight W [N][K] with the production packer, allocates its own temporaries, asks the production *_supported predicate
  * (an unsupported shape is an error and launches nothing) and calls the production launch_* functions unchanged. All tensors are device pointers
@@ -61,6 +61,25 @@ int rdx_rmsnorm_test(rdx_ctx* ctx, void* x, const void* norm_w, float eps, int r
  * row, lowest index on ties. Works on any context (no weights involved). */
 int rdx_select_test(rdx_ctx* ctx, void* logits_inout, int B, int vocab, const int32_t* hist, const int32_t* hist_len, const int32_t* n_generated, int ld,
                     const rdx_logits_rules* rules, int eos_id, int32_t* tokens_out);
+
+/* launch_decode_attention alone (attn.hip, attn_body.h: one new token per row -- LoRA-B add, rotate-half RoPE, in-place KV append, attention over the cache), on
+ * caller data: hidden = 128 heads, qkv_ld = 3 hidden + 2 lora_r rounded up to 16. qkv [B][qkv_ld] (q | k | v | LoRA-A of q [8] | of v [8]), lbq / lbv [hidden][8]
+ * (lora_r 8; else ignored), EITHER cur_rope [B][2][128] (cos | sin row of each row's position) OR cos_t / sin_t [max_pos][128] with pos [B]; slot [B] (the
+ * cache slot the new token is written to = the number of cached positions), key_mask [B][max_len] bytes, kcache / vcache [B][heads][max_len][128] (K in the
+ * order k_perm names, rdx_common.h kperm), updated in place. out (out_bytes) is filled with 0xff bytes, then written in the order out_packed names (ActLayout 0-3;
+ * out_mt: the row tiles of ACT_TILES32). The variant (16, 8 or 4 waves) is the launcher's choice: heads x B, or RDX_ATT_TP. Refused before anything is
+ * written: max_len not a multiple of 32 in (0, 1536], lora_r not 0 or 8, a slot outside [1, max_len - 1], a zero mask byte at a row's own slot, a position
+ * outside the tables, an out_packed whose layout does not hold B rows (or out_bytes below its extent). */
+int rdx_decode_attn_test(rdx_ctx* ctx, int heads, int B, int max_len, int k_perm, int lora_r, float lora_scale, const void* qkv, const void* lbq, const void* lbv,
+                         const void* cur_rope, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos, const int32_t* slot,
+                         const uint8_t* key_mask, void* kcache, void* vcache, void* out, long long out_bytes, int out_packed, int out_mt);
+
+/* launch_rope_kv_prefill alone (attn.hip: the prompt's LoRA-B add, RoPE and KV-cache write), same dims: qkv [B][T][qkv_ld], pos_ids [B][T] (device), cos_t /
+ * sin_t [max_pos][128]; token t of row b lands in cache slot slot0 + t; qout [B T][hidden] is filled with 0xff bytes, then written. Refused before anything is
+ * written: slot0 < 0, slot0 + T > max_len, a position id outside the tables. */
+int rdx_rope_kv_test(rdx_ctx* ctx, int heads, int B, int T, int max_len, int k_perm, int lora_r, float lora_scale, const void* qkv, const void* lbq,
+                     const void* lbv, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos_ids, int slot0, void* kcache, void* vcache,
+                     void* qout);
 
 #ifdef __cplusplus
 }

@@ -125,6 +125,9 @@ DEC_HOOK_SYMBOLS = {
     "rdx_xsplit_blk8_test": (C.c_int, [_P, _P, _P, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_rmsnorm_test": (C.c_int, [_P, _P, _P, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong, _P, C.c_int]),
     "rdx_select_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, _P]),
+    "rdx_decode_attn_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_longlong,
+                                       C.c_int, C.c_int]),
+    "rdx_rope_kv_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
 }
 ALL_HOOK_SYMBOLS = {**HOOK_SYMBOLS, **ENC_HOOK_SYMBOLS, **DEC_HOOK_SYMBOLS}
 

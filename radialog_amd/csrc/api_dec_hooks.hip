@@ -1,5 +1,5 @@
-// librdx_hooks.so, second unit: the decoder's 3-16-row and row-block GEMM kernels and its RMSNorm on caller data (include/rdx_dec_hooks.h;
-// tests/test_gpu_decoder_gemms.py, tests/test_gpu_rmsnorm.py). Every hook packs the caller's fp32 weight with the production packer, allocates its own temporaries (the test
+// librdx_hooks.so, second unit: the decoder's 3-16-row and row-block GEMM kernels, its RMSNorm, decode attention and the prompt's RoPE / KV write on caller data
+// (include/rdx_dec_hooks.h; tests/test_gpu_decoder_gemms.py, tests/test_gpu_rmsnorm.py, tests/test_gpu_decode_attn.py). Every hook packs the caller's fp32 weight with the production packer, allocates its own temporaries (the test
 // engines have no decoder: c->kslab / c->dxs / c->dxn do not exist), asks the production *_supported predicate BEFORE anything is launched on the
 // caller's outputs, and calls the production launch_* functions unchanged. Temporaries the kernels only partly write are filled with 0xff bytes
 // (NaN in both model dtypes and in fp32) first.
@@ -239,5 +239,80 @@ extern "C" int rdx_select_test(rdx_ctx* c, void* logits_inout, int B, int vocab,
     t.vocab = vocab; t.eos_id = eos_id;
     t.hist = const_cast<int32_t*>(hist); t.hist_len = const_cast<int32_t*>(hist_len); t.hist_ld = ld;       // read only: with sel_out set the tail does not run
     launch_select_step(c->cfg.dtype, a, t, B, c->stream);
+    return finish(c);
+}
+
+namespace {
+
+// the dims both attention hooks build: hidden = 128 heads, the QKV row as the engine lays it out (api.hip: wqkv.Npad)
+bool attn_dims(LlamaDims& d, int heads, int max_len, int k_perm, int lora_r, float lora_scale, int max_pos) {
+    if (heads <= 0 || heads > 64 || max_len <= 0 || max_len > 1536 || max_len % 32 || !(lora_r == 0 || lora_r == 8)) return false;
+    d.hidden = 128 * heads; d.heads = heads; d.head_dim = 128; d.qkv_ld = (3 * d.hidden + 2 * lora_r + 15) / 16 * 16;
+    d.lora_r = lora_r; d.lora_scale = lora_scale; d.max_len = max_len; d.max_pos = max_pos; d.k_perm = k_perm ? 1 : 0;
+    return true;
+}
+
+}  // namespace
+
+extern "C" int rdx_decode_attn_test(rdx_ctx* c, int heads, int B, int max_len, int k_perm, int lora_r, float lora_scale, const void* qkv, const void* lbq,
+                                    const void* lbv, const void* cur_rope, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos,
+                                    const int32_t* slot, const uint8_t* key_mask, void* kcache, void* vcache, void* out, long long out_bytes, int out_packed,
+                                    int out_mt) {
+    if (!c || !qkv || !slot || !key_mask || !kcache || !vcache || !out || B <= 0 || B > 4096) return fail(c, -1, "rdx_decode_attn_test: bad arguments");
+    DecAttnArgs a;
+    if (!attn_dims(a.d, heads, max_len, k_perm, lora_r, lora_scale, max_pos))
+        return fail(c, -1, "rdx_decode_attn_test: heads %d, max_len %d (a multiple of 32 in (0, 1536]), lora_r %d (0 or 8)", heads, max_len, lora_r);
+    if (lora_r && (!lbq || !lbv)) return fail(c, -1, "rdx_decode_attn_test: lora_r 8 needs lbq and lbv");
+    const bool tables = cos_t && sin_t && pos && max_pos > 0;
+    if ((cur_rope != nullptr) == tables || (!cur_rope && (cos_t || sin_t || pos) && !tables))
+        return fail(c, -1, "rdx_decode_attn_test: either cur_rope, or cos_t / sin_t / pos with max_pos > 0");
+    const size_t H = a.d.hidden;
+    size_t extent = 0;      // bytes the layout holds; 0: it does not hold B rows
+    switch (out_packed) {
+    case ACT_ROWS: extent = (size_t)B * H * 2; break;
+    case ACT_BLK32: out_mt = 2; extent = B <= 32 ? 32 * H * 2 : 0; break;
+    case ACT_BLK64: extent = (size_t)((B + 31) / 32) * 32 * H * 2; break;
+    case ACT_TILES32: extent = (out_mt > 0 && B <= 16 * out_mt) ? (size_t)16 * out_mt * H * 2 : 0; break;
+    default: break;
+    }
+    if (!extent || out_bytes < (long long)extent)
+        return fail(c, -1, "rdx_decode_attn_test: out_packed %d (out_mt %d, %lld bytes) does not hold %d rows", out_packed, out_mt, out_bytes, B);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int32_t> hs(B), hp(B);
+    std::vector<uint8_t> hm((size_t)B * max_len);
+    HIPCHK(c, hipMemcpy(hs.data(), slot, (size_t)B * 4, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(hm.data(), key_mask, hm.size(), hipMemcpyDeviceToHost));
+    if (tables) HIPCHK(c, hipMemcpy(hp.data(), pos, (size_t)B * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < B; ++b) {
+        if (hs[b] < 1 || hs[b] > max_len - 1) return fail(c, -1, "rdx_decode_attn_test: row %d: slot %d outside [1, %d]", b, hs[b], max_len - 1);
+        if (!hm[(size_t)b * max_len + hs[b]]) return fail(c, -1, "rdx_decode_attn_test: row %d: the mask byte of its own slot %d is zero", b, hs[b]);
+        if (tables && (hp[b] < 0 || hp[b] >= max_pos)) return fail(c, -1, "rdx_decode_attn_test: row %d: position %d outside the tables [0, %d)", b, hp[b], max_pos);
+    }
+    a.qkv = qkv; a.lbq = lbq; a.lbv = lbv; a.cos_t = cos_t; a.sin_t = sin_t; a.cur_rope = cur_rope; a.pos = pos; a.slot_b = slot; a.key_mask = key_mask;
+    a.kcache = kcache; a.vcache = vcache; a.out = out; a.out_packed = (ActLayout)out_packed; a.out_mt = out_mt;
+    HIPCHK(c, hipMemsetAsync(out, 0xff, (size_t)out_bytes, c->stream));
+    launch_decode_attention(c->cfg.dtype, a, B, c->stream);
+    return finish(c);
+}
+
+extern "C" int rdx_rope_kv_test(rdx_ctx* c, int heads, int B, int T, int max_len, int k_perm, int lora_r, float lora_scale, const void* qkv, const void* lbq,
+                                const void* lbv, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos_ids, int slot0, void* kcache,
+                                void* vcache, void* qout) {
+    if (!c || !qkv || !cos_t || !sin_t || !pos_ids || !kcache || !vcache || !qout || B <= 0 || B > 4096 || T <= 0 || max_pos <= 0)
+        return fail(c, -1, "rdx_rope_kv_test: bad arguments");
+    LlamaDims d;
+    if (!attn_dims(d, heads, max_len, k_perm, lora_r, lora_scale, max_pos))
+        return fail(c, -1, "rdx_rope_kv_test: heads %d, max_len %d (a multiple of 32 in (0, 1536]), lora_r %d (0 or 8)", heads, max_len, lora_r);
+    if (lora_r && (!lbq || !lbv)) return fail(c, -1, "rdx_rope_kv_test: lora_r 8 needs lbq and lbv");
+    if (slot0 < 0 || T > max_len || slot0 > max_len - T) return fail(c, -1, "rdx_rope_kv_test: slots [%d, %d + %d) do not fit max_len %d", slot0, slot0, T, max_len);
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<int32_t> hp((size_t)B * T);
+    HIPCHK(c, hipMemcpy(hp.data(), pos_ids, hp.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < hp.size(); ++i)
+        if (hp[i] < 0 || hp[i] >= max_pos) return fail(c, -1, "rdx_rope_kv_test: position id %d (row %d, token %d) outside the tables [0, %d)", hp[i], (int)(i / T), (int)(i % T), max_pos);
+    HIPCHK(c, hipMemsetAsync(qout, 0xff, (size_t)B * T * d.hidden * 2, c->stream));
+    launch_rope_kv_prefill(c->cfg.dtype, d, qkv, lbq, lbv, cos_t, sin_t, pos_ids, qout, kcache, vcache, B, T, slot0, c->stream);
     return finish(c);
 }

@@ -593,6 +593,52 @@ class RdxEngine:
             err = msg.decode() if msg else "?"
         return err, out, xs, x
 
+    def _last_error(self):
+        msg = self.lib.rdx_last_error(self.ctx)
+        return msg.decode() if msg else "?"
+
+    def decode_attn_test(self, qkv, kcache, vcache, slot, key_mask, k_perm, cur_rope=None, cos=None, sin=None, pos=None, lbq=None, lbv=None, lora_scale=1.0,
+                         out_packed=0, out_mt=2, out_bytes=None):
+        """launch_decode_attention alone (rdx_decode_attn_test): qkv [B, qkv_ld], kcache / vcache [B, heads, max_len, 128] (K in the order k_perm names), slot int
+        [B], key_mask uint8 [B, max_len]; cur_rope [B, 2, 128], or cos / sin [max_pos, 128] with pos int [B]; lbq / lbv [128 heads, 8] switch LoRA on. Returns
+        (error message or None, raw output uint8 [out_bytes], updated K cache, updated V cache); the caller's tensors are left as they are, and the output is
+        0xff bytes wherever the kernel wrote nothing -- everywhere after a refusal, which does not raise."""
+        B, heads, max_len = kcache.shape[:3]
+        H = 128 * heads
+        x, kc, vc = self._dev(qkv), self._dev(kcache).clone(), self._dev(vcache).clone()
+        sl, km = self._dev(slot, torch.int32), self._dev(key_mask, torch.uint8)
+        cr, ct, st, ps = self._dev(cur_rope), self._dev(cos), self._dev(sin), self._dev(pos, torch.int32)
+        bq, bv = self._dev(lbq), self._dev(lbv)
+        lora_r = 0 if lbq is None else 8
+        if tuple(x.shape) != (B, (3 * H + 2 * lora_r + 15) // 16 * 16) or vc.shape != kc.shape or kc.shape[3] != 128 or sl.numel() != B or tuple(km.shape) != (B, max_len):
+            raise ValueError("decode_attn_test: qkv [B, qkv_ld], caches [B, heads, max_len, 128], slot [B], key_mask [B, max_len]")
+        if (cr is not None and tuple(cr.shape) != (B, 2, 128)) or (ps is not None and ps.numel() != B) or (bq is not None and (tuple(bq.shape) != (H, 8) or tuple(bv.shape) != (H, 8))):
+            raise ValueError("decode_attn_test: cur_rope [B, 2, 128], pos [B], lbq / lbv [hidden, 8]")
+        out = torch.full((B * H * 2 if out_bytes is None else out_bytes,), 0xff, dtype=torch.uint8, device=self.device)
+        torch.cuda.synchronize(self.device)
+        rc = self.lib.rdx_decode_attn_test(self.ctx, heads, B, max_len, int(k_perm), lora_r, float(lora_scale), _ptr(x), _ptr(bq), _ptr(bv), _ptr(cr), _ptr(ct), _ptr(st),
+                                           0 if ct is None else ct.shape[0], _ptr(ps), _ptr(sl), _ptr(km), _ptr(kc), _ptr(vc), _ptr(out), out.numel(), int(out_packed),
+                                           int(out_mt))
+        return (None if rc == 0 else self._last_error()), out, kc, vc
+
+    def rope_kv_test(self, qkv, pos_ids, cos, sin, slot0, kcache, vcache, k_perm, lbq=None, lbv=None, lora_scale=1.0):
+        """launch_rope_kv_prefill alone (rdx_rope_kv_test): qkv [B, T, qkv_ld], pos_ids int [B, T], cos / sin [max_pos, 128], caches [B, heads, max_len, 128].
+        Returns (error message or None, qout [B T, hidden] (0xff bytes where nothing was written), updated K cache, updated V cache)."""
+        B, heads, max_len = kcache.shape[:3]
+        T, H = qkv.shape[1], 128 * heads
+        x, kc, vc = self._dev(qkv), self._dev(kcache).clone(), self._dev(vcache).clone()
+        pi, ct, st, bq, bv = self._dev(pos_ids, torch.int32), self._dev(cos), self._dev(sin), self._dev(lbq), self._dev(lbv)
+        lora_r = 0 if lbq is None else 8
+        bad_b = bq is not None and (tuple(bq.shape) != (H, 8) or tuple(bv.shape) != (H, 8))
+        if tuple(x.shape) != (B, T, (3 * H + 2 * lora_r + 15) // 16 * 16) or vc.shape != kc.shape or kc.shape[3] != 128 or tuple(pi.shape) != (B, T) or bad_b \
+                or ct.shape != st.shape or ct.shape[1] != 128:
+            raise ValueError("rope_kv_test: qkv [B, T, qkv_ld], pos_ids [B, T], cos / sin [max_pos, 128], caches [B, heads, max_len, 128], lbq / lbv [hidden, 8]")
+        qout = torch.full((B * T * H * 2,), 0xff, dtype=torch.uint8, device=self.device)
+        torch.cuda.synchronize(self.device)
+        rc = self.lib.rdx_rope_kv_test(self.ctx, heads, B, T, max_len, int(k_perm), lora_r, float(lora_scale), _ptr(x), _ptr(bq), _ptr(bv), _ptr(ct), _ptr(st), ct.shape[0],
+                                       _ptr(pi), int(slot0), _ptr(kc), _ptr(vc), _ptr(qout))
+        return (None if rc == 0 else self._last_error()), qout.view(self.tdtype).view(B * T, H), kc, vc
+
     def classify_findings(self, image: torch.Tensor) -> torch.Tensor:
         """ChexpertClassifier.forward: float32[B,3,S,S] on the device -> float32[B,classes] logits."""
         image = image.to(self.device, torch.float32).contiguous()

@@ -74,7 +74,7 @@ def test_encoder_hooks_are_declared_bound_and_only_in_the_hooks_library(monkeypa
 
 def test_decoder_hooks_are_declared_bound_and_only_in_the_hooks_library(monkeypatch):
     """The decoder's GEMM kernel-test hooks (include/rdx_dec_hooks.h: rdx_xstat16_test, rdx_xrow16_test, rdx_xstat_blk_test, rdx_xsplit_blk_test, the
-    fp8 pair and rdx_rmsnorm_test) follow the rules of rdx_hooks.h: header and binding table agree and share no name with the other tables, librdx_hooks.so exports
+    fp8 pair, rdx_rmsnorm_test, rdx_select_test, rdx_decode_attn_test and rdx_rope_kv_test) follow the rules of rdx_hooks.h: header and binding table agree and share no name with the other tables, librdx_hooks.so exports
     them and librdx.so does not, _lib binds them with their argtypes under RDX_DEBUG_HOOKS=1 and replaces them with raising stubs without it; the
     source they are built from is part of the build and of the source hash."""
     from radialog_amd import build
