@@ -15,6 +15,17 @@ HOOK_SOURCES = ["api_debug.hip", "api_dec_hooks.hip"]
 HEADERS = ["rdx_common.h", "rdx_kernels.h", "rdx_ctx.h", "skinny_body.h", "attn_body.h", "handoff.h", os.path.join("..", "..", "include", "rdx.h"),
            os.path.join("..", "..", "include", "rdx_hooks.h"), os.path.join("..", "..", "include", "rdx_enc_hooks.h"), os.path.join("..", "..", "include", "rdx_dec_hooks.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
+# Kernarg preloading, for the units that hold the kernels of the batch-1/2 decode step only (skinny_gemm_k; decode_chain_k, attn_oproj16_k): the command
+# processor places up to 14 dwords of LEADING non-aggregate kernel arguments in SGPRs before the first wave starts, and these kernels address their first
+# weight loads from exactly those (csrc/rdx_common.h late_kernarg; tests/test_isa_entry.py holds the entry blocks to it). Firmware without the feature
+# runs the compatibility header the compiler emits in front of each kernel: the same scalar loads as without the flag.
+PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=14"]
+UNIT_FLAGS = {"chain.hip": PRELOAD, "gemm.hip": PRELOAD}
+
+
+def unit_flags(source: str) -> list:
+    """Every compiler flag of one unit, in order (the ISA tests compile with the same)."""
+    return FLAGS + UNIT_FLAGS.get(source, [])
 
 
 def source_hash() -> str:
@@ -22,6 +33,8 @@ def source_hash() -> str:
     replayed PMC figure whose tree differs from the one that is running)."""
     import hashlib
     h = hashlib.sha256()
+    # the flags are part of what a library is: one built without a unit's own flags must not pass for this tree's
+    h.update(repr((FLAGS, sorted(UNIT_FLAGS.items()))).encode())
     # kernels, launchers and the ABI implementation; the two public headers under include/ (declarations and prose) are not part of it
     for s in sorted(SOURCES + HOOK_SOURCES) + sorted(h for h in HEADERS if not h.startswith("..")):
         with open(os.path.join(CSRC, s), "rb") as f:
@@ -67,7 +80,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         # api.hip carries the hash (rdx_build_hash): recompiled on every rebuild; the other units only when they or a header changed
         if not force and s != "api.hip" and not _obj_stale(src, o, hdr_mtime):
             continue
-        cmd = [hipcc] + FLAGS + ([f'-DRDX_BUILD_HASH="{h}"'] if s == "api.hip" else []) + ["-c", src, "-o", o]
+        cmd = [hipcc] + unit_flags(s) + ([f'-DRDX_BUILD_HASH="{h}"'] if s == "api.hip" else []) + ["-c", src, "-o", o]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((cmd, subprocess.Popen(cmd)))

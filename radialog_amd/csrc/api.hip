@@ -264,15 +264,6 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
         HIPCHK(c, hipMemset(c->d_epoch, 0, sizeof(int)));
         c->d_hint = reinterpret_cast<int*>(reinterpret_cast<char*>(c->d_gran) + (size_t)2 * H * 4);
         HIPCHK(c, hipMemset(c->d_err, 0, sizeof(int)));
-        {
-            std::vector<ChainLayer> cl(f.layers);
-            for (int l = 0; l < f.layers; ++l) {
-                const LlamaLayer& L = c->ll[l];
-                cl[l] = ChainLayer{L.wqkv.w, L.wdown.w, L.attn_norm, L.wqkv.w8, L.wdown.w8, L.wqkv.scale, L.wdown.scale};
-            }
-            ALLOC(c, c->d_clayers, cl.size() * sizeof(ChainLayer));
-            HIPCHK(c, hipMemcpy(c->d_clayers, cl.data(), cl.size() * sizeof(ChainLayer), hipMemcpyHostToDevice));
-        }
         ALLOC(c, c->d_cur_rope, (size_t)B * 256 * 2);
         ALLOC(c, c->d_pos_ids, (size_t)B * f.max_len * sizeof(int));
         c->n_vtiles = c->lm_head.Npad / 16;

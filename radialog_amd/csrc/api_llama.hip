@@ -348,7 +348,7 @@ static void step_chained(rdx_ctx* c, int B, std::vector<hipEvent_t>* evs) {
     hipStream_t s = c->stream;
     ChainArgs ca;
     memset(&ca, 0, sizeof(ca));
-    ca.layers = c->d_clayers; ca.hidden = f.hidden; ca.inter = f.inter; ca.qkv_n = c->ll[0].wqkv.Npad; ca.qkv_ld = c->ld.qkv_ld; ca.B = B; ca.eps = f.rms_eps;
+    ca.hidden = f.hidden; ca.inter = f.inter; ca.qkv_n = c->ll[0].wqkv.Npad; ca.qkv_ld = c->ld.qkv_ld; ca.B = B; ca.eps = f.rms_eps;
     ca.dx = c->dx; ca.dqkv = c->dqkv; ca.dgu = c->dgu; ca.ctr = c->d_cctr; ca.err = c->d_err; ca.naps = c->chain_naps;
     const LlamaLayer& L0 = c->ll[0];        // fp8 weights: the chained roles stream the e4m3 bytes too
     ca.w8 = (L0.wqkv.w8 && L0.wdown.w8 && f.hidden % 64 == 0 && f.inter % 64 == 0) ? 1 : 0;
@@ -359,6 +359,13 @@ static void step_chained(rdx_ctx* c, int B, std::vector<hipEvent_t>* evs) {
         skinny(c, unit_args(c, &c->ll[l], UNIT_GATE_UP, B), EPI_SILU_MUL);
         mark();
         ca.layer = l;
+        {       // the layer's pointers by value: down_proj of l, norm + QKV of l + 1 (the last launch has no QKV role)
+            const LlamaLayer& L = c->ll[l];
+            const LlamaLayer* Ln = l + 1 < f.layers ? &c->ll[l + 1] : nullptr;
+            ca.wdown = L.wdown.w; ca.wdown8 = L.wdown.w8; ca.sdown = L.wdown.scale;
+            ca.wqkv = Ln ? Ln->wqkv.w : nullptr; ca.wqkv8 = Ln ? Ln->wqkv.w8 : nullptr; ca.sqkv = Ln ? Ln->wqkv.scale : nullptr;
+            ca.attn_norm = Ln ? Ln->attn_norm : nullptr;
+        }
         ca.trace = l == c->chain_trace_layer ? c->chain_trace : nullptr;
         launch_decode_chain(f.dtype, ca, l + 1 < f.layers, s);
         mark();

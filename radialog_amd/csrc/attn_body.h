@@ -46,9 +46,20 @@ template <> __device__ __forceinline__ float dot2<f16>(unsigned a, unsigned b, f
     return __builtin_amdgcn_fdot2(__builtin_bit_cast(v2h, a), __builtin_bit_cast(v2h, b), c, false);
 }
 
-template <typename T, int WAVES, bool DED = (WAVES == 8), typename WaitFn = NoWait, bool V_EARLY_ = !DED, int KG_ = 0, bool COH = false>
-__device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, const int h, const int b, float* dsm,
-                                                      WaitFn wait_inputs = WaitFn(), const unsigned tag = 0u, int* hint = nullptr) {
+// What the first loads of a workgroup are addressed from -- wave 0: the q / k / v pieces of the qkv row; the cache waves: their K fragments and V rows.
+// In the fused launch these are preloaded kernel arguments (chain.hip) and everything else is read behind those loads: `late()` returns the whole
+// DecAttnArgs (late_kernarg there; the stand-alone kernels pass AttnNow, a reference), `late.hint()` the workgroup's hint word.
+struct AttnEarly { const void* qkv; void *kcache, *vcache; LlamaDims d; };      // d: hidden, heads, qkv_ld, max_len, k_perm (the rest of it: late().d)
+struct AttnNow {
+    const DecAttnArgs& a;
+    __device__ __forceinline__ const DecAttnArgs& operator()() const { return a; }
+    __device__ __forceinline__ int* hint() const { return nullptr; }
+};
+
+// COH: the OUTPUT is in-launch traffic (tagged granules + hint of the fused attention + o_proj launch, tag from a.epoch). COHX: the qkv row was
+// published by other workgroups of THIS launch and is read with agent-scope loads; in the fused launch the row predates the launch (COHX = false)
+template <typename T, int WAVES, bool DED, typename WaitFn, bool V_EARLY_, int KG_, bool COH, bool COHX, typename Late>
+__device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late late, const int h, const int b, float* dsm, WaitFn wait_inputs) {
     typedef typename Vec8<T>::type V8;
     constexpr int D = 128;
     // DED (register-tight launches): wave 0 is dedicated to the new token and holds no cache rows, so its register-hungry
@@ -62,12 +73,8 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
     // 4-wave build (it has 19 VGPRs to spare since the new token's registers are retired early): 3 groups, 8 rows or both are 1.0-1.3 us SLOWER at
     // every context from 96 to 448 (30.8 -> 31.9-32.1 us at 288) -- as with every earlier attempt to put more of this kernel's requests in flight
     constexpr int KT = 2, VT = 4;
-    const LlamaDims& d = a.d;
-    const T* qkv = reinterpret_cast<const T*>(a.qkv);
-    const T* lbq = reinterpret_cast<const T*>(a.lbq);
-    const T* lbv = reinterpret_cast<const T*>(a.lbv);
-    const T* cos_t = reinterpret_cast<const T*>(a.cos_t);
-    const T* sin_t = reinterpret_cast<const T*>(a.sin_t);
+    const LlamaDims& d = e.d;
+    const T* qkv = reinterpret_cast<const T*>(e.qkv);
 
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
     float* part = dsm;                                   // [WAVES][D]
@@ -78,17 +85,19 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
     const int g = lane >> 4, r = lane & 15;              // K view (MFMA A fragment): position r of the group, dims 32*c + 8*g
     const int H = d.hidden;
     const T* x = qkv + (size_t)b * d.qkv_ld;
-    T* kc = reinterpret_cast<T*>(a.kcache) + ((size_t)b * d.heads + h) * d.max_len * D;
-    T* vc = reinterpret_cast<T*>(a.vcache) + ((size_t)b * d.heads + h) * d.max_len * D;
-    const uint8_t* km = a.key_mask + (size_t)b * d.max_len;
+    T* kc = reinterpret_cast<T*>(e.kcache) + ((size_t)b * d.heads + h) * d.max_len * D;
+    T* vc = reinterpret_cast<T*>(e.vcache) + ((size_t)b * d.heads + h) * d.max_len * D;
 
     // debug timeline (null in every product launch), 100 MHz ticks, thread 0. Stand-alone launches: workgroup (0, 0) alone, slots as rdx_attn_trace
     // documents them. COH (the fused launch, rdx_gemv_trace 8): one record per workgroup at trace[(b heads + h) * 8]: [0] entry, [1] qkv row loaded (new
     // token done), [2] scores done, [3] softmax done, [4] P.V reduced, [5] output stored (stores issued); [6] is the caller's
-    long long* trc = !(a.trace && tid == 0) ? nullptr : COH ? a.trace + ((size_t)b * d.heads + h) * 8 : (h == 0 && b == 0) ? a.trace : nullptr;
+    // (COH: the entry time is taken unconditionally and stored behind the first loads -- the trace pointer is not among the preloaded arguments)
+    long long t_entry = 0;
+    if (COH) t_entry = (long long)__builtin_amdgcn_s_memrealtime();
+    long long* trc = nullptr;
 #define ATT_T(i) do { constexpr int ts_ = COH ? ((i) == 7 ? 0 : (i) == 2 ? 1 : (i) == 4 ? 2 : (i) == 5 ? 3 : (i) == 6 ? 4 : (i) == 8 ? 5 : -1) : ((i) < 8 ? (i) : -1); \
                       if (ts_ >= 0 && trc) trc[ts_] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
-    ATT_T(7);                                    // entry
+    if (!COH) { const DecAttnArgs& a0 = late(); trc = !(a0.trace && tid == 0) ? nullptr : (h == 0 && b == 0) ? a0.trace : nullptr; ATT_T(7); }      // entry
     // ---- cache loads of this lane in flight first ------------------------------------------------------------------
     const int cw = DED ? w - 1 : w;              // cache-wave index (-1: the dedicated new-token wave)
     const bool owns_rows = !DED || w > 0;        // wave-uniform
@@ -98,7 +107,8 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
     // is known and only by the waves whose rows exist (all of a head's cache traffic funnels through ONE CU's L1 at
     // 64 B/clk, so a fully loaded 480-position window costs ~2 us whatever the context length).
     constexpr int KG_LO = (KG + 1) / 2, VR_LO = 4 * KG_LO;
-    auto load_k = [&](int u0, int u1, int limit) {
+    // mask(): the row's key-mask bytes -- a late argument, so the entry window fetches the pointer behind its first K loads and later calls pass `km`
+    auto load_k = [&](int u0, int u1, int limit, auto&& mask) {
 #pragma unroll
         for (int u = 0; u < KG; ++u) {
             const int gb = (u * CW + cw) * 16;
@@ -106,7 +116,7 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
                 const int j = min(gb + r, d.max_len - 1);
 #pragma unroll
                 for (int c = 0; c < 4; ++c) kr[u][c] = ldg16(kc + kperm(j, c * 32 + g * 8, d.k_perm));
-                kmw[u] = *reinterpret_cast<const unsigned*>(km + min(gb + 4 * g, d.max_len - 4));
+                kmw[u] = *reinterpret_cast<const unsigned*>(mask() + min(gb + 4 * g, d.max_len - 4));
             }
         }
     };
@@ -127,21 +137,26 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
     const int n0 = h * D + doct * 8;
     u4 nq, nk_, nv, ncos, nsin, naq, nav, nbq0, nbq1, nbv0, nbv1;
     auto load_newtok = [&]() {
-        // COH (chained launches): the qkv row was published write-through by other workgroups of THIS launch -> read it
+        // COHX (chained launches): the qkv row was published write-through by other workgroups of THIS launch -> read it
         // with agent-scope loads (L1 bypass); everything else this kernel reads predates the launch
         auto ldx = [&](const T* p) -> u4 {
-            if (!COH) return ldg16(p);
+            if (!COHX) return ldg16(p);
             const unsigned long long lo = ld8_agent(p), hi = ld8_agent(p + 4);
             return (u4){(unsigned)lo, (unsigned)(lo >> 32), (unsigned)hi, (unsigned)(hi >> 32)};
         };
         nq = ldx(x + n0); nk_ = ldx(x + H + n0); nv = ldx(x + 2 * H + n0);
+        const DecAttnArgs& a = late();
+        const T* lbq = reinterpret_cast<const T*>(a.lbq);
+        const T* lbv = reinterpret_cast<const T*>(a.lbv);
+        const T* cos_t = reinterpret_cast<const T*>(a.cos_t);
+        const T* sin_t = reinterpret_cast<const T*>(a.sin_t);
         // cos/sin row of this token's position: from the per-row copy greedy_step_k left behind (no pos -> table
         // dependent load on the critical path), else from the tables
         const T* cs = reinterpret_cast<const T*>(a.cur_rope);
         const T* cp = cs ? cs + (size_t)b * 2 * D : cos_t + (size_t)a.pos[b] * D;
         const T* sp = cs ? cs + (size_t)b * 2 * D + D : sin_t + (size_t)a.pos[b] * D;
         ncos = ldg16(cp + doct * 8); nsin = ldg16(sp + doct * 8);
-        if (d.lora_r == 8) {
+        if (a.d.lora_r == 8) {
             // The four jsub groups of the wave hold the same 8 dims; each takes two of the eight LoRA-B rows, so all
             // B loads are ONE round trip (4 x 16 B per lane), and the deltas come back through shuffles.
             const int e0 = 2 * jsub;
@@ -150,13 +165,28 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
             nbv0 = ldg16(lbv + (size_t)(n0 + e0) * 8); nbv1 = ldg16(lbv + (size_t)(n0 + e0 + 1) * 8);
         }
     };
-    if (!HAS_WAIT && w == 0) load_newtok();
-    if (owns_rows) {
-        load_k(0, KG_LO, 0x7fffffff);            // unconditional (addresses clamped into the cache): these registers are
+    auto entry_window = [&] {
+        load_k(0, KG_LO, 0x7fffffff, [&] { return late().key_mask + (size_t)b * d.max_len; });      // unconditional (addresses clamped into the cache): these registers are
         if (V_EARLY) load_v(0, VR_LO, 0x7fffffff);   // always consumed, with P = 0 for rows past the context
+    };
+    if (DED) {                                   // one branch, two paths: the new-token wave or a cache wave, each with its first loads at its head
+        if (w == 0) { if (!HAS_WAIT) load_newtok(); }
+        else entry_window();
+    } else {
+        if (!HAS_WAIT && w == 0) load_newtok();
+        entry_window();
     }
+    // the rest of the arguments (the fused launch: loaded here, behind the first loads of every wave)
+    const DecAttnArgs& a = late();
+    int* const hint = late.hint();
+    const uint8_t* const km = a.key_mask + (size_t)b * d.max_len;
     const int slot = a.slot_b[b];
     const int nk = slot + 1;
+    if (COH) {                                   // behind the first loads: trace record of this workgroup, entry time, and the step's tag
+        trc = (a.trace && tid == 0) ? a.trace + ((size_t)b * d.heads + h) * 8 : nullptr;
+        if (trc) trc[0] = t_entry;
+    }
+    const unsigned tag = COH ? handoff_tag(*a.epoch, a.layers, a.layer) : 0u;
     ATT_T(0);
     wait_inputs();      // chained launches: the cache loads are already in flight; block until this step's qkv row is published
     ATT_T(1);
@@ -169,7 +199,7 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
         const V8 qv = as_vec8<T>(nq), kv = as_vec8<T>(nk_), vv = as_vec8<T>(nv), cv = as_vec8<T>(ncos), sv_ = as_vec8<T>(nsin);
 #pragma unroll
         for (int e = 0; e < 8; ++e) { q8n[e] = tof<T>(qv[e]); k8[e] = tof<T>(kv[e]); v8[e] = tof<T>(vv[e]); }
-        if (d.lora_r == 8) {
+        if (a.d.lora_r == 8) {
             const V8 aq = as_vec8<T>(naq), av = as_vec8<T>(nav);
             const V8 bq0 = as_vec8<T>(nbq0), bq1 = as_vec8<T>(nbq1), bv0 = as_vec8<T>(nbv0), bv1 = as_vec8<T>(nbv1);
             float sq0 = 0.f, sq1 = 0.f, sv0 = 0.f, sv1 = 0.f;
@@ -178,8 +208,8 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
                 sq0 += tof<T>(bq0[i]) * tof<T>(aq[i]); sq1 += tof<T>(bq1[i]) * tof<T>(aq[i]);
                 sv0 += tof<T>(bv0[i]) * tof<T>(av[i]); sv1 += tof<T>(bv1[i]) * tof<T>(av[i]);
             }
-            sq0 = rnd<T>(rnd<T>(sq0) * d.lora_scale); sq1 = rnd<T>(rnd<T>(sq1) * d.lora_scale);   // lora_B(lora_A(x)) * scaling
-            sv0 = rnd<T>(rnd<T>(sv0) * d.lora_scale); sv1 = rnd<T>(rnd<T>(sv1) * d.lora_scale);
+            sq0 = rnd<T>(rnd<T>(sq0) * a.d.lora_scale); sq1 = rnd<T>(rnd<T>(sq1) * a.d.lora_scale);   // lora_B(lora_A(x)) * scaling
+            sv0 = rnd<T>(rnd<T>(sv0) * a.d.lora_scale); sv1 = rnd<T>(rnd<T>(sv1) * a.d.lora_scale);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int src = ((e >> 1) << 4) | doct;
@@ -219,7 +249,7 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
         }
     }
     if (owns_rows) {                             // upper half of the window, now that the context length is known
-        load_k(KG_LO, KG, slot);
+        load_k(KG_LO, KG, slot, [&] { return km; });
         if (V_EARLY) load_v(VR_LO, VR, slot);
     }
     ATT_T(2);
@@ -383,6 +413,12 @@ __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, cons
         ATT_T(8);
     }
 #undef ATT_T
+}
+
+// the stand-alone kernels (attn.hip): every argument is at hand when the kernel starts
+template <typename T, int WAVES, bool DED = (WAVES == 8), typename WaitFn = NoWait, bool V_EARLY_ = !DED, int KG_ = 0>
+__device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, const int h, const int b, float* dsm, WaitFn wait_inputs = WaitFn()) {
+    decode_attention_core<T, WAVES, DED, WaitFn, V_EARLY_, KG_, false, false>(AttnEarly{a.qkv, a.kcache, a.vcache, a.d}, AttnNow{a}, h, b, dsm, wait_inputs);
 }
 
 }  // namespace rdx

@@ -17,6 +17,10 @@
 // Payloads are written write-through (8-byte agent-scope stores) and read with agent-scope loads: no cache fences. Arithmetic,
 // rounding points and the fixed-order LDS reduction are those of skinny_body.h (same oracle parity).
 // Liveness: a workgroup only waits on counters fed by lower-indexed workgroups; spins are bounded (handoff.h).
+// Arguments: every launch is a graph node of ONE layer, so the layer's pointers travel by value (there is no device table of layers). What a role's
+// first loads are addressed from are LEADING scalar kernel arguments, which kernarg preloading (build.py UNIT_FLAGS) has in SGPRs when the first wave
+// starts; everything else is read behind those loads (rdx_common.h late_kernarg). No scalar load, and no wait for one, stands in front of the first
+// loads of any role (tests/test_isa_entry.py holds the assembly to that).
 // (Round 3: the all-roles chained kernel RDX_MEGA, the gate/up -> down -> QKV chain RDX_CHAIN=1 and the 8-wave fused attention of
 // fused.hip were measured slower in rounds 1-2 and have been removed; DESIGN.md 4 keeps the measurements.)
 #include "rdx_common.h"
@@ -31,19 +35,23 @@ constexpr int CH_WAVES = 16;
 constexpr int CH_THREADS = CH_WAVES * 64;
 constexpr int CH_MAXM = 2;                       // batch rows supported (LDS staging of [M][inter] activations)
 
-struct ChainGemm {                                // one weight-streaming unit
+// One weight-streaming unit, WITHOUT what its ring needs: the weight base (model dtype, or the e4m3 bytes of a W8 instantiation) and K reach
+// chain_tile as values of their own -- leading kernel arguments, which the command processor preloads into SGPRs (rdx_kernels.h), so the ring
+// is issued before the first scalar load of the rest has come back
+struct ChainGemm {
     const void* X; int ldx;
-    const void* W;
     const void* resid; int ldr;
     void* out; int ldo;
-    int M, N, K;
+    int M, N;
     const void* norm_w; float eps;
-    const void* W8; const float* wscale;         // fp8 weights (64-deep fragment order) + per-row scale, see skinny_body.h
+    const float* wscale;                          // fp8 weights: per-row scale, see skinny_body.h
 };
 
-template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false>
-__device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, const int ntiles, unsigned char* smem, WaitFn wait_inputs,
-                                           long long* trace = nullptr) {
+template <typename WaitFn> struct ChainLate { ChainGemm a; WaitFn wait; long long* trace; };   // what `late()` hands chain_tile behind the ring
+
+// Wb, K, wg, ntiles: from preloaded kernel arguments. late(): the rest (ChainLate), built from kernel arguments that are loaded only now (late_kernarg)
+template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false, typename Late>
+__device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const int K, const int wg, const int ntiles, unsigned char* smem, Late late) {
     typedef typename Vec8<T>::type V8;
     constexpr int WPS = CH_WAVES / SUB;           // waves per tile
     // U chunks per register batch, two batches in flight (a ring of 2 U fragments): 32 VGPRs at U = 4, 64 at U = 8; every role stays <= 128
@@ -57,16 +65,14 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
     const int tile = wg * SUB + sub;
     const int tile_c = min(tile, ntiles - 1);     // ragged last workgroup: duplicate loads, masked stores
     const int r = lane & 15, g = lane >> 4;
-    const int K = a.K, KC = W8 ? (K >> 6) : (K >> 5);                   // W8: a chunk is 64 k-values (16 fp8 bytes per lane, two MFMAs)
+    const int KC = W8 ? (K >> 6) : (K >> 5);                            // W8: a chunk is 64 k-values (16 fp8 bytes per lane, two MFMAs)
     const int c0 = (KC * w) / WPS, c1 = (KC * (w + 1)) / WPS;
-    const T* X = reinterpret_cast<const T*>(a.X);
-    const u4* wbase = reinterpret_cast<const u4*>(W8 ? a.W8 : a.W) + (size_t)tile_c * KC * 64 + lane;
+    const u4* wbase = reinterpret_cast<const u4*>(Wb) + (size_t)tile_c * KC * 64 + lane;
     const int clast = min(max(c1 - 1, c0), KC - 1);
-    // debug timeline of this workgroup (rdx_gemv_trace 7; null in every product launch), 100 MHz ticks, wave 0: [0] entry, [5] first weight KiB
-    // back, [3] inputs ready, [6] first MFMA (row staged), [1] K loop done, [7] end; [2] = arrival, written by the down_proj role's caller
-    long long* trc = (trace && threadIdx.x == 0) ? trace : nullptr;
-#define CH_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
-    CH_T(0);
+    // Everything up to here comes from preloaded kernel arguments, the workgroup id and the lane id: the ring below is issued with no scalar load
+    // in front of it. The entry time is taken unconditionally (one scalar instruction, nothing waits for it before the ring is out) because the
+    // trace pointer is one of the arguments that are only loaded behind the ring.
+    const long long t_entry = (long long)__builtin_amdgcn_s_memrealtime();
 
     // two register batches (A, B) in flight before anything else; the main loop ping-pongs between them (no register
     // rotation: a rotated pair makes the compiler wait for the batch it has just issued)
@@ -75,6 +81,17 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
     for (int u = 0; u < U; ++u) wa_[u] = ldg16_nt(wbase + (size_t)min(c0 + u, clast) * 64);
 #pragma unroll
     for (int u = 0; u < U; ++u) wb_[u] = ldg16_nt(wbase + (size_t)min(c0 + U + u, clast) * 64);
+    __builtin_amdgcn_sched_barrier(0);            // nothing of what follows is scheduled in front of the ring
+    const ChainLate<WaitFn> lt = late();
+    const ChainGemm& a = lt.a;
+    const WaitFn& wait_inputs = lt.wait;
+    long long* const trace = lt.trace;
+    // debug timeline of this workgroup (rdx_gemv_trace 7; null in every product launch), 100 MHz ticks, wave 0: [0] entry, [5] first weight KiB
+    // back, [3] inputs ready, [6] first MFMA (row staged), [1] K loop done, [7] end; [2] = arrival, written by the down_proj role's caller
+    const T* X = reinterpret_cast<const T*>(a.X);
+    long long* trc = (trace && threadIdx.x == 0) ? trace : nullptr;
+#define CH_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
+    if (trc) trc[0] = t_entry;
     if (trace) {        // traced launches only: wave 0 watches its first KiB come back (it stalls here, which a product launch never does)
         if (threadIdx.x < 64) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * U - 1) : "memory");
         CH_T(5);
@@ -271,6 +288,7 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
     }
     CH_T(7);
 #undef CH_T
+    return lt;          // what the caller still needs of the late arguments (the down_proj role: its counters and its trace record)
 }
 
 // down_proj(l) then RMSNorm + QKV(l + 1): blocks [0, nwg_down) are down_proj tiles (one tile per workgroup, 16 waves split K; their
@@ -278,24 +296,30 @@ __device__ __forceinline__ void chain_tile(const ChainGemm& a, const int wg, con
 // normalised row staged once per workgroup) that wait for all down_proj tiles on the layer's sharded counter. The QKV role's ring is 16
 // fragments deep (U = 8; fp8 weights keep 8: 16 measured slower there): it is issued at entry and is what HBM carries while the
 // workgroup waits for the last arrival and stages the row. Same chunks in the same order per wave: the sums do not change by a bit.
+// Leading arguments (preloaded into SGPRs, rdx_kernels.h): the two weight bases -- down_proj of `layer`, QKV of `layer + 1`; the e4m3 bytes in the W8
+// instantiation -- and the four ints the roles' tile and K-slice arithmetic needs. The rest of the two layers travels by value in ChainArgs, read late.
 template <typename T, bool W8>
-__global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_k(ChainArgs ca) {
+__global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_k(const void* wdown, const void* wqkv, int hidden, int inter, int qkv_n, int nwg_down, ChainArgs) {
     extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
-    const ChainLayer& L = ca.layers[ca.layer];
-    int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
-    const int H = ca.hidden, B = ca.B;
-    long long* trace = ca.trace ? ca.trace + (size_t)blockIdx.x * 8 : nullptr;
-    if ((int)blockIdx.x < ca.nwg_down) {
-        ChainGemm g = {ca.dgu, ca.inter, L.wdown, ca.dx, H, ca.dx, H, B, H, ca.inter, nullptr, 0.f, L.wdown8, L.sdown};
-        chain_tile<T, EPI_RESID, false, 1, 6, WaitSharded, 4, false, W8>(g, blockIdx.x, ca.nwg_down, msm, WaitSharded{ctr, 0, ca.err, ca.naps, nullptr}, trace);
-        publish_sc1(ctr, blockIdx.x);
-        if (trace && threadIdx.x == 0) trace[2] = (long long)__builtin_amdgcn_s_memrealtime();      // arrival
+    const int H = hidden;
+    auto args = [] { return late_kernarg<ChainArgs>(kernarg_offset<6>(decltype(&decode_chain_k<T, W8>){})); };      // argument 6: the ChainArgs
+    if ((int)blockIdx.x < nwg_down) {
+        const ChainLate<WaitSharded> lt = chain_tile<T, EPI_RESID, false, 1, 6, WaitSharded, 4, false, W8>(wdown, inter, blockIdx.x, nwg_down, msm, [&] {
+            const ChainArgs ca = args();
+            int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
+            return ChainLate<WaitSharded>{ChainGemm{ca.dgu, inter, ca.dx, H, ca.dx, H, ca.B, H, nullptr, 0.f, ca.sdown},
+                                          WaitSharded{ctr, 0, ca.err, ca.naps, nullptr}, ca.trace ? ca.trace + (size_t)blockIdx.x * 8 : nullptr};
+        });
+        publish_sc1(lt.wait.ctr, blockIdx.x);
+        if (lt.trace && threadIdx.x == 0) lt.trace[2] = (long long)__builtin_amdgcn_s_memrealtime();      // arrival
         return;
     }
-    const ChainLayer& Ln = ca.layers[ca.layer + 1];
-    ChainGemm g = {ca.dx, H, Ln.wqkv, nullptr, 0, ca.dqkv, ca.qkv_ld, B, ca.qkv_n, H, Ln.attn_norm, ca.eps, Ln.wqkv8, Ln.sqkv};
-    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, W8 ? 4 : 8, false, W8>(g, blockIdx.x - ca.nwg_down, (ca.qkv_n + 15) / 16, msm,
-                                                                             WaitSharded{ctr, ca.nwg_down, ca.err, ca.naps, nullptr}, trace);
+    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, W8 ? 4 : 8, false, W8>(wqkv, H, blockIdx.x - nwg_down, (qkv_n + 15) / 16, msm, [&] {
+        const ChainArgs ca = args();
+        int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
+        return ChainLate<WaitSharded>{ChainGemm{ca.dx, H, nullptr, 0, ca.dqkv, ca.qkv_ld, ca.B, qkv_n, ca.attn_norm, ca.eps, ca.sqkv},
+                                      WaitSharded{ctr, nwg_down, ca.err, ca.naps, nullptr}, ca.trace ? ca.trace + (size_t)blockIdx.x * 8 : nullptr};
+    });
 }
 
 // ---- decode attention + o_proj(+residual) in ONE launch, 16-wave workgroups -------------------------------------------------
@@ -304,28 +328,48 @@ __global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_k(ChainArgs ca) {
 // K slice (16 chunks per wave) goes in flight at entry and sits in registers while attention runs; then the data-tagged
 // hand-off (handoff.h: hint poll, granule sweep straight into the LDS staging) and ~2 us of work. heads*B + ntiles/2 <= 256 workgroups
 // of <= 128 VGPRs: all resident, one per CU.
+// Leading arguments (preloaded into SGPRs, rdx_kernels.h; 14 dwords, all there are): what the first loads of either role are addressed from -- o_proj:
+// its weight base (the e4m3 bytes in the W8 instantiation), K, the tile count and where its workgroups start; attention: the qkv row(s), the layer's
+// K / V cache and their geometry. K is also the hidden size and 128 heads' worth of it (attn_oproj16_supported), so neither travels twice.
+// *at.epoch changes every step and stays a load: it is read behind the first loads of both roles (the tag is first needed by the hand-off).
+template <typename Kernel> struct AttnOprojLate {       // the attention role's late arguments (attn_body.h); Kernel = attn_oproj16_k's own type
+    // arguments 10 .. 13 of the kernel: DecAttnArgs, ChainGemm, hint, err
+    static constexpr unsigned AT = kernarg_offset<10>(Kernel{}), G = kernarg_offset<11>(Kernel{}), HINT = kernarg_offset<12>(Kernel{}), ERR = kernarg_offset<13>(Kernel{});
+    __device__ __forceinline__ DecAttnArgs operator()() const { return late_kernarg<DecAttnArgs>(AT); }
+    __device__ __forceinline__ int* hint() const { return late_kernarg<int*>(HINT) + blockIdx.x; }
+};
 template <typename T, bool W8>
-__global__ __launch_bounds__(CH_THREADS, 4) void attn_oproj16_k(DecAttnArgs at, ChainGemm g, int n_attn, int ntiles, int* hint, int* err) {
+__global__ __launch_bounds__(CH_THREADS, 4) void attn_oproj16_k(const void* wo, const void* qkv, void* kcache, void* vcache, int K, int ntiles, int n_attn,
+                                                                 int max_len, int qkv_ld, int k_perm, DecAttnArgs, ChainGemm, int*, int*) {
     extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
     // debug timeline (rdx_gemv_trace 8; null in every product launch): one 8-slot record per workgroup, attention's slots in attn_body.h
     // ([6] = its stores acknowledged, written here: only a traced launch drains them), o_proj's those of chain_tile
-    long long* trace = at.trace ? at.trace + (size_t)blockIdx.x * 8 : nullptr;
-    const unsigned tag = handoff_tag(*at.epoch, at.layers, at.layer);
     if ((int)blockIdx.x < n_attn) {
-        const int b = blockIdx.x / at.d.heads, h = blockIdx.x - b * at.d.heads;
-        decode_attention_body<T, CH_WAVES, true, NoWait, true, 0, true>(at, h, b, reinterpret_cast<float*>(msm), NoWait(), tag, hint + blockIdx.x);
-        if (trace && threadIdx.x == 0) {
+        const int heads = K >> 7;
+        const int b = blockIdx.x / heads, h = blockIdx.x - b * heads;
+        const AttnEarly e = {qkv, kcache, vcache, LlamaDims{K, heads, 128, qkv_ld, 0, 0.f, max_len, 0, k_perm}};
+        const AttnOprojLate<decltype(&attn_oproj16_k<T, W8>)> late;
+        decode_attention_core<T, CH_WAVES, true, NoWait, true, 0, true, false>(e, late, h, b, reinterpret_cast<float*>(msm), NoWait());
+        const DecAttnArgs at = late();
+        if (at.trace && threadIdx.x == 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            trace[6] = (long long)__builtin_amdgcn_s_memrealtime();
+            at.trace[(size_t)blockIdx.x * 8 + 6] = (long long)__builtin_amdgcn_s_memrealtime();
         }
     } else {
-        chain_tile<T, EPI_RESID, false, 2, 2, WaitTagged, W8 ? 4 : 8, true, W8>(g, blockIdx.x - n_attn, ntiles, msm, WaitTagged{hint, n_attn, tag, err}, trace);
+        chain_tile<T, EPI_RESID, false, 2, 2, WaitTagged, W8 ? 4 : 8, true, W8>(wo, K, blockIdx.x - n_attn, ntiles, msm, [&] {
+            typedef AttnOprojLate<decltype(&attn_oproj16_k<T, W8>)> L;
+            const DecAttnArgs at = late_kernarg<DecAttnArgs>(L::AT);
+            const ChainGemm g = late_kernarg<ChainGemm>(L::G);
+            int* hint = late_kernarg<int*>(L::HINT);
+            int* err = late_kernarg<int*>(L::ERR);
+            return ChainLate<WaitTagged>{g, WaitTagged{hint, n_attn, at.epoch, at.layers, at.layer, err}, at.trace ? at.trace + (size_t)blockIdx.x * 8 : nullptr};
+        });
     }
 }
 
 bool attn_oproj16_supported(const LlamaDims& d, int N, int K, int B) {
     const int ntiles = (N + 15) / 16;
-    return B <= CH_MAXM && d.head_dim == 128 && K % 32 == 0 && N % 4 == 0 && (size_t)B * K <= 8192 &&
+    return B <= CH_MAXM && d.head_dim == 128 && K == d.heads * 128 && K == d.hidden && K % 32 == 0 && N % 4 == 0 && (size_t)B * K <= 8192 &&
            d.heads * B + (ntiles + 1) / 2 <= 256;
 }
 
@@ -333,14 +377,16 @@ void launch_attn_oproj16(int dtype, const DecAttnArgs& a, const GemmArgs& ga, in
     const int n_attn = a.d.heads * B, ntiles = (ga.N + 15) / 16;
     const bool w8 = ga.W8 && ga.wscale && ga.K % 64 == 0;
     // a.out = ga.X = the granule buffer: [B][K] elements as 8-byte {pair, tag} granules
-    ChainGemm g = {ga.X, ga.ldx, ga.W, ga.resid, ga.ldr, ga.out, ga.ldo, ga.M, ga.N, ga.K, nullptr, 0.f, ga.W8, ga.wscale};
+    ChainGemm g = {ga.X, ga.ldx, ga.resid, ga.ldr, ga.out, ga.ldo, ga.M, ga.N, nullptr, 0.f, ga.wscale};
     const size_t sm_gemm = (size_t)(CH_WAVES * 256 + CH_WAVES * CH_MAXM + 16) * 4 + (size_t)B * ga.K * 2;
     const size_t sm_att = decode_attention_smem_floats(CH_WAVES, a.d.max_len) * sizeof(float);
     const size_t smem = sm_gemm > sm_att ? sm_gemm : sm_att;
     dim3 grid(n_attn + (ntiles + 1) / 2), block(CH_THREADS);
     RDX_DISPATCH_T(dtype, T, {
-        if (w8) hipLaunchKernelGGL((attn_oproj16_k<T, true>), grid, block, smem, s, a, g, n_attn, ntiles, hint, err);
-        else hipLaunchKernelGGL((attn_oproj16_k<T, false>), grid, block, smem, s, a, g, n_attn, ntiles, hint, err);
+        if (w8) hipLaunchKernelGGL((attn_oproj16_k<T, true>), grid, block, smem, s, ga.W8, a.qkv, a.kcache, a.vcache, ga.K, ntiles, n_attn, a.d.max_len, a.d.qkv_ld,
+                                   a.d.k_perm, a, g, hint, err);
+        else hipLaunchKernelGGL((attn_oproj16_k<T, false>), grid, block, smem, s, ga.W, a.qkv, a.kcache, a.vcache, ga.K, ntiles, n_attn, a.d.max_len, a.d.qkv_ld,
+                                a.d.k_perm, a, g, hint, err);
     });
 }
 
@@ -354,21 +400,21 @@ bool chain_supported(const LlamaDims& d, int inter, int B) {
 size_t chain_ctr_ints(int layers) { return (size_t)layers * HO_CTR_INTS; }
 
 void launch_decode_chain(int dtype, ChainArgs ca, bool with_next_qkv, hipStream_t s) {
-    ca.nwg_down = ca.hidden / 16;
+    const int nwg_down = ca.hidden / 16;
     const int nwg_qkv = with_next_qkv ? ((ca.qkv_n + 15) / 16 + 3) / 4 : 0;
     const int kmax = ca.inter > ca.hidden ? ca.inter : ca.hidden;
     const size_t sm_gemm = (size_t)(CH_WAVES * 256 + CH_WAVES * CH_MAXM + 16) * 4 + (size_t)ca.B * kmax * 2;
     // ONE workgroup per CU: the register budget alone (<= 128 VGPRs) would admit two, so reserve more than half of the LDS
     const size_t smem = sm_gemm > (size_t)84 * 1024 ? sm_gemm : (size_t)84 * 1024;
-    dim3 grid(ca.nwg_down + nwg_qkv), block(CH_THREADS);
+    dim3 grid(nwg_down + nwg_qkv), block(CH_THREADS);
     RDX_DISPATCH_T(dtype, T, {
         static DevOnce attr_set;
         if (attr_set.first()) {
             hipFuncSetAttribute((const void*)decode_chain_k<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
             hipFuncSetAttribute((const void*)decode_chain_k<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
         }
-        if (ca.w8) hipLaunchKernelGGL((decode_chain_k<T, true>), grid, block, smem, s, ca);
-        else hipLaunchKernelGGL((decode_chain_k<T, false>), grid, block, smem, s, ca);
+        if (ca.w8) hipLaunchKernelGGL((decode_chain_k<T, true>), grid, block, smem, s, ca.wdown8, ca.wqkv8, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
+        else hipLaunchKernelGGL((decode_chain_k<T, false>), grid, block, smem, s, ca.wdown, ca.wqkv, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
     });
 }
 

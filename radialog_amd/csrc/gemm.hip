@@ -115,10 +115,17 @@ void launch_pack_weight_fp8(int dtype, const float* src, void* dst8, float* scal
 // ------------------------------------------------------------------------------------------------------------------
 // skinny GEMM (body in skinny_body.h)
 // ------------------------------------------------------------------------------------------------------------------
+// Leading arguments (6 dwords, preloaded into SGPRs: build.py UNIT_FLAGS): the weight base (the e4m3 bytes in the W8 instantiation), X, K and N. The
+// first weight ring is addressed from them alone and issued before any scalar load of the struct behind them, which is read late (rdx_common.h).
 template <typename T, int MT, int EPI, bool NORM, int WAVES, bool XLDS, bool W8 = false>
-__global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 8 : 1) void skinny_gemm_k(GemmArgs a) {
+__global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 8 : 1) void skinny_gemm_k(const void* Wb, const void* X, int K, int N, GemmArgs) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
-    skinny_tile<T, MT, EPI, NORM, WAVES, XLDS, NoWait, false, W8>(a, blockIdx.x, gridDim.x, dyn_smem, NoWait());
+    skinny_tile<T, MT, EPI, NORM, WAVES, XLDS, NoWait, false, W8>(Wb, K, blockIdx.x, (N + 15) / 16, dyn_smem, NoWait(), [&] {
+        constexpr unsigned off = kernarg_offset<4>(decltype(&skinny_gemm_k<T, MT, EPI, NORM, WAVES, XLDS, W8>){});      // argument 4: the GemmArgs
+        GemmArgs a = late_kernarg<GemmArgs>(off);
+        a.X = X; a.K = K; a.N = N;
+        return a;
+    });
 }
 
 template <typename T, int MT, bool NORM, int WAVES, bool XLDS, bool W8 = false>
@@ -126,7 +133,7 @@ static void launch_skinny_epi(const GemmArgs& a, int epi, hipStream_t s) {
     const int nt = (a.N + 15) / 16;
     dim3 grid(nt), block(WAVES * 64);
     const size_t dyn = XLDS ? (size_t)a.M * a.K * 2 : 0;
-#define RDX_SK(E) hipLaunchKernelGGL((skinny_gemm_k<T, MT, E, NORM, WAVES, XLDS, W8>), grid, block, dyn, s, a)
+#define RDX_SK(E) hipLaunchKernelGGL((skinny_gemm_k<T, MT, E, NORM, WAVES, XLDS, W8>), grid, block, dyn, s, W8 ? a.W8 : a.W, a.X, a.K, a.N, a)
     switch (epi) {
         case EPI_NONE: RDX_SK(EPI_NONE); break;
         case EPI_RELU: RDX_SK(EPI_RELU); break;

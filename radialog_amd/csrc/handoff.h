@@ -124,8 +124,12 @@ __device__ __forceinline__ void store_granule(void* gran, size_t i, unsigned pai
 
 struct WaitTagged {      // inputs arrive as tagged granules from `n` producers (hint words 0..n-1)
     static constexpr bool TAGGED = true;
-    const int* hint; int n; unsigned tag; int* err;
+    // the tag is derived HERE, from the step epoch (a device word that predates the launch): the consumer's weight ring is issued before this
+    // load, not behind it
+    const int* hint; int n; const int* epoch; int layers, layer; int* err;
+    __device__ __forceinline__ unsigned the_tag() const { return handoff_tag(*epoch, layers, layer); }
     __device__ __forceinline__ void operator()() const {      // the opener: wave 0 polls the hints; a timeout here only starts the sweep early
+        const unsigned tag = the_tag();
         if (threadIdx.x < 64) {
             for (int it = 0; it < (1 << 16); ++it) {
                 bool ok = true;
@@ -142,6 +146,7 @@ struct WaitTagged {      // inputs arrive as tagged granules from `n` producers 
     template <int XL>
     __device__ __forceinline__ void sweep(unsigned long long (&xr)[XL], const void* gran, int ld, int K4, int total4, int nthreads) const {
         const unsigned long long* g = reinterpret_cast<const unsigned long long*>(gran);
+        const unsigned tag = the_tag();
         bool ok = false;
         for (int it = 0; it < (1 << 14); ++it) {
             ok = true;

@@ -38,10 +38,34 @@ __device__ __forceinline__ v4f mfma16(v8h a, v8h b, v4f c) { return __builtin_am
 __device__ __forceinline__ v4f mfma16(v8b a, v8b b, v4f c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
 
 // 16-byte GLOBAL-memory loads/stores. `ldg_nt` = streamed-once data (decode weights): non-temporal policy.
-// The explicit address_space(1) cast matters: a pointer fetched from a device-memory table (chain.hip) is generic, and
+// The explicit address_space(1) cast matters: a pointer that does not come straight from a kernel argument is generic, and
 // generic accesses become FLAT instructions, whose completion order is not guaranteed -- the compiler then falls back
 // to s_waitcnt vmcnt(0) everywhere and a software-pipelined weight stream collapses to one batch in flight.
 typedef __attribute__((address_space(1))) u4 g_u4;
+// Kernel arguments read LATE (the batch-1/2 step: gemm.hip skinny_gemm_k, chain.hip). What a launch's first loads are addressed from travels as leading
+// scalar arguments, which kernarg preloading (build.py UNIT_FLAGS) has in SGPRs when the first wave starts; the rest is a struct by value behind them.
+// The compiler would load that struct's fields where the kernel begins -- common fields of a kernel's roles end up in its entry block, with a wait for
+// them in front of everything. late_kernarg<A>(offset) copies the struct found `offset` bytes into the kernarg segment through a pointer that an empty
+// volatile asm has made opaque: its scalar loads are issued at the call, and no memory access of the program is moved across it. `offset` is the
+// struct's offset in the kernel's argument list: kernarg_offset<I>(kernel) computes it from the kernel's OWN signature (argument I, counted from 0;
+// the kernarg segment lays the arguments out in order, each at its natural alignment), so an argument added or moved moves the offset with it.
+template <int I, typename... A> constexpr unsigned kernarg_offset_of() {
+    static_assert(I >= 0 && I < (int)sizeof...(A), "no such kernel argument");
+    unsigned off = 0, r = 0;
+    int i = 0;
+    ((off = (off + (unsigned)alignof(A) - 1u) / (unsigned)alignof(A) * (unsigned)alignof(A), r = (i == I ? off : r), off += (unsigned)sizeof(A), ++i), ...);
+    return r;
+}
+template <int I, typename... A> constexpr unsigned kernarg_offset(void (*)(A...)) { return kernarg_offset_of<I, A...>(); }
+template <typename A> __device__ __forceinline__ A late_kernarg(unsigned offset) {
+    typedef __attribute__((address_space(4))) const unsigned char kbyte;
+    typedef __attribute__((address_space(4))) const A kA;          // typed: the copy is made of aligned dword loads, which the scalar unit can do
+    kA* p = (kA*)((kbyte*)__builtin_amdgcn_kernarg_segment_ptr() + offset);
+    asm volatile("" : "+s"(p) :: "memory");
+    A a;
+    __builtin_memcpy(&a, p, sizeof(A));
+    return a;
+}
 __device__ __forceinline__ u4 ldg16(const void* p) { return *(const g_u4*)p; }
 __device__ __forceinline__ u4 ldg16_nt(const void* p) { return __builtin_nontemporal_load((const g_u4*)p); }
 __device__ __forceinline__ void stg16(void* p, u4 v) { *(g_u4*)p = v; }

@@ -110,7 +110,7 @@ struct rdx_ctx {
     void *cls_pooled = nullptr, *cls_h = nullptr, *cls_out = nullptr;
     void* zero16 = nullptr;          // 16 zero bytes: source of padding taps in the DMA conv gather
     void* d_cur_rope = nullptr;      // [B][2][128] cos | sin row of each row's current position (written by greedy_step_k)
-    ChainLayer* d_clayers = nullptr; int* d_cctr = nullptr;
+    int* d_cctr = nullptr;
     int *d_ctr = nullptr, *d_err = nullptr;   // hand-off counters of the chained launches (= d_cctr), sticky error flag
     void* d_gran = nullptr; int *d_hint = nullptr, *d_epoch = nullptr;   // fused attention + o_proj launch: tagged-granule buffer [2][hidden] x 4 B, hint words, step epoch (handoff.h)
     int flash_min = 512;             // batched causal prefill attention: flash_prefill_k from this many workgroups (RDX_FLASH_MIN at create / rdx_set_option)

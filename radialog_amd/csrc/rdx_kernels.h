@@ -201,12 +201,16 @@ struct DecAttnArgs {
 void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, hipStream_t s);
 // Chained decode launches of the batch <= 2 step (chain.hip): units run as roles of one launch, chained by a fence-free counter
 // hand-off (handoff.h) instead of a kernel boundary.
-struct ChainLayer { const void *wqkv, *wdown, *attn_norm;
-                    // fp8 weights (e4m3, 64-deep fragment order) + per-row scales, null when the model dtype copy is streamed
-                    const void *wqkv8, *wdown8; const float *sqkv, *sdown; };
+// Every launch is a graph node of ONE layer, so the layer's pointers travel by value (no device table, no dependent read in front of the weight
+// stream). The launcher hands the kernel the fields its weight rings are addressed from (wdown / wqkv or their fp8 twins, hidden, inter, qkv_n, the
+// down_proj workgroup count) as LEADING scalar arguments in front of the struct: the units of the batch-1/2 step are compiled with kernarg
+// preloading (build.py UNIT_FLAGS), which has the command processor place leading non-aggregate arguments in SGPRs before the first wave starts.
 struct ChainArgs {
-    const ChainLayer* layers;        // device table, one entry per decoder layer
-    int layer;                       // down_proj of this layer, QKV of the next
+    const void *wdown, *wqkv;        // down_proj of `layer`; QKV of `layer + 1` (unused by the last layer's launch)
+    const void *wdown8, *wqkv8;      // fp8 weights (e4m3, 64-deep fragment order), null when the model dtype copy is streamed
+    const float *sdown, *sqkv;       // their per-row scales
+    const void* attn_norm;           // RMSNorm weight in front of QKV(layer + 1)
+    int layer;                       // down_proj of this layer, QKV of the next (selects the hand-off counters)
     int hidden, inter, qkv_n, qkv_ld, B;
     int w8;                          // stream the fp8 weights (every projection quantised)
     float eps;
@@ -214,7 +218,6 @@ struct ChainArgs {
     int* ctr;                        // chain_ctr_ints(layers) ints, zero at the start of every step
     int* err;
     int naps;                        // poll back-off (x s_sleep(8) between polls)
-    int nwg_down;                    // filled by the launcher
     long long* trace;                // debug: [workgroup][8] timestamps (100 MHz ticks) of one launch, slots in chain.hip; null in every product launch
 };
 bool chain_supported(const LlamaDims& d, int inter, int B);

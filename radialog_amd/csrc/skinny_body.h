@@ -24,9 +24,11 @@ template <typename T> __device__ __forceinline__ float swiglu(float gate_acc, fl
 }
 
 
-template <typename T, int MT, int EPI, bool NORM, int WAVES, bool XLDS, typename WaitFn, bool COHX = false, bool W8 = false>
-__device__ __forceinline__ void skinny_tile(const GemmArgs& a, const int tile, const int ntiles, unsigned char* dyn_smem,
-                                            WaitFn wait_inputs) {
+// Wb (the weight base: model dtype, or the e4m3 bytes when W8), K, tile, ntiles: from preloaded kernel arguments -- all that the first ring needs.
+// late(): the GemmArgs, from kernel arguments that are loaded only behind the ring (rdx_common.h late_kernarg)
+template <typename T, int MT, int EPI, bool NORM, int WAVES, bool XLDS, typename WaitFn, bool COHX = false, bool W8 = false, typename Late>
+__device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const int tile, const int ntiles, unsigned char* dyn_smem,
+                                            WaitFn wait_inputs, Late late) {
     typedef typename Vec8<T>::type V8;
     // W8: fp8 (e4m3) weights with one fp32 scale per output row. A chunk is then 64 k-values (16 bytes per lane, two MFMAs:
     // lane (g, r) holds W[16*tile + r][64*c + 16*g .. +16]); the bytes are expanded to the model dtype in registers (exact)
@@ -43,19 +45,15 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& a, const int tile, c
     // EXEC-masked per-lane branch (MFMA ignores EXEC -- a masked-off MFMA would still accumulate)
     const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int r = lane & 15, g = lane >> 4;
-    const int K = a.K, KC = W8 ? (K >> 6) : (K >> 5);
+    const int KC = W8 ? (K >> 6) : (K >> 5);
     const int c0 = (KC * w) / WAVES, c1 = (KC * (w + 1)) / WAVES;
-    const T* X = reinterpret_cast<const T*>(a.X);
-    const u4* wbase = reinterpret_cast<const u4*>(W8 ? a.W8 : a.W) + (size_t)tile * KC * 64 + lane;
+    const u4* wbase = reinterpret_cast<const u4*>(Wb) + (size_t)tile * KC * 64 + lane;
     const int clast = min(max(c1 - 1, c0), KC - 1);
 
-    long long* trc = (a.trace && threadIdx.x == 0) ? a.trace + (size_t)tile * 8 : nullptr;
-#define SK_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
-    SK_T(0);
-    if (trc) {       // where this workgroup runs: HW_ID (wave/simd/cu/sh/se fields) and the XCC (XCD) id
-        trc[6] = (long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));     // HW_REG_HW_ID (id 4), bits 0..31
-        trc[7] = (long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));    // HW_REG_XCC_ID (id 20)
-    }
+    // Everything up to here comes from the leading kernel arguments (preloaded into SGPRs: gemm.hip skinny_gemm_k), the workgroup id and the lane
+    // id, so the ring is issued with no scalar load in front of it. The entry time is taken unconditionally (one scalar instruction that nothing
+    // waits for before the ring is out): the trace pointer is only loaded behind the ring.
+    const long long t_entry = (long long)__builtin_amdgcn_s_memrealtime();
     // two weight batches in flight before anything else (HBM latency overlaps the wait and the prologue)
     // (unconditional, addresses clamped into the slice: a short slice re-reads its last KiB)
     u4 ring[2 * U];
@@ -63,6 +61,17 @@ __device__ __forceinline__ void skinny_tile(const GemmArgs& a, const int tile, c
     for (int u = 0; u < 2 * U; ++u) ring[u] = ldg16_nt(wbase + (size_t)min(c0 + u, clast) * 64);
     u4* const wv = ring;            // the two-batch view of the direct-activation path below
     u4* const wn = ring + U;
+    __builtin_amdgcn_sched_barrier(0);            // nothing of what follows is scheduled in front of the ring
+    const GemmArgs a = late();
+    const T* X = reinterpret_cast<const T*>(a.X);
+
+    long long* trc = (a.trace && threadIdx.x == 0) ? a.trace + (size_t)tile * 8 : nullptr;
+#define SK_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
+    if (trc) {       // [0] entry; where this workgroup runs: HW_ID (wave/simd/cu/sh/se fields) and the XCC (XCD) id
+        trc[0] = t_entry;
+        trc[6] = (long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));     // HW_REG_HW_ID (id 4), bits 0..31
+        trc[7] = (long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11));    // HW_REG_XCC_ID (id 20)
+    }
 
     SK_T(1);
     wait_inputs();          // fused launches: block until the producer workgroups have published X (and resid)
