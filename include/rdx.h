@@ -139,6 +139,32 @@ int rdx_decode_step_ids(rdx_ctx* ctx, const int32_t* ids, void* logits);
 typedef struct rdx_logits_rules { float repetition_penalty; int no_repeat_ngram_size; int min_new_tokens; } rdx_logits_rules;
 int rdx_set_logits_rules(rdx_ctx* ctx, const rdx_logits_rules* rules);
 
+/* Sampled decoding: transformers 4.28.1 `sample` as generate(do_sample=True, temperature=, top_k=, top_p=) runs it -- processors, then warpers, then
+ * the draw -- inside the decode step, in the place of the argmax. Row b at draw index n (= the number of tokens the row has generated so far: 0 for the
+ * token the prefill selects):
+ *   1. the logits rules above, exactly as without sampling, give x (model dtype T)
+ *   2. temperature t, finite, > 0 (1.0 = off): s_i = T(float(x_i) / t), an fp32 IEEE division and one round-to-nearest-even -- scores / temperature on a
+ *      CPU tensor of the model dtype, the convention of the repetition penalty
+ *   3. top_k k >= 0 (0 = off): v = the min(k, vocab)-th largest s; every s_i < v is dropped, ties with v stay (TopKLogitsWarper)
+ *   4. top_p p in (0, 1] (1.0 = off): over the survivors w_i = exp(s_i - max s); for a value v, M(v) = sum of w_j over s_j <= v, divided by the sum of all
+ *      w; element i is dropped iff M(s_i) <= 1 - p and s_i is not the maximum. This is TopPLogitsWarper(min_tokens_to_keep=1) stated on values
+ *      instead of on a sort order; it differs from HF only inside a group of EQUAL values that straddles the boundary, where HF's result depends on
+ *      the order an unstable sort leaves them in (here the whole group stays or goes)
+ *   5. the processed row is what `logits` / `scores` receive, in place: kept elements hold s_i, dropped ones -inf (HF's .scores)
+ *   6. the draw: u24 = philox4x32_10(counter = (b, n, 0, 0), key = (seed_lo, seed_hi))[0] >> 8. Masses are integers, q_i = rint(w_i * 2^32) as uint64
+ *      (w_i in fp32 on the device); C = their inclusive prefix sum in index order over the kept elements; target = (u24 * C_last) >> 24; the token is
+ *      the first i with C_i > target. Then the EOS / pad rule and the state advance of every step.
+ * Integer masses make every sum independent of the order it is taken in: the same inputs, seed and draw index give the same token and the same scores
+ * row on every run, eager or replayed from the step graph.
+ * rdx_set_sampling sets the selection of the NEXT rdx_prefill / rdx_generate / rdx_decode_step* / rdx_prefill_append / rdx_generate_append calls; NULL or
+ * do_sample == 0 = off: launches, graph and outputs are exactly those of a context that never sampled, with or without rules. Returns -1 for a t that
+ * is not finite and > 0, k < 0, p outside (0, 1], weights not finalised, or a vocab whose row does not fit the kernel's LDS. It composes with
+ * rdx_set_logits_rules (rules, then warpers, then the draw); the append calls work while the rules are off (sampling needs no history);
+ * rdx_beam_search returns -1 while sampling is on (beam-sample is not built). Without a caller buffer the lm_head writes into the context's own rows.
+ * The seed is read from device memory by the kernel: a new seed does not re-capture the step graph, a change of t / k / p or of do_sample does. */
+typedef struct rdx_sampling { int do_sample; float temperature; int top_k; float top_p; uint64_t seed; } rdx_sampling;
+int rdx_set_sampling(rdx_ctx* ctx, const rdx_sampling* s);
+
 /* Multi-turn re-prompting (test.py:440-674, demo.py:277-305: the reference re-runs the whole conversation each turn). The
  * next turn's prompt usually starts with the previous prompt + answer; its KV rows are still in the cache. These calls keep the
  * first keep_len cache slots of every row (keep_len <= cached positions = previous T + tokens consumed; the caller compares

@@ -81,6 +81,15 @@ int rdx_rope_kv_test(rdx_ctx* ctx, int heads, int B, int T, int max_len, int k_p
                      const void* lbv, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos_ids, int slot0, void* kcache, void* vcache,
                      void* qout);
 
+/* sample_step_k alone (elem.hip: the sampled step): rules, warpers and the draw on caller data, without the decode-state tail. Arguments as
+ * rdx_select_test; rules NULL or neutral: none (hist / hist_len may then be NULL). n_generated [B] is the draw index of each row as well as what
+ * min_new_tokens compares with; the row index of the Philox counter is the row's position in the launch. logits_inout receives the processed rows
+ * (kept: scaled value, dropped: -inf), tokens_out the drawn tokens. Works on any context (no weights involved). */
+int rdx_sample_test(rdx_ctx* ctx, void* logits_inout, int B, int vocab, const int32_t* hist, const int32_t* hist_len, const int32_t* n_generated, int ld,
+                    const rdx_logits_rules* rules, int eos_id, const rdx_sampling* sampling, int32_t* tokens_out);
+/* The 24 random bits of (seed, row, draw index) on the host: the same function the kernel calls (csrc/philox.h). No context, no device. */
+int rdx_sample_u24_host(uint64_t seed, uint32_t row, uint32_t draw, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

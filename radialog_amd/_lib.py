@@ -34,6 +34,11 @@ class RdxLogitsRules(C.Structure):
     _fields_ = [("repetition_penalty", C.c_float), ("no_repeat_ngram_size", C.c_int), ("min_new_tokens", C.c_int)]
 
 
+class RdxSampling(C.Structure):
+    """rdx_sampling (include/rdx.h): do_sample 0 = off."""
+    _fields_ = [("do_sample", C.c_int), ("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64)]
+
+
 class RdxConfig(C.Structure):
     _fields_ = [
         ("dtype", C.c_int),
@@ -76,6 +81,7 @@ SYMBOLS = {
     "rdx_decode_step": (C.c_int, [_P, _P]),
     "rdx_decode_step_ids": (C.c_int, [_P, _P, _P]),
     "rdx_set_logits_rules": (C.c_int, [_P, C.POINTER(RdxLogitsRules)]),
+    "rdx_set_sampling": (C.c_int, [_P, C.POINTER(RdxSampling)]),
     "rdx_prefill_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rdx_generate_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
                                       C.POINTER(C.c_int), C.c_int]),
@@ -125,6 +131,8 @@ DEC_HOOK_SYMBOLS = {
     "rdx_xsplit_blk8_test": (C.c_int, [_P, _P, _P, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_rmsnorm_test": (C.c_int, [_P, _P, _P, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong, _P, C.c_int]),
     "rdx_select_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, _P]),
+    "rdx_sample_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, C.POINTER(RdxSampling), _P]),
+    "rdx_sample_u24_host": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rdx_decode_attn_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_longlong,
                                        C.c_int, C.c_int]),
     "rdx_rope_kv_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),

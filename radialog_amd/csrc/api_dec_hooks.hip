@@ -3,7 +3,10 @@
 // engines have no decoder: c->kslab / c->dxs / c->dxn do not exist), asks the production *_supported predicate BEFORE anything is launched on the
 // caller's outputs, and calls the production launch_* functions unchanged. Temporaries the kernels only partly write are filled with 0xff bytes
 // (NaN in both model dtypes and in fp32) first.
+#include <cmath>
+
 #include "rdx_ctx.h"
+#include "philox.h"
 #include "../../include/rdx_dec_hooks.h"
 
 namespace {
@@ -315,4 +318,35 @@ extern "C" int rdx_rope_kv_test(rdx_ctx* c, int heads, int B, int T, int max_len
     HIPCHK(c, hipMemsetAsync(qout, 0xff, (size_t)B * T * d.hidden * 2, c->stream));
     launch_rope_kv_prefill(c->cfg.dtype, d, qkv, lbq, lbv, cos_t, sin_t, pos_ids, qout, kcache, vcache, B, T, slot0, c->stream);
     return finish(c);
+}
+
+extern "C" int rdx_sample_test(rdx_ctx* c, void* logits_inout, int B, int vocab, const int32_t* hist, const int32_t* hist_len, const int32_t* n_generated, int ld,
+                               const rdx_logits_rules* rules, int eos_id, const rdx_sampling* sm, int32_t* tokens_out) {
+    if (!c || !logits_inout || !n_generated || !sm || !tokens_out || B <= 0) return fail(c, -1, "rdx_sample_test: bad arguments");
+    const rdx_logits_rules r = rules ? *rules : rdx_logits_rules{1.0f, 0, 0};
+    const bool ruled = r.repetition_penalty != 1.0f || r.no_repeat_ngram_size != 0 || r.min_new_tokens != 0;
+    if (!(r.repetition_penalty > 0.f) || r.no_repeat_ngram_size < 0 || r.min_new_tokens < 0) return fail(c, -1, "rdx_sample_test: bad rules");
+    if (ruled && (!hist || !hist_len || ld <= 0)) return fail(c, -1, "rdx_sample_test: rules need a history");
+    if (!(sm->temperature > 0.f) || !std::isfinite(sm->temperature) || sm->top_k < 0 || !(sm->top_p > 0.f) || !(sm->top_p <= 1.0f))
+        return fail(c, -1, "rdx_sample_test: bad sampling parameters");
+    if (!sample_step_supported(vocab) || (ruled && !select_step_supported(vocab))) return fail(c, -1, "rdx_sample_test: a row of vocab %d does not fit the LDS of sample_step_k", vocab);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_seed) ALLOC(c, c->d_seed, sizeof(unsigned long long));
+    const unsigned long long seed = sm->seed;
+    HIPCHK(c, hipMemcpyAsync(c->d_seed, &seed, sizeof(seed), hipMemcpyHostToDevice, c->stream));
+    SelectArgs a;
+    a.logits = logits_inout; a.step_stride = 0; a.n_gen = n_generated;
+    a.penalty = r.repetition_penalty; a.ngram = r.no_repeat_ngram_size; a.min_new = r.min_new_tokens; a.sel_out = tokens_out;
+    StepTail t = {};
+    t.vocab = vocab; t.eos_id = eos_id;
+    if (ruled) { t.hist = const_cast<int32_t*>(hist); t.hist_len = const_cast<int32_t*>(hist_len); t.hist_ld = ld; }     // read only: with sel_out set the tail does not run
+    const SampleArgs sp = {sm->temperature, sm->top_k, sm->top_p, c->d_seed};
+    launch_sample_step(c->cfg.dtype, a, sp, t, B, c->stream);
+    return finish(c);
+}
+
+extern "C" int rdx_sample_u24_host(uint64_t seed, uint32_t row, uint32_t draw, uint32_t* out) {
+    if (!out) return -1;
+    *out = sample_u24(seed, row, draw);
+    return 0;
 }

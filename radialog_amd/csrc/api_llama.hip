@@ -33,7 +33,7 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
                                int advance) {
     const rdx_config& f = c->cfg;
     // logits rules: the row select_step_k processes must exist, so without a caller buffer the lm_head writes into the context's own
-    if (c->rules_on && !logits) { logits = c->rule_logits; out_step = nullptr; }
+    if ((c->rules_on || c->sampling.do_sample) && !logits) { logits = c->rule_logits; out_step = nullptr; }
     auto lm = [&](GemmArgs a) { a.X = x; a.out = logits; a.out_step = out_step; a.out_step_stride = step_stride; return a; };
     switch (decode_family(c, B)) {
     case DEC_UNSUPPORTED: c->unsupported = k_need_blk; return;
@@ -53,13 +53,41 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
     t.ctr_zero = c->chain_mlp ? c->d_ctr : nullptr;
     t.n_zero = (int)chain_ctr_ints(f.layers);
     t.epoch = c->d_epoch;
-    if (!c->rules_on) { launch_greedy_step(f.dtype, c->part_val, c->part_idx, c->n_vtiles, B, t, c->stream); return; }
+    if (!c->rules_on && !c->sampling.do_sample) { launch_greedy_step(f.dtype, c->part_val, c->part_idx, c->n_vtiles, B, t, c->stream); return; }
     // the row at the address the lm_head just wrote (a captured step with scores: both offset it by the step count, read from d_step before the tail advances it)
-    t.hist = c->d_hist; t.hist_len = c->d_hist_len; t.hist_ld = f.max_len;
+    if (c->rules_on) { t.hist = c->d_hist; t.hist_len = c->d_hist_len; t.hist_ld = f.max_len; }
     SelectArgs sa;
     sa.logits = logits; sa.step_stride = out_step ? step_stride : 0; sa.n_gen = c->d_step;
     sa.penalty = c->rules.repetition_penalty; sa.ngram = c->rules.no_repeat_ngram_size; sa.min_new = c->rules.min_new_tokens; sa.sel_out = nullptr;
-    launch_select_step(f.dtype, sa, t, B, c->stream);
+    if (!c->sampling.do_sample) { launch_select_step(f.dtype, sa, t, B, c->stream); return; }
+    // sampled: the draw index of row b is d_step[b] too (0 for the token the prefill selects)
+    const SampleArgs sp = {c->sampling.temperature, c->sampling.top_k, c->sampling.top_p, c->d_seed};
+    launch_sample_step(f.dtype, sa, sp, t, B, c->stream);
+}
+
+static const rdx_sampling k_sampling_off = {0, 1.0f, 0, 1.0f, 0};
+
+extern "C" int rdx_set_sampling(rdx_ctx* c, const rdx_sampling* sm) {
+    if (!c) return -1;
+    if (!sm || !sm->do_sample) { c->sampling = k_sampling_off; return 0; }
+    const rdx_sampling v = *sm;
+    if (!(v.temperature > 0.f) || !std::isfinite(v.temperature)) return fail(c, -1, "rdx_set_sampling: temperature must be a finite float > 0 (1.0 = off)");
+    if (v.top_k < 0) return fail(c, -1, "rdx_set_sampling: top_k %d is negative (0 = off)", v.top_k);
+    if (!(v.top_p > 0.f) || !(v.top_p <= 1.0f)) return fail(c, -1, "rdx_set_sampling: top_p must be in (0, 1] (1.0 = off)");
+    if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_set_sampling: llama weights not finalized");
+    const rdx_config& f = c->cfg;
+    if (!sample_step_supported(f.vocab)) return fail(c, -1, "rdx_set_sampling: a row of vocab %d does not fit the LDS of sample_step_k", f.vocab);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->rule_logits) ALLOC(c, c->rule_logits, (size_t)f.max_batch * f.vocab * 2);
+    if (!c->d_seed) ALLOC(c, c->d_seed, sizeof(unsigned long long));
+    // in stream order behind every step already queued; the source is copied before the call returns (pageable memory)
+    const unsigned long long seed = v.seed;
+    HIPCHK(c, hipMemcpyAsync(c->d_seed, &seed, sizeof(seed), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->sampling = v;
+    c->sampling.do_sample = 1;
+    c->sampling.seed = 0;           // lives on the device
+    return 0;
 }
 
 static const rdx_logits_rules k_neutral_rules = {1.0f, 0, 0};
@@ -429,6 +457,7 @@ int build_graph(rdx_ctx* c, void* scores, bool fixed) {
     GraphKey k;
     k.B = c->cur_B; k.max_new = c->cur_max_new; k.eos = c->cur_eos; k.pad = c->cur_pad; k.tokens = c->cur_tokens; k.scores = scores; k.fixed = fixed;
     k.rules = c->rules;
+    k.sampling = c->sampling;
     if (int rrc = rules_need_prefill(c, "decode step graph")) return rrc;
     if (c->graph && k == c->gkey) return 0;
     if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }
@@ -549,6 +578,7 @@ extern "C" int rdx_beam_search(rdx_ctx* c, const int32_t* ids, const int32_t* ma
     if (!c) return -1;
     if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_beam_search: llama weights not finalized");
     const rdx_config& f = c->cfg;
+    if (c->sampling.do_sample) return fail(c, -1, "rdx_beam_search: not available while sampling is on (beam-sample is not built); rdx_set_sampling(ctx, NULL) first");
     if (c->rules_on) return fail(c, -1, "rdx_beam_search: not available under logits rules (beam search applies them to log-softmax scores and reorders histories); rdx_set_logits_rules(ctx, NULL) first");
     const int rows = groups * num_beams;
     if (groups <= 0 || num_beams < 2 || num_beams > RDX_MAX_BEAMS) return fail(c, -1, "rdx_beam_search: num_beams must be in [2, %d]", RDX_MAX_BEAMS);

@@ -2,6 +2,7 @@
 #include <algorithm>
 #include "rdx_common.h"
 #include "rdx_kernels.h"
+#include "philox.h"
 
 namespace rdx {
 
@@ -642,16 +643,12 @@ __device__ __forceinline__ T apply_rules(T v, bool seen, bool ban, float p) {
     }
     return ban ? fromf<T>(-INFINITY) : v;
 }
-template <typename T>
-__global__ __launch_bounds__(256) void select_step_k(SelectArgs a, StepTail t) {
-    extern __shared__ unsigned sel_bits[];           // seen[W] | ban[W]
-    const int b = blockIdx.x, V = t.vocab, W = (V + 31) >> 5;
-    unsigned* seen = sel_bits;
-    unsigned* ban = sel_bits + W;
-    zero_handoff_counters(t.ctr_zero, t.n_zero);
-    for (int i = threadIdx.x; i < 2 * W; i += blockDim.x) sel_bits[i] = 0u;
+// The rules phase both selection kernels share: row b's history marks `seen` and `ban` ([W] words each, W = ceil(V / 32)). hist null: no history.
+__device__ __forceinline__ void mark_rules_bitmaps(const SelectArgs& a, const StepTail& t, int b, int gen, unsigned* seen, unsigned* ban, int W) {
+    const int V = t.vocab;
+    for (int i = threadIdx.x; i < W; i += blockDim.x) { seen[i] = 0u; ban[i] = 0u; }
     __syncthreads();
-    const int L = min(t.hist_len[b], t.hist_ld), gen = a.n_gen[b], n = a.ngram;
+    const int L = t.hist ? min(t.hist_len[b], t.hist_ld) : 0, n = a.ngram;
     const int* h = t.hist + (size_t)b * t.hist_ld;
     if (a.penalty != 1.0f)
         for (int j = threadIdx.x; j < L; j += blockDim.x) {
@@ -667,6 +664,16 @@ __global__ __launch_bounds__(256) void select_step_k(SelectArgs a, StepTail t) {
         }
     if (threadIdx.x == 0 && a.min_new > 0 && t.eos_id >= 0 && t.eos_id < V && gen < a.min_new) atomicOr(&ban[t.eos_id >> 5], 1u << (t.eos_id & 31));
     __syncthreads();
+}
+template <typename T>
+__global__ __launch_bounds__(256) void select_step_k(SelectArgs a, StepTail t) {
+    extern __shared__ unsigned sel_bits[];           // seen[W] | ban[W]
+    const int b = blockIdx.x, V = t.vocab, W = (V + 31) >> 5;
+    unsigned* seen = sel_bits;
+    unsigned* ban = sel_bits + W;
+    zero_handoff_counters(t.ctr_zero, t.n_zero);
+    const int gen = a.n_gen[b];
+    mark_rules_bitmaps(a, t, b, gen, seen, ban, W);
 
     T* row = (T*)a.logits + (size_t)gen * a.step_stride + (size_t)b * V;
     const float p = a.penalty;
@@ -706,6 +713,208 @@ __global__ __launch_bounds__(256) void select_step_k(SelectArgs a, StepTail t) {
     }
     step_tail<T>(t, b, tok);
 }
+// ---- sampled step (transformers 4.28.1 sample: processors -> temperature -> top-k -> top-p -> multinomial; include/rdx.h, rdx_sampling) ----------
+// One workgroup per batch row, behind the lm_head launch, in select_step_k's place. The row is read ONCE from memory: rules and temperature are applied on
+// the way into LDS (a 32001-element row is 64 KB), every later pass runs from there, and one pass at the end stores the processed row (kept: s_i,
+// dropped: -inf). top-k and top-p are radix selections over the order-preserving 16-bit key of the model-dtype value, two 256-bin passes each (high byte,
+// low byte): top-k counts elements, top-p sums integer masses q_i = rint(exp(s_i - max) * 2^32). Integer LDS atomics only, so no result depends on the
+// order the threads arrive in. The draw: every thread sums the masses of one contiguous index chunk, a block scan of the 256 sums, and the one thread
+// whose chunk holds target = (u24 * C_last) >> 24 walks it. u24 comes from Philox at counter (row, tokens generated), key = the seed word in memory.
+typedef unsigned long long u64s;
+typedef unsigned short v8us __attribute__((ext_vector_type(8)));
+// a < b as values <=> okey(a) < okey(b); -0 and +0 share one key; -inf has the lowest key of all non-NaN values
+__device__ __forceinline__ unsigned okey(unsigned u) {
+    if (u == 0x8000u) u = 0u;
+    return (u & 0x8000u) ? (~u & 0xffffu) : (u | 0x8000u);
+}
+template <typename T> __device__ __forceinline__ u64s mass_q(unsigned short u, float smax) {
+    return __float2ull_rn(__expf(tof<T>(from_bits16<T>(u)) - smax) * 4294967296.f);     // exp(0) = 1 -> 2^32; NaN (an all -inf row) -> 0
+}
+// inclusive prefix sum over the 256 threads in thread order; buf = [2][256]; *total = the sum of all. Integer: the same for every schedule.
+__device__ __forceinline__ u64s block_scan256(u64s v, u64s* buf, u64s* total) {
+    __syncthreads();                     // the previous user of buf is done
+    buf[threadIdx.x] = v;
+    __syncthreads();
+    int src = 0;
+#pragma unroll
+    for (int o = 1; o < 256; o <<= 1) {
+        u64s x = buf[src * 256 + threadIdx.x];
+        if ((int)threadIdx.x >= o) x += buf[src * 256 + threadIdx.x - o];
+        buf[(src ^ 1) * 256 + threadIdx.x] = x;
+        src ^= 1;
+        __syncthreads();
+    }
+    *total = buf[src * 256 + 255];
+    return buf[src * 256 + threadIdx.x];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void sample_step_k(SelectArgs a, SampleArgs sp, StepTail t) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smp_lds[];
+    const int b = blockIdx.x, V = t.vocab, W = (V + 31) >> 5, tid = threadIdx.x;
+    // layout = sample_step_lds(): bitmaps | masses[256] | scan[2][256] | counts[256] | words[16] | row
+    unsigned* seen = (unsigned*)smp_lds;
+    unsigned* ban = seen + W;
+    u64s* hmass = (u64s*)(smp_lds + (((size_t)2 * W * 4 + 15) & ~(size_t)15));
+    u64s* scan = hmass + 256;
+    int* hcnt = (int*)(scan + 512);
+    int* words = hcnt + 256;             // 0: max key, 1: selected high byte, 2: rank / unused, 3: low byte, 4: token, 5..6: base mass
+    unsigned short* srow = (unsigned short*)(words + 16);
+    zero_handoff_counters(t.ctr_zero, t.n_zero);
+    const int gen = a.n_gen[b];
+    const bool ruled = a.penalty != 1.0f || a.ngram != 0 || a.min_new != 0;
+    if (tid < 16) words[tid] = tid == 4 ? 0x7fffffff : (tid == 1 || tid == 3 ? -1 : 0);
+    if (ruled) mark_rules_bitmaps(a, t, b, gen, seen, ban, W);
+
+    // ---- the row into LDS: rules, then temperature. Element i lives at srow[pad + i], so that the 16-byte pieces of the row in memory are 16-byte pieces here
+    T* row = (T*)a.logits + (size_t)gen * a.step_stride + (size_t)b * V;
+    const int head = min(V, (int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 1));
+    const int nvec = (V - head) >> 3, pad = (8 - head) & 7;
+    unsigned short* sr = srow + pad;
+    const float p = a.penalty, temp = sp.temperature;
+    int kmax = 0;
+    auto cook = [&](T v, bool s, bool x) -> unsigned short {
+        if (ruled) v = apply_rules<T>(v, s, x, p);
+        if (temp != 1.0f) v = fromf<T>(__fdiv_rn(tof<T>(v), temp));        // scores / temperature on a model-dtype tensor: fp32 IEEE division, one rounding
+        const unsigned short u = bits16<T>(v);
+        kmax = max(kmax, (int)okey(u));
+        return u;
+    };
+    auto one = [&](int i) {
+        const bool s = ruled && ((seen[i >> 5] >> (i & 31)) & 1u), x = ruled && ((ban[i >> 5] >> (i & 31)) & 1u);
+        sr[i] = cook(row[i], s, x);
+    };
+    if (tid < head) one(tid);
+    for (int i = head + nvec * 8 + tid; i < V; i += 256) one(i);
+    for (int q = tid; q < nvec; q += 256) {
+        const int i = head + q * 8;
+        typename Vec8<T>::type v = as_vec8<T>(ldg16(row + i));
+        const unsigned s = ruled ? bits8(seen, i) : 0u, x = ruled ? bits8(ban, i) : 0u;
+        v8us o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = cook(v[j], (s >> j) & 1u, (x >> j) & 1u);
+        *(v8us*)(sr + i) = o;
+    }
+    __syncthreads();                     // words[] initialised (and the row complete for the other threads)
+    atomicMax(&words[0], kmax);
+    __syncthreads();
+    const int maxkey = words[0];
+    unsigned short maxbits = (unsigned short)((maxkey & 0x8000) ? (maxkey & 0x7fff) : (~maxkey & 0xffff));
+    const float smax = tof<T>(from_bits16<T>(maxbits));
+
+    // ---- top-k: the key of the min(k, V)-th largest value; smaller keys are dropped, ties with it stay
+    int floor_key = 0;
+    if (sp.top_k > 0 && sp.top_k < V) {
+        int want = sp.top_k, hb = 0;
+        for (int pass = 0; pass < 2; ++pass) {
+            hcnt[tid] = 0;
+            __syncthreads();
+            for (int i = tid; i < V; i += 256) {
+                const int k = (int)okey(sr[i]);
+                if (pass == 0) atomicAdd(&hcnt[k >> 8], 1);
+                else if ((k >> 8) == hb) atomicAdd(&hcnt[k & 255], 1);
+            }
+            __syncthreads();
+            const int bin = 255 - tid;   // from the top: thread order = descending bins
+            const u64s cnt = (u64s)hcnt[bin];
+            u64s tot;
+            const u64s S = block_scan256(cnt, scan, &tot);
+            if (S >= (u64s)want && S - cnt < (u64s)want) { words[1 + 2 * pass] = bin; words[2] = want - (int)(S - cnt); }
+            __syncthreads();
+            if (pass == 0) { hb = words[1]; want = words[2]; }
+        }
+        floor_key = (words[1] << 8) | words[3];
+        __syncthreads();
+        if (tid == 0) { words[1] = -1; words[3] = -1; }
+    }
+
+    // ---- top-p over the survivors: the lowest key v with M(v) = mass(keys <= v) / mass(all) > 1 - p; smaller keys are dropped
+    if (sp.top_p < 1.0f) {
+        int pb = 0;
+        u64s base = 0;
+        double thr = 0.0;
+        for (int pass = 0; pass < 2; ++pass) {
+            hmass[tid] = 0;
+            __syncthreads();
+            for (int i = tid; i < V; i += 256) {
+                const unsigned short u = sr[i];
+                const int k = (int)okey(u);
+                if (k < floor_key) continue;
+                if (pass == 0) atomicAdd(&hmass[k >> 8], mass_q<T>(u, smax));
+                else if ((k >> 8) == pb) atomicAdd(&hmass[k & 255], mass_q<T>(u, smax));
+            }
+            __syncthreads();
+            const u64s m = hmass[tid];   // ascending bins
+            u64s tot;
+            const u64s S = block_scan256(m, scan, &tot) + base;
+            if (pass == 0) thr = (1.0 - (double)sp.top_p) * (double)tot;
+            if ((double)S > thr && !((double)(S - m) > thr)) {
+                words[1 + 2 * pass] = tid;
+                words[5] = (int)(unsigned)(S - m); words[6] = (int)(unsigned)((S - m) >> 32);
+            }
+            __syncthreads();
+            if (pass == 0) {
+                pb = words[1];
+                base = (u64s)(unsigned)words[5] | ((u64s)(unsigned)words[6] << 32);
+                if (pb < 0) break;       // uniform: no bin passes the threshold (a p below 2^-53, or an all -inf row): the maximum alone stays
+            }
+        }
+        const int pkey = (words[1] < 0 || words[3] < 0) ? maxkey : ((words[1] << 8) | words[3]);
+        floor_key = max(floor_key, pkey);
+    }
+    floor_key = min(floor_key, maxkey);  // the maximum always stays
+
+    // ---- the draw: contiguous chunks in index order
+    const int chunk = (V + 255) >> 8, i0 = min(V, tid * chunk), i1 = min(V, i0 + chunk);
+    u64s mine = 0;
+    for (int i = i0; i < i1; ++i) {
+        const unsigned short u = sr[i];
+        if ((int)okey(u) >= floor_key) mine += mass_q<T>(u, smax);
+    }
+    u64s c_last;
+    const u64s incl = block_scan256(mine, scan, &c_last);
+    uint32_t u24 = 0;
+    {
+        const u64s seed = *sp.seed;
+        u24 = sample_u24((uint64_t)seed, (uint32_t)b, (uint32_t)gen);
+    }
+    const u64s target = __umul64hi((u64s)u24 << 40, c_last);         // (u24 * C_last) >> 24 < C_last
+    if (c_last > 0 && incl > target && incl - mine <= target) {
+        u64s cacc = incl - mine;
+        int tok = i1 - 1;
+        for (int i = i0; i < i1; ++i) {
+            const unsigned short u = sr[i];
+            if ((int)okey(u) >= floor_key) {
+                cacc += mass_q<T>(u, smax);
+                if (cacc > target) { tok = i; break; }
+            }
+        }
+        words[4] = tok;
+    }
+    if (c_last == 0)                     // no mass anywhere (an all -inf or NaN row): the lowest index of the maximum, like the greedy kernels
+        for (int i = i0; i < i1; ++i) if ((int)okey(sr[i]) == maxkey) { atomicMin(&words[4], i); break; }
+
+    // ---- the processed row back to memory: what the caller's logits / scores hold (HF's .scores)
+    const unsigned short ninf = bits16<T>(fromf<T>(-INFINITY));
+    auto out1 = [&](unsigned short u) -> unsigned short { return (int)okey(u) >= floor_key ? u : ninf; };
+    if (tid < head) row[tid] = from_bits16<T>(out1(sr[tid]));
+    for (int i = head + nvec * 8 + tid; i < V; i += 256) row[i] = from_bits16<T>(out1(sr[i]));
+    for (int q = tid; q < nvec; q += 256) {
+        const int i = head + q * 8;
+        v8us o = *(const v8us*)(sr + i);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = out1(o[j]);
+        stg16(row + i, __builtin_bit_cast(u4, o));
+    }
+    __syncthreads();
+    int tok = words[4];
+    tok = tok < 0 ? 0 : (tok >= V ? V - 1 : tok);
+    if (a.sel_out) {                     // the kernel-test hook: the selection alone, no decode state behind it
+        if (tid == 0) a.sel_out[b] = tok;
+        return;
+    }
+    step_tail<T>(t, b, tok);
+}
 // ---- avg_pool2d(pool) + NCHW flatten of the NHWC projector output (chexpert_model.py:17-18) ----------------------------
 template <typename T>
 __global__ void avgpool_flatten_k(const T* __restrict__ in, T* __restrict__ out, int B, int G, int C, int pool) {
@@ -734,6 +943,20 @@ bool select_step_supported(int vocab) { return vocab > 0 && select_step_lds(voca
 
 void launch_select_step(int dtype, const SelectArgs& a, const StepTail& t, int B, hipStream_t s) {
     RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((select_step_k<T>), dim3(B), dim3(256), select_step_lds(t.vocab), s, a, t));
+}
+
+bool sample_step_supported(int vocab) { return vocab > 0 && sample_step_lds(vocab) <= 144 * 1024; }     // of the CU's 160 KB; step_tail's own words on top
+
+void launch_sample_step(int dtype, const SelectArgs& a, const SampleArgs& sp, const StepTail& t, int B, hipStream_t s) {
+    const size_t smem = sample_step_lds(t.vocab);
+    if (dtype == DT_F16) {
+        static DevOnce attr;
+        if (attr.first()) (void)hipFuncSetAttribute((const void*)sample_step_k<f16>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+    } else {
+        static DevOnce attr;
+        if (attr.first()) (void)hipFuncSetAttribute((const void*)sample_step_k<bf16>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
+    }
+    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((sample_step_k<T>), dim3(B), dim3(256), smem, s, a, sp, t));
 }
 
 // the caller's ids replace the token the previous step appended (rdx_decode_step_ids under logits rules)

@@ -51,10 +51,12 @@ struct GraphKey {
     const void* tokens = nullptr; const void* scores = nullptr;
     bool fixed = false;             // logits always to `scores` itself (beam search) instead of scores + step * stride
     rdx_logits_rules rules = {1.0f, 0, 0};      // the captured step selects through select_step_k unless neutral
+    rdx_sampling sampling = {0, 1.0f, 0, 1.0f, 0};      // do_sample: through sample_step_k, t / k / p its arguments; the seed is no part of the key (a device word)
     bool operator==(const GraphKey& o) const {
         return B == o.B && max_new == o.max_new && eos == o.eos && pad == o.pad && tokens == o.tokens && scores == o.scores && fixed == o.fixed &&
                rules.repetition_penalty == o.rules.repetition_penalty && rules.no_repeat_ngram_size == o.rules.no_repeat_ngram_size &&
-               rules.min_new_tokens == o.rules.min_new_tokens;
+               rules.min_new_tokens == o.rules.min_new_tokens && sampling.do_sample == o.sampling.do_sample &&
+               sampling.temperature == o.sampling.temperature && sampling.top_k == o.sampling.top_k && sampling.top_p == o.sampling.top_p;
     }
 };
 
@@ -125,6 +127,9 @@ struct rdx_ctx {
     bool rules_on = false;                          // any rule differs from neutral: the step selects through select_step_k (elem.hip)
     int *d_hist = nullptr, *d_hist_len = nullptr;   // [max_batch][max_len] token history (index = cache slot), [max_batch] its lengths
     void* rule_logits = nullptr;                    // [max_batch][vocab]: where the lm_head writes when the caller passes no logits / scores buffer
+    // ---- sampled decoding (rdx_set_sampling): do_sample == 0 = off; on: the step selects through sample_step_k (elem.hip), rules included ----
+    rdx_sampling sampling = {0, 1.0f, 0, 1.0f, 0};
+    unsigned long long* d_seed = nullptr;           // the seed word sample_step_k reads (rewritten in stream order by every rdx_set_sampling call)
 
     // ---- beam search workspaces (rdx_beam_search), sized on first use ----
     void* bm_logits = nullptr; float* bm_scores = nullptr; float* bm_cand_s = nullptr; int* bm_cand_i = nullptr;

@@ -294,6 +294,18 @@ struct SelectArgs {
 inline size_t select_step_lds(int vocab) { return (size_t)2 * ((vocab + 31) / 32) * sizeof(unsigned); }     // two bitmaps over the vocabulary
 bool select_step_supported(int vocab);
 void launch_select_step(int dtype, const SelectArgs& a, const StepTail& t, int B, hipStream_t s);       // t.hist* = the rows' history
+// Sampled step (sample_step_k): the rules of SelectArgs (neutral = none; t.hist may then be null), then temperature, top-k, top-p and the draw of
+// include/rdx.h (rdx_sampling) on the same row, in place, then the tail. `seed` is a device word: a new seed needs no new graph.
+struct SampleArgs {
+    float temperature; int top_k; float top_p;
+    const unsigned long long* seed;
+};
+// dynamic LDS of sample_step_k: two bitmaps | masses u64[256] | scan u64[2][256] | counts int[256] | 16 words | the row (+ 8 elements of alignment slack)
+inline size_t sample_step_lds(int vocab) {
+    return (((size_t)2 * ((vocab + 31) / 32) * sizeof(unsigned) + 15) & ~(size_t)15) + 256 * 8 + 512 * 8 + 256 * 4 + 64 + ((((size_t)vocab + 8) * 2 + 15) & ~(size_t)15);
+}
+bool sample_step_supported(int vocab);
+void launch_sample_step(int dtype, const SelectArgs& a, const SampleArgs& sp, const StepTail& t, int B, hipStream_t s);
 void launch_hist_init(const int* ids, int B, int T, int* hist, int* hist_len, int ld, hipStream_t s);
 void launch_hist_set_last(const int* ids, int* hist, const int* hist_len, int ld, int B, hipStream_t s);
 

@@ -55,6 +55,34 @@ class LogitsRules:
         return rules if isinstance(rules, cls) else cls(*rules)
 
 
+@dataclass(frozen=True)
+class Sampling:
+    """Sampled decoding (rdx_sampling, include/rdx.h): transformers' `temperature`, `top_k` and `top_p` warpers in that order, then one draw per row and
+    step from a counter RNG keyed by `seed`. Neutral values: temperature 1.0, top_k 0, top_p 1.0. Raises ValueError on what the library refuses."""
+    temperature: float = 1.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int = 0
+
+    def __post_init__(self):
+        t, k, p, s = self.temperature, self.top_k, self.top_p, self.seed
+        if isinstance(t, bool) or not isinstance(t, numbers.Real) or not math.isfinite(t) or not t > 0:
+            raise ValueError(f"`temperature` has to be a strictly positive float, but is {t}")
+        if isinstance(k, bool) or not isinstance(k, numbers.Integral) or k < 0:
+            raise ValueError(f"`top_k` has to be a non-negative integer (0 = off), but is {k}")
+        if isinstance(p, bool) or not isinstance(p, numbers.Real) or not (0 < p <= 1.0):
+            raise ValueError(f"`top_p` has to be a float > 0 and <= 1 (1.0 = off), but is {p}")
+        if isinstance(s, bool) or not isinstance(s, numbers.Integral) or not (0 <= s < 1 << 64):
+            raise ValueError(f"`seed` has to be an integer in [0, 2^64), but is {s}")
+
+    @classmethod
+    def of(cls, sampling) -> Optional["Sampling"]:
+        """None (greedy), a Sampling or a (temperature, top_k, top_p, seed) tuple."""
+        if sampling is None or isinstance(sampling, cls):
+            return sampling
+        return cls(*sampling)
+
+
 class RdxEngine:
     def __init__(self, cfg: RaDialogCfg, dtype: str = "bf16", device: int = 0, max_batch: int = 1, max_len: int = 512,
                  lora: bool = True, vision: bool = True, llama: bool = True, classifier: bool = False,
@@ -96,6 +124,7 @@ class RdxEngine:
         self._finalized = False
         self._keep = {}
         self._rules = LogitsRules()                  # what the context holds (set_logits_rules is the one place that changes it)
+        self._sampling = None                        # likewise (set_sampling); None = greedy
 
     # ------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -192,6 +221,35 @@ class RdxEngine:
         self._rules = r
         return r
 
+    def set_sampling(self, sampling=None) -> Optional[Sampling]:
+        """rdx_set_sampling: the selection of the next prefill / generate / decode_step calls; None = greedy (the argmax)."""
+        sm = Sampling.of(sampling)
+        c = None if sm is None else _lib.RdxSampling(1, float(sm.temperature), int(sm.top_k), float(sm.top_p), int(sm.seed))
+        check(self.ctx, self.lib.rdx_set_sampling(self.ctx, None if c is None else C.byref(c)), "rdx_set_sampling")
+        self._sampling = sm
+        return sm
+
+    def sample_test(self, logits, n_generated, sampling, rules=None, hist=None, hist_len=None, eos_id=-1):
+        """sample_step_k alone (rdx_sample_test): logits [B, V] model dtype, n_generated int [B] (the draw indices), sampling a Sampling or tuple; rules with
+        hist int [B, ld] and hist_len int [B] as in select_test. Returns (processed logits [B, V], tokens int32 [B]); the caller's tensors stay."""
+        B, V = logits.shape
+        r, sm = LogitsRules.of(rules), Sampling.of(sampling)
+        x = logits.to(self.device, self.tdtype).contiguous().clone()
+        ng = n_generated.to(self.device, torch.int32).contiguous()
+        h = None if hist is None else hist.to(self.device, torch.int32).contiguous()
+        hl = None if hist_len is None else hist_len.to(self.device, torch.int32).contiguous()
+        if ng.numel() != B or (r.active and (h is None or hl is None)):
+            raise ValueError("sample_test: n_generated [B]; active rules need hist [B, ld] and hist_len [B]")
+        if h is not None and (h.shape[0] != B or hl.numel() != B or int(hl.max()) > h.shape[1] or int(hl.min()) < 0):
+            raise ValueError("sample_test: hist [B, ld], hist_len [B] in 0 .. ld")
+        out = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        cr = _lib.RdxLogitsRules(float(r.repetition_penalty), int(r.no_repeat_ngram_size), int(r.min_new_tokens))
+        cs = _lib.RdxSampling(1, float(sm.temperature), int(sm.top_k), float(sm.top_p), int(sm.seed))
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_sample_test(self.ctx, _ptr(x), B, V, _ptr(h), _ptr(hl), _ptr(ng), 0 if h is None else h.shape[1], C.byref(cr),
+                                                 int(eos_id), C.byref(cs), _ptr(out)), "rdx_sample_test")
+        return x, out
+
     def select_test(self, logits, hist, hist_len, n_generated, rules, eos_id=-1):
         """select_step_k alone (rdx_select_test): logits [B, V] model dtype, hist int [B, ld], hist_len / n_generated int [B]. Returns (processed
         logits [B, V], tokens int32 [B]); the caller's tensors are left as they are."""
@@ -231,13 +289,15 @@ class RdxEngine:
 
     def generate(self, ids: torch.Tensor, qformer_embs: Optional[torch.Tensor], max_new: int, eos_id: int = 2,
                  pad_id: int = 0, mask: Optional[torch.Tensor] = None, output_scores: bool = False, use_graph: bool = True,
-                 reuse_prefix: bool = False, logits_rules=None):
-        """Greedy generation. Returns (tokens int32[B,n_steps], scores [n_steps,B,V] model dtype or None, n_steps).
+                 reuse_prefix: bool = False, logits_rules=None, sampling=None):
+        """Greedy (sampling=None) or sampled generation. Returns (tokens int32[B,n_steps], scores [n_steps,B,V] model dtype or None, n_steps).
         reuse_prefix: multi-turn conversations -- keep the KV rows of the token prefix this prompt shares with the previous
         reuse_prefix call and prefill only the rest (rdx_generate_append); outputs are those of the full prompt.
         logits_rules: LogitsRules or (repetition_penalty, no_repeat_ngram_size, min_new_tokens); the scores are then the processed ones
-        (HF's .scores). An active rule prefills the whole prompt: the token history is not carried across calls."""
+        (HF's .scores). An active rule prefills the whole prompt: the token history is not carried across calls.
+        sampling: Sampling or (temperature, top_k, top_p, seed): rules, then the warpers, then one draw per row and step; the scores are the warped ones."""
         B, T = ids.shape
+        self.set_sampling(sampling)
         if self.set_logits_rules(logits_rules).active:
             reuse_prefix = False
         ids32 = ids.to(device=self.device, dtype=torch.int32).contiguous()
@@ -286,6 +346,7 @@ class RdxEngine:
         rep = lambda t, dt: None if t is None else t.to(device=self.device, dtype=dt).repeat_interleave(k, dim=0).contiguous()   # noqa: E731
         ids32, m32, qf = rep(ids, torch.int32), rep(mask, torch.int32), rep(qformer_embs, torch.float32)
         self.set_logits_rules(None)                  # rules are a greedy-search feature; a call that left some behind must not make this one fail
+        self.set_sampling(None)                      # likewise: beam-sample is not built
         toks = torch.zeros(B, max_new, dtype=torch.int32)
         lens = torch.zeros(B, dtype=torch.int32)
         seq_scores = torch.zeros(B, dtype=torch.float32)
@@ -299,9 +360,10 @@ class RdxEngine:
               "rdx_beam_search")
         return toks, lens, seq_scores, (None if sc is None else sc[: n.value]), n.value
 
-    def prefill(self, ids, qformer_embs, max_new, eos_id=2, pad_id=0, mask=None, want_logits=True, logits_rules=None):
-        """The prompt and token 0. logits_rules (as in generate) stay in force for the decode_step calls behind this prefill."""
+    def prefill(self, ids, qformer_embs, max_new, eos_id=2, pad_id=0, mask=None, want_logits=True, logits_rules=None, sampling=None):
+        """The prompt and token 0. logits_rules and sampling (as in generate) stay in force for the decode_step calls behind this prefill."""
         B, T = ids.shape
+        self.set_sampling(sampling)
         self.set_logits_rules(logits_rules)
         ids32 = ids.to(device=self.device, dtype=torch.int32).contiguous()
         m32 = None if mask is None else mask.to(device=self.device, dtype=torch.int32).contiguous()
@@ -316,11 +378,13 @@ class RdxEngine:
         self.sync()
         return toks, logits
 
-    def decode_step(self, want_logits=True, input_ids: Optional[torch.Tensor] = None, logits_rules=None):
+    def decode_step(self, want_logits=True, input_ids: Optional[torch.Tensor] = None, logits_rules=None, sampling=None):
         """One decode step on the token the previous step selected, or on caller-supplied `input_ids` int[B] (rdx_decode_step_ids).
         logits_rules: None keeps the rules the context holds (those of the prefill, unless a generate / beam_search call came in between); rules
-        cannot be switched on behind a prefill that ran without any."""
+        cannot be switched on behind a prefill that ran without any. sampling: None keeps what the context holds, too."""
         ids32, m32, qf, toks = self._keep["prefill"]
+        if sampling is not None and Sampling.of(sampling) != self._sampling:
+            self.set_sampling(sampling)
         if logits_rules is not None and LogitsRules.of(logits_rules) != self._rules:
             self.set_logits_rules(logits_rules)
         B = ids32.shape[0]

@@ -215,12 +215,21 @@ class LlamaForCausalLM:
                  attention_mask: Optional[torch.Tensor] = None, num_beams: int = 1, do_sample: bool = False,
                  qformer_embs: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, length_penalty: float = 1.0, early_stopping: bool = False,
-                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, **_unused):
-        if do_sample:
-            raise NotImplementedError("sampling is not on the path: every reference call site decodes deterministically")
+                 repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+                 temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None, **_unused):
+        """do_sample=True on a model with `enable_sampling = True` set on it (the way `reuse_prefix_kv` is set): transformers' `sample` with its
+        temperature / top_k / top_p warpers (top_k=50 is GenerationConfig's default), drawn from a counter RNG: `seed`, or, when None, 63 bits
+        from torch's default CPU generator, so that torch.manual_seed(s) in front of two calls makes them equal. A model without the switch
+        refuses do_sample=True with NotImplementedError, as it always has: every reference call site decodes deterministically, and a caller
+        that relied on that is not given a stochastic result unasked. With do_sample=False the three warper arguments are ignored, as
+        transformers ignores them in greedy search."""
+        if do_sample and not getattr(self, "enable_sampling", False):
+            raise NotImplementedError("sampling is off on this model (every reference call site decodes deterministically): set "
+                                      "`model.enable_sampling = True` to let generate(do_sample=True) sample")
         if num_beams < 1:
             raise ValueError("`num_beams` has to be an integer strictly greater than 0")
         from .engine import LogitsRules
+        sampling = _sampling_of(do_sample, num_beams, temperature, top_k, top_p, seed, _unused)        # ValueError before an engine exists
         # transformers builds RepetitionPenaltyLogitsProcessor, which takes a float only, when the value differs from 1.0: 1 (int) is "off" there too
         if not isinstance(repetition_penalty, float) and not (isinstance(repetition_penalty, numbers.Real) and repetition_penalty == 1):
             raise ValueError(f"`repetition_penalty` has to be a strictly positive float, but is {repetition_penalty}")
@@ -246,7 +255,7 @@ class LlamaForCausalLM:
         toks, scores, n = self._engine.generate(input_ids, embs, max_new=max_new_tokens, eos_id=eos, pad_id=pad,
                                                 mask=attention_mask, output_scores=output_scores,
                                                 reuse_prefix=bool(getattr(self, "reuse_prefix_kv", False)) and attention_mask is None,
-                                                logits_rules=rules)
+                                                logits_rules=rules, sampling=sampling)
         toks = toks[:, :n].to(torch.int64)
         # HF stops as soon as every row has emitted EOS; the engine polls every 4th step (api_llama.hip decode_loop), so trim the all-pad tail
         if eos >= 0 and n > 0:
@@ -260,6 +269,36 @@ class LlamaForCausalLM:
         # fresh tensors like HF's: the engine reuses its score buffer on the next call
         sc = tuple(scores[i].clone() for i in range(n)) if output_scores else None
         return GenerateOutput(sequences=seq, scores=sc)
+
+
+def _sampling_of(do_sample, num_beams, temperature, top_k, top_p, seed, other):
+    """generate()'s sampling arguments as an engine.Sampling, or None for do_sample=False. The checks are those of transformers 4.28.1's
+    _get_logits_warper and its warper classes: a value that switches a warper off there (temperature 1, top_k 0, top_p 1) does so here."""
+    if not do_sample:
+        return None
+    from .engine import Sampling
+    if num_beams > 1:
+        raise ValueError("do_sample=True applies to num_beams=1 only: beam-sample is not built")
+    for name, neutral in (("typical_p", 1.0), ("epsilon_cutoff", 0.0), ("eta_cutoff", 0.0)):
+        v = other.get(name)
+        if v is not None and v != neutral:
+            raise ValueError(f"`{name}`={v}: this warper is not built (only temperature, top_k and top_p are)")
+    if not isinstance(temperature, float) and not (isinstance(temperature, numbers.Real) and not isinstance(temperature, bool) and temperature == 1):
+        raise ValueError(f"`temperature` has to be a strictly positive float, but is {temperature}")
+    if not temperature > 0:
+        raise ValueError(f"`temperature` has to be a strictly positive float, but is {temperature}")
+    if top_k is None:
+        top_k = 0
+    if isinstance(top_k, bool) or not isinstance(top_k, numbers.Integral) or top_k < 0:
+        raise ValueError(f"`top_k` has to be a strictly positive integer, but is {top_k}")
+    top_p = 1.0 if top_p is None else float(top_p)
+    if top_p < 0 or top_p > 1.0 or top_p != top_p:
+        raise ValueError(f"`top_p` has to be a float > 0 and < 1, but is {top_p}")
+    if top_p == 0.0:
+        top_p = 2.0 ** -126             # transformers keeps the one top token; here: the maximum's value group (the library wants p > 0)
+    if seed is None:
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64))      # the default CPU generator: torch.manual_seed governs it
+    return Sampling(float(temperature), int(top_k), top_p, seed)         # ValueError for a seed outside [0, 2^64)
 
 
 def _beam_generate(self, input_ids, embs, num_beams, max_new_tokens, eos, pad, attention_mask, length_penalty, early_stopping,

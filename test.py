@@ -60,6 +60,9 @@ def main(argv=None):
     p.add_argument("--repetition_penalty", type=float, default=1.0, help="greedy decode: divide / multiply the logits of tokens already in the sequence (1.0 = off)")
     p.add_argument("--no_repeat_ngram_size", type=int, default=0, help="greedy decode: no n-gram of this size occurs twice (0 = off)")
     p.add_argument("--min_new_tokens", type=int, default=0, help="greedy decode: no EOS before this many generated tokens (0 = off)")
+    p.add_argument("--do_sample", action="store_true", help="sample the report instead of decoding greedily (top_k 50, top_p 1.0, as transformers' defaults)")
+    p.add_argument("--temperature", type=float, default=1.0, help="with --do_sample: divide the logits by this (1.0 = off)")
+    p.add_argument("--seed", type=int, default=None, help="with --do_sample: the sampler's seed (default: drawn from torch's CPU generator)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     p.add_argument("--synthetic", action="store_true", help="deterministic random-init weights (no checkpoints reachable offline)")
     p.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: decoder GEMMs in OCP e4m3 on the fp8 MFMA (weights_fp8=True)")
@@ -104,10 +107,11 @@ def main(argv=None):
             conv.append_message(conv.roles[1], None)
             texts.append(conv.get_prompt())
         input_ids = tok.batch_encode_plus(texts, return_tensors="pt", padding=True)["input_ids"]
+        lang_model.enable_sampling = args.do_sample
         out = lang_model.generate(input_ids=input_ids, dicom=batch if args.use_embs else None, return_dict_in_generate=True,
                                   output_scores=True, max_new_tokens=args.max_new_tokens, num_beams=args.num_beams,
                                   repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
-                                  min_new_tokens=args.min_new_tokens)
+                                  min_new_tokens=args.min_new_tokens, do_sample=args.do_sample, temperature=args.temperature, seed=args.seed)
         preds = tok.batch_decode(out.sequences, skip_special_tokens=True)
         preds_history.extend(preds)
         all_preds.extend([q.split("ASSISTANT:")[1] if "ASSISTANT:" in q else q for q in preds])
