@@ -90,6 +90,16 @@ int rdx_sample_test(rdx_ctx* ctx, void* logits_inout, int B, int vocab, const in
 /* The 24 random bits of (seed, row, draw index) on the host: the same function the kernel calls (csrc/philox.h). No context, no device. */
 int rdx_sample_u24_host(uint64_t seed, uint32_t row, uint32_t draw, uint32_t* out);
 
+/* The device encoder of the coded bf16 weights alone (csrc/gemm.hip encode_wc_k; the format: radialog_amd/wcode.py): W fp32 [N][K] (device) is packed
+ * as rdx_set_weight packs it (rows padded to whole tiles of 16), then encoded. packed_out: the packed bf16 buffer [Npad / 16][K / 32][64][8]; planes_out:
+ * (Npad / 16) (K / 128) 3328 bytes; hdr_out: Npad / 16 words (base | raw << 8). All device pointers. bf16 contexts, K % 128 == 0. */
+int rdx_wcode_test(rdx_ctx* ctx, const float* W, int N, int K, void* packed_out, void* planes_out, uint32_t* hdr_out);
+/* The coded copies a finalized decoder holds (every gate/up, down_proj and QKV, the lm_head; none in f16 / fp8-weight contexts): out[0] = their 16-row
+ * tiles, out[1] = of those, the tiles flagged raw in their header (the kernels read the packed bf16 bytes of these), out[2] = bytes of planes and headers,
+ * out[3] / out[4] = launches of skinny_gemm_wc_k / decode_chain_wc_k this context has issued so far (a captured step graph counts once, at capture):
+ * how a test sees that the coded kernels, and not their raw twins, ran. out holds 5 values. */
+int rdx_wcode_stats(rdx_ctx* ctx, long long* out);
+
 #ifdef __cplusplus
 }
 #endif

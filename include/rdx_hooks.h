@@ -37,6 +37,9 @@ int rdx_gemv_trace(rdx_ctx* ctx, int what, int layer, long long* host, int max_t
  * RMS-normalised or just re-laid into the fragment-packed order (ACT_TILES32) by launch_rmsnorm, then streamed past the register-resident weights),
  * 9 / 10 / 11 = the fp8 path's prefill GEMM gemm8 (e4m3 weights x e4m3 activations with 1 / 2 / 4 K groups; K % 64 == 0, epi 0 / 3 / 4).
  * force 4 / 6 hold the fp8 weights as the engine does (e4m3 bytes + scales only): batch >= 3 shapes multiply fp8 x fp8.
+ * 12 = the skinny GEMV on CODED bf16 weights (13 bits per weight, decoded exactly in registers: radialog_amd/wcode.py): the hook encodes the packed W
+ * itself, as rdx_finalize_weights does for the batch <= 2 step; bf16 contexts, M <= 2, K % 128 == 0, epi 0 / 3 / 4 (the logits epilogue: rdx_logits_test); the same bits as force 1.
+ * force 1 and 12 accept any N > 0 (rows are padded to whole tiles of 16, as the loader pads them); every other force needs N % 16 == 0.
  * Test / benchmark hook. */
 int rdx_gemm_test(rdx_ctx* ctx, const void* X, const float* W, const float* bias, const void* resid, void* out, int M, int N,
                   int K, int epi, const void* norm_w, float eps, int force);
@@ -58,7 +61,8 @@ int rdx_conv_test(rdx_ctx* ctx, const void* X, const float* W, const float* bias
 int rdx_l2_bench(rdx_ctx* ctx, int mode, long long bytes_per_wg, int shared, int reps, int wgs, float* gbps_host);
 
 /* the lm_head epilogue of the weight-streaming kernels on a bare GEMM (M <= 32): logits model-dtype [M][N] (columns >=
- * n_valid are not written) and the greedy choice per row (argmax over n < n_valid, ties -> lowest index). Test hook. */
+ * n_valid are not written) and the greedy choice per row (argmax over n < n_valid, ties -> lowest index). fp8: 0 = model-dtype weights, 1 = e4m3
+ * weights, 2 = the coded bf16 copy of W (bf16 contexts, M <= 2, K % 128 == 0; the same bits as 0). Test hook. */
 int rdx_logits_test(rdx_ctx* ctx, const void* X, const float* W, int M, int N, int n_valid, int K, void* out_logits,
                     int32_t* argmax_host, int fp8);
 

@@ -136,6 +136,8 @@ DEC_HOOK_SYMBOLS = {
     "rdx_decode_attn_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_longlong,
                                        C.c_int, C.c_int]),
     "rdx_rope_kv_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "rdx_wcode_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "rdx_wcode_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
 }
 ALL_HOOK_SYMBOLS = {**HOOK_SYMBOLS, **ENC_HOOK_SYMBOLS, **DEC_HOOK_SYMBOLS}
 

@@ -239,6 +239,28 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
             }
         }
         if (R.rc) return R.rc;
+        // Coded bf16 copies (rdx_common.h WcChunk) of what the batch <= 2 step streams outside the fused attention launch: every gate/up and down_proj,
+        // the QKV of layers 1.. (the chained launch's second role) and the lm_head. Layer 0's stand-alone QKV measured no lower coded and stays raw. Encoded from the PACKED buffers, which stay (prefill, batch >= 3 and the tiles the code cannot express read them).
+        // The dispatch rule of the coded path, first half (the second is coded_unit / step_chained): bf16, NOT the fp8-weight mode, both K multiples of
+        // the coded chunk, and a context whose step can run the batch <= 2 chained family at all.
+        const bool fp8_mode = fp8_weights(c->ll[0].wqkv) || fp8_weights(c->ll[0].wgu) || fp8_weights(c->lm_head);
+        LlamaDims probe = {}; probe.hidden = H; probe.heads = f.heads; probe.head_dim = 128;
+        if (f.dtype == DT_BF16 && !fp8_mode && H % WC_CHUNK_K == 0 && I % WC_CHUNK_K == 0 && chain_supported(probe, I, 1)) {
+            auto encode = [&](GemmW& W) -> int {
+                if (!W.w || W.wc) return 0;
+                ALLOC(c, W.wc, wc_bytes(W.Npad, W.K));
+                ALLOC(c, W.wch, (size_t)(W.Npad / 16) * sizeof(unsigned));
+                launch_encode_wc(W.w, W.wc, W.wch, W.Npad, W.K, c->stream);
+                return 0;
+            };
+            if (int erc = encode(c->lm_head)) return erc;
+            for (int l = 0; l < f.layers; ++l) {
+                if (l > 0) if (int erc = encode(c->ll[l].wqkv)) return erc;
+                if (int erc = encode(c->ll[l].wgu)) return erc;
+                if (int erc = encode(c->ll[l].wdown)) return erc;
+            }
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+        }
         c->ld.hidden = H; c->ld.heads = f.heads; c->ld.head_dim = 128; c->ld.qkv_ld = c->ll[0].wqkv.Npad;
         c->ld.lora_r = f.lora_r; c->ld.lora_scale = f.lora_scale; c->ld.max_len = f.max_len; c->ld.max_pos = f.max_pos;
         c->ld.k_perm = (getenv("RDX_KPERM") ? atoi(getenv("RDX_KPERM")) : (f.max_batch * f.heads <= 256)) ? 1 : 0;
@@ -365,7 +387,8 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
 
 // Test / experiment switches of one context (read from the environment once, at rdx_create): "flash_min" = workgroups from which the batched
 // prefill attention takes flash_prefill_k (0 = never, 1 = always; RDX_FLASH_MIN), "pconv" = the encoder on fragment-packed activations (RDX_PCONV),
-// "xs16" = batch 3-16 decode on the one-row-tile family (RDX_XS16), "prompt_blk" = one prompt's K = 4096 projections on 32-row blocks (RDX_PBLK).
+// "xs16" = batch 3-16 decode on the one-row-tile family (RDX_XS16), "prompt_blk" = one prompt's K = 4096 projections on 32-row blocks (RDX_PBLK),
+// "wcode" = the batch <= 2 step streams the coded bf16 weights (no environment variable: on unless switched off here).
 extern "C" int rdx_set_option(rdx_ctx* c, const char* name, int value) {
     if (!c || !name) return -1;
     if (!strcmp(name, "flash_min")) { c->flash_min = value; return 0; }
@@ -373,6 +396,11 @@ extern "C" int rdx_set_option(rdx_ctx* c, const char* name, int value) {
     if (!strcmp(name, "prompt_blk")) { c->prompt_blk = value != 0; return 0; }
     if (!strcmp(name, "xs16")) {          // batch 3-16 decode family (xs16.hip) on / off; a captured step graph of the other family is dropped
         c->xs16 = value != 0;
+        if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; c->gkey = GraphKey(); }
+        return 0;
+    }
+    if (!strcmp(name, "wcode")) {         // the batch <= 2 step's GEMVs and chained launches on the coded bf16 weights (on) or on the raw packed ones (the A/B leg); same bits either way
+        c->wcode = value != 0;
         if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; c->gkey = GraphKey(); }
         return 0;
     }

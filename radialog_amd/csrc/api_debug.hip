@@ -85,6 +85,7 @@ extern "C" int rdx_gemv_trace(rdx_ctx* c, int what, int layer, long long* host, 
     if (what != 1 && what != 2) { a.out = c->dqkv; a.resid = nullptr; a.ldr = 0; }      // down_proj alone: into a scratch buffer, no residual (dx stays as it is)
     if ((a.N + 15) / 16 > max_tiles) { hipFree(dtr); return fail(c, -1, "rdx_gemv_trace: need room for %d tiles", (a.N + 15) / 16); }
     a.trace = dtr;
+    if (what == 1) a = coded_unit(c, a, L.wgu, B);                    // as the step launches them: on the coded bf16 copy where it streams one
     skinny(c, a, what == 1 ? EPI_SILU_MUL : EPI_NONE);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(host, dtr, bytes, hipMemcpyDeviceToHost);
@@ -257,13 +258,29 @@ static int fp8_block_for_test(rdx_ctx* c, GemmArgs& a, int epi, char** tmp) {
 extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const float* bias, const void* resid, void* out,
                              int M, int N, int K, int epi, const void* norm_w, float eps, int force) {
     if (!c || !X || !W || !out) return fail(c, -1, "rdx_gemm_test: null argument");
-    if (K % 32 || N % 16) return fail(c, -1, "rdx_gemm_test: need K %% 32 == 0 and N %% 16 == 0");
+    // the GEMV forces (1, 12) pad N to whole 16-row tiles themselves (zero rows, as the engine's loader does); every other kernel needs N % 16 == 0
+    const bool gemv = force == 1 || force == 12;
+    if (K % 32 || (N % 16 && !gemv) || N <= 0) return fail(c, -1, "rdx_gemm_test: need K %% 32 == 0 and N %% 16 == 0");
     HIPCHK(c, hipSetDevice(c->device));
     GemmW w;
-    w.N = N; w.K = K; w.Npad = N;
+    w.N = N; w.K = K; w.Npad = (N + 15) / 16 * 16;
     void* wp = nullptr;
-    HIPCHK(c, hipMalloc(&wp, (size_t)N * K * 2 + ((force == 4 || (force >= 9 && force <= 11)) ? (size_t)N * K + (size_t)N * 4 : 0)));
+    HIPCHK(c, hipMalloc(&wp, (size_t)w.Npad * K * 2 + ((force == 4 || (force >= 9 && force <= 11)) ? (size_t)N * K + (size_t)N * 4 : 0)));
     w.w = wp;
+    struct Coded {          // force 12: the coded bf16 copy the hook encodes itself, freed on every return path
+        void* planes = nullptr; unsigned* hdr = nullptr;
+        ~Coded() { if (planes) hipFree(planes); if (hdr) hipFree(hdr); }
+    } coded;
+    if (force == 12) {
+        if (c->cfg.dtype != DT_BF16 || K % WC_CHUNK_K || M >= xs_min_rows() || !skinny_fits_lds(M, K)) {
+            hipFree(wp);
+            return fail(c, -1, "rdx_gemm_test: force 12 (coded bf16 weights) needs a bf16 context, K %% 128 == 0 and M <= 2 rows that fit the GEMV's LDS stage");
+        }
+        if (hipMalloc(&coded.planes, wc_bytes(w.Npad, K)) != hipSuccess || hipMalloc((void**)&coded.hdr, (size_t)(w.Npad / 16) * sizeof(unsigned)) != hipSuccess) {
+            hipFree(wp);
+            return fail(c, -2, "rdx_gemm_test: out of device memory");
+        }
+    }
     if (force >= 9 && force <= 11) {
         // the fp8 path's prefill GEMM (gemm8.hip): e4m3 weights x e4m3 activations with 1 / 2 / 4 K groups; RMSNorm -> fp8 (one group) or quant_rows_k
         const int G = force == 9 ? 1 : (force == 10 ? 2 : 4);
@@ -296,10 +313,17 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
         launch_pack_weight_fp8(c->cfg.dtype, W, w.w8, w.scale, nullptr, N, K, N, c->stream);
         force = 1;
     } else
-    launch_pack_weight(c->cfg.dtype, W, wp, N, K, N, nullptr, c->stream);
+    launch_pack_weight(c->cfg.dtype, W, wp, N, K, w.Npad, nullptr, c->stream);
     GemmArgs a = gargs(X, K, w, bias, out, epi == EPI_SILU_MUL ? N / 2 : N, M);
     a.resid = resid; a.ldr = N;
     a.norm_w = norm_w; a.eps = eps;
+    if (force == 12) {      // the skinny GEMV on the coded copy of the packed buffer (what rdx_finalize_weights builds for the batch <= 2 step)
+        launch_encode_wc(wp, coded.planes, coded.hdr, w.Npad, K, c->stream);
+        a.WC = coded.planes; a.wchdr = coded.hdr;
+        // the epilogue as given: what is not a coded epilogue (6, relu(+resid), among them) is refused, not mapped onto one that is
+        if (epi == EPI_LOGITS || !skinny_wc_supported(c->cfg.dtype, a, epi)) { hipFree(wp); return fail(c, -1, "rdx_gemm_test: force 12: no coded GEMV for epilogue %d", epi); }
+        force = 1;
+    }
     void* xn = nullptr;
     bool split8 = false;
     if (force == 6) {       // force 5 with fp8 weights
@@ -397,13 +421,19 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
 extern "C" int rdx_logits_test(rdx_ctx* c, const void* X, const float* W, int M, int N, int n_valid, int K, void* out_logits,
                                int32_t* argmax_host, int fp8) {
     if (!c || !X || !W || !out_logits || !argmax_host) return fail(c, -1, "rdx_logits_test: null argument");
+    const bool coded = fp8 == 2;          // 2: the GEMV on the coded bf16 copy of W (as rdx_gemm_test force 12)
+    if (coded) fp8 = 0;
     if (K % 32 || N % 16 || M > 32 || n_valid > N || (fp8 && K % 64)) return fail(c, -1, "rdx_logits_test: bad shape");
+    if (coded && (c->cfg.dtype != DT_BF16 || K % WC_CHUNK_K || M >= xs_min_rows() || !skinny_fits_lds(M, K)))
+        return fail(c, -1, "rdx_logits_test: coded bf16 weights need a bf16 context, K %% 128 == 0 and M <= 2 rows that fit the GEMV's LDS stage");
     HIPCHK(c, hipSetDevice(c->device));
     GemmW w;
     w.N = N; w.K = K; w.Npad = N;
     const int nt = N / 16;
     char* wp = nullptr;
-    const size_t wb = (size_t)N * K * 2, qb = fp8 ? (size_t)N * K + (size_t)N * 4 : 0, pb = (size_t)M * nt * 4;
+    // qb: the fp8 copy and its scales, or the coded copy's planes (16-byte aligned behind wb) and header words
+    const size_t cpb = coded ? wc_bytes(N, K) : 0;
+    const size_t wb = (size_t)N * K * 2, qb = fp8 ? (size_t)N * K + (size_t)N * 4 : cpb + (coded ? (size_t)nt * 4 : 0), pb = (size_t)M * nt * 4;
     HIPCHK(c, hipMalloc((void**)&wp, wb + qb + 2 * pb + (size_t)M * K * 2));
     w.w = wp;
     if (fp8) {
@@ -415,6 +445,10 @@ extern "C" int rdx_logits_test(rdx_ctx* c, const void* X, const float* W, int M,
     GemmArgs a = gargs(X, K, w, nullptr, out_logits, N, M);
     a.n_valid = n_valid;
     a.part_val = (float*)(wp + wb + qb); a.part_idx = (int*)(wp + wb + qb + pb);
+    if (coded) {
+        launch_encode_wc(wp, wp + wb, (unsigned*)(wp + wb + cpb), N, K, c->stream);
+        a.WC = wp + wb; a.wchdr = (const unsigned*)(wp + wb + cpb);
+    }
     char* blk = nullptr;
     int brc = fp8_block_for_test(c, a, EPI_LOGITS, &blk);
     if (brc) { hipFree(wp); return brc; }

@@ -350,3 +350,36 @@ extern "C" int rdx_sample_u24_host(uint64_t seed, uint32_t row, uint32_t draw, u
     *out = sample_u24(seed, row, draw);
     return 0;
 }
+
+extern "C" int rdx_wcode_test(rdx_ctx* c, const float* W, int N, int K, void* packed_out, void* planes_out, uint32_t* hdr_out) {
+    if (!c || !W || !packed_out || !planes_out || !hdr_out || N <= 0 || K <= 0) return fail(c, -1, "rdx_wcode_test: bad arguments");
+    if (c->cfg.dtype != DT_BF16 || K % WC_CHUNK_K) return fail(c, -1, "rdx_wcode_test: coded weights need a bf16 context and K %% 128 == 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int npad = (N + 15) / 16 * 16;
+    launch_pack_weight(c->cfg.dtype, W, packed_out, N, K, npad, nullptr, c->stream);
+    launch_encode_wc(packed_out, planes_out, hdr_out, npad, K, c->stream);
+    return finish(c);
+}
+
+extern "C" int rdx_wcode_stats(rdx_ctx* c, long long* out) {
+    if (!c || !out || !c->finalized) return fail(c, -1, "rdx_wcode_stats: a finalized context and an output are needed");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out[0] = out[1] = out[2] = 0;
+    out[3] = c->n_wc_gemv; out[4] = c->n_wc_chain;
+    std::vector<const GemmW*> ws;
+    if (c->cfg.enable_llama) {
+        ws.push_back(&c->lm_head);
+        for (const LlamaLayer& L : c->ll) { ws.push_back(&L.wqkv); ws.push_back(&L.wo); ws.push_back(&L.wgu); ws.push_back(&L.wdown); }
+    }
+    for (const GemmW* W : ws) {
+        if (!W->wc || !W->wch) continue;
+        const int nt = W->Npad / 16;
+        std::vector<unsigned> h(nt);
+        HIPCHK(c, hipMemcpy(h.data(), W->wch, (size_t)nt * sizeof(unsigned), hipMemcpyDeviceToHost));
+        out[0] += nt;
+        for (unsigned v : h) out[1] += (v >> 8) & 1u;
+        out[2] += (long long)wc_bytes(W->Npad, W->K) + (long long)nt * 4;
+    }
+    return 0;
+}

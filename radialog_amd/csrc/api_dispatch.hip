@@ -51,6 +51,13 @@ GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     return a;
 }
 
+// The coded bf16 copy of a unit's weight (GemmW::wc) instead of the raw packed one: only where the step runs the batch <= 2 chained family, the option is
+// on and the copy exists (bf16, model-dtype weights: api.hip rdx_finalize_weights). Everything else -- and every tile flagged in the header -- reads a.W.
+GemmArgs coded_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B) {
+    if (c->wcode && W.wc && W.wch && decode_family(c, B) == DEC_CHAINED) { a.WC = W.wc; a.wchdr = W.wch; }
+    return a;
+}
+
 GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     GemmArgs a = unit_args(c, L, u, B);
     if (u == UNIT_GATE_UP) a.out_packed = ACT_BLK32;
@@ -136,6 +143,7 @@ void skinny(rdx_ctx* c, GemmArgs a, int epi) {
             return;
         }
     }
+    if (skinny_wc_supported(c->cfg.dtype, a, epi) && !xstat32_supported(a, epi)) ++c->n_wc_gemv;       // launch_skinny_gemm's own choice, counted for the tests
     launch_skinny_gemm(c->cfg.dtype, a, epi, c->stream);
 }
 

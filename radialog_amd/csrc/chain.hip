@@ -47,10 +47,13 @@ struct ChainGemm {
     const float* wscale;                          // fp8 weights: per-row scale, see skinny_body.h
 };
 
-template <typename WaitFn> struct ChainLate { ChainGemm a; WaitFn wait; long long* trace; };   // what `late()` hands chain_tile behind the ring
+// what `late()` hands chain_tile behind the ring. wraw / wchdr: a WC instantiation's raw packed weight (what a flagged tile streams) and header words
+template <typename WaitFn> struct ChainLate { ChainGemm a; WaitFn wait; long long* trace; const void* wraw = nullptr; const unsigned* wchdr = nullptr; };
 
 // Wb, K, wg, ntiles: from preloaded kernel arguments. late(): the rest (ChainLate), built from kernel arguments that are loaded only now (late_kernarg)
-template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false, typename Late>
+// WC: Wb is the coded bf16 copy of the weight (rdx_common.h WcChunk): the ring holds U / 2 coded chunks (the 2 U packed chunks of the raw ring at 13/16 of
+// the bytes), decoded in registers into the fragments the raw ring holds, in the same order: the sums do not change. As skinny_body.h.
+template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false, bool WC = false, typename Late>
 __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const int K, const int wg, const int ntiles, unsigned char* smem, Late late) {
     typedef typename Vec8<T>::type V8;
     constexpr int WPS = CH_WAVES / SUB;           // waves per tile
@@ -69,6 +72,13 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
     const int c0 = (KC * w) / WPS, c1 = (KC * (w + 1)) / WPS;
     const u4* wbase = reinterpret_cast<const u4*>(Wb) + (size_t)tile_c * KC * 64 + lane;
     const int clast = min(max(c1 - 1, c0), KC - 1);
+    // WC: the slice stays [c0, c1) in PACKED chunks; the coded chunks [q0, q1) cover it, the first and the last may reach into the neighbours' (down_proj:
+    // 344 chunks over 16 waves), whose fragments multiply the zero line behind the staged rows
+    static_assert(!WC || (!W8 && U % 2 == 0), "coded weights: model dtype");
+    constexpr int RC = U / 2;
+    const int KQ = K >> 7, q0 = c0 >> 2, q1 = c1 > c0 ? (c1 + 3) >> 2 : q0, qlast = min(max(q1 - 1, q0), KQ - 1);
+    const unsigned char* cb16 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile_c * KQ * WC_CHUNK_BYTES + lane * 16;
+    const unsigned char* cb4 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile_c * KQ * WC_CHUNK_BYTES + 3072 + lane * 4;
     // Everything up to here comes from preloaded kernel arguments, the workgroup id and the lane id: the ring below is issued with no scalar load
     // in front of it. The entry time is taken unconditionally (one scalar instruction, nothing waits for it before the ring is out) because the
     // trace pointer is one of the arguments that are only loaded behind the ring.
@@ -77,15 +87,23 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
     // two register batches (A, B) in flight before anything else; the main loop ping-pongs between them (no register
     // rotation: a rotated pair makes the compiler wait for the batch it has just issued)
     u4 wa_[U], wb_[U];
+    WcChunk cring[RC];
+    if constexpr (WC) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) wa_[u] = ldg16_nt(wbase + (size_t)min(c0 + u, clast) * 64);
+        for (int u = 0; u < RC; ++u) { const size_t o = (size_t)min(q0 + u, qlast) * WC_CHUNK_BYTES; cring[u] = wc_load(cb16 + o, cb4 + o); }
+    } else {
 #pragma unroll
-    for (int u = 0; u < U; ++u) wb_[u] = ldg16_nt(wbase + (size_t)min(c0 + U + u, clast) * 64);
+        for (int u = 0; u < U; ++u) wa_[u] = ldg16_nt(wbase + (size_t)min(c0 + u, clast) * 64);
+#pragma unroll
+        for (int u = 0; u < U; ++u) wb_[u] = ldg16_nt(wbase + (size_t)min(c0 + U + u, clast) * 64);
+    }
     __builtin_amdgcn_sched_barrier(0);            // nothing of what follows is scheduled in front of the ring
     const ChainLate<WaitFn> lt = late();
     const ChainGemm& a = lt.a;
     const WaitFn& wait_inputs = lt.wait;
     long long* const trace = lt.trace;
+    unsigned wc_hdr = 0;          // the tile's header word: a scalar load (constant address space) behind the ring, see skinny_body.h
+    if constexpr (WC) wc_hdr = *(reinterpret_cast<const __attribute__((address_space(4))) unsigned*>((uintptr_t)lt.wchdr) + tile_c);
     // debug timeline of this workgroup (rdx_gemv_trace 7; null in every product launch), 100 MHz ticks, wave 0: [0] entry, [5] first weight KiB
     // back, [3] inputs ready, [6] first MFMA (row staged), [1] K loop done, [7] end; [2] = arrival, written by the down_proj role's caller
     const T* X = reinterpret_cast<const T*>(a.X);
@@ -93,7 +111,7 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
 #define CH_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
     if (trc) trc[0] = t_entry;
     if (trace) {        // traced launches only: wave 0 watches its first KiB come back (it stalls here, which a product launch never does)
-        if (threadIdx.x < 64) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * U - 1) : "memory");
+        if (threadIdx.x < 64) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(WC ? 4 * RC - 1 : 2 * U - 1) : "memory");
         CH_T(5);
     }
 
@@ -177,6 +195,7 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
                 *reinterpret_cast<unsigned long long*>(xs + (size_t)m * K + (size_t)k4 * 4) = v;
             }
         }
+        if (WC && threadIdx.x == 0) *reinterpret_cast<u4*>(xs + (size_t)a.M * K) = (u4){0u, 0u, 0u, 0u};     // the zero line (launchers reserve it)
         __syncthreads();
     }
 
@@ -224,18 +243,73 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             acc = mfma16(as_vec8<T>(wv), as_vec8<T>(xv), acc);
         }
     };
-    int cb = c0;
-    for (; cb + 2 * U < c1; cb += 2 * U) {
+    if constexpr (WC) {
+        if (wc_hdr & 0x100u) {
+            // a tile the code cannot express (wave-uniform, once per tile): the coded ring is dropped and the raw loop runs on the packed copy, in four
+            // of the ring's registers (a rare path; registers of its own would be carried through it)
+            const u4* wraw = reinterpret_cast<const u4*>(lt.wraw) + (size_t)tile_c * KC * 64 + lane;
+            auto slot = [&](int u) -> u4& { return u == 0 ? cring[0].lo0 : u == 1 ? cring[0].lo1 : u == 2 ? cring[0].ix : cring[1].lo0; };
 #pragma unroll
-        for (int u = 0; u < 2 * U; ++u) {
-            u4& wr = u < U ? wa_[u] : wb_[u - U];
-            consume1(wr, cb + u);
-            wr = ldg16_nt(wbase + (size_t)min(cb + 2 * U + u, clast) * 64);
-            __builtin_amdgcn_sched_barrier(0);
+            for (int u = 0; u < 4; ++u) slot(u) = ldg16_nt(wraw + (size_t)min(c0 + u, clast) * 64);
+            int cb = c0;
+            for (; cb + 4 < c1; cb += 4) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    consume1(slot(u), cb + u);
+                    slot(u) = ldg16_nt(wraw + (size_t)min(cb + 4 + u, clast) * 64);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if (cb + u < c1) consume1(slot(u), cb + u);
+        } else {
+            const unsigned base4 = (wc_hdr & 0xffu) * 0x01010101u;
+            const T* zptr = xs + (size_t)a.M * K;
+            // guard (first trip and tail only): fragments outside [c0, c1) read the zero line. Exact because (1) every weight of an unflagged tile is
+            // finite, so the products are zeros; (2) the fp32 accumulator starts at +0 and a sum is -0 only if all its terms are, so it is never -0 and
+            // x + (+-0) = x leaves its bits alone; (3) an MFMA whose 32 products are all zero returns its accumulator operand.
+            auto consumeC = [&](const WcChunk& ch, int q, bool guard) {
+                auto one = [&](const u4 wd, int c) {
+                    const T* xp = (!guard || (c >= c0 && c < c1)) ? xrow + (size_t)c * 32 : zptr;
+                    acc = mfma16(as_vec8<T>(wd), as_vec8<T>(*reinterpret_cast<const u4*>(xp)), acc);
+                    // one fragment at a time. Without this barrier the compiler interleaves the four decodes of a chunk with the refill and waits
+                    // vmcnt(0) once per trip: the ring drains (tests/test_isa_wcode.py)
+                    __builtin_amdgcn_sched_barrier(0);
+                };
+                one(wc_frag<0>(ch, base4), 4 * q); one(wc_frag<1>(ch, base4), 4 * q + 1);
+                one(wc_frag<2>(ch, base4), 4 * q + 2); one(wc_frag<3>(ch, base4), 4 * q + 3);
+            };
+            auto trip = [&](int q, bool guard) {
+#pragma unroll
+                for (int u = 0; u < RC; ++u) {
+                    consumeC(cring[u], q + u, guard);
+                    const size_t o = (size_t)min(q + RC + u, qlast) * WC_CHUNK_BYTES;
+                    cring[u] = wc_load(cb16 + o, cb4 + o);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            };
+            int q = q0;
+            if (q + RC < q1) { trip(q, true); q += RC; }
+            for (; q + RC < q1; q += RC) trip(q, false);
+#pragma unroll
+            for (int u = 0; u < RC; ++u)
+                if (q + u < q1) consumeC(cring[u], q + u, true);
         }
+    } else {
+        int cb = c0;
+        for (; cb + 2 * U < c1; cb += 2 * U) {
+    #pragma unroll
+            for (int u = 0; u < 2 * U; ++u) {
+                u4& wr = u < U ? wa_[u] : wb_[u - U];
+                consume1(wr, cb + u);
+                wr = ldg16_nt(wbase + (size_t)min(cb + 2 * U + u, clast) * 64);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+        consume(wa_, cb, true);
+        consume(wb_, cb + U, true);
     }
-    consume(wa_, cb, true);
-    consume(wb_, cb + U, true);
     CH_T(1);
     // D[n_local = g*4+reg][m_local = r] -> red[wave][m_local*16 + n_local]
     *reinterpret_cast<float4*>(&red[wa * 256 + r * 16 + g * 4]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -322,6 +396,33 @@ __global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_k(const void* wdow
     });
 }
 
+// The same launch on coded bf16 weights (chain_tile WC; a kernel name of its own): the leading weight arguments are the coded planes of down_proj(layer)
+// and QKV(layer + 1); the raw packed copies (what a flagged tile streams) and the header words travel in ChainArgs and are read behind the rings. The
+// QKV role's ring is four coded chunks (the raw role's sixteen fragments), down_proj's two.
+__global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_wc_k(const void* cdown, const void* cqkv, int hidden, int inter, int qkv_n, int nwg_down, ChainArgs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
+    typedef bf16 T;
+    const int H = hidden;
+    auto args = [] { return late_kernarg<ChainArgs>(kernarg_offset<6>(decltype(&decode_chain_wc_k){})); };      // argument 6: the ChainArgs
+    if ((int)blockIdx.x < nwg_down) {
+        const ChainLate<WaitSharded> lt = chain_tile<T, EPI_RESID, false, 1, 6, WaitSharded, 4, false, false, true>(cdown, inter, blockIdx.x, nwg_down, msm, [&] {
+            const ChainArgs ca = args();
+            int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
+            return ChainLate<WaitSharded>{ChainGemm{ca.dgu, inter, ca.dx, H, ca.dx, H, ca.B, H, nullptr, 0.f, nullptr},
+                                          WaitSharded{ctr, 0, ca.err, ca.naps, nullptr}, ca.trace ? ca.trace + (size_t)blockIdx.x * 8 : nullptr, ca.wdown, ca.hdown};
+        });
+        publish_sc1(lt.wait.ctr, blockIdx.x);
+        if (lt.trace && threadIdx.x == 0) lt.trace[2] = (long long)__builtin_amdgcn_s_memrealtime();      // arrival
+        return;
+    }
+    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, 8, false, false, true>(cqkv, H, blockIdx.x - nwg_down, (qkv_n + 15) / 16, msm, [&] {
+        const ChainArgs ca = args();
+        int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
+        return ChainLate<WaitSharded>{ChainGemm{ca.dx, H, nullptr, 0, ca.dqkv, ca.qkv_ld, ca.B, qkv_n, ca.attn_norm, ca.eps, nullptr},
+                                      WaitSharded{ctr, nwg_down, ca.err, ca.naps, nullptr}, ca.trace ? ca.trace + (size_t)blockIdx.x * 8 : nullptr, ca.wqkv, ca.hqkv};
+    });
+}
+
 // ---- decode attention + o_proj(+residual) in ONE launch, 16-wave workgroups -------------------------------------------------
 // Workgroups [0, heads*B): attention exactly as the stand-alone latency kernel (wave 0 = new token, 15 cache waves),
 // output stored write-through as tagged granules. Workgroups [heads*B, +ntiles/2): two o_proj tiles each (8 waves per tile), whose WHOLE
@@ -403,7 +504,7 @@ void launch_decode_chain(int dtype, ChainArgs ca, bool with_next_qkv, hipStream_
     const int nwg_down = ca.hidden / 16;
     const int nwg_qkv = with_next_qkv ? ((ca.qkv_n + 15) / 16 + 3) / 4 : 0;
     const int kmax = ca.inter > ca.hidden ? ca.inter : ca.hidden;
-    const size_t sm_gemm = (size_t)(CH_WAVES * 256 + CH_WAVES * CH_MAXM + 16) * 4 + (size_t)ca.B * kmax * 2;
+    const size_t sm_gemm = (size_t)(CH_WAVES * 256 + CH_WAVES * CH_MAXM + 16) * 4 + (size_t)ca.B * kmax * 2 + 16;      // + the coded kernel's zero line
     // ONE workgroup per CU: the register budget alone (<= 128 VGPRs) would admit two, so reserve more than half of the LDS
     const size_t smem = sm_gemm > (size_t)84 * 1024 ? sm_gemm : (size_t)84 * 1024;
     dim3 grid(nwg_down + nwg_qkv), block(CH_THREADS);
@@ -413,7 +514,11 @@ void launch_decode_chain(int dtype, ChainArgs ca, bool with_next_qkv, hipStream_
             hipFuncSetAttribute((const void*)decode_chain_k<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
             hipFuncSetAttribute((const void*)decode_chain_k<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
         }
-        if (ca.w8) hipLaunchKernelGGL((decode_chain_k<T, true>), grid, block, smem, s, ca.wdown8, ca.wqkv8, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
+        if (ca.wc && dtype == DT_BF16 && !ca.w8) {        // coded bf16 weights (api_llama.hip sets wc only where every copy of the launch exists)
+            static DevOnce wc_attr_set;
+            if (wc_attr_set.first()) hipFuncSetAttribute((const void*)decode_chain_wc_k, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
+            hipLaunchKernelGGL(decode_chain_wc_k, grid, block, smem, s, ca.cdown, with_next_qkv ? ca.cqkv : ca.cdown, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
+        } else if (ca.w8) hipLaunchKernelGGL((decode_chain_k<T, true>), grid, block, smem, s, ca.wdown8, ca.wqkv8, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
         else hipLaunchKernelGGL((decode_chain_k<T, false>), grid, block, smem, s, ca.wdown, ca.wqkv, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
     });
 }

@@ -112,6 +112,65 @@ void launch_pack_weight_fp8(int dtype, const float* src, void* dst8, float* scal
                                                 scale, (T*)dst, N, K, Npad));
 }
 
+// coded bf16 weights (rdx_common.h WcChunk; radialog_amd/wcode.py is the definition): one workgroup per 16-row tile of the PACKED buffer -- what
+// the GEMV streams, after every fusion and interleave of the loader. Pass 1: the largest h = (e7..e1) of the tile and whether any weight is Inf / NaN
+// (h = 127); base = max(top - 15, 0), so indices 1..15 name h = base + 1 .. base + 15 and index 0 names h = 0 (zero, subnormals, the binade above
+// them). Pass 2: the planes, and the raw flag for a tile that holds a weight with 0 < h <= base or h = 127. A flagged tile's planes are written all
+// the same (the kernels' first loads are unconditional), its out-of-window indices as 0.
+__global__ __launch_bounds__(256) void encode_wc_k(const u4* __restrict__ packed, unsigned char* __restrict__ planes, unsigned* __restrict__ hdr, int K) {
+    __shared__ int s_top, s_raw;
+    const int tile = blockIdx.x, KC = K >> 5, KQ = K >> 7, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    if (threadIdx.x == 0) { s_top = 0; s_raw = 0; }
+    __syncthreads();
+    const u4* src = packed + (size_t)tile * KC * 64;
+    int top = 0, bad = 0;
+    for (int i = threadIdx.x; i < KC * 64; i += 256) {
+        const u4 v = src[i];
+#pragma unroll
+        for (int d = 0; d < 4; ++d)
+#pragma unroll
+            for (int hlf = 0; hlf < 2; ++hlf) {
+                const int h = (int)((v[d] >> (16 * hlf + 8)) & 0x7fu);
+                if (h == 127) bad = 1; else top = max(top, h);
+            }
+    }
+    atomicMax(&s_top, top);
+    if (bad) atomicOr(&s_raw, 1);
+    __syncthreads();
+    const int base = max(s_top - 15, 0);
+    for (int q = wv; q < KQ; q += 4) {
+        unsigned lo[8], ix[4], sg = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const u4 v = src[(size_t)(4 * q + j) * 64 + lane];
+            unsigned l0 = 0, l1 = 0, n = 0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const unsigned wbits = (v[e >> 1] >> (16 * (e & 1))) & 0xffffu;
+                const int h = (int)((wbits >> 8) & 0x7fu);
+                int idx = h ? h - base : 0;
+                if (h && (idx < 1 || idx > 15)) { bad = 1; idx = 0; }
+                if (e < 4) l0 |= (wbits & 0xffu) << (8 * e); else l1 |= (wbits & 0xffu) << (8 * (e - 4));
+                n |= (unsigned)idx << (4 * (e < 4 ? 2 * e : 2 * (e - 4) + 1));
+                sg |= (wbits >> 15) << ((2 * j + (e >> 2)) + 8 * (e & 3));
+            }
+            lo[2 * j] = l0; lo[2 * j + 1] = l1; ix[j] = n;
+        }
+        unsigned char* p = planes + ((size_t)tile * KQ + q) * WC_CHUNK_BYTES;
+        reinterpret_cast<u4*>(p)[lane] = (u4){lo[0], lo[1], lo[2], lo[3]};
+        reinterpret_cast<u4*>(p + 1024)[lane] = (u4){lo[4], lo[5], lo[6], lo[7]};
+        reinterpret_cast<u4*>(p + 2048)[lane] = (u4){ix[0], ix[1], ix[2], ix[3]};
+        reinterpret_cast<unsigned*>(p + 3072)[lane] = sg;
+    }
+    if (bad) atomicOr(&s_raw, 1);
+    __syncthreads();
+    if (threadIdx.x == 0) hdr[tile] = (unsigned)base | (s_raw ? 0x100u : 0u);
+}
+
+void launch_encode_wc(const void* packed, void* planes, unsigned* hdr, int npad, int K, hipStream_t s) {
+    hipLaunchKernelGGL(encode_wc_k, dim3(npad / 16), dim3(256), 0, s, (const u4*)packed, (unsigned char*)planes, hdr, K);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // skinny GEMM (body in skinny_body.h)
 // ------------------------------------------------------------------------------------------------------------------
@@ -126,6 +185,39 @@ __global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 8 : 1) void skinny_gemm_k(
         a.X = X; a.K = K; a.N = N;
         return a;
     });
+}
+
+// The same GEMV on coded bf16 weights (skinny_body.h WC): a kernel name of its own. Leading arguments (8 dwords): the coded planes, X, K, N and the
+// header words -- the ring is addressed from the first four alone, the tile's header is a scalar load behind it. GemmArgs::W stays the raw packed copy.
+template <int EPI, bool NORM, int WAVES>
+__global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 8 : 1) void skinny_gemm_wc_k(const void* Wc, const void* X, int K, int N, const unsigned* hdr, GemmArgs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
+    skinny_tile<bf16, 1, EPI, NORM, WAVES, true, NoWait, false, false, true>(Wc, K, blockIdx.x, (N + 15) / 16, dyn_smem, NoWait(), [&] {
+        constexpr unsigned off = kernarg_offset<5>(decltype(&skinny_gemm_wc_k<EPI, NORM, WAVES>){});      // argument 5: the GemmArgs
+        GemmArgs a = late_kernarg<GemmArgs>(off);
+        a.X = X; a.K = K; a.N = N;
+        return a;
+    }, hdr);
+}
+
+template <bool NORM, int WAVES>
+static void launch_skinny_wc(const GemmArgs& a, int epi, hipStream_t s) {
+    dim3 grid((a.N + 15) / 16), block(WAVES * 64);
+    const size_t dyn = (size_t)a.M * a.K * 2 + 16;        // the staged rows + the zero line
+#define RDX_SKC(E) hipLaunchKernelGGL((skinny_gemm_wc_k<E, NORM, WAVES>), grid, block, dyn, s, a.WC, a.X, a.K, a.N, a.wchdr, a)
+    switch (epi) {
+        case EPI_NONE: RDX_SKC(EPI_NONE); break;
+        case EPI_RESID: RDX_SKC(EPI_RESID); break;
+        case EPI_SILU_MUL: RDX_SKC(EPI_SILU_MUL); break;
+        case EPI_LOGITS: RDX_SKC(EPI_LOGITS); break;
+        default: break;
+    }
+#undef RDX_SKC
+}
+
+bool skinny_wc_supported(int dtype, const GemmArgs& a, int epi) {
+    return dtype == DT_BF16 && a.WC && a.wchdr && a.W && skinny_fits_lds(a.M, a.K) && a.K % WC_CHUNK_K == 0 && a.M < xs_min_rows() &&
+           (epi == EPI_NONE || epi == EPI_RESID || epi == EPI_SILU_MUL || epi == EPI_LOGITS);
 }
 
 template <typename T, int MT, bool NORM, int WAVES, bool XLDS, bool W8 = false>
@@ -149,6 +241,18 @@ static void launch_skinny_epi(const GemmArgs& a, int epi, hipStream_t s) {
 // activations fit the LDS staging path when M*K*2 bytes <= 32 KiB (keeps >= 2 workgroups per CU resident)
 bool skinny_fits_lds(int M, int K) { return M <= 16 && (size_t)M * K * 2 <= 32 * 1024; }
 
+// Waves per tile of the LDS-staged GEMV -- ONE choice for the raw and the coded kernels: the K split over the waves is part of the sums, and the coded
+// form must reproduce the raw one bit for bit.
+//   16: few output tiles (at most one workgroup per CU) and a long K: twice as many weight loads in flight per CU
+//    4: many output tiles: 4-wave workgroups at <= 64 VGPRs keep up to 2048 tiles resident at once (8 per CU), ONE round of workgroups sharing HBM evenly
+//    8: everything else
+static int skinny_lds_waves(const GemmArgs& a) {
+    const int nt = (a.N + 15) / 16;
+    if (nt <= 256 && a.K >= 4096) return 16;
+    if (nt > 512 && (size_t)a.M * a.K * 2 <= 16 * 1024) return 4;
+    return 8;
+}
+
 template <typename T>
 static void launch_skinny_T(const GemmArgs& a, int epi, hipStream_t s) {
     const bool norm = a.norm_w != nullptr;
@@ -157,7 +261,8 @@ static void launch_skinny_T(const GemmArgs& a, int epi, hipStream_t s) {
     // weight loads in flight per CU
     constexpr bool wide = true;
     const bool w8 = a.W8 && a.wscale && skinny_fits_lds(a.M, a.K) && a.K % 64 == 0;   // fp8 weight stream (else: W, which only the test hooks provide)
-    if (wide && skinny_fits_lds(a.M, a.K) && (a.N + 15) / 16 <= 256 && a.K >= 4096) {
+    const int lds_waves = skinny_fits_lds(a.M, a.K) ? skinny_lds_waves(a) : 0;
+    if (wide && lds_waves == 16) {
         if (w8) { if (norm) launch_skinny_epi<T, 1, true, 16, true, true>(a, epi, s); else launch_skinny_epi<T, 1, false, 16, true, true>(a, epi, s); return; }
         if (norm) launch_skinny_epi<T, 1, true, 16, true>(a, epi, s); else launch_skinny_epi<T, 1, false, 16, true>(a, epi, s);
         return;
@@ -165,7 +270,7 @@ static void launch_skinny_T(const GemmArgs& a, int epi, hipStream_t s) {
     // many output tiles: 4-wave workgroups at <= 64 VGPRs keep up to 2048 tiles resident at once (8 per CU), so the
     // whole GEMV runs as ONE round of workgroups sharing HBM evenly instead of 2-4 quantised rounds
     constexpr bool smallwg = true;
-    if (smallwg && skinny_fits_lds(a.M, a.K) && (a.N + 15) / 16 > 512 && (size_t)a.M * a.K * 2 <= 16 * 1024) {
+    if (smallwg && lds_waves == 4) {
         if (w8) { if (norm) launch_skinny_epi<T, 1, true, 4, true, true>(a, epi, s); else launch_skinny_epi<T, 1, false, 4, true, true>(a, epi, s); return; }
         if (norm) launch_skinny_epi<T, 1, true, 4, true>(a, epi, s); else launch_skinny_epi<T, 1, false, 4, true>(a, epi, s);
         return;
@@ -183,6 +288,14 @@ static void launch_skinny_T(const GemmArgs& a, int epi, hipStream_t s) {
 void launch_skinny_gemm(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
     // (fp8 weights: only with the e4m3 activation block, ACT_BLK64_E4M3 -- the batch >= 3 rule of the fp8 scheme; callers go through skinny())
     if (xstat32_supported(a, epi) && (!(a.W8 && a.wscale) || (a.xpacked == ACT_BLK64_E4M3 && a.xscale))) { launch_xstat32(dtype, a, epi, s); return; }
+    if (skinny_wc_supported(dtype, a, epi)) {       // coded weights: the wave counts of launch_skinny_T (the K split is part of the sums)
+        const bool norm = a.norm_w != nullptr;
+        const int waves = skinny_lds_waves(a);
+        if (waves == 16) { if (norm) launch_skinny_wc<true, 16>(a, epi, s); else launch_skinny_wc<false, 16>(a, epi, s); }
+        else if (waves == 4) { if (norm) launch_skinny_wc<true, 4>(a, epi, s); else launch_skinny_wc<false, 4>(a, epi, s); }
+        else { if (norm) launch_skinny_wc<true, 8>(a, epi, s); else launch_skinny_wc<false, 8>(a, epi, s); }
+        return;
+    }
     RDX_DISPATCH_T(dtype, T, launch_skinny_T<T>(a, epi, s));
 }
 

@@ -91,6 +91,39 @@ template <> __device__ __forceinline__ u4 dequant8<f16>(unsigned lo, unsigned hi
                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(c[0], c[1])), __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(d[0], d[1]))};
 }
 
+// ---- coded bf16 weights ("WC", 13 bits per weight, exact; the format's definition is radialog_amd/wcode.py) ------------------------------
+// A coded chunk is 128 k-values of one 16-row tile = four of the packed 32-k chunks, WC_CHUNK_BYTES bytes in three planes, each a run of whole-wave
+// contiguous loads: [lo0: 64 lanes x 16 B][lo1: 64 x 16 B][idx: 64 x 16 B][sign: 64 x 4 B]. Lane (g, r) holds the 32 weights of ITS four MFMA A
+// fragments j = 0..3 (fragment j = the lane's 16 bytes of packed chunk 4 q + j), weight e = 0..7 of fragment j:
+//   low byte (e0 m6..m0), verbatim: byte 8 (j & 1) + e of lo0 (j < 2) or lo1;
+//   4-bit index: dword j of the idx plane, nibble 2 e (e < 4) or 2 (e - 4) + 1 -- so the even nibbles are weights 0..3 and the odd ones 4..7;
+//   sign: bit (2 j + e / 4) + 8 (e % 4) of the sign dword.
+// The high byte is sign << 7 | h with h = (e7..e1) = 0 for index 0 and base + index otherwise; base comes from the tile's header word
+// (bits 0..7; bit 8 = the tile is not expressible: the kernels read its raw packed copy instead).
+struct WcChunk { u4 lo0, lo1, ix; unsigned sg; };
+__device__ __forceinline__ unsigned ldg4_nt(const void* p) { return __builtin_nontemporal_load((const __attribute__((address_space(1))) unsigned*)p); }
+// p16 = the tile's coded base + lane * 16, p4 = + 3 KiB + lane * 4 (both advanced by q * WC_CHUNK_BYTES by the caller)
+__device__ __forceinline__ WcChunk wc_load(const unsigned char* p16, const unsigned char* p4) {
+    WcChunk c;
+    c.lo0 = ldg16_nt(p16); c.lo1 = ldg16_nt(p16 + 1024); c.ix = ldg16_nt(p16 + 2048); c.sg = ldg4_nt(p4);
+    return c;
+}
+// four high bytes from four index bytes (0..15 each): GI = 2 j + (weights 4..7 ? 1 : 0) selects their sign bits
+template <int GI> __device__ __forceinline__ unsigned wc_hi4(unsigned x, unsigned base4, unsigned sg) {
+    const unsigned m = (x + 0x7f7f7f7fu) & 0x80808080u;       // bit 7 of a byte: its index is not 0
+    const unsigned keep = m - (m >> 7);                        // 0x7f there, 0 where the index is 0
+    return ((x + base4) & keep) | ((sg << (7 - GI)) & 0x80808080u);
+}
+// fragment J (constant) of a chunk: the 16 bytes pack_weight_k wrote for this lane in packed chunk 4 q + J
+template <int J> __device__ __forceinline__ u4 wc_frag(const WcChunk& c, unsigned base4) {
+    const unsigned n = c.ix[J];
+    const u4& lo = J < 2 ? c.lo0 : c.lo1;
+    const unsigned l0 = lo[2 * (J & 1)], l1 = lo[2 * (J & 1) + 1];
+    const unsigned h0 = wc_hi4<2 * J>(n & 0x0f0f0f0fu, base4, c.sg), h1 = wc_hi4<2 * J + 1>((n >> 4) & 0x0f0f0f0fu, base4, c.sg);
+    return (u4){__builtin_amdgcn_perm(h0, l0, 0x05010400u), __builtin_amdgcn_perm(h0, l0, 0x07030602u),
+                __builtin_amdgcn_perm(h1, l1, 0x05010400u), __builtin_amdgcn_perm(h1, l1, 0x07030602u)};
+}
+
 // ---- model dtype -> fp8 (OCP e4m3) activation quantisation of the fp8 path: q = RNE_e4m3(x * (448 / absmax)), scale = absmax / 448 ----------
 // (the arithmetic of pack_weight_fp8_k and of the oracle's fake quantisation; an all-zero range gets scale 1)
 __device__ __forceinline__ void fp8_scale(float amax, float& sc, float& inv) {

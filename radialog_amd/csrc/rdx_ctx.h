@@ -22,7 +22,10 @@ using namespace rdx;
 // tile walker sharing an XCD's L2: xstat32_k / xsplit32_k<.., BLK>; fp8 weights: the 32-row fp8 kernels per block). 128 rows x 512 slots of KV = 68 GB of the 288.
 constexpr int RDX_MAX_ROWS = 128;
 
-struct GemmW { void* w = nullptr; int N = 0, K = 0, Npad = 0; void* w8 = nullptr; float* scale = nullptr; };   // w8/scale: fp8 copy
+struct GemmW {
+    void* w = nullptr; int N = 0, K = 0, Npad = 0; void* w8 = nullptr; float* scale = nullptr;   // w8/scale: fp8 copy
+    void* wc = nullptr; unsigned* wch = nullptr;     // coded bf16 copy of w (13 bits per weight, exact) and its per-tile header words: what the batch <= 2 GEMV streams
+};
 struct RawW { void* p = nullptr; int64_t rows = 0, cols = 0; };
 
 struct LlamaLayer {
@@ -105,7 +108,9 @@ struct rdx_ctx {
                                      // per layer); RDX_XS16=0 at create / rdx_set_option("xs16", 0): the 32-row family of xstat32.hip (7 launches; A/B leg of the tests)
     bool prompt_blk = true;          // one prompt's K = 4096 projections on xstat32_k<.., BLK> (RDX_PBLK=0 / rdx_set_option("prompt_blk", 0): wstat_k, the A/B leg)
     bool blk_down = true;            // 33-128 rows, model-dtype weights: down_proj K-split into fp32 slabs (xsplit32_k<.., BLK>); RDX_BLK_DOWN=0 at create: wstat_k, the A/B leg
-    int chain_naps = 1;              // poll back-off of the chained launch (x s_sleep(8) between polls)
+    bool wcode = true;               // batch <= 2 chained family, bf16: gate/up, down_proj, QKV and the lm_head stream their coded copy (GemmW::wc); rdx_set_option("wcode", 0): the raw one
+    long long n_wc_gemv = 0, n_wc_chain = 0;      // launches of skinny_gemm_wc_k / decode_chain_wc_k issued by this context (a captured graph counts once): rdx_wcode_stats
+    int chain_naps = 1;             // poll back-off of the chained launch (x s_sleep(8) between polls)
     long long* chain_trace = nullptr; int chain_trace_layer = -1;     // rdx_gemv_trace(7): device timeline buffer of ONE chained launch of the next step
     long long* ao_trace = nullptr; int ao_trace_layer = -1;           // rdx_gemv_trace(8): the same for ONE fused attention + o_proj launch
     GemmW cls_fc1, cls_fc2; const float *cls_fc1_b = nullptr, *cls_fc2_b = nullptr;   // findings classifier head
@@ -200,6 +205,7 @@ AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer);      
 // down_proj as its epilogue. L may be null for UNIT_LM_HEAD, whose callers set X (when not dx), out and out_step.
 GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);
 // ... and in the layout of a family (what its probe checks IS what its step function launches):
+GemmArgs coded_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B);         // batch <= 2 chained family, "wcode" on: the GEMV streams W's coded bf16 copy
 GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);      // one row tile: gate/up writes, o_proj / down_proj read the fragment-packed block
 GemmArgs blk_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);       // row blocks: fragment-packed row tiles of 16 in and (gate/up) out
 GemmArgs blk8_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);      // ... fp8 weights: e4m3 blocks + xscale in; 64-deep model-dtype blocks into the K-split o_proj / down_proj

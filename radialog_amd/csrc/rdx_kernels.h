@@ -51,7 +51,18 @@ struct GemmArgs {
     // equal K ranges (1 behind an RMSNorm, 2 o_proj, 4 down_proj); see ActLayout
     const float* xscale; int xgroups;
     long long* trace;                // debug: [tile][8] timestamps (100 MHz ticks) written by thread 0 of every workgroup (skinny_tile)
+    // coded bf16 weights (rdx_common.h WcChunk): the planes of launch_encode_wc and one header word per tile; the batch <= 2 GEMV streams them
+    // instead of W (13 bits per weight, decoded exactly), W stays what the tiles flagged in their header read. Null: W is streamed.
+    const void* WC; const unsigned* wchdr;
 };
+
+// coded bf16 weights: 128 k-values per chunk; per (tile, chunk) three planes of whole-wave contiguous loads (rdx_common.h)
+constexpr int WC_CHUNK_K = 128, WC_CHUNK_BYTES = 64 * 52;
+inline size_t wc_bytes(int npad, int k) { return (size_t)(npad / 16) * (size_t)(k / WC_CHUNK_K) * WC_CHUNK_BYTES; }
+// bf16 only: reads the PACKED buffer of launch_pack_weight, writes the planes and hdr[npad / 16] = base | raw << 8; K % 128 == 0
+void launch_encode_wc(const void* packed, void* planes, unsigned* hdr, int npad, int K, hipStream_t s);
+// the batch <= 2 GEMV has a coded form for these arguments (a.WC set, bf16, LDS-staged activations, K % 128 == 0)
+bool skinny_wc_supported(int dtype, const GemmArgs& a, int epi);
 
 struct ConvGeom {        // mode 0: plain row-major A.  mode 1: im2col gather from NHWC, K ordered (kh, kw, c)
     int mode;
@@ -213,6 +224,9 @@ struct ChainArgs {
     int layer;                       // down_proj of this layer, QKV of the next (selects the hand-off counters)
     int hidden, inter, qkv_n, qkv_ld, B;
     int w8;                          // stream the fp8 weights (every projection quantised)
+    // coded bf16 weights (bf16, K % 128 == 0 for both roles): the planes of down_proj(layer) / QKV(layer + 1) and their header words; wdown / wqkv stay
+    // the raw packed copies, which the tiles flagged in the headers stream. wc = 0: decode_chain_k on the raw copies.
+    const void *cdown, *cqkv; const unsigned *hdown, *hqkv; int wc;
     float eps;
     void *dx, *dqkv, *dgu;           // [B][hidden] residual stream, [B][qkv_ld], [B][inter]
     int* ctr;                        // chain_ctr_ints(layers) ints, zero at the start of every step

@@ -13,6 +13,7 @@
 #include "rdx_common.h"
 #include "rdx_kernels.h"
 #include "handoff.h"
+#include <type_traits>
 
 namespace rdx {
 
@@ -26,14 +27,18 @@ template <typename T> __device__ __forceinline__ float swiglu(float gate_acc, fl
 
 // Wb (the weight base: model dtype, or the e4m3 bytes when W8), K, tile, ntiles: from preloaded kernel arguments -- all that the first ring needs.
 // late(): the GemmArgs, from kernel arguments that are loaded only behind the ring (rdx_common.h late_kernarg)
-template <typename T, int MT, int EPI, bool NORM, int WAVES, bool XLDS, typename WaitFn, bool COHX = false, bool W8 = false, typename Late>
+// WC: Wb is the coded copy of a bf16 weight (rdx_common.h WcChunk) and wchdr its header words: the ring holds coded chunks, decoded in registers into
+// the very fragments the raw ring would hold, in the same order (same MFMAs, same sums). A tile whose header says "raw" streams late().W as ever.
+template <typename T, int MT, int EPI, bool NORM, int WAVES, bool XLDS, typename WaitFn, bool COHX = false, bool W8 = false, bool WC = false, typename Late>
 __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const int tile, const int ntiles, unsigned char* dyn_smem,
-                                            WaitFn wait_inputs, Late late) {
+                                            WaitFn wait_inputs, Late late, const unsigned* wchdr = nullptr) {
     typedef typename Vec8<T>::type V8;
     // W8: fp8 (e4m3) weights with one fp32 scale per output row. A chunk is then 64 k-values (16 bytes per lane, two MFMAs:
     // lane (g, r) holds W[16*tile + r][64*c + 16*g .. +16]); the bytes are expanded to the model dtype in registers (exact)
     // and the scale is applied to the fp32 sums in the epilogue. LDS-staged activations only.
     static_assert(!W8 || (XLDS && MT == 1), "fp8 weights: LDS-staged activations, one M tile");
+    static_assert(!WC || (XLDS && MT == 1 && !W8), "coded weights: LDS-staged activations, one M tile, model dtype");
+    constexpr int R = 2;                               // coded chunks in flight per wave: 8 loads, 104 bytes per lane (the raw ring: 8 loads, 128 bytes)
     constexpr int U = (XLDS && WAVES >= 8) ? 8 : 4;    // 4-wave workgroups stay <= 64 VGPRs: 8 workgroups per CU
     constexpr int NTHR = WAVES * 64;
     __shared__ __attribute__((aligned(16))) float red[WAVES][MT][256];   // [wave][mt][m_local*16 + n_local]
@@ -49,6 +54,11 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
     const int c0 = (KC * w) / WAVES, c1 = (KC * (w + 1)) / WAVES;
     const u4* wbase = reinterpret_cast<const u4*>(Wb) + (size_t)tile * KC * 64 + lane;
     const int clast = min(max(c1 - 1, c0), KC - 1);
+    // WC: the slice [c0, c1) stays the raw one (the sums must not change); it is covered by the coded chunks [q0, q1), whose first and last may
+    // reach past it -- those fragments multiply zeros (below)
+    const int KQ = K >> 7, q0 = c0 >> 2, q1 = c1 > c0 ? (c1 + 3) >> 2 : q0, qlast = min(max(q1 - 1, q0), KQ - 1);
+    const unsigned char* cb16 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile * KQ * WC_CHUNK_BYTES + lane * 16;
+    const unsigned char* cb4 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile * KQ * WC_CHUNK_BYTES + 3072 + lane * 4;
 
     // Everything up to here comes from the leading kernel arguments (preloaded into SGPRs: gemm.hip skinny_gemm_k), the workgroup id and the lane
     // id, so the ring is issued with no scalar load in front of it. The entry time is taken unconditionally (one scalar instruction that nothing
@@ -57,13 +67,23 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
     // two weight batches in flight before anything else (HBM latency overlaps the wait and the prologue)
     // (unconditional, addresses clamped into the slice: a short slice re-reads its last KiB)
     u4 ring[2 * U];
+    WcChunk cring[R];
+    if constexpr (WC) {
 #pragma unroll
-    for (int u = 0; u < 2 * U; ++u) ring[u] = ldg16_nt(wbase + (size_t)min(c0 + u, clast) * 64);
+        for (int u = 0; u < R; ++u) { const size_t o = (size_t)min(q0 + u, qlast) * WC_CHUNK_BYTES; cring[u] = wc_load(cb16 + o, cb4 + o); }
+    } else {
+#pragma unroll
+        for (int u = 0; u < 2 * U; ++u) ring[u] = ldg16_nt(wbase + (size_t)min(c0 + u, clast) * 64);
+    }
     u4* const wv = ring;            // the two-batch view of the direct-activation path below
     u4* const wn = ring + U;
     __builtin_amdgcn_sched_barrier(0);            // nothing of what follows is scheduled in front of the ring
     const GemmArgs a = late();
     const T* X = reinterpret_cast<const T*>(a.X);
+    unsigned wc_hdr = 0;
+    // the tile's header word, behind the ring. Through the constant address space (the words never change while a kernel runs): a SCALAR load, so the
+    // choice between the two loops is a scalar branch -- as a vector load it was waited for with vmcnt(0), the ring with it, and both loops ran under EXEC masks
+    if constexpr (WC) wc_hdr = *(reinterpret_cast<const __attribute__((address_space(4))) unsigned*>((uintptr_t)wchdr) + tile);
 
     long long* trc = (a.trace && threadIdx.x == 0) ? a.trace + (size_t)tile * 8 : nullptr;
 #define SK_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
@@ -122,6 +142,7 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
             }
             *reinterpret_cast<u4*>(xs + (size_t)m * K + (size_t)k8 * 8) = as_u4<T>(xv);
         }
+        if (WC && threadIdx.x == 0) *reinterpret_cast<u4*>(xs + (size_t)a.M * K) = (u4){0u, 0u, 0u, 0u};     // what fragments outside a wave's slice multiply
         __syncthreads();
     }
 
@@ -173,18 +194,69 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
                 }
             }
         };
-        int cb = c0;
-        for (; cb + 2 * U < c1; cb += 2 * U) {
+        // the raw loop over NR ring slots (slot(u), u constant after unrolling): the ring of 2 U fragments, or -- a flagged tile of the coded kernel --
+        // registers of the dropped coded ring (as registers of their own they were carried, spilled, through this branch)
+        auto raw_loop = [&](const u4* wb, auto slot, auto nr) {
+            constexpr int NR = decltype(nr)::value;
+            int cb = c0;
+            for (; cb + NR < c1; cb += NR) {
 #pragma unroll
-            for (int u = 0; u < 2 * U; ++u) {
-                consume1(ring[u], cb + u);
-                ring[u] = ldg16_nt(wbase + (size_t)min(cb + 2 * U + u, clast) * 64);
-                __builtin_amdgcn_sched_barrier(0);
+                for (int u = 0; u < NR; ++u) {
+                    consume1(slot(u), cb + u);
+                    slot(u) = ldg16_nt(wb + (size_t)min(cb + NR + u, clast) * 64);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
             }
-        }
 #pragma unroll
-        for (int u = 0; u < 2 * U; ++u)
-            if (cb + u < c1) consume1(ring[u], cb + u);
+            for (int u = 0; u < NR; ++u)
+                if (cb + u < c1) consume1(slot(u), cb + u);
+        };
+        if constexpr (WC) {
+            if (wc_hdr & 0x100u) {
+                // a tile the code cannot express (wave-uniform, once per tile): the coded ring is dropped, today's loop runs on the raw packed copy
+                const u4* wraw = reinterpret_cast<const u4*>(a.W) + (size_t)tile * KC * 64 + lane;
+                // (four of its six 16-byte registers: a rare path, and the 4-wave form has no VGPR to spare for the addresses of more)
+                auto slot = [&](int u) -> u4& { return u == 0 ? cring[0].lo0 : u == 1 ? cring[0].lo1 : u == 2 ? cring[0].ix : cring[1].lo0; };
+#pragma unroll
+                for (int u = 0; u < 4; ++u) slot(u) = ldg16_nt(wraw + (size_t)min(c0 + u, clast) * 64);
+                raw_loop(wraw, slot, std::integral_constant<int, 4>());
+            } else {
+                const unsigned base4 = (wc_hdr & 0xffu) * 0x01010101u;
+                const T* zptr = xs + (size_t)a.M * K;
+                // guard: the first and the last coded chunk of a slice may hold packed chunks of the neighbouring waves; their fragments read the
+                // zero line instead of the row -- a scalar select of the address, no branch. The sums keep their bits because (1) every weight of an
+                // unflagged tile is finite (the encoder flags Inf / NaN), so every product is a zero; (2) the fp32 accumulator starts at +0 and a sum is
+                // -0 only when all its terms are, so it is never -0, and x + (+-0) = x for every other x; (3) an MFMA whose 32 products are all zero
+                // therefore returns its accumulator operand unchanged, wherever in the sequence it stands. Cost: at most 3 fragments decoded in vain
+                // at either end of a slice (K = 11008 over 16 waves: 21.5 packed chunks per wave, 24 or 28 decoded); aligned slices pay nothing.
+                auto consumeC = [&](const WcChunk& ch, int q, bool guard) {
+                    auto one = [&](const u4 wd, int c) {
+                        const T* xp = (!guard || (c >= c0 && c < c1)) ? xrow[0] + (size_t)c * 32 : zptr;
+                        acc[0] = mfma16(as_vec8<T>(wd), as_vec8<T>(*reinterpret_cast<const u4*>(xp)), acc[0]);
+                        __builtin_amdgcn_sched_barrier(0);       // one fragment decoded at a time: four at once do not fit the 64 VGPRs of the 4-wave form
+                    };
+                    one(wc_frag<0>(ch, base4), 4 * q); one(wc_frag<1>(ch, base4), 4 * q + 1);
+                    one(wc_frag<2>(ch, base4), 4 * q + 2); one(wc_frag<3>(ch, base4), 4 * q + 3);
+                };
+                auto trip = [&](int q, bool guard) {
+#pragma unroll
+                    for (int u = 0; u < R; ++u) {
+                        consumeC(cring[u], q + u, guard);
+                        const size_t o = (size_t)min(q + R + u, qlast) * WC_CHUNK_BYTES;
+                        cring[u] = wc_load(cb16 + o, cb4 + o);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                };
+                int q = q0;
+                if (q + R < q1) { trip(q, true); q += R; }       // the trip that holds the slice's first chunk, outside the loop
+                for (; q + R < q1; q += R) trip(q, false);
+#pragma unroll
+                for (int u = 0; u < R; ++u)
+                    if (q + u < q1) consumeC(cring[u], q + u, true);
+            }
+        } else {
+            raw_loop(wbase, [&](int u) -> u4& { return ring[u]; }, std::integral_constant<int, 2 * U>());
+        }
     } else
     for (int cb = c0; cb < c1; cb += U) {
         if (!XLDS && cb + U < c1) load_x(xn, cb + U);

@@ -436,7 +436,8 @@ class RdxEngine:
         return out8, sc
 
     def set_option(self, name: str, value: int):
-        """rdx_set_option: "flash_min" (batched prefill attention kernel choice), "pconv" (packed / row-major encoder kernels)."""
+        """rdx_set_option: "flash_min" (batched prefill attention kernel choice), "pconv" (packed / row-major encoder kernels), "xs16", "prompt_blk",
+        "wcode" (the batch <= 2 step streams the coded bf16 weights: on by default; 0 = the raw packed ones, same bits)."""
         check(self.ctx, self.lib.rdx_set_option(self.ctx, name.encode(), int(value)), "rdx_set_option")
 
     def conv_test(self, x, w, bias=None, resid=None, ksize=1, stride=1, epi=0, path=0, iters=0):
@@ -561,6 +562,27 @@ class RdxEngine:
         check(self.ctx, self.lib.rdx_xstat16_test(self.ctx, _ptr(x), _ptr(nw), eps, _ptr(w), M, N, epi, N if n_valid is None else n_valid, _ptr(out),
                                                   ldo, out_packed, ctypes.cast(am, ctypes.c_void_p)), "rdx_xstat16_test")
         return (out, torch.tensor(list(am), dtype=torch.int32)) if epi == 5 else out
+
+    def wcode_test(self, w):
+        """The device encoder of the coded bf16 weights alone (rdx_wcode_test; the format: radialog_amd/wcode.py): w fp32 [N, K], K % 128 == 0. Returns
+        (packed uint16 [tiles, K / 32, 64, 8], planes uint8 [tiles, K / 128, 3328], hdr uint32 [tiles]) as NumPy arrays."""
+        from . import wcode
+        N, K = w.shape
+        nt = (N + 15) // 16
+        w = self._dev(w, torch.float32)
+        packed = torch.zeros(nt, K // 32, 64, 8, dtype=torch.int16, device=self.device)
+        planes = torch.zeros(nt, K // wcode.CHUNK_K, wcode.CHUNK_BYTES, dtype=torch.uint8, device=self.device)
+        hdr = torch.zeros(nt, dtype=torch.int32, device=self.device)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_wcode_test(self.ctx, _ptr(w), N, K, _ptr(packed), _ptr(planes), _ptr(hdr)), "rdx_wcode_test")
+        return packed.cpu().numpy().view("uint16"), planes.cpu().numpy(), hdr.cpu().numpy().view("uint32")
+
+    def wcode_stats(self):
+        """(tiles, fallback tiles, bytes, coded GEMV launches, coded chained launches) of this engine's decoder (rdx_wcode_stats): the coded bf16 weight
+        copies it holds (zeros where it holds none) and how many launches of the coded kernels it has issued (a captured graph counts once)."""
+        out = (C.c_longlong * 5)()
+        check(self.ctx, self.lib.rdx_wcode_stats(self.ctx, out), "rdx_wcode_stats")
+        return tuple(int(v) for v in out)
 
     def xrow16_test(self, x, w, resid, M=None, ldo=None):
         """xrow16_k (rdx_xrow16_test): out [M + 2, ldo] = resid [M, N] + T(x w^T). x [M, K] row-major, or (4-d) the packed block [K / 32, 2, 64, 8]
