@@ -165,6 +165,29 @@ int rdx_set_logits_rules(rdx_ctx* ctx, const rdx_logits_rules* rules);
 typedef struct rdx_sampling { int do_sample; float temperature; int top_k; float top_p; uint64_t seed; } rdx_sampling;
 int rdx_set_sampling(rdx_ctx* ctx, const rdx_sampling* s);
 
+/* Scoring given tokens: LlamaForCausalLM.forward(input_ids, attention_mask, labels=) of the reference (modeling_llama_imgemb.py:705-793) -- the logits of
+ * every position and what its shifted cross-entropy is made of -- from ONE pass over the prompt's kernels (no decode steps).
+ *   ids / mask / qformer_embs  device pointers as for the prefill call: the left-padded prompt, the mask (NULL -> ids != 0), the image splice
+ *   labels_host  HOST int32[B][T], HF's convention: the token at position t, or -100 for "not scored"
+ *   logprob      float[B][T] (device): at t >= 1 with labels[b][t] != -100, log p(labels[b][t] | ids[b][:t]); 0 at every other entry and at t = 0
+ *   top1         nullable int32[B][T] (device): at the same entries the model's argmax for position t (lowest index on ties); -1 elsewhere
+ *   logits       nullable model dtype [B][T][vocab] (device): the logits of every position (forward().logits). NULL: only the rows whose successor is
+ *                scored pass the lm_head, and the library never holds more than one chunk of logits
+ * For a scored entry, with x the model-dtype logits row of position t - 1 over columns 0 .. vocab - 1 only (the lm_head's pad columns never enter):
+ *   m = max x, S = sum exp(float(x_i) - m), logprob = (float(x_label) - m) - log(S) in fp32, not rounded to the model dtype (score_rows_k, score.hip).
+ * Every reduction runs in a fixed order without floating-point atomics: the same inputs give the same bits on every run. The loss of the reference is
+ * -(sum of the scored logprob entries) / (their number).
+ * The rows pass the final RMSNorm and the lm_head in chunks of "score_chunk" rows (an option of the set-option call; 0 = all at once) through one
+ * logits workspace [chunk][vocab padded to 16].
+ * Returns -1, with a message and nothing written, for: a label outside [0, vocab) other than -100; T > max_len, T > max_position_embeddings or
+ * batch > max_batch; weights not finalised; an fp8-weight context (an all-position lm_head would need a quantisation convention that the oracle
+ * does not define below batch 3).
+ * The call overwrites the KV cache and leaves the context without a conversation, as after creation: the decode-step and append calls return -1 until the
+ * next prefill, and a token history of the logits rules is gone. Rules and sampling set on the context stay set and are ignored here: nothing is selected.
+ * The call returns after the stream has drained. No scoring behind a kept prefix, none under beam search. */
+int rdx_score(rdx_ctx* ctx, const int32_t* ids, const int32_t* mask, int batch, int T, const float* qformer_embs, const int32_t* labels_host,
+              float* logprob, int32_t* top1, void* logits);
+
 /* Multi-turn re-prompting (test.py:440-674, demo.py:277-305: the reference re-runs the whole conversation each turn). The
  * next turn's prompt usually starts with the previous prompt + answer; its KV rows are still in the cache. These calls keep the
  * first keep_len cache slots of every row (keep_len <= cached positions = previous T + tokens consumed; the caller compares
@@ -226,7 +249,8 @@ int rdx_time(rdx_ctx* ctx, int what, int iters, float* ms_host);
  * family of xs16.hip (1, default) or on the 32-row family (0; RDX_XS16), "prompt_blk" = one prompt's K = 4096 projections on 32-row blocks (1, default) or on
  * the weight-stationary kernel (0; RDX_PBLK), "wcode" = the batch <= 2 decode step of a bf16 context streams the 13-bit coded copies of its gate/up, down_proj,
  * QKV and lm_head weights (1, default) or the raw packed ones (0); the results are the same bits either way, a captured step graph is dropped (no
- * environment variable). Unknown names return -1. No reference counterpart.
+ * environment variable), "score_chunk" = logits rows per lm_head launch of the scoring pass (default 2048, the fastest of 128 / 512 / 2048 / all on 3382 rows: profiles/r11_score.md; 0 = all rows of a call at once; negative values
+ * return -1). Unknown names return -1. No reference counterpart.
  * At batch 3-16 on the xs16 family rdx_time units 1-5 time THOSE kernels (the RMSNorm is their prologue); max_batch > 32 needs the Vicuna-7B widths
  * (hidden 4096, inter 11008): rdx_finalize_weights refuses other models with more than 32 rows. */
 int rdx_set_option(rdx_ctx* ctx, const char* name, int value);

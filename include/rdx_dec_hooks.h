@@ -62,6 +62,11 @@ int rdx_rmsnorm_test(rdx_ctx* ctx, void* x, const void* norm_w, float eps, int r
 int rdx_select_test(rdx_ctx* ctx, void* logits_inout, int B, int vocab, const int32_t* hist, const int32_t* hist_len, const int32_t* n_generated, int ld,
                     const rdx_logits_rules* rules, int eos_id, int32_t* tokens_out);
 
+/* score_rows_k alone (score.hip: the kernel of the scoring pass, see include/rdx.h): logits [M][ld] model dtype (device, 16-byte aligned; ld a multiple of 8,
+ * >= vocab: columns vocab .. ld - 1 are pad columns that must not be looked at), target int32 [M] (device; -100 = row not scored), logprob_out float [M],
+ * top1_out int32 [M] (device). Works on any context (no weights involved). */
+int rdx_score_rows_test(rdx_ctx* ctx, const void* logits, int M, int vocab, int ld, const int32_t* target, float* logprob_out, int32_t* top1_out);
+
 /* launch_decode_attention alone (attn.hip, attn_body.h: one new token per row -- LoRA-B add, rotate-half RoPE, in-place KV append, attention over the cache), on
  * caller data: hidden = 128 heads, qkv_ld = 3 hidden + 2 lora_r rounded up to 16. qkv [B][qkv_ld] (q | k | v | LoRA-A of q [8] | of v [8]), lbq / lbv [hidden][8]
  * (lora_r 8; else ignored), EITHER cur_rope [B][2][128] (cos | sin row of each row's position) OR cos_t / sin_t [max_pos][128] with pos [B]; slot [B] (the

@@ -80,6 +80,7 @@ SYMBOLS = {
     "rdx_prefill": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rdx_decode_step": (C.c_int, [_P, _P]),
     "rdx_decode_step_ids": (C.c_int, [_P, _P, _P]),
+    "rdx_score": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "rdx_set_logits_rules": (C.c_int, [_P, C.POINTER(RdxLogitsRules)]),
     "rdx_set_sampling": (C.c_int, [_P, C.POINTER(RdxSampling)]),
     "rdx_prefill_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
@@ -131,6 +132,7 @@ DEC_HOOK_SYMBOLS = {
     "rdx_xsplit_blk8_test": (C.c_int, [_P, _P, _P, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_rmsnorm_test": (C.c_int, [_P, _P, _P, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong, _P, C.c_int]),
     "rdx_select_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, _P]),
+    "rdx_score_rows_test": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_sample_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, C.POINTER(RdxSampling), _P]),
     "rdx_sample_u24_host": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rdx_decode_attn_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_longlong,

@@ -404,5 +404,10 @@ extern "C" int rdx_set_option(rdx_ctx* c, const char* name, int value) {
         if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; c->gkey = GraphKey(); }
         return 0;
     }
+    if (!strcmp(name, "score_chunk")) {   // rdx_score: logits rows per lm_head launch (0 = all rows of a call at once)
+        if (value < 0) return fail(c, -1, "rdx_set_option: score_chunk %d is negative (0 = all rows at once)", value);
+        c->score_chunk = value;
+        return 0;
+    }
     return fail(c, -1, "rdx_set_option: unknown option '%s'", name);
 }

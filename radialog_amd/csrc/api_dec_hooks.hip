@@ -245,6 +245,15 @@ extern "C" int rdx_select_test(rdx_ctx* c, void* logits_inout, int B, int vocab,
     return finish(c);
 }
 
+extern "C" int rdx_score_rows_test(rdx_ctx* c, const void* logits, int M, int vocab, int ld, const int32_t* target, float* logprob_out, int32_t* top1_out) {
+    if (!c || !logits || !target || !logprob_out || !top1_out || M <= 0) return fail(c, -1, "rdx_score_rows_test: bad arguments");
+    if (((uintptr_t)logits & 15) || !score_rows_supported(vocab, ld))
+        return fail(c, -1, "rdx_score_rows_test: rows of vocab %d at stride %d (a multiple of 8 >= vocab, 16-byte aligned base, the row within the LDS of score_rows_k)", vocab, ld);
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_score_rows(c->cfg.dtype, logits, ld, target, vocab, logprob_out, top1_out, M, c->stream);
+    return finish(c);
+}
+
 namespace {
 
 // the dims both attention hooks build: hidden = 128 heads, the QKV row as the engine lays it out (api.hip: wqkv.Npad)

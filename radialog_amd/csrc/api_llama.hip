@@ -129,6 +129,8 @@ static int rules_need_prefill(rdx_ctx* c, const char* who) {
     return 0;
 }
 
+static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep, int pad_id, bool hist);
+
 // keep == 0: a fresh prompt. keep > 0: `T` further prompt tokens behind the first `keep` cache slots of the previous call(s)
 // (the shared prefix of a multi-turn conversation is not recomputed; no image splice in the continuation).
 int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep,
@@ -149,13 +151,27 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
         for (int b = 0; b < B; ++b)
             if (keep > slot[b]) return fail(c, -1, "rdx_prefill_append: keep_len %d exceeds the %d cached positions of row %d", keep, slot[b], b);
     }
-    const size_t M = (size_t)B * T;
-    int rc = ensure_prefill_ws(c, M);
+    int rc = ensure_prefill_ws(c, (size_t)B * T);
     if (rc) return rc;
-    const int dt = f.dtype, H = f.hidden;
-    hipStream_t s = c->stream;
     c->cur_B = B; c->cur_T = keep + T; c->cur_max_new = max_new; c->cur_eos = eos_id; c->cur_pad = pad_id; c->cur_tokens = out_tokens;
     c->cur_steps = 1;
+    rc = prompt_layers(c, ids, mask, B, T, qformer_embs, keep, pad_id, c->rules_on);
+    if (rc) return rc;
+    launch_gather_last(f.dtype, c->px, c->datt, B, T, f.hidden, c->stream);      // datt doubles as the [B][H] last-position buffer
+    lm_head_and_greedy(c, c->datt, B, logits, nullptr, 0, /*advance=*/0);
+    HIPCHK(c, hipGetLastError());
+    return take_unsupported(c);
+}
+
+// The prompt through every layer: the residual stream of all B x T positions ends in c->px (row-major [B T][hidden]), K / V in the cache behind `keep` kept
+// slots, the per-row decode state (d_pos / d_slot / d_step / d_unf, the key mask) is that of a prompt of T tokens. What the callers do with px is theirs: the
+// prefill gathers the last row of each prompt for token 0, the scoring pass the rows whose successor is scored. The workspace (ensure_prefill_ws) holds B x T
+// rows. hist: start the token history of the logits rules from `ids`.
+static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep, int pad_id, bool hist) {
+    const rdx_config& f = c->cfg;
+    const size_t M = (size_t)B * T;
+    const int dt = f.dtype, H = f.hidden;
+    hipStream_t s = c->stream;
 
     if (keep > 0) {
         launch_prep_append(B, T, keep, c->d_img_pos, c->d_pos_ids, c->d_pos, c->d_slot, c->d_step, c->d_unf, s);
@@ -164,8 +180,8 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
         launch_prep_prompt(ids, mask, B, T, 32000, pad_id, c->d_img_pos, c->d_pos_ids, c->key_mask, f.max_len, c->d_pos, c->d_slot,
                            c->d_step, c->d_unf, s);
     }
-    c->hist_ready = c->rules_on;
-    if (c->rules_on) launch_hist_init(ids, B, T, c->d_hist, c->d_hist_len, f.max_len, s);
+    c->hist_ready = hist;
+    if (hist) launch_hist_init(ids, B, T, c->d_hist, c->d_hist_len, f.max_len, s);
     if (qformer_embs) {
         // a8: img_proj_layer on the model-dtype copy of the Q-Former output (".half()", modeling_llama_imgemb.py:576-579)
         launch_from_f32(dt, qformer_embs, c->pqe, (size_t)B * 32 * f.qformer_dim, s);
@@ -256,10 +272,7 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
     }
     if (pend) prompt_norm(c->ll[0].attn_norm, c->pxn, xl, mtl, pend);
     }
-    launch_gather_last(dt, c->px, c->datt, B, T, H, s);      // datt doubles as the [B][H] last-position buffer
-    lm_head_and_greedy(c, c->datt, B, logits, nullptr, 0, /*advance=*/0);
-    HIPCHK(c, hipGetLastError());
-    return take_unsupported(c);
+    return 0;
 }
 
 extern "C" int rdx_prefill(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs,
@@ -273,6 +286,93 @@ extern "C" int rdx_prefill_append(rdx_ctx* c, const int32_t* ids_tail, int B, in
     if (c->rules_on) return fail(c, -1, "rdx_prefill_append: not available under logits rules (the token history is not carried across calls); rdx_set_logits_rules(ctx, NULL) first");
     if (keep_len <= 0 || c->cur_B <= 0) return fail(c, -1, "rdx_prefill_append: no cached conversation to continue (keep_len %d)", keep_len);
     return prefill_impl(c, ids_tail, nullptr, B, T_tail, nullptr, keep_len, max_new, eos_id, pad_id, out_tokens, logits);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Scoring given tokens (include/rdx.h): what LlamaForCausalLM.forward(input_ids, attention_mask, labels) computes in the reference
+// (modeling_llama_imgemb.py:705-793) -- the prompt's layers as in the prefill, then the final RMSNorm, the lm_head and score_rows_k (score.hip) on the rows
+// whose successor position is scored (every row when the caller wants the logits), in chunks of score_chunk rows through ONE logits workspace.
+// ------------------------------------------------------------------------------------------------------------------
+static int ensure_score_ws(rdx_ctx* c, size_t rows, size_t chunk) {
+    const rdx_config& f = c->cfg;
+    if (rows > c->sc_rows) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->sc_rows = 0;
+        dfree(c, c->sc_x); dfree(c, c->sc_xn); dfree(c, c->sc_idx); dfree(c, c->sc_lp); dfree(c, c->sc_t1);
+        ALLOC(c, c->sc_x, rows * f.hidden * 2); ALLOC(c, c->sc_xn, rows * f.hidden * 2);
+        ALLOC(c, c->sc_idx, rows * 4 * sizeof(int)); ALLOC(c, c->sc_lp, rows * sizeof(float)); ALLOC(c, c->sc_t1, rows * sizeof(int));
+        c->sc_rows = rows;
+    }
+    if (chunk > c->sc_ws_rows) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        c->sc_ws_rows = 0;
+        dfree(c, c->sc_logits);
+        ALLOC(c, c->sc_logits, chunk * (size_t)c->lm_head.Npad * 2);
+        c->sc_ws_rows = chunk;
+    }
+    return 0;
+}
+
+extern "C" int rdx_score(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, const int32_t* labels_host,
+                         float* logprob, int32_t* top1, void* logits) {
+    if (!c) return -1;
+    if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_score: llama weights not finalized");
+    const rdx_config& f = c->cfg;
+    if (!ids || !labels_host || !logprob || B <= 0 || B > f.max_batch) return fail(c, -1, "rdx_score: batch %d outside [1, %d]", B, f.max_batch);
+    if (T <= 0 || T > f.max_len) return fail(c, -1, "rdx_score: T (%d) exceeds max_len %d", T, f.max_len);
+    if (T > f.max_pos) return fail(c, -1, "rdx_score: sequence exceeds max_position_embeddings %d", f.max_pos);
+    if (qformer_embs && T < 32) return fail(c, -1, "rdx_score: image splice needs T >= 32");
+    if (fp8_weights(c->ll[0].wqkv) || fp8_weights(c->lm_head))
+        return fail(c, -1, "rdx_score: not available on an fp8-weight context (an all-position lm_head needs a quantisation convention the oracle does not define below batch 3)");
+    const int V = f.vocab, ld = c->lm_head.Npad, H = f.hidden;
+    if (!score_rows_supported(V, ld)) return fail(c, -1, "rdx_score: a logits row of vocab %d (stride %d) does not fit the LDS of score_rows_k", V, ld);
+    for (size_t i = 0; i < (size_t)B * T; ++i)
+        if (labels_host[i] != -100 && (labels_host[i] < 0 || labels_host[i] >= V))
+            return fail(c, -1, "rdx_score: label %d (row %d, position %d) outside [0, %d) and not -100", labels_host[i], (int)(i / T), (int)(i % T), V);
+    HIPCHK(c, hipSetDevice(c->device));
+    // row i of the tail = position (b, t): its logits score the label of position t + 1. With `logits` every position takes part.
+    std::vector<int> rows, tgt, dst, ldst;
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < T; ++t) {
+            const bool scored = t + 1 < T && labels_host[(size_t)b * T + t + 1] != -100;
+            if (!scored && !logits) continue;
+            rows.push_back(b * T + t); tgt.push_back(scored ? labels_host[(size_t)b * T + t + 1] : -100);
+            dst.push_back(scored ? b * T + t + 1 : -1); ldst.push_back(logits ? b * T + t : -1);
+        }
+    const size_t n = rows.size();
+    const size_t chunk = c->score_chunk > 0 ? std::min<size_t>((size_t)c->score_chunk, n) : n;
+    int rc = ensure_prefill_ws(c, (size_t)B * T);
+    if (rc) return rc;
+    if (n && (rc = ensure_score_ws(c, n, chunk))) return rc;
+    hipStream_t s = c->stream;
+    // no conversation behind this call: the decode steps and the append calls refuse until the next prefill
+    c->cur_B = 0; c->cur_T = 0; c->cur_max_new = 0; c->cur_steps = 0; c->cur_tokens = nullptr;
+    c->hist_ready = false;
+    HIPCHK(c, hipMemsetAsync(logprob, 0, (size_t)B * T * sizeof(float), s));
+    if (top1) HIPCHK(c, hipMemsetAsync(top1, 0xff, (size_t)B * T * sizeof(int32_t), s));       // -1
+    if (n) {
+        rc = prompt_layers(c, ids, mask, B, T, qformer_embs, 0, /*pad_id=*/0, /*hist=*/false);
+        if (rc) return rc;
+        int* d_rows = c->sc_idx; int *d_tgt = d_rows + n, *d_dst = d_tgt + n, *d_ldst = d_dst + n;
+        HIPCHK(c, hipMemcpyAsync(d_rows, rows.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(d_tgt, tgt.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(d_dst, dst.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(c, hipMemcpyAsync(d_ldst, ldst.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
+        launch_gather_rows(f.dtype, c->px, d_rows, c->sc_x, (int)n, H, s);
+        run_rmsnorm(c, NormArgs{c->sc_x, c->final_norm, c->sc_xn, nullptr, (int)n, H, f.rms_eps, ACT_ROWS, 0, nullptr, 0});
+        for (size_t i0 = 0; i0 < n; i0 += chunk) {
+            const int m = (int)std::min(chunk, n - i0);
+            GemmArgs a = gargs((const char*)c->sc_xn + i0 * H * 2, H, c->lm_head, nullptr, c->sc_logits, ld, m);
+            a.N = ld;      // whole tiles: the pad columns are written too and never read back
+            run_gemm(c, a, EPI_NONE);
+            launch_score_rows(f.dtype, c->sc_logits, ld, d_tgt + i0, V, c->sc_lp + i0, c->sc_t1 + i0, m, s);
+            if (logits) launch_logits_out(f.dtype, c->sc_logits, ld, d_ldst + i0, logits, V, m, s);
+        }
+        launch_score_scatter(c->sc_lp, c->sc_t1, d_dst, logprob, top1, (int)n, s);
+    }
+    HIPCHK(c, hipStreamSynchronize(s));      // the index lists are this call's host vectors
+    HIPCHK(c, hipGetLastError());
+    return take_unsupported(c);
 }
 
 static int decode_loop(rdx_ctx* c, int B, int max_new, int eos_id, void* scores, int* n_steps_host, int use_graph);

@@ -136,6 +136,14 @@ struct rdx_ctx {
     rdx_sampling sampling = {0, 1.0f, 0, 1.0f, 0};
     unsigned long long* d_seed = nullptr;           // the seed word sample_step_k reads (rewritten in stream order by every rdx_set_sampling call)
 
+    // ---- scoring pass (rdx_score), sized on first use ----
+    int score_chunk = 2048;                         // logits rows per lm_head launch (rdx_set_option("score_chunk", rows); 0 = all rows at once): profiles/r11_score.md
+    void *sc_x = nullptr, *sc_xn = nullptr;         // [rows][hidden]: the gathered residual rows and their final RMSNorm
+    void* sc_logits = nullptr;                      // [chunk rows][lm_head.Npad]: the one chunk of logits the library ever holds
+    int* sc_idx = nullptr;                          // rows[n] | target[n] | dst[n] | ldst[n]: the host-built index lists of one call
+    float* sc_lp = nullptr; int* sc_t1 = nullptr;   // [rows] compact results, scattered to [batch][T] by one launch
+    size_t sc_rows = 0, sc_ws_rows = 0;
+
     // ---- beam search workspaces (rdx_beam_search), sized on first use ----
     void* bm_logits = nullptr; float* bm_scores = nullptr; float* bm_cand_s = nullptr; int* bm_cand_i = nullptr;
     int *bm_tok = nullptr, *bm_src = nullptr; int32_t* bm_out = nullptr; void* bm_scratch = nullptr;

@@ -323,6 +323,15 @@ void launch_sample_step(int dtype, const SelectArgs& a, const SampleArgs& sp, co
 void launch_hist_init(const int* ids, int B, int T, int* hist, int* hist_len, int ld, hipStream_t s);
 void launch_hist_set_last(const int* ids, int* hist, const int* hist_len, int ld, int B, hipStream_t s);
 
+// Scoring given tokens (score.hip). score_rows_k: one workgroup per row of logits [M][ld] (model dtype; ld % 8 == 0, base 16-byte aligned), over columns
+// 0 .. vocab - 1 only: logprob[r] = (x_target - max) - log(sum exp(x - max)) in fp32, top1[r] = argmax (lowest index on ties); target -100: (0.0f, -1).
+inline size_t score_rows_lds(int vocab) { return (size_t)((vocab + 7) / 8) * 16; }      // dynamic LDS: the row
+bool score_rows_supported(int vocab, long ld);
+void launch_score_rows(int dtype, const void* logits, long ld, const int* target, int vocab, float* logprob, int* top1, int M, hipStream_t s);
+void launch_gather_rows(int dtype, const void* x, const int* rows, void* out, int n, int H, hipStream_t s);       // out[i] = x[rows[i]], rows of H elements (H % 8 == 0)
+void launch_score_scatter(const float* lp, const int* t1, const int* dst, float* logprob, int* top1, int n, hipStream_t s);   // logprob[dst[i]] = lp[i] (top1 likewise, nullable); dst < 0: skipped
+void launch_logits_out(int dtype, const void* ws, long ld, const int* dst, void* out, int vocab, int n, hipStream_t s);       // out[dst[i]][0 .. vocab) = ws[i][0 .. vocab)
+
 // beam search (beam.hip)
 #define RDX_MAX_BEAMS 8
 void launch_beam_topk(int dtype, const void* logits, const float* beam_scores, int groups, int beams, int vocab, float* cand_score,

@@ -400,6 +400,43 @@ class RdxEngine:
         self.sync()
         return toks, logits
 
+    def score(self, ids, qformer_embs, labels, mask=None, want_top1=False, want_logits=False):
+        """rdx_score: per-token log-probabilities of given text from one pass over the prompt's kernels. ids int [B, T]; labels int [B, T] in HF's
+        convention (the token at position t, -100 = not scored); mask as in prefill (None -> ids != 0). Returns (logprob float32 [B, T]: at t >= 1 with
+        labels[b, t] != -100, log p(labels[b, t] | ids[b, :t]), 0 elsewhere; top1 int32 [B, T] or None: the model's argmax at the same entries, -1
+        elsewhere; logits [B, T, V] model dtype or None). Overwrites the KV cache and leaves no conversation: decode_step needs a new prefill.
+        Logits rules and sampling held by the context stay as they are and are ignored."""
+        B, T = ids.shape
+        lab = torch.as_tensor(labels).to(device="cpu", dtype=torch.int32).contiguous()
+        if tuple(lab.shape) != (B, T):
+            raise ValueError(f"labels must have the shape of ids {(B, T)}, got {tuple(lab.shape)}")
+        ids32 = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        m32 = None if mask is None else mask.to(device=self.device, dtype=torch.int32).contiguous()
+        qf = None if qformer_embs is None else qformer_embs.to(device=self.device, dtype=torch.float32).contiguous()
+        logprob = torch.empty(B, T, dtype=torch.float32, device=self.device)
+        top1 = torch.empty(B, T, dtype=torch.int32, device=self.device) if want_top1 else None
+        logits = torch.empty(B, T, self.cfg.llama.vocab, dtype=self.tdtype, device=self.device) if want_logits else None
+        self._conv = None                            # the KV cache is overwritten: nothing of an earlier conversation can be reused
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_score(self.ctx, _ptr(ids32), _ptr(m32), B, T, _ptr(qf), C.c_void_p(lab.data_ptr()), _ptr(logprob), _ptr(top1),
+                                           _ptr(logits)), "rdx_score")
+        return logprob, top1, logits
+
+    def score_rows_test(self, logits, target, vocab=None):
+        """score_rows_k alone (rdx_score_rows_test): logits [M, ld] model dtype (ld a multiple of 8; columns vocab .. ld - 1 are pad columns), target int [M]
+        (-100 = not scored). Returns (logprob float32 [M], top1 int32 [M])."""
+        M, ld = logits.shape
+        V = ld if vocab is None else int(vocab)
+        x = logits.to(self.device, self.tdtype).contiguous()
+        tg = target.to(self.device, torch.int32).contiguous()
+        if tg.numel() != M:
+            raise ValueError("score_rows_test: target [M]")
+        lp = torch.full((M,), float("nan"), dtype=torch.float32, device=self.device)
+        t1 = torch.full((M,), -7, dtype=torch.int32, device=self.device)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_score_rows_test(self.ctx, _ptr(x), M, V, ld, _ptr(tg), _ptr(lp), _ptr(t1)), "rdx_score_rows_test")
+        return lp, t1
+
     def kv_read(self, layer: int, which: int, batch: int) -> torch.Tensor:
         l = self.cfg.llama
         out = torch.empty(self.max_batch, l.heads, self.max_len, l.head_dim, dtype=self.tdtype, device=self.device)
@@ -437,7 +474,7 @@ class RdxEngine:
 
     def set_option(self, name: str, value: int):
         """rdx_set_option: "flash_min" (batched prefill attention kernel choice), "pconv" (packed / row-major encoder kernels), "xs16", "prompt_blk",
-        "wcode" (the batch <= 2 step streams the coded bf16 weights: on by default; 0 = the raw packed ones, same bits)."""
+        "wcode" (the batch <= 2 step streams the coded bf16 weights: on by default; 0 = the raw packed ones, same bits), "score_chunk" (logits rows per lm_head launch of score(); default 2048, 0 = all at once)."""
         check(self.ctx, self.lib.rdx_set_option(self.ctx, name.encode(), int(value)), "rdx_set_option")
 
     def conv_test(self, x, w, bias=None, resid=None, ksize=1, stride=1, epi=0, path=0, iters=0):

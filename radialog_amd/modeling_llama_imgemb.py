@@ -271,6 +271,61 @@ class LlamaForCausalLM:
         return GenerateOutput(sequences=seq, scores=sc)
 
 
+    # -- scoring given tokens ------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def forward(self, input_ids: torch.Tensor = None, attention_mask: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
+                dicom: Optional[List[str]] = None, use_img: bool = False, qformer_embs: Optional[torch.Tensor] = None,
+                return_dict: bool = True, return_logits: bool = True, past_key_values=None, inputs_embeds=None, **_unused):
+        """The reference's forward(input_ids, attention_mask, labels=, dicom=, use_img=) (modeling_llama_imgemb.py:705-793) from one scoring pass
+        (RdxEngine.score): `.logits` [B, T, V] of every position and `.loss`, the shifted cross-entropy -- logits[:, :-1] against labels[:, 1:], the
+        mean of -log p over the labels != -100 (summed on the host in float64, returned as an fp32 scalar; NaN when nothing is counted, as
+        CrossEntropyLoss gives). `.token_logprobs` [B, T] float32 (no reference counterpart): log p(labels[b, t] | input_ids[b, :t]) where
+        labels[b, t] != -100 and t >= 1, 0 elsewhere. attention_mask=None attends every position, as the reference does. labels=None scores
+        nothing and returns the logits. return_logits=False (no reference counterpart) is the cheap path for the loss alone: only the scored
+        rows pass the lm_head and `.logits` is None. return_dict=False: the reference's tuple, (loss, logits) or (logits,).
+        Not built: past_key_values and inputs_embeds (ValueError)."""
+        if past_key_values is not None or inputs_embeds is not None:
+            raise ValueError("forward(past_key_values=) / forward(inputs_embeds=) are not built: pass the whole sequence as input_ids")
+        if input_ids is None or input_ids.dim() != 2:
+            raise ValueError("You have to specify input_ids of shape [batch, seq]")
+        B, T = input_ids.shape
+        lab = None
+        if labels is not None:
+            lab = torch.as_tensor(labels).detach().to("cpu", torch.int64)
+            if tuple(lab.shape) != (B, T):
+                raise ValueError(f"labels of shape {tuple(lab.shape)} do not match input_ids of shape {(B, T)}")
+            bad = (lab != -100) & ((lab < 0) | (lab >= self.lcfg.vocab))
+            if bool(bad.any()):
+                raise ValueError(f"label {int(lab[bad][0])} is outside the vocabulary [0, {self.lcfg.vocab}) and is not -100")
+        if attention_mask is not None and tuple(attention_mask.shape) != (B, T):
+            raise ValueError(f"attention_mask of shape {tuple(attention_mask.shape)} does not match input_ids of shape {(B, T)}")
+        if lab is None and not return_logits:
+            raise ValueError("forward(labels=None, return_logits=False) asks for nothing")
+        embs = self._image_embs(B, dicom, use_img, qformer_embs)
+        if embs is not None and tuple(embs.shape) != (B, 32, self.lcfg.qformer_dim):
+            raise ValueError(f"image embeddings should be of size {(B, 32, self.lcfg.qformer_dim)}, but are {tuple(embs.shape)}")
+        self._ensure_engine()
+        mask = torch.ones(B, T, dtype=torch.int32) if attention_mask is None else attention_mask
+        # the shift: position t is scored against labels[t] from the logits of t - 1; position 0 has no predecessor (the engine ignores labels[:, 0])
+        eng_labels = torch.full((B, T), -100, dtype=torch.int32) if lab is None else lab.to(torch.int32)
+        logprob, _, logits = self._engine.score(input_ids, embs, eng_labels, mask=mask, want_top1=False, want_logits=bool(return_logits))
+        loss = None
+        if lab is not None:
+            counted = lab[:, 1:] != -100
+            n = int(counted.sum())
+            total = float(logprob[:, 1:].double().cpu()[counted].sum())
+            loss = torch.tensor(-total / n if n else float("nan"), dtype=torch.float32, device=logprob.device)
+        if not return_dict:
+            return (logits,) if loss is None else (loss, logits)
+        return CausalLMOutput(loss=loss, logits=logits, token_logprobs=logprob if lab is not None else None)
+
+    __call__ = forward
+
+
+class CausalLMOutput(SimpleNamespace):
+    """`.loss`, `.logits` like transformers' CausalLMOutputWithPast; `.token_logprobs` on top."""
+
+
 def _sampling_of(do_sample, num_beams, temperature, top_k, top_p, seed, other):
     """generate()'s sampling arguments as an engine.Sampling, or None for do_sample=False. The checks are those of transformers 4.28.1's
     _get_logits_warper and its warper classes: a value that switches a warper off there (temperature 1, top_k 0, top_p 1) does so here."""
@@ -361,6 +416,12 @@ class PeftModelForCausalLM:
 
     def generate(self, **kw):
         return self.base_model.model.generate(**kw)
+
+    def forward(self, *a, **kw):
+        return self.base_model.model.forward(*a, **kw)
+
+    def __call__(self, *a, **kw):
+        return self.base_model.model.forward(*a, **kw)
 
 
 def _load_hf_dir(path: str):
