@@ -25,12 +25,23 @@ enum { RDX_DTYPE_F16 = 0, RDX_DTYPE_BF16 = 1 };
 enum { RDX_W_GEMM = 0,   /* [rows=N][cols=K] fp32 -> model dtype, re-laid-out into MFMA fragment order            */
        RDX_W_TENSOR = 1, /* [rows][cols] fp32 -> model dtype, row-major (embeddings, norm weights, LoRA B, RoPE)    */
        RDX_W_F32 = 2,    /* [rows][cols] fp32 kept as fp32 (biases, LayerNorm gamma/beta)                           */
-       RDX_W_GEMM_FP8 = 3 }; /* quantised to OCP e4m3 with one absmax/448 scale per output row and stored ONLY in that
+       RDX_W_GEMM_FP8 = 3, /* quantised to OCP e4m3 with one absmax/448 scale per output row and stored ONLY in that
                             * form (64-deep MFMA fragment order): prefill and batch >= 3 decode multiply fp8 x fp8
                             * (activations e4m3 with a scale per row and K group), batch <= 2 expands the bytes in
                             * registers; a shape without an fp8 kernel makes the call return -8, there is no
                             * dequantised copy to fall back to (BASELINE configs[4]). The 2r LoRA-A rows ride the QKV weight
                             * and are therefore e4m3 too (own row scales, e4m3 input); only LoRA-B is a model-dtype epilogue */
+       RDX_W_GEMM_W4 = 4 };  /* int4 group-quantised (W4A16; the format: radialog_amd/w4.py): groups of 128 k of one row, symmetric,
+                            * s = T(absmax / 7), q = clamp(rint(w / s), -8, 7). int4 is a STORAGE format of the batch <= 2 step's weight
+                            * stream, not an arithmetic: the weight IS its dequantised value W' = T(q s). The library keeps a fragment-packed
+                            * model-dtype copy of W', which prefill, batch >= 3, scoring, beam search and the append calls multiply with the
+                            * kernels of RDX_W_GEMM, and for gate/up, down_proj and QKV the int4 stream (4.125 bits per weight), which the
+                            * batch <= 2 step decodes to exactly W' in registers: the same bits as a RDX_W_GEMM context loaded with W'. Rows
+                            * of "l<i>.wqkv" from 3 * hidden on (the 2r LoRA-A rows) are NOT quantised (W' = T(W)); their tiles stream raw.
+                            * o_proj is quantised as a model weight but still streams its packed W' bytes inside the fused attention
+                            * launch, and the lm_head is meant to stay RDX_W_GEMM. Returns -8 with a message in an f16 context (not built),
+                            * for K % 128 != 0 and in a context that also holds RDX_W_GEMM_FP8 weights; -1 for an Inf / NaN weight. Not
+                            * built: batch >= 3 / prefill int4 kernels, pre-quantised GPTQ / AWQ tensors, zero points. */
 
 typedef struct rdx_config {
     int dtype;                                     /* RDX_DTYPE_* : arithmetic type of weights/activations         */
@@ -249,7 +260,8 @@ int rdx_time(rdx_ctx* ctx, int what, int iters, float* ms_host);
  * family of xs16.hip (1, default) or on the 32-row family (0; RDX_XS16), "prompt_blk" = one prompt's K = 4096 projections on 32-row blocks (1, default) or on
  * the weight-stationary kernel (0; RDX_PBLK), "wcode" = the batch <= 2 decode step of a bf16 context streams the 13-bit coded copies of its gate/up, down_proj,
  * QKV and lm_head weights (1, default) or the raw packed ones (0); the results are the same bits either way, a captured step graph is dropped (no
- * environment variable), "score_chunk" = logits rows per lm_head launch of the scoring pass (default 2048, the fastest of 128 / 512 / 2048 / all on 3382 rows: profiles/r11_score.md; 0 = all rows of a call at once; negative values
+ * environment variable), "w4" = likewise for RDX_W_GEMM_W4 weights: the batch <= 2 step streams the int4 copies of gate/up, down_proj and QKV (1, default) or
+ * the packed bytes of their dequantised values (0); the same bits, a captured step graph is dropped, "score_chunk" = logits rows per lm_head launch of the scoring pass (default 2048, the fastest of 128 / 512 / 2048 / all on 3382 rows: profiles/r11_score.md; 0 = all rows of a call at once; negative values
  * return -1). Unknown names return -1. No reference counterpart.
  * At batch 3-16 on the xs16 family rdx_time units 1-5 time THOSE kernels (the RMSNorm is their prologue); max_batch > 32 needs the Vicuna-7B widths
  * (hidden 4096, inter 11008): rdx_finalize_weights refuses other models with more than 32 rows. */

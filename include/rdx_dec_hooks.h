@@ -105,6 +105,17 @@ int rdx_wcode_test(rdx_ctx* ctx, const float* W, int N, int K, void* packed_out,
  * how a test sees that the coded kernels, and not their raw twins, ran. out holds 5 values. */
 int rdx_wcode_stats(rdx_ctx* ctx, long long* out);
 
+/* The device quantiser of the int4 group-quantised weights alone (csrc/gemm.hip quant_w4_k; the format: radialog_amd/w4.py): W fp32 [N][K] (device) is
+ * quantised as rdx_set_weight(RDX_W_GEMM_W4) does it, every tile int4 (rows padded to whole tiles of 16). wprime_out: the packed bf16 buffer of the
+ * dequantised weight [Npad / 16][K / 32][64][8]; stream_out: (Npad / 16) (K / 128) 1056 bytes; scales_out: the bf16 scale bits as they stand in the
+ * stream, [Npad / 16][K / 128][16 rows]. All device pointers. Returns -8 outside a bf16 context or for K % 128 != 0, -1 for an Inf / NaN weight. */
+int rdx_w4_test(rdx_ctx* ctx, const float* W, int N, int K, void* wprime_out, void* stream_out, void* scales_out);
+/* The int4 streams a finalized decoder holds (RDX_W_GEMM_W4: every gate/up, down_proj and QKV): out[0] = their int4 16-row tiles, out[1] = their raw
+ * tiles (the LoRA-A rows of the fused QKV weights: the kernels stream the packed bf16 bytes of these), out[2] = bytes of streams and headers,
+ * out[3] / out[4] = launches of skinny_gemm_w4_k / decode_chain_w4_k this context has issued so far (a captured step graph counts once, at capture).
+ * out holds 5 values. */
+int rdx_w4_stats(rdx_ctx* ctx, long long* out);
+
 #ifdef __cplusplus
 }
 #endif

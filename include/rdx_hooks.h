@@ -39,7 +39,10 @@ int rdx_gemv_trace(rdx_ctx* ctx, int what, int layer, long long* host, int max_t
  * force 4 / 6 hold the fp8 weights as the engine does (e4m3 bytes + scales only): batch >= 3 shapes multiply fp8 x fp8.
  * 12 = the skinny GEMV on CODED bf16 weights (13 bits per weight, decoded exactly in registers: radialog_amd/wcode.py): the hook encodes the packed W
  * itself, as rdx_finalize_weights does for the batch <= 2 step; bf16 contexts, M <= 2, K % 128 == 0, epi 0 / 3 / 4 (the logits epilogue: rdx_logits_test); the same bits as force 1.
- * force 1 and 12 accept any N > 0 (rows are padded to whole tiles of 16, as the loader pads them); every other force needs N % 16 == 0.
+ * 13 = the skinny GEMV on int4 group-quantised weights (radialog_amd/w4.py): the hook quantises W itself, as rdx_set_weight(RDX_W_GEMM_W4) does, and streams
+ * the nibbles; the constraints of force 12, epi 0 / 3 / 4; the same bits as force 1 on the dequantised weight. 14 = the same with the tile of rows 16..31
+ * left raw (not quantised: its packed bf16 bytes are streamed, as the LoRA-A tiles of a fused QKV weight are; N >= 48).
+ * force 1 and 12 - 14 accept any N > 0 (rows are padded to whole tiles of 16, as the loader pads them); every other force needs N % 16 == 0.
  * Test / benchmark hook. */
 int rdx_gemm_test(rdx_ctx* ctx, const void* X, const float* W, const float* bias, const void* resid, void* out, int M, int N,
                   int K, int epi, const void* norm_w, float eps, int force);

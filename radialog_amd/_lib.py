@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("RDX_LIB_PATH") or os.path.join(HERE, "librdx.so")
 HOOKS_PATH = os.environ.get("RDX_HOOKS_PATH") or os.path.join(HERE, "librdx_hooks.so")
 
 RDX_DTYPE_F16, RDX_DTYPE_BF16 = 0, 1
-RDX_W_GEMM, RDX_W_TENSOR, RDX_W_F32, RDX_W_GEMM_FP8 = 0, 1, 2, 3
+RDX_W_GEMM, RDX_W_TENSOR, RDX_W_F32, RDX_W_GEMM_FP8, RDX_W_GEMM_W4 = 0, 1, 2, 3, 4
 RDX_SRC_F32, RDX_SRC_F16, RDX_SRC_BF16 = 0, 1, 2
 
 
@@ -140,6 +140,8 @@ DEC_HOOK_SYMBOLS = {
     "rdx_rope_kv_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
     "rdx_wcode_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_wcode_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "rdx_w4_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "rdx_w4_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
 }
 ALL_HOOK_SYMBOLS = {**HOOK_SYMBOLS, **ENC_HOOK_SYMBOLS, **DEC_HOOK_SYMBOLS}
 

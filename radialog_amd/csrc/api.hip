@@ -130,12 +130,45 @@ extern "C" int rdx_set_weight(rdx_ctx* c, const char* name, const float* data, i
         c->gemm[key] = w;
     } else if (kind == RDX_W_GEMM_FP8) {
         if (cols % 64) return fail(c, -1, "rdx_set_weight(%s): fp8 GEMM K=%lld must be a multiple of 64", name, (long long)cols);
+        if (c->has_w4_w) return fail(c, -8, "rdx_set_weight(%s): RDX_W_GEMM_FP8 in a context that holds RDX_W_GEMM_W4 weights (the two do not mix)", name);
+        c->has_fp8_w = true;
         if (c->gemm.count(key)) return fail(c, -1, "rdx_set_weight(%s): duplicate", name);
         GemmW w;
         w.N = (int)rows; w.K = (int)cols; w.Npad = (int)((rows + 15) / 16 * 16);
         ALLOC(c, w.w8, (size_t)w.Npad * w.K);                     // the ONLY copy: e4m3 bytes + one scale per row (w.w stays null)
         ALLOC(c, w.scale, (size_t)w.Npad * sizeof(float));
         launch_pack_weight_fp8(c->cfg.dtype, data, w.w8, w.scale, nullptr, w.N, w.K, w.Npad, c->stream);
+        c->gemm[key] = w;
+    } else if (kind == RDX_W_GEMM_W4) {
+        // int4 group-quantised (radialog_amd/w4.py): the weight becomes its dequantised value W' -- a packed model-dtype copy like RDX_W_GEMM's, which
+        // everything but the batch <= 2 step reads -- plus the int4 stream of the batch <= 2 GEMV (rdx_finalize_weights drops the streams no unit reads)
+        if (c->cfg.dtype != DT_BF16) return fail(c, -8, "rdx_set_weight(%s): RDX_W_GEMM_W4 needs a bf16 context (f16 is not built)", name);
+        if (cols % W4_CHUNK_K) return fail(c, -8, "rdx_set_weight(%s): int4 GEMM K=%lld must be a multiple of %d (the quantisation group)", name, (long long)cols, W4_CHUNK_K);
+        if (c->has_fp8_w) return fail(c, -8, "rdx_set_weight(%s): RDX_W_GEMM_W4 in a context that holds RDX_W_GEMM_FP8 weights (the two do not mix)", name);
+        if (c->gemm.count(key)) return fail(c, -1, "rdx_set_weight(%s): duplicate", name);
+        GemmW w;
+        w.N = (int)rows; w.K = (int)cols; w.Npad = (int)((rows + 15) / 16 * 16);
+        // the fused QKV weight of a decoder layer ("l<i>.wqkv": q, k, v rows, then the 2r LoRA-A rows): the tiles from row 3 * hidden on stay raw
+        int raw_lo = w.Npad;
+        const size_t nl = strlen(name);
+        if (c->cfg.enable_llama && name[0] == 'l' && nl > 5 && !strcmp(name + nl - 5, ".wqkv") && rows > 3 * (int64_t)c->cfg.hidden) {
+            if ((3 * c->cfg.hidden) % 16) return fail(c, -8, "rdx_set_weight(%s): 3 * hidden = %d is no multiple of 16: a tile would be part int4, part raw", name, 3 * c->cfg.hidden);
+            raw_lo = 3 * c->cfg.hidden;
+        }
+        ALLOC(c, w.w, (size_t)w.Npad * w.K * esz(c));
+        ALLOC(c, w.w4, w4_bytes(w.Npad, w.K));
+        ALLOC(c, w.w4h, (size_t)(w.Npad / 16) * sizeof(unsigned));
+        if (!c->w4_bad) ALLOC(c, c->w4_bad, sizeof(int));
+        HIPCHK(c, hipMemsetAsync(c->w4_bad, 0, sizeof(int), c->stream));
+        launch_quant_w4(data, w.w, w.w4, w.w4h, c->w4_bad, w.N, w.K, w.Npad, raw_lo, w.Npad, c->stream);
+        int bad = 0;
+        HIPCHK(c, hipMemcpyAsync(&bad, c->w4_bad, sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (bad) {
+            dfree(c, w.w); dfree(c, w.w4); dfree(c, w.w4h);
+            return fail(c, -1, "rdx_set_weight(%s): RDX_W_GEMM_W4: the weight holds an Inf or a NaN", name);
+        }
+        c->has_w4_w = true;
         c->gemm[key] = w;
     } else if (kind == RDX_W_TENSOR) {
         if (c->tens.count(key)) return fail(c, -1, "rdx_set_weight(%s): duplicate", name);
@@ -239,6 +272,10 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
             }
         }
         if (R.rc) return R.rc;
+        // int4 streams (RDX_W_GEMM_W4) are read by the batch <= 2 step's gate/up, down_proj and QKV units; o_proj streams the packed bytes of its
+        // dequantised weight inside the fused attention launch, and nothing else has an int4 kernel: those streams are dropped
+        for (int l = 0; l < f.layers; ++l) { dfree(c, c->ll[l].wo.w4); dfree(c, c->ll[l].wo.w4h); }
+        dfree(c, c->lm_head.w4); dfree(c, c->lm_head.w4h);
         // Coded bf16 copies (rdx_common.h WcChunk) of what the batch <= 2 step streams outside the fused attention launch: every gate/up and down_proj,
         // the QKV of layers 1.. (the chained launch's second role) and the lm_head. Layer 0's stand-alone QKV measured no lower coded and stays raw. Encoded from the PACKED buffers, which stay (prefill, batch >= 3 and the tiles the code cannot express read them).
         // The dispatch rule of the coded path, first half (the second is coded_unit / step_chained): bf16, NOT the fp8-weight mode, both K multiples of
@@ -247,7 +284,7 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
         LlamaDims probe = {}; probe.hidden = H; probe.heads = f.heads; probe.head_dim = 128;
         if (f.dtype == DT_BF16 && !fp8_mode && H % WC_CHUNK_K == 0 && I % WC_CHUNK_K == 0 && chain_supported(probe, I, 1)) {
             auto encode = [&](GemmW& W) -> int {
-                if (!W.w || W.wc) return 0;
+                if (!W.w || W.wc || W.w4) return 0;       // (a weight with an int4 stream gets no coded copy)
                 ALLOC(c, W.wc, wc_bytes(W.Npad, W.K));
                 ALLOC(c, W.wch, (size_t)(W.Npad / 16) * sizeof(unsigned));
                 launch_encode_wc(W.w, W.wc, W.wch, W.Npad, W.K, c->stream);
@@ -388,7 +425,7 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
 // Test / experiment switches of one context (read from the environment once, at rdx_create): "flash_min" = workgroups from which the batched
 // prefill attention takes flash_prefill_k (0 = never, 1 = always; RDX_FLASH_MIN), "pconv" = the encoder on fragment-packed activations (RDX_PCONV),
 // "xs16" = batch 3-16 decode on the one-row-tile family (RDX_XS16), "prompt_blk" = one prompt's K = 4096 projections on 32-row blocks (RDX_PBLK),
-// "wcode" = the batch <= 2 step streams the coded bf16 weights (no environment variable: on unless switched off here).
+// "wcode" = the batch <= 2 step streams the coded bf16 weights (no environment variable: on unless switched off here), "w4" = ... the int4 streams.
 extern "C" int rdx_set_option(rdx_ctx* c, const char* name, int value) {
     if (!c || !name) return -1;
     if (!strcmp(name, "flash_min")) { c->flash_min = value; return 0; }
@@ -396,6 +433,11 @@ extern "C" int rdx_set_option(rdx_ctx* c, const char* name, int value) {
     if (!strcmp(name, "prompt_blk")) { c->prompt_blk = value != 0; return 0; }
     if (!strcmp(name, "xs16")) {          // batch 3-16 decode family (xs16.hip) on / off; a captured step graph of the other family is dropped
         c->xs16 = value != 0;
+        if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; c->gkey = GraphKey(); }
+        return 0;
+    }
+    if (!strcmp(name, "w4")) {            // likewise for int4 group-quantised weights: their int4 streams (on) or the packed bytes of their dequantised values; same bits
+        c->w4 = value != 0;
         if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; c->gkey = GraphKey(); }
         return 0;
     }

@@ -86,6 +86,7 @@ extern "C" int rdx_gemv_trace(rdx_ctx* c, int what, int layer, long long* host, 
     if ((a.N + 15) / 16 > max_tiles) { hipFree(dtr); return fail(c, -1, "rdx_gemv_trace: need room for %d tiles", (a.N + 15) / 16); }
     a.trace = dtr;
     if (what == 1) a = coded_unit(c, a, L.wgu, B);                    // as the step launches them: on the coded bf16 copy where it streams one
+    if (what == 1 || what == 2) a = w4_unit(c, a, what == 1 ? L.wgu : L.wqkv, B);      // ... or on the int4 stream
     skinny(c, a, what == 1 ? EPI_SILU_MUL : EPI_NONE);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(host, dtr, bytes, hipMemcpyDeviceToHost);
@@ -259,7 +260,7 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
                              int M, int N, int K, int epi, const void* norm_w, float eps, int force) {
     if (!c || !X || !W || !out) return fail(c, -1, "rdx_gemm_test: null argument");
     // the GEMV forces (1, 12) pad N to whole 16-row tiles themselves (zero rows, as the engine's loader does); every other kernel needs N % 16 == 0
-    const bool gemv = force == 1 || force == 12;
+    const bool gemv = force == 1 || force == 12 || force == 13 || force == 14;
     if (K % 32 || (N % 16 && !gemv) || N <= 0) return fail(c, -1, "rdx_gemm_test: need K %% 32 == 0 and N %% 16 == 0");
     HIPCHK(c, hipSetDevice(c->device));
     GemmW w;
@@ -271,6 +272,16 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
         void* planes = nullptr; unsigned* hdr = nullptr;
         ~Coded() { if (planes) hipFree(planes); if (hdr) hipFree(hdr); }
     } coded;
+    if (force == 13 || force == 14) {
+        if (c->cfg.dtype != DT_BF16 || K % W4_CHUNK_K || M >= xs_min_rows() || !skinny_fits_lds(M, K) || (force == 14 && N < 48)) {
+            hipFree(wp);
+            return fail(c, -1, "rdx_gemm_test: force 13 / 14 (int4 weights) needs a bf16 context, K %% 128 == 0 and M <= 2 rows that fit the GEMV's LDS stage (14: N >= 48)");
+        }
+        if (hipMalloc(&coded.planes, w4_bytes(w.Npad, K) + 16) != hipSuccess || hipMalloc((void**)&coded.hdr, (size_t)(w.Npad / 16) * sizeof(unsigned)) != hipSuccess) {
+            hipFree(wp);
+            return fail(c, -2, "rdx_gemm_test: out of device memory");
+        }
+    }
     if (force == 12) {
         if (c->cfg.dtype != DT_BF16 || K % WC_CHUNK_K || M >= xs_min_rows() || !skinny_fits_lds(M, K)) {
             hipFree(wp);
@@ -312,11 +323,21 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
         w.scale = (float*)((char*)wp + (size_t)N * K * 3);
         launch_pack_weight_fp8(c->cfg.dtype, W, w.w8, w.scale, nullptr, N, K, N, c->stream);
         force = 1;
+    } else if (force == 13 || force == 14) {
+        // quantised here as rdx_set_weight(RDX_W_GEMM_W4) does it: wp becomes the packed copy of the dequantised weight (what a raw tile streams)
+        int* badf = (int*)((char*)coded.planes + w4_bytes(w.Npad, K));
+        hipMemsetAsync(badf, 0, sizeof(int), c->stream);
+        launch_quant_w4(W, wp, coded.planes, coded.hdr, badf, N, K, w.Npad, force == 14 ? 16 : w.Npad, force == 14 ? 32 : w.Npad, c->stream);
     } else
     launch_pack_weight(c->cfg.dtype, W, wp, N, K, w.Npad, nullptr, c->stream);
     GemmArgs a = gargs(X, K, w, bias, out, epi == EPI_SILU_MUL ? N / 2 : N, M);
     a.resid = resid; a.ldr = N;
     a.norm_w = norm_w; a.eps = eps;
+    if (force == 13 || force == 14) {      // the skinny GEMV on the int4 stream
+        a.W4 = coded.planes; a.w4hdr = coded.hdr;
+        if (!skinny_w4_supported(c->cfg.dtype, a, epi)) { hipFree(wp); return fail(c, -1, "rdx_gemm_test: force %d: no int4 GEMV for epilogue %d", force, epi); }
+        force = 1;
+    }
     if (force == 12) {      // the skinny GEMV on the coded copy of the packed buffer (what rdx_finalize_weights builds for the batch <= 2 step)
         launch_encode_wc(wp, coded.planes, coded.hdr, w.Npad, K, c->stream);
         a.WC = coded.planes; a.wchdr = coded.hdr;

@@ -392,3 +392,45 @@ extern "C" int rdx_wcode_stats(rdx_ctx* c, long long* out) {
     }
     return 0;
 }
+
+extern "C" int rdx_w4_test(rdx_ctx* c, const float* W, int N, int K, void* wprime_out, void* stream_out, void* scales_out) {
+    if (!c || !W || !wprime_out || !stream_out || !scales_out || N <= 0 || K <= 0) return fail(c, -1, "rdx_w4_test: bad arguments");
+    if (c->cfg.dtype != DT_BF16 || K % W4_CHUNK_K) return fail(c, -8, "rdx_w4_test: int4 weights need a bf16 context and K %% 128 == 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int npad = (N + 15) / 16 * 16;
+    char* tmp = nullptr;        // header words + the quantiser's non-finite flag
+    HIPCHK(c, hipMalloc((void**)&tmp, (size_t)(npad / 16) * sizeof(unsigned) + sizeof(int)));
+    int* badf = (int*)(tmp + (size_t)(npad / 16) * sizeof(unsigned));
+    hipMemsetAsync(badf, 0, sizeof(int), c->stream);
+    launch_quant_w4(W, wprime_out, stream_out, (unsigned*)tmp, badf, N, K, npad, npad, npad, c->stream);
+    // the scales as they stand in the stream: the 32 bytes behind every chunk's nibbles
+    hipMemcpy2DAsync(scales_out, 32, (const char*)stream_out + 1024, W4_CHUNK_BYTES, 32, (size_t)(npad / 16) * (K / W4_CHUNK_K), hipMemcpyDeviceToDevice, c->stream);
+    int bad = 0;
+    hipMemcpyAsync(&bad, badf, sizeof(int), hipMemcpyDeviceToHost, c->stream);
+    const int rc = finish(c);
+    hipFree(tmp);
+    if (rc) return rc;
+    if (bad) return fail(c, -1, "rdx_w4_test: the weight holds an Inf or a NaN");
+    return 0;
+}
+
+extern "C" int rdx_w4_stats(rdx_ctx* c, long long* out) {
+    if (!c || !out || !c->finalized) return fail(c, -1, "rdx_w4_stats: a finalized context and an output are needed");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    out[0] = out[1] = out[2] = 0;
+    out[3] = c->n_w4_gemv; out[4] = c->n_w4_chain;
+    if (!c->cfg.enable_llama) return 0;
+    for (const LlamaLayer& L : c->ll)
+        for (const GemmW* W : {&L.wqkv, &L.wo, &L.wgu, &L.wdown}) {
+            if (!W->w4 || !W->w4h) continue;
+            const int nt = W->Npad / 16;
+            std::vector<unsigned> h(nt);
+            HIPCHK(c, hipMemcpy(h.data(), W->w4h, (size_t)nt * sizeof(unsigned), hipMemcpyDeviceToHost));
+            long long raw = 0;
+            for (unsigned v : h) raw += (v >> 8) & 1u;
+            out[0] += nt - raw; out[1] += raw;
+            out[2] += (long long)w4_bytes(W->Npad, W->K) + (long long)nt * 4;
+        }
+    return 0;
+}

@@ -58,6 +58,12 @@ GemmArgs coded_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B) {
     return a;
 }
 
+// The int4 stream of a unit's weight (GemmW::w4, RDX_W_GEMM_W4) instead of the packed bf16 copy of its dequantised values: the same rule.
+GemmArgs w4_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B) {
+    if (c->w4 && W.w4 && W.w4h && decode_family(c, B) == DEC_CHAINED) { a.W4 = W.w4; a.w4hdr = W.w4h; }
+    return a;
+}
+
 GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     GemmArgs a = unit_args(c, L, u, B);
     if (u == UNIT_GATE_UP) a.out_packed = ACT_BLK32;
@@ -143,7 +149,8 @@ void skinny(rdx_ctx* c, GemmArgs a, int epi) {
             return;
         }
     }
-    if (skinny_wc_supported(c->cfg.dtype, a, epi) && !xstat32_supported(a, epi)) ++c->n_wc_gemv;       // launch_skinny_gemm's own choice, counted for the tests
+    if (skinny_w4_supported(c->cfg.dtype, a, epi) && !xstat32_supported(a, epi)) ++c->n_w4_gemv;
+    else if (skinny_wc_supported(c->cfg.dtype, a, epi) && !xstat32_supported(a, epi)) ++c->n_wc_gemv;       // launch_skinny_gemm's own choice, counted for the tests
     launch_skinny_gemm(c->cfg.dtype, a, epi, c->stream);
 }
 

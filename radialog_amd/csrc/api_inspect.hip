@@ -117,6 +117,7 @@ extern "C" int rdx_time(rdx_ctx* c, int what, int iters, float* ms_host) {
                     GemmArgs a = unit_args(c, L, u, B);
                     // as the step launches them: on the coded bf16 copy where it streams one (batch <= 2 chained family, "wcode" on)
                     if (u != UNIT_QKV) a = coded_unit(c, a, u == UNIT_GATE_UP ? L->wgu : c->lm_head, B);      // (layer 0's stand-alone QKV is raw in the step)
+                    if (u == UNIT_QKV || u == UNIT_GATE_UP) a = w4_unit(c, a, u == UNIT_QKV ? L->wqkv : L->wgu, B);            // ... or on the int4 stream ("w4" on)
                     if (hoisted) { a = prenormed(c, a); a.xpacked = pn.xpacked; a.xscale = pn.xscale; a.xgroups = pn.xgroups; }
                     launch_skinny_gemm(dt, a, epi, c->stream);
                 }

@@ -487,10 +487,12 @@ static void step_chained(rdx_ctx* c, int B, std::vector<hipEvent_t>* evs) {
     auto mark = [&] { if (evs) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, s); evs->push_back(e); } };
     // gate/up and the lm_head stream the coded bf16 copies of their weights where those exist (coded_unit), the chained launch likewise (ca.wc);
     // layer 0's QKV (one launch per step, three workgroups per CU: 18.0 / 18.5 us raw, 18.7 / 18.6 coded) and o_proj stay raw
-    skinny(c, unit_args(c, &L0, UNIT_QKV, B), EPI_NONE);
+    // int4 group-quantised weights (RDX_W_GEMM_W4, "w4" on): layer 0's QKV, gate/up and both roles of the chained launch stream their int4 copies
+    // (w4_unit, ca.wc = 2); o_proj streams the packed bytes of its dequantised weight, the lm_head is not quantised
+    skinny(c, w4_unit(c, unit_args(c, &L0, UNIT_QKV, B), L0.wqkv, B), EPI_NONE);
     for (int l = 0; l < f.layers; ++l) {
         attn_oproj(c, l, B);
-        skinny(c, coded_unit(c, unit_args(c, &c->ll[l], UNIT_GATE_UP, B), c->ll[l].wgu, B), EPI_SILU_MUL);
+        skinny(c, w4_unit(c, coded_unit(c, unit_args(c, &c->ll[l], UNIT_GATE_UP, B), c->ll[l].wgu, B), c->ll[l].wgu, B), EPI_SILU_MUL);
         mark();
         ca.layer = l;
         {       // the layer's pointers by value: down_proj of l, norm + QKV of l + 1 (the last launch has no QKV role)
@@ -503,6 +505,12 @@ static void step_chained(rdx_ctx* c, int B, std::vector<hipEvent_t>* evs) {
             ca.wc = (c->wcode && !ca.w8 && L.wdown.wc && L.wdown.wch && (!Ln || (Ln->wqkv.wc && Ln->wqkv.wch))) ? 1 : 0;
             ca.cdown = L.wdown.wc; ca.hdown = L.wdown.wch;
             ca.cqkv = Ln ? Ln->wqkv.wc : nullptr; ca.hqkv = Ln ? Ln->wqkv.wch : nullptr;
+            if (c->w4 && !ca.w8 && f.dtype == DT_BF16 && L.wdown.w4 && L.wdown.w4h && (!Ln || (Ln->wqkv.w4 && Ln->wqkv.w4h))) {       // decode_chain_w4_k
+                ca.wc = 2;
+                ca.cdown = L.wdown.w4; ca.hdown = L.wdown.w4h;
+                ca.cqkv = Ln ? Ln->wqkv.w4 : nullptr; ca.hqkv = Ln ? Ln->wqkv.w4h : nullptr;
+                ++c->n_w4_chain;
+            } else
             if (ca.wc && f.dtype == DT_BF16) ++c->n_wc_chain;
         }
         ca.trace = l == c->chain_trace_layer ? c->chain_trace : nullptr;

@@ -53,7 +53,7 @@ template <typename WaitFn> struct ChainLate { ChainGemm a; WaitFn wait; long lon
 // Wb, K, wg, ntiles: from preloaded kernel arguments. late(): the rest (ChainLate), built from kernel arguments that are loaded only now (late_kernarg)
 // WC: Wb is the coded bf16 copy of the weight (rdx_common.h WcChunk): the ring holds U / 2 coded chunks (the 2 U packed chunks of the raw ring at 13/16 of
 // the bytes), decoded in registers into the fragments the raw ring holds, in the same order: the sums do not change. As skinny_body.h.
-template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false, bool WC = false, typename Late>
+template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false, int WC = 0, typename Late>
 __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const int K, const int wg, const int ntiles, unsigned char* smem, Late late) {
     typedef typename Vec8<T>::type V8;
     constexpr int WPS = CH_WAVES / SUB;           // waves per tile
@@ -75,10 +75,11 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
     // WC: the slice stays [c0, c1) in PACKED chunks; the coded chunks [q0, q1) cover it, the first and the last may reach into the neighbours' (down_proj:
     // 344 chunks over 16 waves), whose fragments multiply the zero line behind the staged rows
     static_assert(!WC || (!W8 && U % 2 == 0), "coded weights: model dtype");
-    constexpr int RC = U / 2;
+    typedef Coded<WC> CD;         // WC = 2: the int4 stream (rdx_common.h W4Chunk), rings of four chunks (8 loads) in both roles
+    constexpr int RC = WC == 2 ? 4 : U / 2;
     const int KQ = K >> 7, q0 = c0 >> 2, q1 = c1 > c0 ? (c1 + 3) >> 2 : q0, qlast = min(max(q1 - 1, q0), KQ - 1);
-    const unsigned char* cb16 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile_c * KQ * WC_CHUNK_BYTES + lane * 16;
-    const unsigned char* cb4 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile_c * KQ * WC_CHUNK_BYTES + 3072 + lane * 4;
+    const unsigned char* cb16 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile_c * KQ * CD::BYTES + lane * 16;
+    const unsigned char* cb4 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile_c * KQ * CD::BYTES + CD::off2(lane);
     // Everything up to here comes from preloaded kernel arguments, the workgroup id and the lane id: the ring below is issued with no scalar load
     // in front of it. The entry time is taken unconditionally (one scalar instruction, nothing waits for it before the ring is out) because the
     // trace pointer is one of the arguments that are only loaded behind the ring.
@@ -87,10 +88,10 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
     // two register batches (A, B) in flight before anything else; the main loop ping-pongs between them (no register
     // rotation: a rotated pair makes the compiler wait for the batch it has just issued)
     u4 wa_[U], wb_[U];
-    WcChunk cring[RC];
+    typename CD::Chunk cring[RC];
     if constexpr (WC) {
 #pragma unroll
-        for (int u = 0; u < RC; ++u) { const size_t o = (size_t)min(q0 + u, qlast) * WC_CHUNK_BYTES; cring[u] = wc_load(cb16 + o, cb4 + o); }
+        for (int u = 0; u < RC; ++u) { const size_t o = (size_t)min(q0 + u, qlast) * CD::BYTES; cring[u] = CD::load(cb16 + o, cb4 + o); }
     } else {
 #pragma unroll
         for (int u = 0; u < U; ++u) wa_[u] = ldg16_nt(wbase + (size_t)min(c0 + u, clast) * 64);
@@ -111,7 +112,7 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
 #define CH_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
     if (trc) trc[0] = t_entry;
     if (trace) {        // traced launches only: wave 0 watches its first KiB come back (it stalls here, which a product launch never does)
-        if (threadIdx.x < 64) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(WC ? 4 * RC - 1 : 2 * U - 1) : "memory");
+        if (threadIdx.x < 64) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(WC ? CD::LOADS * RC - 1 : 2 * U - 1) : "memory");
         CH_T(5);
     }
 
@@ -248,7 +249,7 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             // a tile the code cannot express (wave-uniform, once per tile): the coded ring is dropped and the raw loop runs on the packed copy, in four
             // of the ring's registers (a rare path; registers of its own would be carried through it)
             const u4* wraw = reinterpret_cast<const u4*>(lt.wraw) + (size_t)tile_c * KC * 64 + lane;
-            auto slot = [&](int u) -> u4& { return u == 0 ? cring[0].lo0 : u == 1 ? cring[0].lo1 : u == 2 ? cring[0].ix : cring[1].lo0; };
+            auto slot = [&](int u) -> u4& { return CD::slot(cring, u); };
 #pragma unroll
             for (int u = 0; u < 4; ++u) slot(u) = ldg16_nt(wraw + (size_t)min(c0 + u, clast) * 64);
             int cb = c0;
@@ -269,7 +270,7 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             // guard (first trip and tail only): fragments outside [c0, c1) read the zero line. Exact because (1) every weight of an unflagged tile is
             // finite, so the products are zeros; (2) the fp32 accumulator starts at +0 and a sum is -0 only if all its terms are, so it is never -0 and
             // x + (+-0) = x leaves its bits alone; (3) an MFMA whose 32 products are all zero returns its accumulator operand.
-            auto consumeC = [&](const WcChunk& ch, int q, bool guard) {
+            auto consumeC = [&](const typename CD::Chunk& ch, int q, bool guard) {
                 auto one = [&](const u4 wd, int c) {
                     const T* xp = (!guard || (c >= c0 && c < c1)) ? xrow + (size_t)c * 32 : zptr;
                     acc = mfma16(as_vec8<T>(wd), as_vec8<T>(*reinterpret_cast<const u4*>(xp)), acc);
@@ -277,15 +278,15 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
                     // vmcnt(0) once per trip: the ring drains (tests/test_isa_wcode.py)
                     __builtin_amdgcn_sched_barrier(0);
                 };
-                one(wc_frag<0>(ch, base4), 4 * q); one(wc_frag<1>(ch, base4), 4 * q + 1);
-                one(wc_frag<2>(ch, base4), 4 * q + 2); one(wc_frag<3>(ch, base4), 4 * q + 3);
+                one(CD::template frag<0>(ch, base4), 4 * q); one(CD::template frag<1>(ch, base4), 4 * q + 1);
+                one(CD::template frag<2>(ch, base4), 4 * q + 2); one(CD::template frag<3>(ch, base4), 4 * q + 3);
             };
             auto trip = [&](int q, bool guard) {
 #pragma unroll
                 for (int u = 0; u < RC; ++u) {
                     consumeC(cring[u], q + u, guard);
-                    const size_t o = (size_t)min(q + RC + u, qlast) * WC_CHUNK_BYTES;
-                    cring[u] = wc_load(cb16 + o, cb4 + o);
+                    const size_t o = (size_t)min(q + RC + u, qlast) * CD::BYTES;
+                    cring[u] = CD::load(cb16 + o, cb4 + o);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
@@ -398,14 +399,16 @@ __global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_k(const void* wdow
 
 // The same launch on coded bf16 weights (chain_tile WC; a kernel name of its own): the leading weight arguments are the coded planes of down_proj(layer)
 // and QKV(layer + 1); the raw packed copies (what a flagged tile streams) and the header words travel in ChainArgs and are read behind the rings. The
-// QKV role's ring is four coded chunks (the raw role's sixteen fragments), down_proj's two.
-__global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_wc_k(const void* cdown, const void* cqkv, int hidden, int inter, int qkv_n, int nwg_down, ChainArgs) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
+// QKV role's ring is four coded chunks (the raw role's sixteen fragments), down_proj's two. decode_chain_w4_k is the same launch on the int4 streams
+// (WC = 2; ChainArgs::wdown / wqkv are then the packed bf16 copies of the dequantised weights, which the LoRA-A tiles of the QKV role stream).
+typedef void (*ChainCodedFn)(const void*, const void*, int, int, int, int, ChainArgs);       // the signature of both kernels
+template <int WC>
+__device__ __forceinline__ void chain_coded(const void* cdown, const void* cqkv, int hidden, int inter, int qkv_n, int nwg_down, unsigned char* msm) {
     typedef bf16 T;
     const int H = hidden;
-    auto args = [] { return late_kernarg<ChainArgs>(kernarg_offset<6>(decltype(&decode_chain_wc_k){})); };      // argument 6: the ChainArgs
+    auto args = [] { return late_kernarg<ChainArgs>(kernarg_offset<6>(ChainCodedFn{})); };      // argument 6: the ChainArgs
     if ((int)blockIdx.x < nwg_down) {
-        const ChainLate<WaitSharded> lt = chain_tile<T, EPI_RESID, false, 1, 6, WaitSharded, 4, false, false, true>(cdown, inter, blockIdx.x, nwg_down, msm, [&] {
+        const ChainLate<WaitSharded> lt = chain_tile<T, EPI_RESID, false, 1, 6, WaitSharded, 4, false, false, WC>(cdown, inter, blockIdx.x, nwg_down, msm, [&] {
             const ChainArgs ca = args();
             int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
             return ChainLate<WaitSharded>{ChainGemm{ca.dgu, inter, ca.dx, H, ca.dx, H, ca.B, H, nullptr, 0.f, nullptr},
@@ -415,12 +418,20 @@ __global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_wc_k(const void* c
         if (lt.trace && threadIdx.x == 0) lt.trace[2] = (long long)__builtin_amdgcn_s_memrealtime();      // arrival
         return;
     }
-    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, 8, false, false, true>(cqkv, H, blockIdx.x - nwg_down, (qkv_n + 15) / 16, msm, [&] {
+    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, 8, false, false, WC>(cqkv, H, blockIdx.x - nwg_down, (qkv_n + 15) / 16, msm, [&] {
         const ChainArgs ca = args();
         int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
         return ChainLate<WaitSharded>{ChainGemm{ca.dx, H, nullptr, 0, ca.dqkv, ca.qkv_ld, ca.B, qkv_n, ca.attn_norm, ca.eps, nullptr},
                                       WaitSharded{ctr, nwg_down, ca.err, ca.naps, nullptr}, ca.trace ? ca.trace + (size_t)blockIdx.x * 8 : nullptr, ca.wqkv, ca.hqkv};
     });
+}
+__global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_wc_k(const void* cdown, const void* cqkv, int hidden, int inter, int qkv_n, int nwg_down, ChainArgs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
+    chain_coded<1>(cdown, cqkv, hidden, inter, qkv_n, nwg_down, msm);
+}
+__global__ __launch_bounds__(CH_THREADS, 4) void decode_chain_w4_k(const void* cdown, const void* cqkv, int hidden, int inter, int qkv_n, int nwg_down, ChainArgs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char msm[];
+    chain_coded<2>(cdown, cqkv, hidden, inter, qkv_n, nwg_down, msm);
 }
 
 // ---- decode attention + o_proj(+residual) in ONE launch, 16-wave workgroups -------------------------------------------------
@@ -514,7 +525,11 @@ void launch_decode_chain(int dtype, ChainArgs ca, bool with_next_qkv, hipStream_
             hipFuncSetAttribute((const void*)decode_chain_k<T, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
             hipFuncSetAttribute((const void*)decode_chain_k<T, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
         }
-        if (ca.wc && dtype == DT_BF16 && !ca.w8) {        // coded bf16 weights (api_llama.hip sets wc only where every copy of the launch exists)
+        if (ca.wc == 2 && dtype == DT_BF16 && !ca.w8) {       // int4 streams (api_llama.hip: every weight of the launch has one)
+            static DevOnce w4_attr_set;
+            if (w4_attr_set.first()) hipFuncSetAttribute((const void*)decode_chain_w4_k, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
+            hipLaunchKernelGGL(decode_chain_w4_k, grid, block, smem, s, ca.cdown, with_next_qkv ? ca.cqkv : ca.cdown, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
+        } else if (ca.wc && dtype == DT_BF16 && !ca.w8) {        // coded bf16 weights (api_llama.hip sets wc only where every copy of the launch exists)
             static DevOnce wc_attr_set;
             if (wc_attr_set.first()) hipFuncSetAttribute((const void*)decode_chain_wc_k, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
             hipLaunchKernelGGL(decode_chain_wc_k, grid, block, smem, s, ca.cdown, with_next_qkv ? ca.cqkv : ca.cdown, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);

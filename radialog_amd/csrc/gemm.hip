@@ -171,6 +171,66 @@ void launch_encode_wc(const void* packed, void* planes, unsigned* hdr, int npad,
     hipLaunchKernelGGL(encode_wc_k, dim3(npad / 16), dim3(256), 0, s, (const u4*)packed, (unsigned char*)planes, hdr, K);
 }
 
+// int4 group-quantised weights (rdx_common.h W4Chunk; radialog_amd/w4.py is the definition): one workgroup per 16-row tile, one wave per 128 k. Lane
+// (g, r) reads the 32 fp32 weights of its four MFMA A fragments of the chunk; the four lanes of a row hold one group of 128, their absmax meets over
+// two shuffles. s = bf16(a / 7) and q = rint(w / s) are IEEE fp32 divisions (no reciprocal), q goes through an int (rint(-0.3) is -0, the format's
+// q = 0 dequantises to +0). Written: the packed bf16 copy of W' = bf16(q s), the nibbles q + 8 and the scale bits. Tiles of rows [raw_lo, raw_hi) are raw:
+// W' = bf16(W), nibbles 8, scales 0, header bit 8. Rows past N are zeros. An Inf / NaN anywhere sets *bad.
+__global__ __launch_bounds__(256) void quant_w4_k(const float* __restrict__ W, u4* __restrict__ packed, unsigned char* __restrict__ stream, unsigned* __restrict__ hdr,
+                                                  int* __restrict__ bad, int N, int K, int raw_lo, int raw_hi) {
+    const int tile = blockIdx.x, KC = K >> 5, KQ = K >> 7, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int r = lane & 15, g = lane >> 4, row = tile * 16 + r;
+    const bool raw = tile * 16 >= raw_lo && tile * 16 < raw_hi;
+    int nonfinite = 0;
+    for (int q = wv; q < KQ; q += 4) {
+        float v[4][8];
+        float amax = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            float4 x0 = make_float4(0.f, 0.f, 0.f, 0.f), x1 = x0;
+            if (row < N) {
+                const float4* src = reinterpret_cast<const float4*>(W + (size_t)row * K + (size_t)q * 128 + j * 32 + g * 8);
+                x0 = src[0]; x1 = src[1];
+            }
+            v[j][0] = x0.x; v[j][1] = x0.y; v[j][2] = x0.z; v[j][3] = x0.w; v[j][4] = x1.x; v[j][5] = x1.y; v[j][6] = x1.z; v[j][7] = x1.w;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const float ax = fabsf(v[j][e]);
+                if (!(ax <= 3.4028234663852886e38f)) nonfinite = 1;
+                amax = fmaxf(amax, ax);
+            }
+        }
+        amax = fmaxf(amax, __shfl_xor(amax, 16));
+        amax = fmaxf(amax, __shfl_xor(amax, 32));
+        const bf16 sb = raw ? fromf<bf16>(0.f) : fromf<bf16>(amax / 7.0f);
+        const float sf = tof<bf16>(sb);
+        unsigned nib[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v8b o;
+            unsigned n = 0;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                int qi = 0;
+                if (!raw && sf != 0.f) qi = (int)fminf(fmaxf(rintf(v[j][e] / sf), -8.f), 7.f);
+                o[e] = raw ? fromf<bf16>(v[j][e]) : fromf<bf16>((float)qi * sf);
+                n |= (unsigned)(qi + 8) << (4 * (e < 4 ? 2 * e : 2 * (e - 4) + 1));
+            }
+            nib[j] = n;
+            packed[((size_t)tile * KC + 4 * q + j) * 64 + lane] = as_u4<bf16>(o);
+        }
+        unsigned char* p = stream + ((size_t)tile * KQ + q) * W4_CHUNK_BYTES;
+        reinterpret_cast<u4*>(p)[lane] = (u4){nib[0], nib[1], nib[2], nib[3]};
+        if (g == 0) reinterpret_cast<unsigned short*>(p + 1024)[r] = bits16<bf16>(sb);
+    }
+    if (nonfinite) atomicOr(bad, 1);
+    if (threadIdx.x == 0) hdr[tile] = raw ? 0x100u : 0u;
+}
+
+void launch_quant_w4(const float* W, void* packed, void* stream, unsigned* hdr, int* bad, int N, int K, int npad, int raw_lo, int raw_hi, hipStream_t s) {
+    hipLaunchKernelGGL(quant_w4_k, dim3(npad / 16), dim3(256), 0, s, W, (u4*)packed, (unsigned char*)stream, hdr, bad, N, K, raw_lo, raw_hi);
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // skinny GEMM (body in skinny_body.h)
 // ------------------------------------------------------------------------------------------------------------------
@@ -213,6 +273,38 @@ static void launch_skinny_wc(const GemmArgs& a, int epi, hipStream_t s) {
         default: break;
     }
 #undef RDX_SKC
+}
+
+// The same GEMV on int4 group-quantised weights (skinny_body.h WC = 2): the leading arguments are the int4 stream, X, K, N and the header words;
+// GemmArgs::W is the packed bf16 copy of the dequantised weight, which a raw-flagged tile (the fused QKV weight's LoRA-A rows) streams.
+template <int EPI, bool NORM, int WAVES>
+__global__ __launch_bounds__(WAVES * 64, WAVES == 4 ? 8 : 1) void skinny_gemm_w4_k(const void* W4, const void* X, int K, int N, const unsigned* hdr, GemmArgs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
+    skinny_tile<bf16, 1, EPI, NORM, WAVES, true, NoWait, false, false, 2>(W4, K, blockIdx.x, (N + 15) / 16, dyn_smem, NoWait(), [&] {
+        constexpr unsigned off = kernarg_offset<5>(decltype(&skinny_gemm_w4_k<EPI, NORM, WAVES>){});      // argument 5: the GemmArgs
+        GemmArgs a = late_kernarg<GemmArgs>(off);
+        a.X = X; a.K = K; a.N = N;
+        return a;
+    }, hdr);
+}
+
+template <bool NORM, int WAVES>
+static void launch_skinny_w4(const GemmArgs& a, int epi, hipStream_t s) {
+    dim3 grid((a.N + 15) / 16), block(WAVES * 64);
+    const size_t dyn = (size_t)a.M * a.K * 2 + 16;        // the staged rows + the zero line
+#define RDX_SK4(E) hipLaunchKernelGGL((skinny_gemm_w4_k<E, NORM, WAVES>), grid, block, dyn, s, a.W4, a.X, a.K, a.N, a.w4hdr, a)
+    switch (epi) {
+        case EPI_NONE: RDX_SK4(EPI_NONE); break;
+        case EPI_RESID: RDX_SK4(EPI_RESID); break;
+        case EPI_SILU_MUL: RDX_SK4(EPI_SILU_MUL); break;
+        default: break;
+    }
+#undef RDX_SK4
+}
+
+bool skinny_w4_supported(int dtype, const GemmArgs& a, int epi) {
+    return dtype == DT_BF16 && a.W4 && a.w4hdr && a.W && skinny_fits_lds(a.M, a.K) && a.K % W4_CHUNK_K == 0 && a.M < xs_min_rows() &&
+           (epi == EPI_NONE || epi == EPI_RESID || epi == EPI_SILU_MUL);
 }
 
 bool skinny_wc_supported(int dtype, const GemmArgs& a, int epi) {
@@ -288,6 +380,14 @@ static void launch_skinny_T(const GemmArgs& a, int epi, hipStream_t s) {
 void launch_skinny_gemm(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
     // (fp8 weights: only with the e4m3 activation block, ACT_BLK64_E4M3 -- the batch >= 3 rule of the fp8 scheme; callers go through skinny())
     if (xstat32_supported(a, epi) && (!(a.W8 && a.wscale) || (a.xpacked == ACT_BLK64_E4M3 && a.xscale))) { launch_xstat32(dtype, a, epi, s); return; }
+    if (skinny_w4_supported(dtype, a, epi)) {       // int4 weights: likewise
+        const bool norm = a.norm_w != nullptr;
+        const int waves = skinny_lds_waves(a);
+        if (waves == 16) { if (norm) launch_skinny_w4<true, 16>(a, epi, s); else launch_skinny_w4<false, 16>(a, epi, s); }
+        else if (waves == 4) { if (norm) launch_skinny_w4<true, 4>(a, epi, s); else launch_skinny_w4<false, 4>(a, epi, s); }
+        else { if (norm) launch_skinny_w4<true, 8>(a, epi, s); else launch_skinny_w4<false, 8>(a, epi, s); }
+        return;
+    }
     if (skinny_wc_supported(dtype, a, epi)) {       // coded weights: the wave counts of launch_skinny_T (the K split is part of the sums)
         const bool norm = a.norm_w != nullptr;
         const int waves = skinny_lds_waves(a);

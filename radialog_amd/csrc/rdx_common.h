@@ -124,6 +124,62 @@ template <int J> __device__ __forceinline__ u4 wc_frag(const WcChunk& c, unsigne
                 __builtin_amdgcn_perm(h1, l1, 0x05010400u), __builtin_amdgcn_perm(h1, l1, 0x07030602u)};
 }
 
+// ---- int4 group-quantised weights ("W4", 4.125 bits per weight; the format's definition is radialog_amd/w4.py) ------------------------------
+// A W4 chunk is the same 128 k-values of one 16-row tile, W4_CHUNK_BYTES bytes: [nibbles: 64 lanes x 16 B][scales: 16 rows x 2 B]. Dword j of lane
+// (g, r)'s 16 bytes holds the 8 weights of ITS MFMA A fragment j (packed chunk 4 q + j) as nibbles q + 8, weight e in nibble 2 e (e < 4) or 2 (e - 4) + 1;
+// the group's bf16 scale s is the 2 bytes at 1024 + 2 r. The decode gives exactly W' = bf16(float(q) * float(s)): fma(float(nibble), s, -8 s) is
+// (nibble - 8) * s, which fp32 holds exactly (4 x 8 significant bits), then ONE round-to-nearest-even to bf16 -- the packed bf16 copy's bits.
+struct W4Chunk { u4 nib; unsigned sc; };
+__device__ __forceinline__ unsigned ldg2_nt(const void* p) { return __builtin_nontemporal_load((const __attribute__((address_space(1))) unsigned short*)p); }
+// p16 = the tile's stream base + lane * 16, p2 = + 1 KiB + 2 r (both advanced by q * W4_CHUNK_BYTES by the caller)
+__device__ __forceinline__ W4Chunk w4_load(const unsigned char* p16, const unsigned char* p2) {
+    W4Chunk c;
+    c.nib = ldg16_nt(p16); c.sc = ldg2_nt(p2);
+    return c;
+}
+__device__ __forceinline__ unsigned w4_pk(float a, float b) {
+    typedef __bf16 v2b __attribute__((ext_vector_type(2)));
+    const v2b p = {(__bf16)a, (__bf16)b};
+    return __builtin_bit_cast(unsigned, p);
+}
+// fragment J (constant) of a chunk: the 16 bytes the packed bf16 copy of W' holds for this lane in packed chunk 4 q + J
+template <int J> __device__ __forceinline__ u4 w4_frag(const W4Chunk& c) {
+    const float s = __builtin_bit_cast(float, c.sc << 16), m8 = -8.f * s;
+    const unsigned n = c.nib[J];
+    const unsigned lo = n & 0x0f0f0f0fu, hi = (n >> 4) & 0x0f0f0f0fu;     // weights 0..3, 4..7: one per byte (v_cvt_f32_ubyte0..3)
+    // Two VALU instructions per weight, written out: left to itself the compiler extracts every nibble with a shift and a mask of its own and pairs
+    // the multiplies into v_pk_fma_f32 on register PAIRS -- whose second register is the pending scale load of the next chunk, so every trip of the K
+    // loop waited vmcnt(0) (tests/test_isa_w4.py).
+#define RDX_W4F(x, k) ({ float t_, f_; asm("v_cvt_f32_ubyte" #k " %0, %1" : "=v"(t_) : "v"(x)); asm("v_fma_f32 %0, %1, %2, %3" : "=v"(f_) : "v"(t_), "v"(s), "v"(m8)); f_; })
+    const u4 f = (u4){w4_pk(RDX_W4F(lo, 0), RDX_W4F(lo, 1)), w4_pk(RDX_W4F(lo, 2), RDX_W4F(lo, 3)),
+                      w4_pk(RDX_W4F(hi, 0), RDX_W4F(hi, 1)), w4_pk(RDX_W4F(hi, 2), RDX_W4F(hi, 3))};
+#undef RDX_W4F
+    return f;
+}
+
+// What the two alternative weight streams of the batch <= 2 GEMV differ in (skinny_body.h / chain.hip, template switch WC: 1 = the 13-bit code,
+// 2 = int4): the chunk in registers, its bytes, where the lane's second pointer starts, its loads (LOADS per chunk), the decode of fragment J (hp: the
+// 13-bit code's window base from the tile's header; int4 carries its scale in the chunk) and which four 16-byte registers of a dropped ring a
+// raw-flagged tile reuses.
+template <int WC> struct Coded;
+template <> struct Coded<1> {
+    typedef WcChunk Chunk;
+    static constexpr int BYTES = WC_CHUNK_BYTES, LOADS = 4;
+    static __device__ __forceinline__ int off2(int lane) { return 3072 + lane * 4; }
+    static __device__ __forceinline__ Chunk load(const unsigned char* p16, const unsigned char* p2) { return wc_load(p16, p2); }
+    template <int J> static __device__ __forceinline__ u4 frag(const Chunk& c, unsigned hp) { return wc_frag<J>(c, hp); }
+    static __device__ __forceinline__ u4& slot(Chunk* ring, int u) { return u == 0 ? ring[0].lo0 : u == 1 ? ring[0].lo1 : u == 2 ? ring[0].ix : ring[1].lo0; }
+};
+template <> struct Coded<2> {
+    typedef W4Chunk Chunk;
+    static constexpr int BYTES = W4_CHUNK_BYTES, LOADS = 2;
+    static __device__ __forceinline__ int off2(int lane) { return 1024 + (lane & 15) * 2; }
+    static __device__ __forceinline__ Chunk load(const unsigned char* p16, const unsigned char* p2) { return w4_load(p16, p2); }
+    template <int J> static __device__ __forceinline__ u4 frag(const Chunk& c, unsigned) { return w4_frag<J>(c); }
+    static __device__ __forceinline__ u4& slot(Chunk* ring, int u) { return ring[u].nib; }       // (rings of at least four chunks)
+};
+template <> struct Coded<0> : Coded<1> {};      // the raw instantiations declare an unused ring of this type
+
 // ---- model dtype -> fp8 (OCP e4m3) activation quantisation of the fp8 path: q = RNE_e4m3(x * (448 / absmax)), scale = absmax / 448 ----------
 // (the arithmetic of pack_weight_fp8_k and of the oracle's fake quantisation; an all-zero range gets scale 1)
 __device__ __forceinline__ void fp8_scale(float amax, float& sc, float& inv) {

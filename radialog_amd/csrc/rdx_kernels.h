@@ -54,7 +54,20 @@ struct GemmArgs {
     // coded bf16 weights (rdx_common.h WcChunk): the planes of launch_encode_wc and one header word per tile; the batch <= 2 GEMV streams them
     // instead of W (13 bits per weight, decoded exactly), W stays what the tiles flagged in their header read. Null: W is streamed.
     const void* WC; const unsigned* wchdr;
+    // int4 group-quantised weights (rdx_common.h W4Chunk): the stream of launch_quant_w4 and one header word per tile (bit 8: the tile streams its
+    // packed bf16 bytes from W). W is the packed bf16 copy of the dequantised weight W': the same bits, four times the bytes. Null: not streamed.
+    const void* W4; const unsigned* w4hdr;
 };
+
+// int4 group-quantised weights (radialog_amd/w4.py): groups of 128 k of one row, per (tile, 128 k) one chunk of 1 KiB of nibbles + 16 bf16 scales
+constexpr int W4_CHUNK_K = 128, W4_CHUNK_BYTES = 64 * 16 + 16 * 2;
+inline size_t w4_bytes(int npad, int k) { return (size_t)(npad / 16) * (size_t)(k / W4_CHUNK_K) * W4_CHUNK_BYTES; }
+// bf16 only: quantises W fp32 [N][K] (the 16-row tiles of rows [raw_lo, raw_hi), both multiples of 16, are raw: W' = bf16(W)) and
+// writes the packed bf16 copy of W' (the order of launch_pack_weight, rows padded to npad with zeros), the stream and hdr[npad / 16] = raw << 8.
+// *bad (device, zeroed by the caller) is set when W holds an Inf or a NaN. K % 128 == 0
+void launch_quant_w4(const float* W, void* packed, void* stream, unsigned* hdr, int* bad, int N, int K, int npad, int raw_lo, int raw_hi, hipStream_t s);
+// the batch <= 2 GEMV has an int4 form for these arguments (a.W4 set, bf16, LDS-staged activations, K % 128 == 0)
+bool skinny_w4_supported(int dtype, const GemmArgs& a, int epi);
 
 // coded bf16 weights: 128 k-values per chunk; per (tile, chunk) three planes of whole-wave contiguous loads (rdx_common.h)
 constexpr int WC_CHUNK_K = 128, WC_CHUNK_BYTES = 64 * 52;
@@ -226,6 +239,7 @@ struct ChainArgs {
     int w8;                          // stream the fp8 weights (every projection quantised)
     // coded bf16 weights (bf16, K % 128 == 0 for both roles): the planes of down_proj(layer) / QKV(layer + 1) and their header words; wdown / wqkv stay
     // the raw packed copies, which the tiles flagged in the headers stream. wc = 0: decode_chain_k on the raw copies.
+    // wc = 2: cdown / cqkv are the int4 streams (rdx_common.h W4Chunk) and wdown / wqkv the packed copies of the dequantised weights: decode_chain_w4_k.
     const void *cdown, *cqkv; const unsigned *hdown, *hqkv; int wc;
     float eps;
     void *dx, *dqkv, *dgu;           // [B][hidden] residual stream, [B][qkv_ld], [B][inter]

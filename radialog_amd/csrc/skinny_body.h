@@ -29,7 +29,9 @@ template <typename T> __device__ __forceinline__ float swiglu(float gate_acc, fl
 // late(): the GemmArgs, from kernel arguments that are loaded only behind the ring (rdx_common.h late_kernarg)
 // WC: Wb is the coded copy of a bf16 weight (rdx_common.h WcChunk) and wchdr its header words: the ring holds coded chunks, decoded in registers into
 // the very fragments the raw ring would hold, in the same order (same MFMAs, same sums). A tile whose header says "raw" streams late().W as ever.
-template <typename T, int MT, int EPI, bool NORM, int WAVES, bool XLDS, typename WaitFn, bool COHX = false, bool W8 = false, bool WC = false, typename Late>
+// WC = 2: Wb is the int4 stream of a group-quantised weight (rdx_common.h W4Chunk, Coded<2>) and late().W the packed bf16 copy of its dequantised
+// values: the same loop on chunks of a quarter of the bytes, decoded to exactly those values.
+template <typename T, int MT, int EPI, bool NORM, int WAVES, bool XLDS, typename WaitFn, bool COHX = false, bool W8 = false, int WC = 0, typename Late>
 __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const int tile, const int ntiles, unsigned char* dyn_smem,
                                             WaitFn wait_inputs, Late late, const unsigned* wchdr = nullptr) {
     typedef typename Vec8<T>::type V8;
@@ -38,7 +40,8 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
     // and the scale is applied to the fp32 sums in the epilogue. LDS-staged activations only.
     static_assert(!W8 || (XLDS && MT == 1), "fp8 weights: LDS-staged activations, one M tile");
     static_assert(!WC || (XLDS && MT == 1 && !W8), "coded weights: LDS-staged activations, one M tile, model dtype");
-    constexpr int R = 2;                               // coded chunks in flight per wave: 8 loads, 104 bytes per lane (the raw ring: 8 loads, 128 bytes)
+    typedef Coded<WC> CD;
+    constexpr int R = WC == 2 ? 4 : 2;                 // coded chunks in flight per wave: 8 loads, 104 bytes per lane (the raw ring: 8 loads, 128 bytes); int4: 8 loads, 72 bytes
     constexpr int U = (XLDS && WAVES >= 8) ? 8 : 4;    // 4-wave workgroups stay <= 64 VGPRs: 8 workgroups per CU
     constexpr int NTHR = WAVES * 64;
     __shared__ __attribute__((aligned(16))) float red[WAVES][MT][256];   // [wave][mt][m_local*16 + n_local]
@@ -57,8 +60,8 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
     // WC: the slice [c0, c1) stays the raw one (the sums must not change); it is covered by the coded chunks [q0, q1), whose first and last may
     // reach past it -- those fragments multiply zeros (below)
     const int KQ = K >> 7, q0 = c0 >> 2, q1 = c1 > c0 ? (c1 + 3) >> 2 : q0, qlast = min(max(q1 - 1, q0), KQ - 1);
-    const unsigned char* cb16 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile * KQ * WC_CHUNK_BYTES + lane * 16;
-    const unsigned char* cb4 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile * KQ * WC_CHUNK_BYTES + 3072 + lane * 4;
+    const unsigned char* cb16 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile * KQ * CD::BYTES + lane * 16;
+    const unsigned char* cb4 = reinterpret_cast<const unsigned char*>(Wb) + (size_t)tile * KQ * CD::BYTES + CD::off2(lane);
 
     // Everything up to here comes from the leading kernel arguments (preloaded into SGPRs: gemm.hip skinny_gemm_k), the workgroup id and the lane
     // id, so the ring is issued with no scalar load in front of it. The entry time is taken unconditionally (one scalar instruction that nothing
@@ -67,10 +70,10 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
     // two weight batches in flight before anything else (HBM latency overlaps the wait and the prologue)
     // (unconditional, addresses clamped into the slice: a short slice re-reads its last KiB)
     u4 ring[2 * U];
-    WcChunk cring[R];
+    typename CD::Chunk cring[R];
     if constexpr (WC) {
 #pragma unroll
-        for (int u = 0; u < R; ++u) { const size_t o = (size_t)min(q0 + u, qlast) * WC_CHUNK_BYTES; cring[u] = wc_load(cb16 + o, cb4 + o); }
+        for (int u = 0; u < R; ++u) { const size_t o = (size_t)min(q0 + u, qlast) * CD::BYTES; cring[u] = CD::load(cb16 + o, cb4 + o); }
     } else {
 #pragma unroll
         for (int u = 0; u < 2 * U; ++u) ring[u] = ldg16_nt(wbase + (size_t)min(c0 + u, clast) * 64);
@@ -216,7 +219,7 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
                 // a tile the code cannot express (wave-uniform, once per tile): the coded ring is dropped, today's loop runs on the raw packed copy
                 const u4* wraw = reinterpret_cast<const u4*>(a.W) + (size_t)tile * KC * 64 + lane;
                 // (four of its six 16-byte registers: a rare path, and the 4-wave form has no VGPR to spare for the addresses of more)
-                auto slot = [&](int u) -> u4& { return u == 0 ? cring[0].lo0 : u == 1 ? cring[0].lo1 : u == 2 ? cring[0].ix : cring[1].lo0; };
+                auto slot = [&](int u) -> u4& { return CD::slot(cring, u); };
 #pragma unroll
                 for (int u = 0; u < 4; ++u) slot(u) = ldg16_nt(wraw + (size_t)min(c0 + u, clast) * 64);
                 raw_loop(wraw, slot, std::integral_constant<int, 4>());
@@ -229,21 +232,21 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
                 // -0 only when all its terms are, so it is never -0, and x + (+-0) = x for every other x; (3) an MFMA whose 32 products are all zero
                 // therefore returns its accumulator operand unchanged, wherever in the sequence it stands. Cost: at most 3 fragments decoded in vain
                 // at either end of a slice (K = 11008 over 16 waves: 21.5 packed chunks per wave, 24 or 28 decoded); aligned slices pay nothing.
-                auto consumeC = [&](const WcChunk& ch, int q, bool guard) {
+                auto consumeC = [&](const typename CD::Chunk& ch, int q, bool guard) {
                     auto one = [&](const u4 wd, int c) {
                         const T* xp = (!guard || (c >= c0 && c < c1)) ? xrow[0] + (size_t)c * 32 : zptr;
                         acc[0] = mfma16(as_vec8<T>(wd), as_vec8<T>(*reinterpret_cast<const u4*>(xp)), acc[0]);
                         __builtin_amdgcn_sched_barrier(0);       // one fragment decoded at a time: four at once do not fit the 64 VGPRs of the 4-wave form
                     };
-                    one(wc_frag<0>(ch, base4), 4 * q); one(wc_frag<1>(ch, base4), 4 * q + 1);
-                    one(wc_frag<2>(ch, base4), 4 * q + 2); one(wc_frag<3>(ch, base4), 4 * q + 3);
+                    one(CD::template frag<0>(ch, base4), 4 * q); one(CD::template frag<1>(ch, base4), 4 * q + 1);
+                    one(CD::template frag<2>(ch, base4), 4 * q + 2); one(CD::template frag<3>(ch, base4), 4 * q + 3);
                 };
                 auto trip = [&](int q, bool guard) {
 #pragma unroll
                     for (int u = 0; u < R; ++u) {
                         consumeC(cring[u], q + u, guard);
-                        const size_t o = (size_t)min(q + R + u, qlast) * WC_CHUNK_BYTES;
-                        cring[u] = wc_load(cb16 + o, cb4 + o);
+                        const size_t o = (size_t)min(q + R + u, qlast) * CD::BYTES;
+                        cring[u] = CD::load(cb16 + o, cb4 + o);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 };

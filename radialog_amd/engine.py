@@ -86,9 +86,13 @@ class Sampling:
 class RdxEngine:
     def __init__(self, cfg: RaDialogCfg, dtype: str = "bf16", device: int = 0, max_batch: int = 1, max_len: int = 512,
                  lora: bool = True, vision: bool = True, llama: bool = True, classifier: bool = False,
-                 weights_fp8: bool = False):
+                 weights_fp8: bool = False, weights_w4: bool = False):
         if dtype not in _RDX_DT:
             raise ValueError(f"dtype must be 'f16' or 'bf16', got {dtype!r}")
+        if weights_w4 and weights_fp8:
+            raise ValueError("weights_w4 and weights_fp8 do not mix: one weight format per context")
+        if weights_w4 and dtype == "f16":
+            raise ValueError("weights_w4 needs dtype='bf16' (int4 weights are not built for f16)")
         self.lib = _lib.load()                       # raises RdxLibraryError when the HIP library is absent
         if not torch.cuda.is_available():
             raise _lib.RdxError("RdxEngine needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU path")
@@ -96,6 +100,7 @@ class RdxEngine:
         self.device = torch.device("cuda", device)
         self.lora = lora
         self.weights_fp8 = weights_fp8               # decoder GEMM weights also quantised to e4m3 + per-row scale (configs[4])
+        self.weights_w4 = weights_w4                 # the decoder's seven projections int4 group-quantised (RDX_W_GEMM_W4, radialog_amd/w4.py)
         l, q, v = cfg.llama, cfg.qformer, cfg.vision
         rc = RdxConfig()
         rc.dtype = _RDX_DT[dtype]
@@ -171,7 +176,7 @@ class RdxEngine:
                 self._upload(W.vision_items(get, self.cfg.vision))
                 self._upload(W.qformer_items(get, self.cfg.qformer))
             if llama:
-                self._upload(W.llama_items(get, self.cfg.llama, self.lora, fp8=self.weights_fp8, dtype=self.tdtype))
+                self._upload(W.llama_items(get, self.cfg.llama, self.lora, fp8=self.weights_fp8, dtype=self.tdtype, w4=self.weights_w4))
         check(self.ctx, self.lib.rdx_finalize_weights(self.ctx), "rdx_finalize_weights")
         self._finalized = True
 
@@ -474,7 +479,7 @@ class RdxEngine:
 
     def set_option(self, name: str, value: int):
         """rdx_set_option: "flash_min" (batched prefill attention kernel choice), "pconv" (packed / row-major encoder kernels), "xs16", "prompt_blk",
-        "wcode" (the batch <= 2 step streams the coded bf16 weights: on by default; 0 = the raw packed ones, same bits), "score_chunk" (logits rows per lm_head launch of score(); default 2048, 0 = all at once)."""
+        "wcode" (the batch <= 2 step streams the coded bf16 weights: on by default; 0 = the raw packed ones, same bits), "w4" (likewise for the int4 streams of a weights_w4 engine), "score_chunk" (logits rows per lm_head launch of score(); default 2048, 0 = all at once)."""
         check(self.ctx, self.lib.rdx_set_option(self.ctx, name.encode(), int(value)), "rdx_set_option")
 
     def conv_test(self, x, w, bias=None, resid=None, ksize=1, stride=1, epi=0, path=0, iters=0):
@@ -619,6 +624,27 @@ class RdxEngine:
         copies it holds (zeros where it holds none) and how many launches of the coded kernels it has issued (a captured graph counts once)."""
         out = (C.c_longlong * 5)()
         check(self.ctx, self.lib.rdx_wcode_stats(self.ctx, out), "rdx_wcode_stats")
+        return tuple(int(v) for v in out)
+
+    def w4_test(self, w):
+        """The device quantiser of the int4 group-quantised weights alone (rdx_w4_test; the format: radialog_amd/w4.py): w fp32 [N, K], K % 128 == 0.
+        Returns (wprime uint16 [tiles, K / 32, 64, 8], stream uint8 [tiles, K / 128, 1056], scales uint16 [tiles, K / 128, 16]) as NumPy arrays."""
+        from . import w4 as w4fmt
+        N, K = w.shape
+        nt = (N + 15) // 16
+        w = self._dev(w, torch.float32)
+        wprime = torch.zeros(nt, K // 32, 64, 8, dtype=torch.int16, device=self.device)
+        stream = torch.zeros(nt, max(K // w4fmt.CHUNK_K, 1), w4fmt.CHUNK_BYTES, dtype=torch.uint8, device=self.device)
+        scales = torch.zeros(nt, max(K // w4fmt.CHUNK_K, 1), 16, dtype=torch.int16, device=self.device)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_w4_test(self.ctx, _ptr(w), N, K, _ptr(wprime), _ptr(stream), _ptr(scales)), "rdx_w4_test")
+        return wprime.cpu().numpy().view("uint16"), stream.cpu().numpy(), scales.cpu().numpy().view("uint16")
+
+    def w4_stats(self):
+        """(int4 tiles, raw tiles, bytes, int4 GEMV launches, int4 chained launches) of this engine's decoder (rdx_w4_stats): the int4 streams it holds
+        (zeros where it holds none) and how many launches of the int4 kernels it has issued (a captured graph counts once)."""
+        out = (C.c_longlong * 5)()
+        check(self.ctx, self.lib.rdx_w4_stats(self.ctx, out), "rdx_w4_stats")
         return tuple(int(v) for v in out)
 
     def xrow16_test(self, x, w, resid, M=None, ldo=None):

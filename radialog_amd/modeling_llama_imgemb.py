@@ -57,7 +57,7 @@ class _BaseModel:
 
 class LlamaForCausalLM:
     def __init__(self, cfg: Optional[LlamaCfg] = None, dtype: str = "bf16", max_batch: int = 12, max_len: int = 1024,
-                 lora: bool = True, device: int = 0, weights_fp8: bool = False):
+                 lora: bool = True, device: int = 0, weights_fp8: bool = False, weights_w4: bool = False):
         self.lcfg = cfg or LlamaCfg()
         self.config = SimpleNamespace(hidden_size=self.lcfg.hidden, vocab_size=self.lcfg.vocab,
                                       num_hidden_layers=self.lcfg.layers, pad_token_id=0, eos_token_id=2)
@@ -71,6 +71,8 @@ class LlamaForCausalLM:
         # row scales; weights.py -- the oracle mirrors it, so what this costs on a trained adapter, whose A rows are small against a row's absmax, is
         # NOT measured here: no adapter file is reachable offline). No reference counterpart: `from_pretrained(..., weights_fp8=True)` is this build's extra kwarg
         self.weights_fp8 = bool(weights_fp8)
+        # int4 group-quantised projections (RdxEngine(weights_w4=True), radialog_amd/w4.py): `from_pretrained(..., weights_w4=True)`, next to weights_fp8
+        self.weights_w4 = bool(weights_w4)
         self.device = torch.device("cuda", device)
         self._engine = None
         self._state = None            # reference-named tensors (dict, stored dtype); with _synthetic they overlay the random-init generator
@@ -164,7 +166,7 @@ class LlamaForCausalLM:
         from .engine import RdxEngine, synth_getter
         cfg = RaDialogCfg(llama=self.lcfg)
         eng = RdxEngine(cfg, dtype=self.dtype, device=self.device.index or 0, max_batch=self.max_batch, max_len=self.max_len,
-                        lora=self.lora, vision=False, llama=True, weights_fp8=self.weights_fp8)
+                        lora=self.lora, vision=False, llama=True, weights_fp8=self.weights_fp8, weights_w4=self.weights_w4)
         if self._state is None and not self._synthetic:
             eng.close()
             raise RuntimeError("LlamaForCausalLM has no weights: build it with from_pretrained(local_dir) or from_pretrained(synthetic=True)")

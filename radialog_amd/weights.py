@@ -24,7 +24,7 @@ from typing import Callable, Iterator, Tuple
 import torch
 import torch.nn.functional as F
 
-from ._lib import RDX_W_F32, RDX_W_GEMM, RDX_W_GEMM_FP8, RDX_W_TENSOR
+from ._lib import RDX_W_F32, RDX_W_GEMM, RDX_W_GEMM_FP8, RDX_W_GEMM_W4, RDX_W_TENSOR
 from .config import LlamaCfg, QFormerCfg, VisionCfg
 
 Getter = Callable[[str], torch.Tensor]
@@ -186,10 +186,16 @@ def rope_tables_f32(head_dim: int, max_pos: int, base: float):
     return emb.cos(), emb.sin()
 
 
-def llama_items(get: Getter, c: LlamaCfg, lora: bool, fp8: bool = False, dtype=None) -> Iterator[Item]:
+def llama_items(get: Getter, c: LlamaCfg, lora: bool, fp8: bool = False, dtype=None, w4: bool = False) -> Iterator[Item]:
     # fp8: the decoder's GEMM weights (QKV + LoRA-A rows, o_proj, gate/up, down, lm_head) are additionally quantised to e4m3
     # with one scale per row (RDX_W_GEMM_FP8, BASELINE configs[4]); embeddings, norms, LoRA-B, img_proj keep the model dtype
+    # w4: the seven projections (q / k / v / o / gate / up / down_proj) are int4 group-quantised (RDX_W_GEMM_W4, radialog_amd/w4.py: the weight becomes its
+    # dequantised value); the LoRA-A rows ride the fused QKV weight and stay un-quantised inside it (the library keeps their tiles raw); the lm_head,
+    # embeddings, norms, LoRA-B and img_proj are as without it
+    if fp8 and w4:
+        raise ValueError("llama_items: fp8 and w4 weights do not mix")
     GK = RDX_W_GEMM_FP8 if fp8 else RDX_W_GEMM
+    PK = RDX_W_GEMM_W4 if w4 else GK          # the projections' kind
     H, I = c.hidden, c.inter
     yield "embed", get("model.embed_tokens.weight"), RDX_W_TENSOR
     yield "final_norm", get("model.norm.weight").view(1, -1), RDX_W_TENSOR
@@ -210,14 +216,14 @@ def llama_items(get: Getter, c: LlamaCfg, lora: bool, fp8: bool = False, dtype=N
         parts = [get(L + f"self_attn.{n}.weight") for n in ("q_proj", "k_proj", "v_proj")]
         if lora:
             parts += [get(L + "self_attn.q_proj.lora_A.weight"), get(L + "self_attn.v_proj.lora_A.weight")]
-        yield o + "wqkv", torch.cat(parts, 0).contiguous(), GK
+        yield o + "wqkv", torch.cat(parts, 0).contiguous(), PK
         del parts
         if lora:
             yield o + "lora_bq", get(L + "self_attn.q_proj.lora_B.weight").contiguous(), RDX_W_TENSOR
             yield o + "lora_bv", get(L + "self_attn.v_proj.lora_B.weight").contiguous(), RDX_W_TENSOR
-        yield o + "wo", get(L + "self_attn.o_proj.weight"), GK
+        yield o + "wo", get(L + "self_attn.o_proj.weight"), PK
         g = get(L + "mlp.gate_proj.weight").view(I // 8, 1, 8, H)
         u = get(L + "mlp.up_proj.weight").view(I // 8, 1, 8, H)
-        yield o + "wgu", torch.cat([g, u], 1).reshape(2 * I, H).contiguous(), GK
+        yield o + "wgu", torch.cat([g, u], 1).reshape(2 * I, H).contiguous(), PK
         del g, u
-        yield o + "wdown", get(L + "mlp.down_proj.weight"), GK
+        yield o + "wdown", get(L + "mlp.down_proj.weight"), PK
