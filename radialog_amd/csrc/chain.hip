@@ -34,6 +34,9 @@ namespace rdx {
 constexpr int CH_WAVES = 16;
 constexpr int CH_THREADS = CH_WAVES * 64;
 constexpr int CH_MAXM = 2;                       // batch rows supported (LDS staging of [M][inter] activations)
+// coded chunks a wave decodes ahead of its role's seam (chain_tile PRE) in decode_chain_wc_k; at most the role's ring (4 and 2), 0 = none. Chosen by
+// measurement (profiles/r13_chain_predecode.md): the QKV role is faster with 1 and slower than without any with 2 or 3; down_proj with 2
+constexpr int CH_PRE_QKV = 1, CH_PRE_DOWN = 2;
 
 // One weight-streaming unit, WITHOUT what its ring needs: the weight base (model dtype, or the e4m3 bytes of a W8 instantiation) and K reach
 // chain_tile as values of their own -- leading kernel arguments, which the command processor preloads into SGPRs (rdx_kernels.h), so the ring
@@ -53,7 +56,11 @@ template <typename WaitFn> struct ChainLate { ChainGemm a; WaitFn wait; long lon
 // Wb, K, wg, ntiles: from preloaded kernel arguments. late(): the rest (ChainLate), built from kernel arguments that are loaded only now (late_kernarg)
 // WC: Wb is the coded bf16 copy of the weight (rdx_common.h WcChunk): the ring holds U / 2 coded chunks (the 2 U packed chunks of the raw ring at 13/16 of
 // the bytes), decoded in registers into the fragments the raw ring holds, in the same order: the sums do not change. As skinny_body.h.
-template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false, int WC = 0, typename Late>
+// PRE (WC = 1 only): the first PRE coded chunks of the ring are decoded, and their slots refilled, BEFORE the role's dead time ends instead of behind
+// it -- PRE_POLL: in front of wait_inputs(), by every wave but the polling one (wave 0); otherwise between the issue of the activation loads and
+// their staging, by every wave. Same fragments into the same MFMAs in the same order (profiles/r13_chain_predecode.md).
+template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false, int WC = 0, int PRE = 0,
+          bool PRE_POLL = false, typename Late>
 __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const int K, const int wg, const int ntiles, unsigned char* smem, Late late) {
     typedef typename Vec8<T>::type V8;
     constexpr int WPS = CH_WAVES / SUB;           // waves per tile
@@ -126,6 +133,35 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
         if (wg * SUB + so < ntiles && n < a.N) rs8_early = ld8_agent(reinterpret_cast<const T*>(a.resid) + (size_t)m * a.ldr + n);
     }
 
+    // Pre-decode (PRE): a wave of an unflagged tile turns the first PRE chunks of its ring into their 4 PRE MFMA fragments and refills those slots at
+    // once with the chunks the first trip of the K loop would fetch into them (q0 + RC + u, clamped as every ring load is). Where it stands the wave
+    // has nothing else to do: 15 of 16 waves sit at the barrier of the hand-off wait, and what they decode here they do not decode behind the seam, four
+    // to a SIMD; the refills are in flight that much earlier. No barrier and no wait on another workgroup in here. Wave 0 polls (PRE_POLL): loads
+    // return in order, so its first poll must not stand behind a refill -- it decodes nothing here and runs the same code once the row is staged, in
+    // front of its first MFMA (one path behind the seam for all waves; a wave-0 path of its own cost 20 bytes of scratch).
+    static_assert(PRE == 0 || (WC == 1 && PRE <= RC), "pre-decode: coded bf16 weights, at most the ring");
+    static_assert(PRE == 0 || PRE_POLL || !WaitFn::TAGGED, "pre-decode without a poll stands behind the plain activation loads: a tagged sweep has no such site");
+    u4 pre[PRE ? 4 * PRE : 1];
+    const bool predec = PRE > 0 && !(wc_hdr & 0x100u);        // wave-uniform
+    auto predecode = [&] {
+        if constexpr (PRE > 0) {
+            if (predec) {
+                const unsigned base4 = (wc_hdr & 0xffu) * 0x01010101u;
+#pragma unroll
+                for (int u = 0; u < PRE; ++u) {
+                    pre[4 * u] = CD::template frag<0>(cring[u], base4); pre[4 * u + 1] = CD::template frag<1>(cring[u], base4);
+                    pre[4 * u + 2] = CD::template frag<2>(cring[u], base4); pre[4 * u + 3] = CD::template frag<3>(cring[u], base4);
+                    const size_t o = (size_t)min(q0 + RC + u, qlast) * CD::BYTES;
+                    cring[u] = CD::load(cb16 + o, cb4 + o);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+    };
+    if constexpr (PRE > 0 && PRE_POLL) {
+        if (wa != 0) predecode();
+    }
+
     wait_inputs();
     if (!WaitFn::TAGGED) CH_T(3);
 
@@ -144,6 +180,10 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             const int c = threadIdx.x + i * CH_THREADS;
             xr[i] = 0ull;
             if (c < total4) { const int m = c / K4, k4 = c - m * K4; xr[i] = ld8_agent(X + (size_t)m * a.ldx + (size_t)k4 * 4); }
+        }
+        if constexpr (PRE > 0 && !PRE_POLL) {     // a role whose input predates the launch: under the flight of the loads just issued (the ring is older)
+            __builtin_amdgcn_sched_barrier(0);
+            predecode();
         }
     }
     if (NORM) {
@@ -270,16 +310,29 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             // guard (first trip and tail only): fragments outside [c0, c1) read the zero line. Exact because (1) every weight of an unflagged tile is
             // finite, so the products are zeros; (2) the fp32 accumulator starts at +0 and a sum is -0 only if all its terms are, so it is never -0 and
             // x + (+-0) = x leaves its bits alone; (3) an MFMA whose 32 products are all zero returns its accumulator operand.
+            auto xsel = [&](int c, bool guard) -> const u4* { return reinterpret_cast<const u4*>((!guard || (c >= c0 && c < c1)) ? xrow + (size_t)c * 32 : zptr); };
             auto consumeC = [&](const typename CD::Chunk& ch, int q, bool guard) {
-                auto one = [&](const u4 wd, int c) {
-                    const T* xp = (!guard || (c >= c0 && c < c1)) ? xrow + (size_t)c * 32 : zptr;
-                    acc = mfma16(as_vec8<T>(wd), as_vec8<T>(*reinterpret_cast<const u4*>(xp)), acc);
-                    // one fragment at a time. Without this barrier the compiler interleaves the four decodes of a chunk with the refill and waits
-                    // vmcnt(0) once per trip: the ring drains (tests/test_isa_wcode.py)
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-                one(CD::template frag<0>(ch, base4), 4 * q); one(CD::template frag<1>(ch, base4), 4 * q + 1);
-                one(CD::template frag<2>(ch, base4), 4 * q + 2); one(CD::template frag<3>(ch, base4), 4 * q + 3);
+                if constexpr (WC == 1) {
+                    // operand lookahead: the four activation fragments of the chunk do not depend on its decode, so they are read from LDS in front of
+                    // it (16 VGPRs) and the LDS round trip passes under the decodes -- the waits are lgkmcnt(3..0) across the chunk instead of a
+                    // drain in front of every MFMA. (Not the int4 stream: there the same lookahead makes the K loops wait vmcnt(0).)
+                    const u4 x0 = *xsel(4 * q, guard), x1 = *xsel(4 * q + 1, guard), x2 = *xsel(4 * q + 2, guard), x3 = *xsel(4 * q + 3, guard);
+                    auto one = [&](const u4 wd, const u4& xv) {
+                        acc = mfma16(as_vec8<T>(wd), as_vec8<T>(xv), acc);
+                        __builtin_amdgcn_sched_barrier(0);      // one fragment at a time (below)
+                    };
+                    one(CD::template frag<0>(ch, base4), x0); one(CD::template frag<1>(ch, base4), x1);
+                    one(CD::template frag<2>(ch, base4), x2); one(CD::template frag<3>(ch, base4), x3);
+                } else {
+                    auto one = [&](const u4 wd, int c) {
+                        acc = mfma16(as_vec8<T>(wd), as_vec8<T>(*xsel(c, guard)), acc);
+                        // one fragment at a time. Without this barrier the compiler interleaves the four decodes of a chunk with the refill and waits
+                        // vmcnt(0) once per trip: the ring drains (tests/test_isa_wcode.py)
+                        __builtin_amdgcn_sched_barrier(0);
+                    };
+                    one(CD::template frag<0>(ch, base4), 4 * q); one(CD::template frag<1>(ch, base4), 4 * q + 1);
+                    one(CD::template frag<2>(ch, base4), 4 * q + 2); one(CD::template frag<3>(ch, base4), 4 * q + 3);
+                }
             };
             auto trip = [&](int q, bool guard) {
 #pragma unroll
@@ -291,7 +344,28 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
                 }
             };
             int q = q0;
-            if (q + RC < q1) { trip(q, true); q += RC; }
+            if constexpr (PRE > 0) {
+                // The first trip, unconditional (a slice of at most RC chunks refills from its clamped last chunk, and the guard sends what lies past
+                // c1 to the zero line): chunks q0 .. q0 + PRE - 1 are in `pre`, decoded and their slots refilled ahead of the seam -- by the polling
+                // wave only now -- and take MFMAs only, same guard; the rest of the ring follows as in any trip. The ring is then that of a first
+                // trip taken: nothing is fetched twice that the loop without pre-decode fetches once.
+                if constexpr (PRE_POLL) {
+                    if (wa == 0) predecode();
+                }
+#pragma unroll
+                for (int u = 0; u < 4 * PRE; ++u) {
+                    acc = mfma16(as_vec8<T>(pre[u]), as_vec8<T>(*xsel(4 * q0 + u, true)), acc);
+                    if (u % 4 == 3) __builtin_amdgcn_sched_barrier(0);      // a chunk's four operand reads at a time (16 VGPRs)
+                }
+#pragma unroll
+                for (int u = PRE; u < RC; ++u) {
+                    consumeC(cring[u], q0 + u, true);
+                    const size_t o = (size_t)min(q0 + RC + u, qlast) * CD::BYTES;
+                    cring[u] = CD::load(cb16 + o, cb4 + o);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+                q += RC;
+            } else if (q + RC < q1) { trip(q, true); q += RC; }
             for (; q + RC < q1; q += RC) trip(q, false);
 #pragma unroll
             for (int u = 0; u < RC; ++u)
@@ -408,7 +482,7 @@ __device__ __forceinline__ void chain_coded(const void* cdown, const void* cqkv,
     const int H = hidden;
     auto args = [] { return late_kernarg<ChainArgs>(kernarg_offset<6>(ChainCodedFn{})); };      // argument 6: the ChainArgs
     if ((int)blockIdx.x < nwg_down) {
-        const ChainLate<WaitSharded> lt = chain_tile<T, EPI_RESID, false, 1, 6, WaitSharded, 4, false, false, WC>(cdown, inter, blockIdx.x, nwg_down, msm, [&] {
+        const ChainLate<WaitSharded> lt = chain_tile<T, EPI_RESID, false, 1, 6, WaitSharded, 4, false, false, WC, WC == 1 ? CH_PRE_DOWN : 0, false>(cdown, inter, blockIdx.x, nwg_down, msm, [&] {
             const ChainArgs ca = args();
             int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
             return ChainLate<WaitSharded>{ChainGemm{ca.dgu, inter, ca.dx, H, ca.dx, H, ca.B, H, nullptr, 0.f, nullptr},
@@ -418,7 +492,7 @@ __device__ __forceinline__ void chain_coded(const void* cdown, const void* cqkv,
         if (lt.trace && threadIdx.x == 0) lt.trace[2] = (long long)__builtin_amdgcn_s_memrealtime();      // arrival
         return;
     }
-    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, 8, false, false, WC>(cqkv, H, blockIdx.x - nwg_down, (qkv_n + 15) / 16, msm, [&] {
+    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, 8, false, false, WC, WC == 1 ? CH_PRE_QKV : 0, true>(cqkv, H, blockIdx.x - nwg_down, (qkv_n + 15) / 16, msm, [&] {
         const ChainArgs ca = args();
         int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
         return ChainLate<WaitSharded>{ChainGemm{ca.dx, H, nullptr, 0, ca.dqkv, ca.qkv_ld, ca.B, qkv_n, ca.attn_norm, ca.eps, nullptr},
