@@ -104,6 +104,13 @@ int rdx_wcode_test(rdx_ctx* ctx, const float* W, int N, int K, void* packed_out,
  * out[3] / out[4] = launches of skinny_gemm_wc_k / decode_chain_wc_k this context has issued so far (a captured step graph counts once, at capture):
  * how a test sees that the coded kernels, and not their raw twins, ran. out holds 5 values. */
 int rdx_wcode_stats(rdx_ctx* ctx, long long* out);
+/* The dense words of the device encoder alone: W as for rdx_wcode_test (packed and encoded into temporaries of the hook); dense_host (HOST memory) gets
+ * Npad / 16 words, 1 for a tile that is not flagged raw and holds no weight with h = 0 (radialog_amd/wcode.py dense()), 0 otherwise. */
+int rdx_wcode_dense_test(rdx_ctx* ctx, const float* W, int N, int K, uint32_t* dense_host);
+/* The header and dense words of one coded copy of a finalized decoder: unit 0 = QKV, 2 = gate/up, 3 = down_proj (of `layer`), 4 = lm_head; `tiles` must
+ * be the weight's Npad / 16; words_host (HOST memory, may be null) gets 2 tiles words, headers then dense words -- which of the three K loops a tile
+ * of that unit runs. dense_total (may be null): the dense tiles over all coded copies of the context. */
+int rdx_wcode_dense_words(rdx_ctx* ctx, int unit, int layer, uint32_t* words_host, int tiles, long long* dense_total);
 
 /* The device quantiser of the int4 group-quantised weights alone (csrc/gemm.hip quant_w4_k; the format: radialog_amd/w4.py): W fp32 [N][K] (device) is
  * quantised as rdx_set_weight(RDX_W_GEMM_W4) does it, every tile int4 (rows padded to whole tiles of 16). wprime_out: the packed bf16 buffer of the

@@ -140,6 +140,8 @@ DEC_HOOK_SYMBOLS = {
     "rdx_rope_kv_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
     "rdx_wcode_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_wcode_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "rdx_wcode_dense_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
+    "rdx_wcode_dense_words": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_longlong)]),
     "rdx_w4_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_w4_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
 }

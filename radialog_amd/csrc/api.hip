@@ -286,7 +286,7 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
             auto encode = [&](GemmW& W) -> int {
                 if (!W.w || W.wc || W.w4) return 0;       // (a weight with an int4 stream gets no coded copy)
                 ALLOC(c, W.wc, wc_bytes(W.Npad, W.K));
-                ALLOC(c, W.wch, (size_t)(W.Npad / 16) * sizeof(unsigned));
+                ALLOC(c, W.wch, wc_hdr_words(W.Npad) * sizeof(unsigned));       // header words, then dense words
                 launch_encode_wc(W.w, W.wc, W.wch, W.Npad, W.K, c->stream);
                 return 0;
             };

@@ -287,7 +287,7 @@ extern "C" int rdx_gemm_test(rdx_ctx* c, const void* X, const float* W, const fl
             hipFree(wp);
             return fail(c, -1, "rdx_gemm_test: force 12 (coded bf16 weights) needs a bf16 context, K %% 128 == 0 and M <= 2 rows that fit the GEMV's LDS stage");
         }
-        if (hipMalloc(&coded.planes, wc_bytes(w.Npad, K)) != hipSuccess || hipMalloc((void**)&coded.hdr, (size_t)(w.Npad / 16) * sizeof(unsigned)) != hipSuccess) {
+        if (hipMalloc(&coded.planes, wc_bytes(w.Npad, K)) != hipSuccess || hipMalloc((void**)&coded.hdr, wc_hdr_words(w.Npad) * sizeof(unsigned)) != hipSuccess) {
             hipFree(wp);
             return fail(c, -2, "rdx_gemm_test: out of device memory");
         }
@@ -454,7 +454,7 @@ extern "C" int rdx_logits_test(rdx_ctx* c, const void* X, const float* W, int M,
     char* wp = nullptr;
     // qb: the fp8 copy and its scales, or the coded copy's planes (16-byte aligned behind wb) and header words
     const size_t cpb = coded ? wc_bytes(N, K) : 0;
-    const size_t wb = (size_t)N * K * 2, qb = fp8 ? (size_t)N * K + (size_t)N * 4 : cpb + (coded ? (size_t)nt * 4 : 0), pb = (size_t)M * nt * 4;
+    const size_t wb = (size_t)N * K * 2, qb = fp8 ? (size_t)N * K + (size_t)N * 4 : cpb + (coded ? wc_hdr_words(N) * 4 : 0), pb = (size_t)M * nt * 4;
     HIPCHK(c, hipMalloc((void**)&wp, wb + qb + 2 * pb + (size_t)M * K * 2));
     w.w = wp;
     if (fp8) {

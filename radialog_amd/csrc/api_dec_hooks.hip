@@ -366,8 +366,61 @@ extern "C" int rdx_wcode_test(rdx_ctx* c, const float* W, int N, int K, void* pa
     HIPCHK(c, hipSetDevice(c->device));
     const int npad = (N + 15) / 16 * 16;
     launch_pack_weight(c->cfg.dtype, W, packed_out, N, K, npad, nullptr, c->stream);
-    launch_encode_wc(packed_out, planes_out, hdr_out, npad, K, c->stream);
+    // the encoder writes the dense words behind the header words: a buffer of both, of which hdr_out gets the first half
+    DevBufs tmp;
+    unsigned* words = (unsigned*)tmp.get(wc_hdr_words(npad) * sizeof(unsigned));
+    if (!words) return fail(c, -2, "rdx_wcode_test: out of device memory");
+    launch_encode_wc(packed_out, planes_out, words, npad, K, c->stream);
+    HIPCHK(c, hipMemcpyAsync(hdr_out, words, (size_t)(npad / 16) * sizeof(unsigned), hipMemcpyDeviceToDevice, c->stream));
     return finish(c);
+}
+
+extern "C" int rdx_wcode_dense_test(rdx_ctx* c, const float* W, int N, int K, uint32_t* dense_host) {
+    if (!c || !W || !dense_host || N <= 0 || K <= 0) return fail(c, -1, "rdx_wcode_dense_test: bad arguments");
+    if (c->cfg.dtype != DT_BF16 || K % WC_CHUNK_K) return fail(c, -1, "rdx_wcode_dense_test: coded weights need a bf16 context and K %% 128 == 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const int npad = (N + 15) / 16 * 16, nt = npad / 16;
+    DevBufs tmp;
+    void* packed = tmp.get((size_t)npad * K * 2);
+    void* planes = tmp.get(wc_bytes(npad, K));
+    unsigned* words = (unsigned*)tmp.get(wc_hdr_words(npad) * sizeof(unsigned));
+    if (!packed || !planes || !words) return fail(c, -2, "rdx_wcode_dense_test: out of device memory");
+    launch_pack_weight(c->cfg.dtype, W, packed, N, K, npad, nullptr, c->stream);
+    launch_encode_wc(packed, planes, words, npad, K, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpy(dense_host, words + nt, (size_t)nt * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int rdx_wcode_dense_words(rdx_ctx* c, int unit, int layer, uint32_t* words_host, int tiles, long long* dense_total) {
+    if (!c || !c->finalized) return fail(c, -1, "rdx_wcode_dense_words: a finalized context is needed");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::vector<const GemmW*> ws;
+    if (c->cfg.enable_llama) {
+        ws.push_back(&c->lm_head);
+        for (const LlamaLayer& L : c->ll) { ws.push_back(&L.wqkv); ws.push_back(&L.wgu); ws.push_back(&L.wdown); }
+    }
+    if (dense_total) {
+        *dense_total = 0;
+        for (const GemmW* W : ws) {
+            if (!W->wc || !W->wch) continue;
+            const int nt = W->Npad / 16;
+            std::vector<unsigned> d(nt);
+            HIPCHK(c, hipMemcpy(d.data(), W->wch + nt, (size_t)nt * sizeof(unsigned), hipMemcpyDeviceToHost));
+            for (unsigned v : d) *dense_total += v & 1u;
+        }
+    }
+    if (!words_host) return 0;
+    const GemmW* W = nullptr;
+    if (unit == UNIT_LM_HEAD) W = &c->lm_head;
+    else if (layer >= 0 && layer < (int)c->ll.size())
+        W = unit == UNIT_QKV ? &c->ll[layer].wqkv : unit == UNIT_GATE_UP ? &c->ll[layer].wgu : unit == UNIT_DOWN ? &c->ll[layer].wdown : nullptr;
+    if (!W || !W->wc || !W->wch) return fail(c, -1, "rdx_wcode_dense_words: unit %d of layer %d has no coded copy", unit, layer);
+    if (tiles != W->Npad / 16) return fail(c, -1, "rdx_wcode_dense_words: the weight has %d tiles, not %d", W->Npad / 16, tiles);
+    HIPCHK(c, hipMemcpy(words_host, W->wch, wc_hdr_words(W->Npad) * sizeof(unsigned), hipMemcpyDeviceToHost));
+    return 0;
 }
 
 extern "C" int rdx_wcode_stats(rdx_ctx* c, long long* out) {
@@ -388,7 +441,7 @@ extern "C" int rdx_wcode_stats(rdx_ctx* c, long long* out) {
         HIPCHK(c, hipMemcpy(h.data(), W->wch, (size_t)nt * sizeof(unsigned), hipMemcpyDeviceToHost));
         out[0] += nt;
         for (unsigned v : h) out[1] += (v >> 8) & 1u;
-        out[2] += (long long)wc_bytes(W->Npad, W->K) + (long long)nt * 4;
+        out[2] += (long long)wc_bytes(W->Npad, W->K) + (long long)wc_hdr_words(W->Npad) * 4;
     }
     return 0;
 }

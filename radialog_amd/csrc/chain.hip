@@ -112,6 +112,16 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
     long long* const trace = lt.trace;
     unsigned wc_hdr = 0;          // the tile's header word: a scalar load (constant address space) behind the ring, see skinny_body.h
     if constexpr (WC) wc_hdr = *(reinterpret_cast<const __attribute__((address_space(4))) unsigned*>((uintptr_t)lt.wchdr) + tile_c);
+    // the 13-bit code's dense word, behind the header words (gemm.hip encode_wc_k): the tile holds no index 0 and is decoded without the zero test
+    // (rdx_common.h wc_hi4 DENSE). Raw, general or dense: one scalar choice per tile, in the pre-decode and in front of the K loops.
+    // The two coded forms stand one BEHIND the other, each stepped over by scalar branches where the tile takes the other (skinny_body.h: as the two
+    // arms of one branch this kernel went from 96 VGPRs to 128 and 104 bytes of scratch). form_d / form_g: which one runs, opaque to the compiler --
+    // what it can prove about them it uses to put the forms side by side again.
+    unsigned wc_dense = 0;
+    if constexpr (WC == 1) wc_dense = *(reinterpret_cast<const __attribute__((address_space(4))) unsigned*>((uintptr_t)lt.wchdr) + ntiles + tile_c);
+    // (bit 0 of the word: exactly one of the two is set, whatever else the word may come to hold)
+    auto form_d = [&]() -> bool { unsigned f = wc_dense & 1u; asm volatile("" : "+s"(f)); return f != 0; };
+    auto form_g = [&]() -> bool { unsigned f = (wc_dense & 1u) ^ 1u; asm volatile("" : "+s"(f)); return f != 0; };
     // debug timeline of this workgroup (rdx_gemv_trace 7; null in every product launch), 100 MHz ticks, wave 0: [0] entry, [5] first weight KiB
     // back, [3] inputs ready, [6] first MFMA (row staged), [1] K loop done, [7] end; [2] = arrival, written by the down_proj role's caller
     const T* X = reinterpret_cast<const T*>(a.X);
@@ -143,19 +153,24 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
     static_assert(PRE == 0 || PRE_POLL || !WaitFn::TAGGED, "pre-decode without a poll stands behind the plain activation loads: a tagged sweep has no such site");
     u4 pre[PRE ? 4 * PRE : 1];
     const bool predec = PRE > 0 && !(wc_hdr & 0x100u);        // wave-uniform
-    auto predecode = [&] {
+    auto predecode_as = [&](auto dn) {         // dn: the tile is dense (std::true_type) or general
         if constexpr (PRE > 0) {
-            if (predec) {
-                const unsigned base4 = (wc_hdr & 0xffu) * 0x01010101u;
+            constexpr bool DN = decltype(dn)::value;
+            const unsigned base4 = (wc_hdr & 0xffu) * 0x01010101u;
 #pragma unroll
-                for (int u = 0; u < PRE; ++u) {
-                    pre[4 * u] = CD::template frag<0>(cring[u], base4); pre[4 * u + 1] = CD::template frag<1>(cring[u], base4);
-                    pre[4 * u + 2] = CD::template frag<2>(cring[u], base4); pre[4 * u + 3] = CD::template frag<3>(cring[u], base4);
-                    const size_t o = (size_t)min(q0 + RC + u, qlast) * CD::BYTES;
-                    cring[u] = CD::load(cb16 + o, cb4 + o);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+            for (int u = 0; u < PRE; ++u) {
+                pre[4 * u] = CD::template frag<0, DN>(cring[u], base4); pre[4 * u + 1] = CD::template frag<1, DN>(cring[u], base4);
+                pre[4 * u + 2] = CD::template frag<2, DN>(cring[u], base4); pre[4 * u + 3] = CD::template frag<3, DN>(cring[u], base4);
+                const size_t o = (size_t)min(q0 + RC + u, qlast) * CD::BYTES;
+                cring[u] = CD::load(cb16 + o, cb4 + o);
+                __builtin_amdgcn_sched_barrier(0);
             }
+        }
+    };
+    auto predecode = [&] {
+        if (predec) {
+            if (form_d()) predecode_as(std::true_type());
+            if (form_g()) predecode_as(std::false_type());
         }
     };
     if constexpr (PRE > 0 && PRE_POLL) {
@@ -311,7 +326,9 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             // finite, so the products are zeros; (2) the fp32 accumulator starts at +0 and a sum is -0 only if all its terms are, so it is never -0 and
             // x + (+-0) = x leaves its bits alone; (3) an MFMA whose 32 products are all zero returns its accumulator operand.
             auto xsel = [&](int c, bool guard) -> const u4* { return reinterpret_cast<const u4*>((!guard || (c >= c0 && c < c1)) ? xrow + (size_t)c * 32 : zptr); };
-            auto consumeC = [&](const typename CD::Chunk& ch, int q, bool guard) {
+            // dn (a type: std::true_type / false_type): the dense form of the decode
+            auto consumeC = [&](auto dn, const typename CD::Chunk& ch, int q, bool guard) {
+                constexpr bool DN = decltype(dn)::value;
                 if constexpr (WC == 1) {
                     // operand lookahead: the four activation fragments of the chunk do not depend on its decode, so they are read from LDS in front of
                     // it (16 VGPRs) and the LDS round trip passes under the decodes -- the waits are lgkmcnt(3..0) across the chunk instead of a
@@ -321,8 +338,8 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
                         acc = mfma16(as_vec8<T>(wd), as_vec8<T>(xv), acc);
                         __builtin_amdgcn_sched_barrier(0);      // one fragment at a time (below)
                     };
-                    one(CD::template frag<0>(ch, base4), x0); one(CD::template frag<1>(ch, base4), x1);
-                    one(CD::template frag<2>(ch, base4), x2); one(CD::template frag<3>(ch, base4), x3);
+                    one(CD::template frag<0, DN>(ch, base4), x0); one(CD::template frag<1, DN>(ch, base4), x1);
+                    one(CD::template frag<2, DN>(ch, base4), x2); one(CD::template frag<3, DN>(ch, base4), x3);
                 } else {
                     auto one = [&](const u4 wd, int c) {
                         acc = mfma16(as_vec8<T>(wd), as_vec8<T>(*xsel(c, guard)), acc);
@@ -330,25 +347,25 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
                         // vmcnt(0) once per trip: the ring drains (tests/test_isa_wcode.py)
                         __builtin_amdgcn_sched_barrier(0);
                     };
-                    one(CD::template frag<0>(ch, base4), 4 * q); one(CD::template frag<1>(ch, base4), 4 * q + 1);
-                    one(CD::template frag<2>(ch, base4), 4 * q + 2); one(CD::template frag<3>(ch, base4), 4 * q + 3);
+                    one(CD::template frag<0, DN>(ch, base4), 4 * q); one(CD::template frag<1, DN>(ch, base4), 4 * q + 1);
+                    one(CD::template frag<2, DN>(ch, base4), 4 * q + 2); one(CD::template frag<3, DN>(ch, base4), 4 * q + 3);
                 }
             };
-            auto trip = [&](int q, bool guard) {
+            auto trip = [&](auto dn, int q, bool guard) {
 #pragma unroll
                 for (int u = 0; u < RC; ++u) {
-                    consumeC(cring[u], q + u, guard);
+                    consumeC(dn, cring[u], q + u, guard);
                     const size_t o = (size_t)min(q + RC + u, qlast) * CD::BYTES;
                     cring[u] = CD::load(cb16 + o, cb4 + o);
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
-            int q = q0;
             if constexpr (PRE > 0) {
                 // The first trip, unconditional (a slice of at most RC chunks refills from its clamped last chunk, and the guard sends what lies past
                 // c1 to the zero line): chunks q0 .. q0 + PRE - 1 are in `pre`, decoded and their slots refilled ahead of the seam -- by the polling
-                // wave only now -- and take MFMAs only, same guard; the rest of the ring follows as in any trip. The ring is then that of a first
-                // trip taken: nothing is fetched twice that the loop without pre-decode fetches once.
+                // wave only now -- and take MFMAs only, same guard; the rest of the ring follows as in any trip, in the tile's form. The ring is then
+                // that of a first trip taken: nothing is fetched twice that the loop without pre-decode fetches once. The MFMAs on `pre` stand in
+                // front of both forms: its 16 PRE registers are dead where the forms' loops begin.
                 if constexpr (PRE_POLL) {
                     if (wa == 0) predecode();
                 }
@@ -357,19 +374,40 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
                     acc = mfma16(as_vec8<T>(pre[u]), as_vec8<T>(*xsel(4 * q0 + u, true)), acc);
                     if (u % 4 == 3) __builtin_amdgcn_sched_barrier(0);      // a chunk's four operand reads at a time (16 VGPRs)
                 }
+            }
+            if constexpr (WC == 1) {
+                // First trip, K loop and tail exist once per form. The two forms stand one BEHIND the other, each stepped over as a whole where the
+                // tile takes the other.
+                auto coded_loop = [&](auto dn) {
+                    int q = q0;
+                    if constexpr (PRE > 0) {
+                        // the rest of the first trip (above): the ring's chunks PRE .. RC - 1 as in any trip, guarded
 #pragma unroll
-                for (int u = PRE; u < RC; ++u) {
-                    consumeC(cring[u], q0 + u, true);
-                    const size_t o = (size_t)min(q0 + RC + u, qlast) * CD::BYTES;
-                    cring[u] = CD::load(cb16 + o, cb4 + o);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                q += RC;
-            } else if (q + RC < q1) { trip(q, true); q += RC; }
-            for (; q + RC < q1; q += RC) trip(q, false);
+                        for (int u = PRE; u < RC; ++u) {
+                            consumeC(dn, cring[u], q0 + u, true);
+                            const size_t o = (size_t)min(q0 + RC + u, qlast) * CD::BYTES;
+                            cring[u] = CD::load(cb16 + o, cb4 + o);
+                            __builtin_amdgcn_sched_barrier(0);
+                        }
+                        q += RC;
+                    } else if (q + RC < q1) { trip(dn, q, true); q += RC; }
+                    for (; q + RC < q1; q += RC) trip(dn, q, false);
 #pragma unroll
-            for (int u = 0; u < RC; ++u)
-                if (q + u < q1) consumeC(cring[u], q + u, true);
+                    for (int u = 0; u < RC; ++u)
+                        if (q + u < q1) consumeC(dn, cring[u], q + u, true);
+                };
+                if (form_d()) coded_loop(std::true_type());
+                if (form_g()) coded_loop(std::false_type());
+            } else {        // the int4 stream: one form, no pre-decode. The driver is written out, not a call of a lambda like coded_loop: only so does
+                            // decode_chain_w4_k compile to the instructions it had (tests/test_isa_chain_predecode.py pins its loops)
+                const std::false_type dn;
+                int q = q0;
+                if (q + RC < q1) { trip(dn, q, true); q += RC; }
+                for (; q + RC < q1; q += RC) trip(dn, q, false);
+#pragma unroll
+                for (int u = 0; u < RC; ++u)
+                    if (q + u < q1) consumeC(dn, cring[u], q + u, true);
+            }
         }
     } else {
         int cb = c0;

@@ -116,14 +116,15 @@ void launch_pack_weight_fp8(int dtype, const float* src, void* dst8, float* scal
 // the GEMV streams, after every fusion and interleave of the loader. Pass 1: the largest h = (e7..e1) of the tile and whether any weight is Inf / NaN
 // (h = 127); base = max(top - 15, 0), so indices 1..15 name h = base + 1 .. base + 15 and index 0 names h = 0 (zero, subnormals, the binade above
 // them). Pass 2: the planes, and the raw flag for a tile that holds a weight with 0 < h <= base or h = 127. A flagged tile's planes are written all
-// the same (the kernels' first loads are unconditional), its out-of-window indices as 0.
+// the same (the kernels' first loads are unconditional), its out-of-window indices as 0. The tile's dense word, hdr[tiles + tile] (wcode.py dense()):
+// 1 iff the tile is not flagged and none of its weights has h = 0 -- the kernels then decode it without the zero test (rdx_common.h wc_hi4 DENSE).
 __global__ __launch_bounds__(256) void encode_wc_k(const u4* __restrict__ packed, unsigned char* __restrict__ planes, unsigned* __restrict__ hdr, int K) {
-    __shared__ int s_top, s_raw;
+    __shared__ int s_top, s_raw, s_zero;
     const int tile = blockIdx.x, KC = K >> 5, KQ = K >> 7, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) { s_top = 0; s_raw = 0; }
+    if (threadIdx.x == 0) { s_top = 0; s_raw = 0; s_zero = 0; }
     __syncthreads();
     const u4* src = packed + (size_t)tile * KC * 64;
-    int top = 0, bad = 0;
+    int top = 0, bad = 0, zero = 0;
     for (int i = threadIdx.x; i < KC * 64; i += 256) {
         const u4 v = src[i];
 #pragma unroll
@@ -132,6 +133,7 @@ __global__ __launch_bounds__(256) void encode_wc_k(const u4* __restrict__ packed
             for (int hlf = 0; hlf < 2; ++hlf) {
                 const int h = (int)((v[d] >> (16 * hlf + 8)) & 0x7fu);
                 if (h == 127) bad = 1; else top = max(top, h);
+                if (h == 0) zero = 1;
             }
     }
     atomicMax(&s_top, top);
@@ -163,8 +165,12 @@ __global__ __launch_bounds__(256) void encode_wc_k(const u4* __restrict__ packed
         reinterpret_cast<unsigned*>(p + 3072)[lane] = sg;
     }
     if (bad) atomicOr(&s_raw, 1);
+    if (zero) atomicOr(&s_zero, 1);
     __syncthreads();
-    if (threadIdx.x == 0) hdr[tile] = (unsigned)base | (s_raw ? 0x100u : 0u);
+    if (threadIdx.x == 0) {
+        hdr[tile] = (unsigned)base | (s_raw ? 0x100u : 0u);
+        hdr[gridDim.x + tile] = (s_raw || s_zero) ? 0u : 1u;
+    }
 }
 
 void launch_encode_wc(const void* packed, void* planes, unsigned* hdr, int npad, int K, hipStream_t s) {

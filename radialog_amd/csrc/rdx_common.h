@@ -109,17 +109,19 @@ __device__ __forceinline__ WcChunk wc_load(const unsigned char* p16, const unsig
     return c;
 }
 // four high bytes from four index bytes (0..15 each): GI = 2 j + (weights 4..7 ? 1 : 0) selects their sign bits
-template <int GI> __device__ __forceinline__ unsigned wc_hi4(unsigned x, unsigned base4, unsigned sg) {
+// DENSE: the tile holds no index 0 (its dense word says so, wcode.py dense()): every byte is base + index <= 126, no zero test, no carry between bytes
+template <int GI, bool DENSE = false> __device__ __forceinline__ unsigned wc_hi4(unsigned x, unsigned base4, unsigned sg) {
+    if constexpr (DENSE) return (x + base4) | ((sg << (7 - GI)) & 0x80808080u);
     const unsigned m = (x + 0x7f7f7f7fu) & 0x80808080u;       // bit 7 of a byte: its index is not 0
     const unsigned keep = m - (m >> 7);                        // 0x7f there, 0 where the index is 0
     return ((x + base4) & keep) | ((sg << (7 - GI)) & 0x80808080u);
 }
 // fragment J (constant) of a chunk: the 16 bytes pack_weight_k wrote for this lane in packed chunk 4 q + J
-template <int J> __device__ __forceinline__ u4 wc_frag(const WcChunk& c, unsigned base4) {
+template <int J, bool DENSE = false> __device__ __forceinline__ u4 wc_frag(const WcChunk& c, unsigned base4) {
     const unsigned n = c.ix[J];
     const u4& lo = J < 2 ? c.lo0 : c.lo1;
     const unsigned l0 = lo[2 * (J & 1)], l1 = lo[2 * (J & 1) + 1];
-    const unsigned h0 = wc_hi4<2 * J>(n & 0x0f0f0f0fu, base4, c.sg), h1 = wc_hi4<2 * J + 1>((n >> 4) & 0x0f0f0f0fu, base4, c.sg);
+    const unsigned h0 = wc_hi4<2 * J, DENSE>(n & 0x0f0f0f0fu, base4, c.sg), h1 = wc_hi4<2 * J + 1, DENSE>((n >> 4) & 0x0f0f0f0fu, base4, c.sg);
     return (u4){__builtin_amdgcn_perm(h0, l0, 0x05010400u), __builtin_amdgcn_perm(h0, l0, 0x07030602u),
                 __builtin_amdgcn_perm(h1, l1, 0x05010400u), __builtin_amdgcn_perm(h1, l1, 0x07030602u)};
 }
@@ -159,15 +161,15 @@ template <int J> __device__ __forceinline__ u4 w4_frag(const W4Chunk& c) {
 
 // What the two alternative weight streams of the batch <= 2 GEMV differ in (skinny_body.h / chain.hip, template switch WC: 1 = the 13-bit code,
 // 2 = int4): the chunk in registers, its bytes, where the lane's second pointer starts, its loads (LOADS per chunk), the decode of fragment J (hp: the
-// 13-bit code's window base from the tile's header; int4 carries its scale in the chunk) and which four 16-byte registers of a dropped ring a
-// raw-flagged tile reuses.
+// 13-bit code's window base from the tile's header; DENSE: the tile's dense word is set, the decode without the zero test; int4 carries its scale in
+// the chunk) and which four 16-byte registers of a dropped ring a raw-flagged tile reuses.
 template <int WC> struct Coded;
 template <> struct Coded<1> {
     typedef WcChunk Chunk;
     static constexpr int BYTES = WC_CHUNK_BYTES, LOADS = 4;
     static __device__ __forceinline__ int off2(int lane) { return 3072 + lane * 4; }
     static __device__ __forceinline__ Chunk load(const unsigned char* p16, const unsigned char* p2) { return wc_load(p16, p2); }
-    template <int J> static __device__ __forceinline__ u4 frag(const Chunk& c, unsigned hp) { return wc_frag<J>(c, hp); }
+    template <int J, bool DENSE = false> static __device__ __forceinline__ u4 frag(const Chunk& c, unsigned hp) { return wc_frag<J, DENSE>(c, hp); }
     static __device__ __forceinline__ u4& slot(Chunk* ring, int u) { return u == 0 ? ring[0].lo0 : u == 1 ? ring[0].lo1 : u == 2 ? ring[0].ix : ring[1].lo0; }
 };
 template <> struct Coded<2> {
@@ -175,7 +177,7 @@ template <> struct Coded<2> {
     static constexpr int BYTES = W4_CHUNK_BYTES, LOADS = 2;
     static __device__ __forceinline__ int off2(int lane) { return 1024 + (lane & 15) * 2; }
     static __device__ __forceinline__ Chunk load(const unsigned char* p16, const unsigned char* p2) { return w4_load(p16, p2); }
-    template <int J> static __device__ __forceinline__ u4 frag(const Chunk& c, unsigned) { return w4_frag<J>(c); }
+    template <int J, bool = false> static __device__ __forceinline__ u4 frag(const Chunk& c, unsigned) { return w4_frag<J>(c); }
     static __device__ __forceinline__ u4& slot(Chunk* ring, int u) { return ring[u].nib; }       // (rings of at least four chunks)
 };
 template <> struct Coded<0> : Coded<1> {};      // the raw instantiations declare an unused ring of this type

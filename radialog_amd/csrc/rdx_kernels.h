@@ -72,7 +72,9 @@ bool skinny_w4_supported(int dtype, const GemmArgs& a, int epi);
 // coded bf16 weights: 128 k-values per chunk; per (tile, chunk) three planes of whole-wave contiguous loads (rdx_common.h)
 constexpr int WC_CHUNK_K = 128, WC_CHUNK_BYTES = 64 * 52;
 inline size_t wc_bytes(int npad, int k) { return (size_t)(npad / 16) * (size_t)(k / WC_CHUNK_K) * WC_CHUNK_BYTES; }
-// bf16 only: reads the PACKED buffer of launch_pack_weight, writes the planes and hdr[npad / 16] = base | raw << 8; K % 128 == 0
+// bf16 only: reads the PACKED buffer of launch_pack_weight, writes the planes, hdr[npad / 16] = base | raw << 8 and, behind them, the dense words
+// hdr[npad / 16 + tile] (hdr holds wc_hdr_words(npad) words); K % 128 == 0
+inline size_t wc_hdr_words(int npad) { return (size_t)(npad / 16) * 2; }
 void launch_encode_wc(const void* packed, void* planes, unsigned* hdr, int npad, int K, hipStream_t s);
 // the batch <= 2 GEMV has a coded form for these arguments (a.WC set, bf16, LDS-staged activations, K % 128 == 0)
 bool skinny_wc_supported(int dtype, const GemmArgs& a, int epi);

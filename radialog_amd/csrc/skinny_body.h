@@ -83,10 +83,12 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
     __builtin_amdgcn_sched_barrier(0);            // nothing of what follows is scheduled in front of the ring
     const GemmArgs a = late();
     const T* X = reinterpret_cast<const T*>(a.X);
-    unsigned wc_hdr = 0;
+    unsigned wc_hdr = 0, wc_dense = 0;
     // the tile's header word, behind the ring. Through the constant address space (the words never change while a kernel runs): a SCALAR load, so the
     // choice between the two loops is a scalar branch -- as a vector load it was waited for with vmcnt(0), the ring with it, and both loops ran under EXEC masks
     if constexpr (WC) wc_hdr = *(reinterpret_cast<const __attribute__((address_space(4))) unsigned*>((uintptr_t)wchdr) + tile);
+    // the 13-bit code's dense word, behind the header words (gemm.hip encode_wc_k): raw, general or dense is one scalar choice per tile
+    if constexpr (WC == 1) wc_dense = *(reinterpret_cast<const __attribute__((address_space(4))) unsigned*>((uintptr_t)wchdr) + ntiles + tile);
 
     long long* trc = (a.trace && threadIdx.x == 0) ? a.trace + (size_t)tile * 8 : nullptr;
 #define SK_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
@@ -232,30 +234,53 @@ __device__ __forceinline__ void skinny_tile(const void* Wb, const int K, const i
                 // -0 only when all its terms are, so it is never -0, and x + (+-0) = x for every other x; (3) an MFMA whose 32 products are all zero
                 // therefore returns its accumulator operand unchanged, wherever in the sequence it stands. Cost: at most 3 fragments decoded in vain
                 // at either end of a slice (K = 11008 over 16 waves: 21.5 packed chunks per wave, 24 or 28 decoded); aligned slices pay nothing.
-                auto consumeC = [&](const typename CD::Chunk& ch, int q, bool guard) {
+                // DN (a type: std::true_type / false_type): the dense form, whose fragments are decoded without the zero test (rdx_common.h wc_hi4). First
+                // trip, K loop and tail exist once per form, each loop one basic block with counted waits. The two forms stand one BEHIND the other, not
+                // side by side: the form the tile does not take is stepped over by a scalar branch, on a flag the compiler cannot see through. (As the
+                // two arms of one branch, each carrying the ring through its own loops, the compiler no longer kept the ring in the registers it was
+                // loaded into: the 4-wave form went from 62 VGPRs to 64 and 52 bytes of scratch, the others to 74.)
+                auto consumeC = [&](auto dn, const typename CD::Chunk& ch, int q, bool guard) {
+                    constexpr bool DN = decltype(dn)::value;
                     auto one = [&](const u4 wd, int c) {
                         const T* xp = (!guard || (c >= c0 && c < c1)) ? xrow[0] + (size_t)c * 32 : zptr;
                         acc[0] = mfma16(as_vec8<T>(wd), as_vec8<T>(*reinterpret_cast<const u4*>(xp)), acc[0]);
                         __builtin_amdgcn_sched_barrier(0);       // one fragment decoded at a time: four at once do not fit the 64 VGPRs of the 4-wave form
                     };
-                    one(CD::template frag<0>(ch, base4), 4 * q); one(CD::template frag<1>(ch, base4), 4 * q + 1);
-                    one(CD::template frag<2>(ch, base4), 4 * q + 2); one(CD::template frag<3>(ch, base4), 4 * q + 3);
+                    one(CD::template frag<0, DN>(ch, base4), 4 * q); one(CD::template frag<1, DN>(ch, base4), 4 * q + 1);
+                    one(CD::template frag<2, DN>(ch, base4), 4 * q + 2); one(CD::template frag<3, DN>(ch, base4), 4 * q + 3);
                 };
-                auto trip = [&](int q, bool guard) {
+                auto trip = [&](auto dn, int q, bool guard) {
 #pragma unroll
                     for (int u = 0; u < R; ++u) {
-                        consumeC(cring[u], q + u, guard);
+                        consumeC(dn, cring[u], q + u, guard);
                         const size_t o = (size_t)min(q + R + u, qlast) * CD::BYTES;
                         cring[u] = CD::load(cb16 + o, cb4 + o);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 };
-                int q = q0;
-                if (q + R < q1) { trip(q, true); q += R; }       // the trip that holds the slice's first chunk, outside the loop
-                for (; q + R < q1; q += R) trip(q, false);
+                if constexpr (WC == 1) {
+                    auto coded_loop = [&](auto dn) {
+                        int q = q0;
+                        if (q + R < q1) { trip(dn, q, true); q += R; }       // the trip that holds the slice's first chunk, outside the loop
+                        for (; q + R < q1; q += R) trip(dn, q, false);
 #pragma unroll
-                for (int u = 0; u < R; ++u)
-                    if (q + u < q1) consumeC(cring[u], q + u, true);
+                        for (int u = 0; u < R; ++u)
+                            if (q + u < q1) consumeC(dn, cring[u], q + u, true);
+                    };
+                    unsigned fd = wc_dense & 1u, fg = fd ^ 1u;        // exactly one of the two, whatever else the word may come to hold
+                    asm volatile("" : "+s"(fd), "+s"(fg));
+                    if (fd) coded_loop(std::true_type());
+                    if (fg) coded_loop(std::false_type());
+                } else {        // the int4 stream: one form. The driver is written out, not a call of a lambda like coded_loop: only so do the int4
+                                // kernels compile to the instructions they had (tests/test_isa_wcode_dense.py pins their loops)
+                    const std::false_type dn;
+                    int q = q0;
+                    if (q + R < q1) { trip(dn, q, true); q += R; }
+                    for (; q + R < q1; q += R) trip(dn, q, false);
+#pragma unroll
+                    for (int u = 0; u < R; ++u)
+                        if (q + u < q1) consumeC(dn, cring[u], q + u, true);
+                }
             }
         } else {
             raw_loop(wbase, [&](int u) -> u4& { return ring[u]; }, std::integral_constant<int, 2 * U>());

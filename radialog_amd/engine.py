@@ -626,6 +626,33 @@ class RdxEngine:
         check(self.ctx, self.lib.rdx_wcode_stats(self.ctx, out), "rdx_wcode_stats")
         return tuple(int(v) for v in out)
 
+    def wcode_dense_test(self, w):
+        """The dense words of the device encoder alone (rdx_wcode_dense_test; the definition: wcode.dense): w fp32 [N, K], K % 128 == 0. Returns uint32
+        [tiles] as a NumPy array."""
+        import numpy as np
+        N, K = w.shape
+        nt = (N + 15) // 16
+        w = self._dev(w, torch.float32)
+        out = (C.c_uint32 * nt)()
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_wcode_dense_test(self.ctx, _ptr(w), N, K, C.cast(out, C.c_void_p)), "rdx_wcode_dense_test")
+        return np.array(out, dtype=np.uint32)
+
+    def wcode_dense_words(self, unit, layer, tiles):
+        """(hdr uint32 [tiles], dense uint32 [tiles]) of one coded copy of this engine's decoder (rdx_wcode_dense_words): unit 0 = QKV, 2 = gate/up,
+        3 = down_proj of `layer`, 4 = lm_head."""
+        import numpy as np
+        out = (C.c_uint32 * (2 * tiles))()
+        check(self.ctx, self.lib.rdx_wcode_dense_words(self.ctx, unit, layer, C.cast(out, C.c_void_p), tiles, None), "rdx_wcode_dense_words")
+        a = np.array(out, dtype=np.uint32)
+        return a[:tiles], a[tiles:]
+
+    def wcode_dense_tiles(self):
+        """The dense tiles over all coded copies of this engine's decoder: those the coded kernels decode without the zero test."""
+        n = C.c_longlong(0)
+        check(self.ctx, self.lib.rdx_wcode_dense_words(self.ctx, 0, 0, None, 0, C.byref(n)), "rdx_wcode_dense_words")
+        return int(n.value)
+
     def w4_test(self, w):
         """The device quantiser of the int4 group-quantised weights alone (rdx_w4_test; the format: radialog_amd/w4.py): w fp32 [N, K], K % 128 == 0.
         Returns (wprime uint16 [tiles, K / 32, 64, 8], stream uint8 [tiles, K / 128, 1056], scales uint16 [tiles, K / 128, 16]) as NumPy arrays."""

@@ -17,7 +17,7 @@ c = 4 q + j) the output is CHUNK_BYTES bytes in three planes of whole-wave conti
     [2048, 3072)  idx:  lane * 16 + 4 j .. + 4       one little-endian dword per fragment, nibble 2 e (e < 4) or 2 (e - 4) + 1 (e >= 4)
     [3072, 3328)  sign: lane * 4 .. + 4              one little-endian dword, bit (2 j + e // 4) + 8 (e % 4)
 
-and one header word per tile: base | raw << 8.
+and one header word per tile: base | raw << 8, and one dense word per tile (dense() below): 1 iff the tile is not raw and holds no index 0.
 """
 import numpy as np
 
@@ -99,6 +99,19 @@ def decode(planes: np.ndarray, hdr: np.ndarray) -> np.ndarray:
     w = (sign << 15) | (h << 8) | lo
     # [tile][q][lane][j][e] -> [tile][4 q + j][lane][e]
     return np.ascontiguousarray(w.transpose(0, 1, 3, 2, 4)).reshape(nt, kq * 4, 64, 8).astype(np.uint16)
+
+
+def dense(packed: np.ndarray) -> np.ndarray:
+    """The dense words of the packed weight [tiles][K / 32][64][8] uint16 (the input of encode): uint32 [tiles], 1 for a tile that is not flagged raw and
+    none of whose weights has h = 0 (index 0: zeros, subnormals, the first normal binade; padding rows are zeros), 0 otherwise. Every index of a dense tile
+    is 1..15, so its high bytes are sign << 7 | (base + index) with no zero case: the kernels decode it without the zero test. The device encoder
+    stores the words behind the header words, hdr[tiles + tile]."""
+    nt = packed.shape[0]
+    assert packed.dtype == np.uint16
+    h = ((packed >> 8) & 0x7F).astype(np.int32).reshape(nt, -1)
+    lo, hi = h.min(axis=1), h.max(axis=1)
+    # no h = 0, no Inf / NaN (then top = hi), and the smallest h inside the window: index >= 1 for every weight
+    return ((lo >= 1) & (hi <= 126) & (lo - np.maximum(hi - WINDOW, 0) >= 1)).astype(np.uint32)
 
 
 def fallback_tiles(hdr: np.ndarray) -> int:
