@@ -225,6 +225,43 @@ int rdx_beam_search(rdx_ctx* ctx, const int32_t* ids, const int32_t* mask, int g
                     int max_new, int eos_id, int pad_id, float length_penalty, int early_stopping, int32_t* out_tokens_host,
                     int32_t* out_len_host, float* out_score_host, void* step_scores, int* n_steps_host);
 
+/* Row sessions: continuous batching. The decode step costs nearly the same with 4 live rows as with 32 (it is bound by weight traffic), so a batch that
+ * waits for its longest report decodes pads in every row that finished early. In a session the step runs on `rows` LIVE rows and the caller refills a
+ * finished row from its queue of waiting prompts while the neighbours go on decoding. No reference counterpart (HF generate has no such loop).
+ * A refill runs R prompts through the prompt path -- the launches of rdx_prefill(batch = R, T) -- into `stage` STAGING rows above the live ones, then moves
+ * each staged row (the KV of all layers, positions [0, ceil16(T)), and its decode state) into its target row; staging rows never take part in a step. A row
+ * nobody uses is PARKED: cache slot 0, position 0, finished, step count = cap; it still runs a one-position step but writes no token, and every rdx_rows_step
+ * call parks it again first, as it does a row whose end a poll has seen, so no number of steps carries such a row out of its cache row.
+ * A request ends at EOS (the rule of every greedy step: then the row emits pad_id) or at its own cap, which the CALLER enforces from steps_host: tokens past a
+ * request's own cap are to be ignored. The library keeps a host mirror of every row's cache slot and step count (T and 1 at the refill, + 1 per step).
+ * Every call returns -1, with a message and nothing enqueued, for: any rdx_rows_* call but begin outside a session; begin inside one; inside a session
+ * rdx_prefill*, rdx_generate*, rdx_decode_step*, rdx_score, rdx_beam_search and rdx_time ("rdx_rows_end first"), and switching rules or sampling on; begin
+ * while logits rules or sampling are on (a moved row's token history and draw index would have to move with it: out of scope); the shape rules below.
+ * All weight formats work (bf16 coded, int4, fp8, f16): only existing prompt and step launches run, plus the two copy kernels of rows.hip. */
+/* Opens a session with every row parked and out_tokens (DEVICE int32[rows][cap], the caller's, alive until rdx_rows_end returns) filled with pad_id.
+ * rows + stage <= max_batch; more than 32 rows + stage need the Vicuna-7B widths; 1 <= cap < max_len. The step's kernel family is that of `rows` rows. */
+int rdx_rows_begin(rdx_ctx* ctx, int rows, int stage, int cap /*tokens per request, max*/, int eos_id, int pad_id, int32_t* out_tokens /*device [rows][cap]*/);
+/* R prompts (ids / mask / qformer_embs as for rdx_prefill: device, left-padded to T) into the live rows rows_host[0 .. R-1] (HOST; distinct, < rows),
+ * enqueued behind the steps so far. 1 <= R <= stage; T + cap <= max_len and <= max_position_embeddings. The target's out_tokens row is cleared to pad_id and
+ * holds token 0 in column 0; logits: nullable model-dtype [R][vocab], the prompts' last-position logits. The results of a row are those of
+ * rdx_generate on its prompt, bit for bit, whatever its neighbours hold and whenever it arrives. */
+int rdx_rows_refill(rdx_ctx* ctx, const int32_t* ids /*dev [R][T], left-padded*/, const int32_t* mask /*nullable*/, int R, int T,
+                    const float* qformer_embs /*nullable*/, const int32_t* rows_host /*[R]*/, void* logits /*nullable [R][vocab]*/);
+/* n decode steps of all rows, enqueued without a sync: eager launches, or (use_graph) replays of the captured step graph, keyed by (rows, cap, eos, pad,
+ * out_tokens, logits). Returns -1 when a live row would pass max_len / max_position_embeddings (host mirror), for n < 1 or n >= max_len, and for logits
+ * with n != 1. logits: nullable model-dtype [rows][vocab] of that one step (parked rows: undefined values). */
+int rdx_rows_step(rdx_ctx* ctx, int n, int use_graph, void* logits /*nullable [rows][vocab]; only with n == 1*/);
+/* Drains the stream, then unfinished_host[rows] (HOST) = the rows' unfinished flags (0: parked, or ended by EOS) and steps_host[rows] (HOST, nullable) =
+ * tokens selected so far by each live row (host mirror; 0 for a parked row). A live row seen finished here is parked from the next step on: its tokens stay,
+ * and so does its count.
+ * Returns -5 when a fused / chained launch reported a hand-off timeout since the last poll (results invalid), like rdx_generate. */
+int rdx_rows_poll(rdx_ctx* ctx, int32_t* unfinished_host /*[rows]*/, int32_t* steps_host /*[rows]*/);
+/* Parks the live rows rows_host[0 .. n-1] (HOST); their out_tokens rows stay as they are. */
+int rdx_rows_park(rdx_ctx* ctx, const int32_t* rows_host, int n);
+/* Drains the stream and closes the session. The context is left without a conversation, as after rdx_score: the decode-step and append calls return -1
+ * until the next prefill. */
+int rdx_rows_end(rdx_ctx* ctx);
+
 /* Data-parallel report generation: every image / report is an independent unit, each rank (one process per GPU)
  * runs encode -> prefill -> decode on its own shard with a full weight replica and NO data-path collective; the generated token ids
  * are gathered once at the end with ONE RCCL all-gather over xGMI. The reference has no inference-time collective (its only

@@ -88,6 +88,13 @@ SYMBOLS = {
                                       C.POINTER(C.c_int), C.c_int]),
     "rdx_beam_search": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P,
                                   C.POINTER(C.c_int)]),
+    # row sessions (continuous batching): rows_host / unfinished_host / steps_host are HOST int32 arrays
+    "rdx_rows_begin": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "rdx_rows_refill": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P]),
+    "rdx_rows_step": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "rdx_rows_poll": (C.c_int, [_P, _P, _P]),
+    "rdx_rows_park": (C.c_int, [_P, _P, C.c_int]),
+    "rdx_rows_end": (C.c_int, [_P]),
     "rdx_comm_unique_id": (C.c_int, [_P]),
     "rdx_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "rdx_allgather_tokens": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),

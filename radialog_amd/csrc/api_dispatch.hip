@@ -20,16 +20,21 @@ DecAttnArgs dec_attn_args(rdx_ctx* c, int layer) {
     return at;
 }
 
-AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer) {
+AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer, int row0) {
     const rdx_config& f = c->cfg;
     const int H = f.hidden;
     AttnArgs at;
     memset(&at, 0, sizeof(at));
     at.Q = c->pq; at.q_bs = (long)T * H; at.q_ts = H; at.q_hs = 128;
     at.K = kv_ptr(c, c->kcache, layer); at.V = kv_ptr(c, c->vcache, layer);
+    at.key_mask = c->key_mask;
+    if (row0) {
+        const size_t kv_row = (size_t)row0 * f.heads * f.max_len * 128 * 2;
+        at.K = (const char*)at.K + kv_row; at.V = (const char*)at.V + kv_row; at.key_mask = c->key_mask + (size_t)row0 * f.max_len;
+    }
     at.k_bs = at.v_bs = (long)f.heads * f.max_len * 128; at.k_ts = at.v_ts = 128; at.k_hs = at.v_hs = (long)f.max_len * 128;
     at.O = c->patt; at.o_bs = (long)T * H; at.o_ts = H; at.o_hs = 128;
-    at.B = B; at.H = f.heads; at.Tq = T; at.Tk = keep + T; at.causal = 1; at.k_perm = c->ld.k_perm; at.key_mask = c->key_mask; at.km_bs = f.max_len;
+    at.B = B; at.H = f.heads; at.Tq = T; at.Tk = keep + T; at.causal = 1; at.k_perm = c->ld.k_perm; at.km_bs = f.max_len;
     at.flash_min = c->flash_min;
     return at;
 }

@@ -22,6 +22,7 @@ extern "C" int rdx_hidden_read(rdx_ctx* c, void* dst) {
 
 extern "C" int rdx_time(rdx_ctx* c, int what, int iters, float* ms_host) {
     if (!c || !c->finalized || !c->cfg.enable_llama || c->cur_B <= 0) return fail(c, -1, "rdx_time: run a prefill first");
+    if (int src = rows_refuse(c, "rdx_time")) return src;       // its replays would advance rows behind the session's host mirror
     if (!ms_host || iters <= 0) return fail(c, -1, "rdx_time: bad arguments");
     HIPCHK(c, hipSetDevice(c->device));
     const rdx_config& f = c->cfg;

@@ -29,8 +29,10 @@ static int ensure_prefill_ws(rdx_ctx* c, size_t rows) {
 
 static const char* const k_need_blk = "more than 32 decoder rows need hidden 4096 / inter 11008 (the row-block family)";
 
+// row0 / tokens (a row session's refill, never under rules or sampling): the selected rows are rows row0 .. row0 + B - 1 of the per-row decode state, and
+// token 0 of row r goes to tokens[r * max_new] instead of the conversation's out_tokens. x, the logits and the argmax partials stay B-row scratch at base 0.
 static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, const int* out_step, long step_stride,
-                               int advance) {
+                               int advance, int row0 = 0, int32_t* tokens = nullptr) {
     const rdx_config& f = c->cfg;
     // logits rules: the row select_step_k processes must exist, so without a caller buffer the lm_head writes into the context's own
     if ((c->rules_on || c->sampling.do_sample) && !logits) { logits = c->rule_logits; out_step = nullptr; }
@@ -57,6 +59,11 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
     t.ctr_zero = c->chain_mlp ? c->d_ctr : nullptr;
     t.n_zero = (int)chain_ctr_ints(f.layers);
     t.epoch = c->d_epoch;
+    if (row0) {       // (advance == 0: pos / slot_b are null)
+        t.unfinished += row0; t.step_b += row0; t.pos_ro += row0;
+        t.x_next = (char*)c->dx + (size_t)row0 * f.hidden * 2; t.cur_rope = (char*)c->d_cur_rope + (size_t)row0 * 512;
+    }
+    if (tokens) t.out_tokens = tokens;
     if (!c->rules_on && !c->sampling.do_sample) { launch_greedy_step(f.dtype, c->part_val, c->part_idx, c->n_vtiles, B, t, c->stream); return; }
     // the row at the address the lm_head just wrote (a captured step with scores: both offset it by the step count, read from d_step before the tail advances it)
     if (c->rules_on) { t.hist = c->d_hist; t.hist_len = c->d_hist_len; t.hist_ld = f.max_len; }
@@ -74,6 +81,7 @@ static const rdx_sampling k_sampling_off = {0, 1.0f, 0, 1.0f, 0};
 extern "C" int rdx_set_sampling(rdx_ctx* c, const rdx_sampling* sm) {
     if (!c) return -1;
     if (!sm || !sm->do_sample) { c->sampling = k_sampling_off; return 0; }
+    if (int src = rows_refuse(c, "rdx_set_sampling")) return src;
     const rdx_sampling v = *sm;
     if (!(v.temperature > 0.f) || !std::isfinite(v.temperature)) return fail(c, -1, "rdx_set_sampling: temperature must be a finite float > 0 (1.0 = off)");
     if (v.top_k < 0) return fail(c, -1, "rdx_set_sampling: top_k %d is negative (0 = off)", v.top_k);
@@ -105,6 +113,7 @@ extern "C" int rdx_set_logits_rules(rdx_ctx* c, const rdx_logits_rules* rules) {
     if (r.min_new_tokens < 0) return fail(c, -1, "rdx_set_logits_rules: min_new_tokens %d is negative (0 = off)", r.min_new_tokens);
     const bool on = r.repetition_penalty != 1.0f || r.no_repeat_ngram_size != 0 || r.min_new_tokens != 0;
     if (on) {
+        if (int src = rows_refuse(c, "rdx_set_logits_rules")) return src;
         if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_set_logits_rules: llama weights not finalized");
         const rdx_config& f = c->cfg;
         if (!select_step_supported(f.vocab)) return fail(c, -1, "rdx_set_logits_rules: vocab %d exceeds the LDS bitmaps of select_step_k", f.vocab);
@@ -129,13 +138,14 @@ static int rules_need_prefill(rdx_ctx* c, const char* who) {
     return 0;
 }
 
-static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep, int pad_id, bool hist);
+static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep, int pad_id, bool hist, int row0 = 0);
 
 // keep == 0: a fresh prompt. keep > 0: `T` further prompt tokens behind the first `keep` cache slots of the previous call(s)
 // (the shared prefix of a multi-turn conversation is not recomputed; no image splice in the continuation).
 int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep,
                         int max_new, int eos_id, int pad_id, int32_t* out_tokens, void* logits) {
     if (!c) return -1;
+    if (int src = rows_refuse(c, keep > 0 ? "rdx_prefill_append" : "rdx_prefill")) return src;
     if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_prefill: llama weights not finalized");
     const rdx_config& f = c->cfg;
     if (!ids || !out_tokens || B <= 0 || B > f.max_batch) return fail(c, -1, "rdx_prefill: batch %d outside [1, %d]", B, f.max_batch);
@@ -167,7 +177,9 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
 // slots, the per-row decode state (d_pos / d_slot / d_step / d_unf, the key mask) is that of a prompt of T tokens. What the callers do with px is theirs: the
 // prefill gathers the last row of each prompt for token 0, the scoring pass the rows whose successor is scored. The workspace (ensure_prefill_ws) holds B x T
 // rows. hist: start the token history of the logits rules from `ids`.
-static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep, int pad_id, bool hist) {
+// row0 (a row session's refill; keep == 0, no history): the B prompts fill rows row0 .. row0 + B - 1 of the KV cache, the key mask and the decode state; the
+// workspaces (px .., the splice rows, img_pos / pos_ids) are prompt-local and stay at base 0. The launches are those of row0 == 0.
+static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep, int pad_id, bool hist, int row0) {
     const rdx_config& f = c->cfg;
     const size_t M = (size_t)B * T;
     const int dt = f.dtype, H = f.hidden;
@@ -177,8 +189,8 @@ static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
         launch_prep_append(B, T, keep, c->d_img_pos, c->d_pos_ids, c->d_pos, c->d_slot, c->d_step, c->d_unf, s);
         qformer_embs = nullptr;
     } else {
-        launch_prep_prompt(ids, mask, B, T, 32000, pad_id, c->d_img_pos, c->d_pos_ids, c->key_mask, f.max_len, c->d_pos, c->d_slot,
-                           c->d_step, c->d_unf, s);
+        launch_prep_prompt(ids, mask, B, T, 32000, pad_id, c->d_img_pos, c->d_pos_ids, c->key_mask + (size_t)row0 * f.max_len, f.max_len, c->d_pos + row0,
+                           c->d_slot + row0, c->d_step + row0, c->d_unf + row0, s);
     }
     c->hist_ready = hist;
     if (hist) launch_hist_init(ids, B, T, c->d_hist, c->d_hist_len, f.max_len, s);
@@ -191,6 +203,7 @@ static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
     launch_embed_splice(dt, ids, c->d_img_pos, c->embed, f.vocab, c->pimg, 32, c->px, B, T, H, qformer_embs ? 1 : 0, s);
 
     const bool fp8 = fp8_weights(c->ll[0].wqkv);
+    const size_t kv_row = (size_t)row0 * f.heads * f.max_len * 128 * 2;        // bytes of row0 cache rows of one layer
     // the RMSNorm of the residual stream px in the layout the projection behind it reads; `pend` slab groups of a K-split down_proj are folded in first
     auto prompt_norm = [&](const void* w, void* out, ActLayout layout, int mtiles, int pend) {
         run_rmsnorm(c, NormArgs{c->px, w, out, c->pxs, (int)M, H, f.rms_eps, layout, mtiles, pend ? c->pslab : nullptr, pend});
@@ -202,8 +215,8 @@ static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
         // attention / SwiGLU output); LoRA-B, RoPE, attention, SwiGLU and the residual adds stay in the model dtype
         for (int l = 0; l < f.layers; ++l) {
             const LlamaLayer& L = c->ll[l];
-            void* kc = kv_ptr(c, c->kcache, l);
-            void* vc = kv_ptr(c, c->vcache, l);
+            void* kc = (char*)kv_ptr(c, c->kcache, l) + kv_row;
+            void* vc = (char*)kv_ptr(c, c->vcache, l) + kv_row;
             auto g8 = [&](const GemmW& W, int K, int groups, void* out, int ldo, const void* resid, int epi) {
                 GemmArgs a = gargs(c->pxq, K, W, nullptr, out, ldo, (int)M);
                 a.N = W.Npad; a.xscale = c->pxs; a.xgroups = groups; a.resid = resid; a.ldr = H;
@@ -213,7 +226,7 @@ static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
             prompt_norm(L.attn_norm, c->pxq, ACT_ROWS_E4M3, 0, 0);
             g8(L.wqkv, H, 1, c->pqkv, c->ld.qkv_ld, nullptr, EPI_NONE);
             launch_rope_kv_prefill(dt, c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq, kc, vc, B, T, keep, s);
-            launch_attention(dt, 128, prefill_attn_args(c, B, T, keep, l), s);
+            launch_attention(dt, 128, prefill_attn_args(c, B, T, keep, l, row0), s);
             launch_quant_rows(dt, c->patt, H, c->pxq, c->pxs, (int)M, H, 2, s);
             g8(L.wo, H, 2, c->px, H, c->px, EPI_RESID);
             prompt_norm(L.mlp_norm, c->pxq, ACT_ROWS_E4M3, 0, 0);
@@ -251,15 +264,15 @@ static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
     const ActLayout xl = ws ? ACT_TILES32 : ACT_ROWS;       // what the norms write and the projections read
     for (int l = 0; l < f.layers; ++l) {
         const LlamaLayer& L = c->ll[l];
-        void* kc = kv_ptr(c, c->kcache, l);
-        void* vc = kv_ptr(c, c->vcache, l);
+        void* kc = (char*)kv_ptr(c, c->kcache, l) + kv_row;
+        void* vc = (char*)kv_ptr(c, c->vcache, l) + kv_row;
         prompt_norm(L.attn_norm, c->pxn, xl, mtl, pend);
         pend = 0;
         { GemmArgs a = gargs(c->pxn, H, L.wqkv, nullptr, c->pqkv, c->ld.qkv_ld, (int)M); a.N = L.wqkv.Npad; prompt_gemm(a, EPI_NONE, false); }
         // new K/V rows land behind the kept slots
         launch_rope_kv_prefill(dt, c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq,
                                kc, vc, B, T, keep, s);
-        AttnArgs at = prefill_attn_args(c, B, T, keep, l);
+        AttnArgs at = prefill_attn_args(c, B, T, keep, l, row0);
         at.o_packed_mt = ws ? mtl : 0;
         launch_attention(dt, 128, at, s);
         { GemmArgs a = gargs(c->patt, H, L.wo, nullptr, c->px, H, (int)M); a.resid = c->px; a.ldr = H; prompt_gemm(a, EPI_RESID, false); }
@@ -273,6 +286,18 @@ static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
     if (pend) prompt_norm(c->ll[0].attn_norm, c->pxn, xl, mtl, pend);
     }
     return 0;
+}
+
+int prefill_rows_at(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int R, int T, const float* qformer_embs, int row0, int32_t* tokens, void* logits) {
+    const rdx_config& f = c->cfg;
+    int rc = ensure_prefill_ws(c, (size_t)R * T);
+    if (rc) return rc;
+    rc = prompt_layers(c, ids, mask, R, T, qformer_embs, 0, c->cur_pad, /*hist=*/false, row0);
+    if (rc) return rc;
+    launch_gather_last(f.dtype, c->px, c->datt, R, T, f.hidden, c->stream);
+    lm_head_and_greedy(c, c->datt, R, logits, nullptr, 0, /*advance=*/0, row0, tokens);
+    HIPCHK(c, hipGetLastError());
+    return take_unsupported(c);
 }
 
 extern "C" int rdx_prefill(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs,
@@ -316,6 +341,7 @@ static int ensure_score_ws(rdx_ctx* c, size_t rows, size_t chunk) {
 extern "C" int rdx_score(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, const int32_t* labels_host,
                          float* logprob, int32_t* top1, void* logits) {
     if (!c) return -1;
+    if (int src = rows_refuse(c, "rdx_score")) return src;
     if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_score: llama weights not finalized");
     const rdx_config& f = c->cfg;
     if (!ids || !labels_host || !logprob || B <= 0 || B > f.max_batch) return fail(c, -1, "rdx_score: batch %d outside [1, %d]", B, f.max_batch);
@@ -536,6 +562,7 @@ bool decode_step_launch(rdx_ctx* c, void* logits, const int* out_step, long step
 
 extern "C" int rdx_decode_step(rdx_ctx* c, void* logits) {
     if (!c) return -1;
+    if (int src = rows_refuse(c, "rdx_decode_step")) return src;
     if (!c->finalized || c->cur_B <= 0) return fail(c, -1, "rdx_decode_step: no prefill has run");
     // every step appends one KV row per batch row and advances the RoPE position: refuse to walk past what the prefill reserved
     if (c->cur_steps >= c->cur_max_new)
@@ -555,6 +582,7 @@ extern "C" int rdx_decode_step(rdx_ctx* c, void* logits) {
 // the rows of the token the previous step selected, then the ordinary decode step runs.
 extern "C" int rdx_decode_step_ids(rdx_ctx* c, const int32_t* ids, void* logits) {
     if (!c) return -1;
+    if (int src = rows_refuse(c, "rdx_decode_step_ids")) return src;
     if (!ids) return fail(c, -1, "rdx_decode_step_ids: null ids");
     if (!c->finalized || c->cur_B <= 0) return fail(c, -1, "rdx_decode_step_ids: no prefill has run");
     if (c->cur_steps >= c->cur_max_new)
@@ -695,6 +723,7 @@ extern "C" int rdx_beam_search(rdx_ctx* c, const int32_t* ids, const int32_t* ma
                                int early_stopping, int32_t* out_tokens_host, int32_t* out_len_host, float* out_score_host,
                                void* step_scores, int* n_steps_host) {
     if (!c) return -1;
+    if (int src = rows_refuse(c, "rdx_beam_search")) return src;
     if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_beam_search: llama weights not finalized");
     const rdx_config& f = c->cfg;
     if (c->sampling.do_sample) return fail(c, -1, "rdx_beam_search: not available while sampling is on (beam-sample is not built); rdx_set_sampling(ctx, NULL) first");

@@ -156,6 +156,13 @@ struct rdx_ctx {
     int *bm_tok = nullptr, *bm_src = nullptr; int32_t* bm_out = nullptr; void* bm_scratch = nullptr;
     size_t bm_scratch_bytes = 0; int bm_rows = 0, bm_new = 0;
 
+    // ---- row session (rdx_rows_*, api_rows.hip): `rs_rows` live rows refilled one by one through `rs_stage` staging rows above them ----
+    bool rs_on = false;
+    int rs_rows = 0, rs_stage = 0, rs_cap = 0;
+    int32_t* rs_stage_tok = nullptr; size_t rs_stage_tok_ints = 0;     // [stage][cap]: where the staged prompts' token 0 lands
+    // the host mirror of every live row: deterministic (slot = T at refill, + 1 per step; step = tokens selected), only `unfinished` needs the poll
+    std::vector<int> rs_slot, rs_step, rs_state;                       // rs_state: RS_PARKED / RS_LIVE / RS_DONE (a poll saw the row finished)
+
     void* tf_ws = nullptr; size_t tf_bytes = 0;      // rdx_transform_image: coefficient tables + the horizontal pass's uint8 rows (grown on demand)
 
     // ---- data-parallel collective (RCCL over xGMI): the one all-gather of generated token ids ----
@@ -215,7 +222,7 @@ enum DecUnit { UNIT_QKV, UNIT_O, UNIT_GATE_UP, UNIT_DOWN, UNIT_LM_HEAD };
 enum DecFamily { DEC_UNSUPPORTED, DEC_CHAINED, DEC_GENERIC, DEC_XS16, DEC_BLK, DEC_BLK8 };
 DecFamily decode_family(rdx_ctx* c, int B);
 DecAttnArgs dec_attn_args(rdx_ctx* c, int layer);                                  // decode attention; callers set out_packed / out_mt / trace
-AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer);         // T prompt tokens behind `keep` cached ones; callers set o_packed_mt
+AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer, int row0 = 0);         // T prompt tokens behind `keep` cached ones; callers set o_packed_mt. row0: the B prompts are cache rows row0 ..
 // a unit in its base form: row-major activations, the RMSNorm in front of QKV / gate-up / lm_head as the kernel's prologue (norm_w), the residual of o_proj /
 // down_proj as its epilogue. L may be null for UNIT_LM_HEAD, whose callers set X (when not dx), out and out_step.
 GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);
@@ -252,4 +259,10 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
 // evs (timing only, eager launches): a pair of events recorded around every chained down(l) -> QKV(l+1) launch of this step
 bool decode_step_launch(rdx_ctx* c, void* logits, const int* out_step, long step_stride, std::vector<hipEvent_t>* evs = nullptr);
 int build_graph(rdx_ctx* c, void* scores, bool fixed = false);
+// R prompts of T tokens through the prompt path into rows row0 .. row0 + R - 1 of every per-row array (KV cache, decode state), token 0 of prompt r into
+// tokens[r * cur_max_new]: the launches of rdx_prefill(B = R, T) on offset bases. The caller has set cur_max_new / cur_eos / cur_pad.
+int prefill_rows_at(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int R, int T, const float* qformer_embs, int row0, int32_t* tokens, void* logits);
+enum { RS_PARKED = 0, RS_LIVE = 1, RS_DONE = 2 };
+// every conversation entry point refuses while a row session is open (-1, "rdx_rows_end first")
+inline int rows_refuse(rdx_ctx* c, const char* who) { return c->rs_on ? fail(c, -1, "%s: a row session is open on this context; rdx_rows_end first", who) : 0; }
 

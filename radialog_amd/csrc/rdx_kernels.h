@@ -356,4 +356,20 @@ void launch_kv_beam_reorder(void* kcache, void* vcache, void* scratch, const int
                             size_t layer_bytes, int p0, int p1, hipStream_t s);
 void launch_embed_rows(int dtype, const int* tokens, const void* embed, int vocab, void* x, int rows, int H, hipStream_t s);
 
+// ---- row sessions (rows.hip): staged rows into live rows, parked rows ----
+constexpr int ROWLIST_MAX = 128;        // = RDX_MAX_ROWS: a list rides in the kernel arguments, no device copy of host indices
+struct RowList { int n; short src[ROWLIST_MAX], dst[ROWLIST_MAX]; };      // absolute row indices; src unused when parking
+// the per-row decode state row_state_move_k moves: [rows] ints, the key mask [rows][max_len], dx [rows][H] and cur_rope [rows][256] (2-byte elements),
+// out_tokens [live rows][cap]; stage_tokens [staging rows][cap] holds token 0 of staged row r at row r - row0
+struct RowState {
+    int *pos, *slot, *step, *unf;
+    uint8_t* key_mask; void* dx; void* cur_rope;
+    int32_t* out_tokens; const int32_t* stage_tokens;
+    int max_len, H, cap, pad_id, row0;
+};
+// positions [0, npos) (a multiple of 16, or max_len) of every layer's K and V: row src[i] -> row dst[i]; the two sets of rows are disjoint
+void launch_kv_rows_move(void* kcache, void* vcache, const RowList& rl, int heads, int layers, int max_len, size_t layer_bytes, int npos, hipStream_t s);
+// park == 0: state of row src[i] -> row dst[i], out_tokens row cleared, token 0 in column 0. park != 0: rows dst[i] parked (bit 1: out_tokens row cleared too)
+void launch_row_state_move(const RowState& st, const RowList& rl, int park, hipStream_t s);
+
 }  // namespace rdx

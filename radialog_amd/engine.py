@@ -405,6 +405,34 @@ class RdxEngine:
         self.sync()
         return toks, logits
 
+    def row_session(self, rows: int, stage: int, cap: int, eos_id: int = 2, pad_id: int = 0, use_graph: bool = True) -> "RowSession":
+        """Open a row session (rdx_rows_begin): `rows` live rows refilled one by one through `stage` staging rows, `cap` tokens per request at most.
+        Greedy search only: logits rules and sampling are switched off first. Close it (or leave the `with` block) before any other decoder call."""
+        self.set_sampling(None)
+        self.set_logits_rules(None)
+        self._conv = None                            # the KV cache is overwritten
+        return RowSession(self, rows, stage, cap, eos_id, pad_id, use_graph)
+
+    def generate_queue(self, requests, rows: int, stage: Optional[int] = None, eos_id: int = 2, pad_id: int = 0, poll: int = 4,
+                       min_refill: Optional[int] = None, use_graph: bool = True, return_scheduler: bool = False):
+        """Continuous batching: `requests` = (ids 1-D, qformer_embs [32, D] or None, max_new) each, run through `rows` live rows by a RowScheduler
+        (radialog_amd/rowqueue.py); a finished row takes the next waiting prompt while its neighbours go on decoding. Returns the generated tokens of every
+        request, in request order (1-D int64, cut at EOS or at the request's max_new); with return_scheduler also the scheduler (its step / refill counts).
+        stage / min_refill default to QUEUE_STAGE / QUEUE_MIN_REFILL (profiles/r15_queue.md), stage bounded by max_batch - rows."""
+        from .rowqueue import RowScheduler
+        requests = list(requests)
+        if stage is None:
+            stage = max(1, min(QUEUE_STAGE, self.max_batch - rows))
+        if min_refill is None:
+            min_refill = QUEUE_MIN_REFILL
+        if not requests:
+            return ([], None) if return_scheduler else []
+        cap = max(int(r[2]) for r in requests)
+        with self.row_session(rows, stage, cap, eos_id=eos_id, pad_id=pad_id, use_graph=use_graph) as ses:
+            sched = RowScheduler(ses, rows, stage, poll=poll, min_refill=min_refill)
+            out = sched.run(requests)
+        return (out, sched) if return_scheduler else out
+
     def score(self, ids, qformer_embs, labels, mask=None, want_top1=False, want_logits=False):
         """rdx_score: per-token log-probabilities of given text from one pass over the prompt's kernels. ids int [B, T]; labels int [B, T] in HF's
         convention (the token at position t, -100 = not scored); mask as in prefill (None -> ids != 0). Returns (logprob float32 [B, T]: at t >= 1 with
@@ -888,6 +916,86 @@ class RdxEngine:
         buf = torch.zeros(max_tiles, 8, dtype=torch.int64)
         check(self.ctx, self.lib.rdx_gemv_trace(self.ctx, what, layer, buf.data_ptr(), max_tiles), "rdx_gemv_trace")
         return buf
+
+
+# generate_queue's defaults: staging rows per session and free rows a refill waits for, by the measured table of profiles/r15_queue.md (stage 4;
+# min_refill 2: 57.2 / 33.6 ms per request at 12 / 32 rows against 57.1 / 34.0 for 1 and 60.5 / 32.9 for 4)
+QUEUE_STAGE = 4
+QUEUE_MIN_REFILL = 2
+
+
+class RowSession:
+    """One open row session of an engine (rdx_rows_begin .. rdx_rows_end): the object a RowScheduler drives. Owns out_tokens [rows][cap]."""
+
+    def __init__(self, eng: RdxEngine, rows: int, stage: int, cap: int, eos_id: int, pad_id: int, use_graph: bool = True):
+        self.eng, self.rows, self.stage, self.cap = eng, int(rows), int(stage), int(cap)
+        self.eos_id, self.pad_id, self.use_graph, self.max_len = int(eos_id), int(pad_id), bool(use_graph), eng.max_len
+        self.tokens = torch.full((max(self.rows, 1), max(self.cap, 1)), self.pad_id, dtype=torch.int32, device=eng.device)
+        self._logits = None                          # ONE [rows][vocab] buffer: a step with logits replays the same graph every time
+        self._keep = None
+        self.open = False
+        torch.cuda.synchronize(eng.device)
+        check(eng.ctx, eng.lib.rdx_rows_begin(eng.ctx, self.rows, self.stage, self.cap, self.eos_id, self.pad_id, _ptr(self.tokens)), "rdx_rows_begin")
+        self.open = True
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def close(self):
+        if self.open:
+            self.open = False
+            check(self.eng.ctx, self.eng.lib.rdx_rows_end(self.eng.ctx), "rdx_rows_end")
+
+    def refill(self, ids, mask, qformer_embs, rows, want_logits: bool = False):
+        """R prompts ids [R, T] (left-padded; mask [R, T] or None -> ids != pad_id) into the live rows `rows`. Returns their last-position logits
+        [R, vocab] (model dtype) with want_logits, else None."""
+        e = self.eng
+        R, T = ids.shape
+        rows_h = torch.as_tensor(list(rows), dtype=torch.int32)
+        if rows_h.numel() != R:
+            raise ValueError(f"refill: {R} prompts for {rows_h.numel()} rows")
+        ids32 = ids.to(device=e.device, dtype=torch.int32).contiguous()
+        m32 = None if mask is None else mask.to(device=e.device, dtype=torch.int32).contiguous()
+        qf = None if qformer_embs is None else qformer_embs.to(device=e.device, dtype=torch.float32).contiguous()
+        logits = torch.empty(R, e.cfg.llama.vocab, dtype=e.tdtype, device=e.device) if want_logits else None
+        torch.cuda.synchronize(e.device)             # the inputs were written on torch's stream
+        check(e.ctx, e.lib.rdx_rows_refill(e.ctx, _ptr(ids32), _ptr(m32), R, T, _ptr(qf), C.c_void_p(rows_h.data_ptr()), _ptr(logits)), "rdx_rows_refill")
+        self._keep = (ids32, m32, qf, logits)        # alive until the stream has consumed them (the next refill syncs first)
+        if want_logits:
+            e.sync()
+        return logits
+
+    def step(self, n: int = 1, want_logits: bool = False):
+        """n decode steps of all rows, enqueued without a sync. want_logits (n == 1 only): a copy of the step's logits [rows, vocab]."""
+        e = self.eng
+        if want_logits and self._logits is None:
+            self._logits = torch.empty(self.rows, e.cfg.llama.vocab, dtype=e.tdtype, device=e.device)
+            torch.cuda.synchronize(e.device)
+        check(e.ctx, e.lib.rdx_rows_step(e.ctx, int(n), int(self.use_graph), _ptr(self._logits) if want_logits else None), "rdx_rows_step")
+        if not want_logits:
+            return None
+        e.sync()
+        return self._logits.clone()
+
+    def poll(self):
+        """(unfinished, steps) per row as lists, after draining the stream."""
+        unf = torch.zeros(self.rows, dtype=torch.int32)
+        steps = torch.zeros(self.rows, dtype=torch.int32)
+        check(self.eng.ctx, self.eng.lib.rdx_rows_poll(self.eng.ctx, C.c_void_p(unf.data_ptr()), C.c_void_p(steps.data_ptr())), "rdx_rows_poll")
+        return unf.tolist(), steps.tolist()
+
+    def park(self, rows):
+        rows_h = torch.as_tensor(list(rows), dtype=torch.int32)
+        check(self.eng.ctx, self.eng.lib.rdx_rows_park(self.eng.ctx, C.c_void_p(rows_h.data_ptr()), int(rows_h.numel())), "rdx_rows_park")
+
+    def read_tokens(self, row: int) -> torch.Tensor:
+        """The row's out_tokens [cap] on the host (drains the stream first)."""
+        self.eng.sync()
+        return self.tokens[row].cpu()
 
 
 def synth_getter(cfg: RaDialogCfg, device, lora: bool = True) -> Callable[[str], torch.Tensor]:

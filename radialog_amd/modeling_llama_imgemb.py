@@ -272,6 +272,44 @@ class LlamaForCausalLM:
         sc = tuple(scores[i].clone() for i in range(n)) if output_scores else None
         return GenerateOutput(sequences=seq, scores=sc)
 
+    @torch.no_grad()
+    def generate_many(self, input_ids: List[torch.Tensor], dicom: Optional[List[str]] = None, qformer_embs: Optional[torch.Tensor] = None,
+                      max_new_tokens=20, rows: Optional[int] = None, stage: Optional[int] = None, num_beams: int = 1, do_sample: bool = False,
+                      repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+                      eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None) -> List[torch.Tensor]:
+        """Greedy generation of many prompts of different lengths through a queue (no reference counterpart; RdxEngine.generate_queue): `rows` rows decode
+        at a time (default: max_batch less the staging rows) and a row whose report has ended takes the next waiting prompt. input_ids: a list of 1-D
+        prompts, unpadded; dicom / qformer_embs ([N, 32, qformer_dim]) as in generate; max_new_tokens: one int or one per prompt. Returns one 1-D int64
+        sequence per prompt, in order: the prompt, then what was generated up to and including EOS or up to the prompt's max_new_tokens.
+        Greedy search only: num_beams > 1, do_sample and active logits rules raise ValueError."""
+        from .engine import LogitsRules, QUEUE_STAGE
+        if num_beams != 1:
+            raise ValueError("generate_many runs greedy search only (num_beams=1): beams in a row session are not built")
+        if do_sample:
+            raise ValueError("generate_many runs greedy search only: sampling in a row session is not built")
+        if LogitsRules(repetition_penalty, no_repeat_ngram_size, min_new_tokens).active:
+            raise ValueError("generate_many: repetition_penalty / no_repeat_ngram_size / min_new_tokens in a row session are not built")
+        prompts = [torch.as_tensor(p).reshape(-1) for p in input_ids]
+        N = len(prompts)
+        caps = [int(max_new_tokens)] * N if isinstance(max_new_tokens, numbers.Integral) else [int(m) for m in max_new_tokens]
+        if len(caps) != N:
+            raise ValueError(f"max_new_tokens lists {len(caps)} values for {N} prompts")
+        eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
+        pad = self.config.pad_token_id if pad_token_id is None else pad_token_id
+        embs = self._image_embs(N, dicom, False, qformer_embs) if N else None
+        if embs is not None and tuple(embs.shape) != (N, 32, self.lcfg.qformer_dim):
+            raise ValueError(f"image embeddings should be of size {(N, 32, self.lcfg.qformer_dim)}, but are {tuple(embs.shape)}")
+        if stage is None:
+            stage = max(1, min(QUEUE_STAGE, self.max_batch // 2))
+        if rows is None:
+            rows = self.max_batch - stage
+        if rows < 1 or rows + stage > self.max_batch:
+            raise ValueError(f"rows ({rows}) + stage ({stage}) must fit max_batch {self.max_batch} of this model")
+        self._ensure_engine()
+        reqs = [(prompts[i], None if embs is None else embs[i], caps[i]) for i in range(N)]
+        outs = self._engine.generate_queue(reqs, rows=rows, stage=stage, eos_id=eos, pad_id=pad)
+        return [torch.cat([prompts[i].to(torch.int64).cpu(), outs[i]]).to(self.device) for i in range(N)]
+
 
     # -- scoring given tokens ------------------------------------------------------------------------------------------------
     @torch.no_grad()

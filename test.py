@@ -66,6 +66,8 @@ def main(argv=None):
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     p.add_argument("--synthetic", action="store_true", help="deterministic random-init weights (no checkpoints reachable offline)")
     p.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: decoder GEMMs in OCP e4m3 on the fp8 MFMA (weights_fp8=True)")
+    p.add_argument("--queue_rows", type=int, default=0, help="report loop through a queue (generate_many): this many rows decode at a time and a finished "
+                   "row takes the next waiting prompt (0 = off: the batched loop; greedy search only)")
     p.add_argument("--do_corr", action="store_true", help="automatic prompt correction on top of the reports (test.py:437-500)")
     p.add_argument("--do_cp_bin_qa", action="store_true", help="14 yes/no CheXpert questions per study (test.py:545-590)")
     p.add_argument("--do_cp_all_qa", action="store_true", help="'List all the findings' follow-up (test.py:608-650)")
@@ -88,6 +90,15 @@ def main(argv=None):
     except ValueError as e:
         p.error(str(e))
     beams = max(args.num_beams, 1)
+    queue_stage = 0
+    if args.queue_rows > 0:
+        if beams > 1 or args.do_sample or args.repetition_penalty != 1.0 or args.no_repeat_ngram_size or args.min_new_tokens:
+            p.error("--queue_rows runs greedy search only (no --num_beams > 1, --do_sample or logits rules)")
+        from radialog_amd.engine import QUEUE_STAGE
+        queue_stage = QUEUE_STAGE
+        if args.queue_rows + queue_stage > (ENGINE_ROWS_FP8 if args.fp8 else ENGINE_ROWS):
+            p.error(f"--queue_rows {args.queue_rows} + {queue_stage} staging rows exceed the engine's rows")
+        max_batch = max(max_batch, args.queue_rows + queue_stage)
     lang_model = LlamaForCausalLM.from_pretrained(args.vicuna, torch_dtype=dt, device_map="auto", max_batch=max_batch,
                                                   max_len=1024, device=local, synthetic=args.synthetic, weights_fp8=args.fp8)
     if args.lora_model:
@@ -98,7 +109,26 @@ def main(argv=None):
         lang_model.model.blip_embeddings.update(dump_embeddings(images, dicoms, dtype=args.dtype, device=local, synthetic=args.synthetic))
 
     all_preds, all_ids, preds_history = [], [], []
-    for s in range(0, len(dicoms), args.batch_size):
+    if args.queue_rows > 0:
+        # opt-in: every study's prompt waits in one queue; rows that finish early are refilled instead of decoding pads to the batch's longest report
+        texts = []
+        for d in dicoms:
+            conv = new_conversation()
+            conv.append_message(conv.roles[0], report_prompt("no finding"))
+            conv.append_message(conv.roles[1], None)
+            texts.append(conv.get_prompt())
+        prompts = [tok.batch_encode_plus([t], return_tensors="pt", padding=True)["input_ids"][0].clone() for t in texts]
+        seqs = lang_model.generate_many(prompts, dicom=dicoms if args.use_embs else None, max_new_tokens=args.max_new_tokens,
+                                        rows=args.queue_rows, stage=queue_stage)
+        preds = [tok.batch_decode(q.unsqueeze(0), skip_special_tokens=True)[0] for q in seqs]
+        preds_history.extend(preds)
+        all_preds.extend([q.split("ASSISTANT:")[1] if "ASSISTANT:" in q else q for q in preds])
+        pad = torch.zeros(len(seqs), args.max_new_tokens, dtype=torch.int32, device=seqs[0].device)
+        for i, (q, pr) in enumerate(zip(seqs, prompts)):
+            gen = q[pr.numel():]
+            pad[i, : gen.numel()] = gen.to(torch.int32)
+        all_ids.append(pad)
+    for s in range(0, len(dicoms) if args.queue_rows <= 0 else 0, args.batch_size):
         batch = dicoms[s: s + args.batch_size]
         texts = []
         for d in batch:
