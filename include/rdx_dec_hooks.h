@@ -122,6 +122,19 @@ int rdx_w4_test(rdx_ctx* ctx, const float* W, int N, int K, void* wprime_out, vo
  * out[3] / out[4] = launches of skinny_gemm_w4_k / decode_chain_w4_k this context has issued so far (a captured step graph counts once, at capture).
  * out holds 5 values. */
 int rdx_w4_stats(rdx_ctx* ctx, long long* out);
+/* ... and the int4 launches of the 3-16-row step (xs16.hip): out[0] = launches of xstat16_w4_k (QKV, gate/up), out[1] = of xrow16_w4_k (down_proj), counted
+ * like the two above. out holds 2 values. */
+int rdx_w4_rows_stats(rdx_ctx* ctx, long long out[2]);
+
+/* launch_xstat16_w4 (bf16 context): rdx_xstat16_test's arguments for epi 0 / 4, but W fp32 [N][4096] is quantised by the production quantiser as
+ * rdx_set_weight(RDX_W_GEMM_W4) does it, and the kernel streams the int4 chunks. The 16-row tiles of rows >= raw_lo (a multiple of 16; >= N: none) stay
+ * raw bf16 and stream their packed bytes; raw_lo < 0: only the ONE tile of rows [-raw_lo, -raw_lo + 16) does, a raw tile between int4 tiles. N need not be a
+ * multiple of 16: the last tile is padded with zero rows, columns >= N are not written (epi 4 writes the 8 columns of every tile that holds a gate row:
+ * ldo >= round_up(N, 16) / 2). The output bits are those of rdx_xstat16_test on the dequantised weight. */
+int rdx_xstat16_w4_test(rdx_ctx* ctx, const void* X, const void* norm_w, float eps, const float* W, int M, int N, int epi, void* out, int ldo,
+                        int out_packed, int raw_lo);
+/* launch_xrow16_w4 (bf16 context): rdx_xrow16_test's arguments with K % 128 == 0, W quantised likewise (every tile int4). */
+int rdx_xrow16_w4_test(rdx_ctx* ctx, const void* X, int x_packed, const float* W, const void* resid, int M, int N, int K, void* out, int ldo);
 
 #ifdef __cplusplus
 }

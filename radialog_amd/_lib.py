@@ -151,6 +151,9 @@ DEC_HOOK_SYMBOLS = {
     "rdx_wcode_dense_words": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, C.POINTER(C.c_longlong)]),
     "rdx_w4_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_w4_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "rdx_w4_rows_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
+    "rdx_xstat16_w4_test": (C.c_int, [_P, _P, _P, _F, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int]),
+    "rdx_xrow16_w4_test": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
 }
 ALL_HOOK_SYMBOLS = {**HOOK_SYMBOLS, **ENC_HOOK_SYMBOLS, **DEC_HOOK_SYMBOLS}
 

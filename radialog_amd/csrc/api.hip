@@ -141,7 +141,7 @@ extern "C" int rdx_set_weight(rdx_ctx* c, const char* name, const float* data, i
         c->gemm[key] = w;
     } else if (kind == RDX_W_GEMM_W4) {
         // int4 group-quantised (radialog_amd/w4.py): the weight becomes its dequantised value W' -- a packed model-dtype copy like RDX_W_GEMM's, which
-        // everything but the batch <= 2 step reads -- plus the int4 stream of the batch <= 2 GEMV (rdx_finalize_weights drops the streams no unit reads)
+        // everything but the 1-16-row decode steps reads -- plus the int4 stream of their kernels (rdx_finalize_weights drops the streams no unit reads)
         if (c->cfg.dtype != DT_BF16) return fail(c, -8, "rdx_set_weight(%s): RDX_W_GEMM_W4 needs a bf16 context (f16 is not built)", name);
         if (cols % W4_CHUNK_K) return fail(c, -8, "rdx_set_weight(%s): int4 GEMM K=%lld must be a multiple of %d (the quantisation group)", name, (long long)cols, W4_CHUNK_K);
         if (c->has_fp8_w) return fail(c, -8, "rdx_set_weight(%s): RDX_W_GEMM_W4 in a context that holds RDX_W_GEMM_FP8 weights (the two do not mix)", name);
@@ -272,8 +272,8 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
             }
         }
         if (R.rc) return R.rc;
-        // int4 streams (RDX_W_GEMM_W4) are read by the batch <= 2 step's gate/up, down_proj and QKV units; o_proj streams the packed bytes of its
-        // dequantised weight inside the fused attention launch, and nothing else has an int4 kernel: those streams are dropped
+        // int4 streams (RDX_W_GEMM_W4) are read by the gate/up, down_proj and QKV units of the batch <= 2 step and of the 3-16-row step; o_proj streams the
+        // packed bytes of its dequantised weight (inside the fused attention launch, xrow16_k), and nothing else has an int4 kernel: those streams are dropped
         for (int l = 0; l < f.layers; ++l) { dfree(c, c->ll[l].wo.w4); dfree(c, c->ll[l].wo.w4h); }
         dfree(c, c->lm_head.w4); dfree(c, c->lm_head.w4h);
         // Coded bf16 copies (rdx_common.h WcChunk) of what the batch <= 2 step streams outside the fused attention launch: every gate/up and down_proj,

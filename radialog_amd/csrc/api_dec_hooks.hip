@@ -100,6 +100,69 @@ extern "C" int rdx_xrow16_test(rdx_ctx* c, const void* X, int x_packed, const fl
     return finish(c);
 }
 
+namespace {
+
+// W fp32 [N][K] quantised as rdx_set_weight(RDX_W_GEMM_W4) does it (launch_quant_w4; the tiles of rows [raw_lo, raw_hi) raw): w.w = the packed copy of W',
+// w.w4 / w.w4h = the stream and its header words. Returns 0, -2 (out of memory) or -1 (an Inf / NaN in W), after a synchronisation.
+int quant_w4_for_test(rdx_ctx* c, DevBufs& b, const float* W, GemmW& w, int raw_lo, int raw_hi) {
+    w.w = b.get((size_t)w.Npad * w.K * 2);
+    w.w4 = b.get(w4_bytes(w.Npad, w.K));
+    w.w4h = (unsigned*)b.get((size_t)(w.Npad / 16) * sizeof(unsigned));
+    int* badf = (int*)b.get(sizeof(int));
+    if (!w.w || !w.w4 || !w.w4h || !badf) return -2;
+    hipMemsetAsync(badf, 0, sizeof(int), c->stream);
+    launch_quant_w4(W, w.w, w.w4, w.w4h, badf, w.N, w.K, w.Npad, raw_lo, raw_hi, c->stream);
+    int bad = 0;
+    if (hipMemcpyAsync(&bad, badf, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+    return bad ? -1 : 0;
+}
+
+}  // namespace
+
+extern "C" int rdx_xstat16_w4_test(rdx_ctx* c, const void* X, const void* norm_w, float eps, const float* W, int M, int N, int epi, void* out, int ldo,
+                                   int out_packed, int raw_lo) {
+    if (!c || !X || !norm_w || !W || !out || M <= 0 || N <= 0) return fail(c, -1, "rdx_xstat16_w4_test: bad arguments");
+    // N need not fill its last tile: the rows up to npad are zeros in the stream and in the packed copy (launch_quant_w4), the kernel stores columns < N
+    // (SwiGLU: the whole 8 columns of a tile that holds a gate row, hence ldo against npad)
+    const int npad = (N + 15) / 16 * 16;
+    if ((epi != EPI_NONE && epi != EPI_SILU_MUL) || !epi_args_ok(epi, epi == EPI_SILU_MUL ? npad : N, N, ldo, out_packed, nullptr, nullptr) ||
+        (out_packed != ACT_ROWS && (out_packed != ACT_BLK32 || epi != EPI_SILU_MUL || N % 64)))
+        return fail(c, -1, "rdx_xstat16_w4_test: epilogue arguments (epi 0 or 4; ldo; out_packed 1 with SwiGLU and N %% 64 == 0 only)");
+    // raw_lo >= 0: the tiles from row raw_lo on are raw, as in rdx_set_weight; raw_lo < 0: the ONE tile of rows [-raw_lo, -raw_lo + 16) is (a raw tile between int4 tiles)
+    const int lo = raw_lo < 0 ? -raw_lo : raw_lo >= N ? npad : raw_lo, hi = raw_lo < 0 ? lo + 16 : npad;
+    if (lo % 16 || hi > npad) return fail(c, -1, "rdx_xstat16_w4_test: raw_lo = %d is no tile boundary inside N = %d", raw_lo, N);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int K = 4096;
+    DevBufs b;
+    GemmW w; w.N = N; w.K = K; w.Npad = npad;
+    if (c->cfg.dtype != DT_BF16) return fail(c, -8, "rdx_xstat16_w4_test: int4 weights need a bf16 context");
+    if (int rc = quant_w4_for_test(c, b, W, w, lo, hi)) return fail(c, rc, "rdx_xstat16_w4_test: %s", rc == -2 ? "out of device memory" : "the weight holds an Inf or a NaN");
+    GemmArgs a = gargs(X, K, w, nullptr, out, ldo, M);
+    a.norm_w = norm_w; a.eps = eps; a.out_packed = (ActLayout)out_packed;
+    a.W4 = w.w4; a.w4hdr = w.w4h;
+    if (!xstat16_w4_supported(c->cfg.dtype, a, epi)) return fail(c, -1, "rdx_xstat16_w4_test: %d x %d (epilogue %d) is not a shape of xstat16_w4_k", M, N, epi);
+    launch_xstat16_w4(a, epi, c->stream);
+    return finish(c);
+}
+
+extern "C" int rdx_xrow16_w4_test(rdx_ctx* c, const void* X, int x_packed, const float* W, const void* resid, int M, int N, int K, void* out, int ldo) {
+    if (!c || !X || !W || !resid || !out || M <= 0 || N <= 0 || K <= 0 || N % 16 || K % W4_CHUNK_K || ldo < N) return fail(c, -1, "rdx_xrow16_w4_test: bad arguments (K %% 128 == 0)");
+    if (c->cfg.dtype != DT_BF16) return fail(c, -8, "rdx_xrow16_w4_test: int4 weights need a bf16 context");
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBufs b;
+    GemmW w; w.N = N; w.K = K; w.Npad = N;
+    void* xp = x_packed ? nullptr : b.get((size_t)32 * K * 2);
+    if (!x_packed && !xp) return fail(c, -2, "rdx_xrow16_w4_test: out of device memory");
+    if (int rc = quant_w4_for_test(c, b, W, w, N, N)) return fail(c, rc, "rdx_xrow16_w4_test: %s", rc == -2 ? "out of device memory" : "the weight holds an Inf or a NaN");
+    GemmArgs a = gargs(x_packed ? X : xp, K, w, nullptr, out, ldo, M);
+    a.resid = resid; a.ldr = N; a.xpacked = ACT_BLK32;
+    a.W4 = w.w4; a.w4hdr = w.w4h;
+    if (!xrow16_w4_supported(c->cfg.dtype, a)) return fail(c, -1, "rdx_xrow16_w4_test: %d x %d x %d is not a shape of xrow16_w4_k", M, N, K);
+    if (!x_packed) run_rmsnorm(c, nargs(X, nullptr, xp, nullptr, M, K, 0.f, ACT_BLK32, 0));      // w = null: re-layout only
+    launch_xrow16_w4(a, c->stream);
+    return finish(c);
+}
+
 extern "C" int rdx_xstat_blk_test(rdx_ctx* c, const void* X, const void* norm_w, float eps, const float* W, const void* resid, int M, int N, int epi,
                                   int n_valid, void* out, int ldo, int out_packed, void* xp_out, int32_t* argmax_host) {
     if (!c || !X || !W || !out || M <= 0 || M > 192 || N <= 0 || N % 16) return fail(c, -1, "rdx_xstat_blk_test: bad arguments (M <= 192, N %% 16 == 0)");
@@ -464,6 +527,12 @@ extern "C" int rdx_w4_test(rdx_ctx* c, const float* W, int N, int K, void* wprim
     hipFree(tmp);
     if (rc) return rc;
     if (bad) return fail(c, -1, "rdx_w4_test: the weight holds an Inf or a NaN");
+    return 0;
+}
+
+extern "C" int rdx_w4_rows_stats(rdx_ctx* c, long long out[2]) {
+    if (!c || !out || !c->finalized) return fail(c, -1, "rdx_w4_rows_stats: a finalized context and an output are needed");
+    out[0] = c->n_w4_xstat16; out[1] = c->n_w4_xrow16;
     return 0;
 }
 

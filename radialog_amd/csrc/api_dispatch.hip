@@ -69,6 +69,13 @@ GemmArgs w4_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B) {
     return a;
 }
 
+// ... and where the step runs the 3-16-row family in bf16: QKV, gate/up (xstat16_w4_k) and down_proj (xrow16_w4_k) take the int4 kernel when the
+// arguments carry the stream and the kernel's own predicate accepts them (api_llama.hip step_xs16); o_proj has no stream (rdx_finalize_weights)
+GemmArgs w4_rows_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B) {
+    if (c->w4 && c->cfg.dtype == DT_BF16 && W.w4 && W.w4h && decode_family(c, B) == DEC_XS16) { a.W4 = W.w4; a.w4hdr = W.w4h; }
+    return a;
+}
+
 GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     GemmArgs a = unit_args(c, L, u, B);
     if (u == UNIT_GATE_UP) a.out_packed = ACT_BLK32;

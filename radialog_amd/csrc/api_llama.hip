@@ -444,18 +444,26 @@ static void step_blk8(rdx_ctx* c, int B) {
 
 // batch 3-16 (xs16.hip): five launches per layer -- QKV with the RMSNorm as its prologue, attention (output fragment-packed), o_proj with the
 // residual epilogue, gate/up with the RMSNorm prologue (SwiGLU output fragment-packed), down_proj with the residual epilogue
+// int4 group-quantised weights (RDX_W_GEMM_W4, "w4" on, bf16): QKV, gate/up and down_proj stream their int4 copies (w4_rows_unit: xstat16_w4_k /
+// xrow16_w4_k, the same output bits); o_proj streams the packed bytes of its dequantised weight, the lm_head is not quantised
 static void step_xs16(rdx_ctx* c, int B) {
     const int dt = c->cfg.dtype;
     hipStream_t s = c->stream;
+    auto xstat = [&](const GemmArgs& a, int epi) {
+        if (xstat16_w4_supported(dt, a, epi)) { ++c->n_w4_xstat16; launch_xstat16_w4(a, epi, s); }
+        else launch_xstat16(dt, a, epi, s);
+    };
     for (int l = 0; l < c->cfg.layers; ++l) {
         const LlamaLayer* L = &c->ll[l];
-        launch_xstat16(dt, xs16_unit(c, L, UNIT_QKV, B), EPI_NONE, s);
+        xstat(w4_rows_unit(c, xs16_unit(c, L, UNIT_QKV, B), L->wqkv, B), EPI_NONE);
         DecAttnArgs at = dec_attn_args(c, l);
         at.out_packed = ACT_BLK32;
         launch_decode_attention(dt, at, B, s);
         launch_xrow16(dt, xs16_unit(c, L, UNIT_O, B), s);
-        launch_xstat16(dt, xs16_unit(c, L, UNIT_GATE_UP, B), EPI_SILU_MUL, s);
-        launch_xrow16(dt, xs16_unit(c, L, UNIT_DOWN, B), s);
+        xstat(w4_rows_unit(c, xs16_unit(c, L, UNIT_GATE_UP, B), L->wgu, B), EPI_SILU_MUL);
+        const GemmArgs dn = w4_rows_unit(c, xs16_unit(c, L, UNIT_DOWN, B), L->wdown, B);
+        if (xrow16_w4_supported(dt, dn)) { ++c->n_w4_xrow16; launch_xrow16_w4(dn, s); }
+        else launch_xrow16(dt, dn, s);
     }
 }
 

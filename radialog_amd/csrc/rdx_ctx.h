@@ -25,7 +25,7 @@ constexpr int RDX_MAX_ROWS = 128;
 struct GemmW {
     void* w = nullptr; int N = 0, K = 0, Npad = 0; void* w8 = nullptr; float* scale = nullptr;   // w8/scale: fp8 copy
     void* wc = nullptr; unsigned* wch = nullptr;     // coded bf16 copy of w (13 bits per weight, exact) and its per-tile header words: what the batch <= 2 GEMV streams
-    // RDX_W_GEMM_W4: w is the packed copy of the DEQUANTISED weight W' (what every kernel but the batch <= 2 step's reads); w4 / w4h: the int4 stream and
+    // RDX_W_GEMM_W4: w is the packed copy of the DEQUANTISED weight W' (what every kernel but the batch <= 16 steps' QKV, gate/up and down_proj reads); w4 / w4h: the int4 stream and
     // its per-tile header words (bit 8: a raw tile, the LoRA-A rows of wqkv). A weight with an int4 stream gets no coded copy.
     void* w4 = nullptr; unsigned* w4h = nullptr;
 };
@@ -112,10 +112,11 @@ struct rdx_ctx {
     bool prompt_blk = true;          // one prompt's K = 4096 projections on xstat32_k<.., BLK> (RDX_PBLK=0 / rdx_set_option("prompt_blk", 0): wstat_k, the A/B leg)
     bool blk_down = true;            // 33-128 rows, model-dtype weights: down_proj K-split into fp32 slabs (xsplit32_k<.., BLK>); RDX_BLK_DOWN=0 at create: wstat_k, the A/B leg
     bool wcode = true;               // batch <= 2 chained family, bf16: gate/up, down_proj, QKV and the lm_head stream their coded copy (GemmW::wc); rdx_set_option("wcode", 0): the raw one
-    bool w4 = true;                  // ... their int4 stream (GemmW::w4) where the weight has one; rdx_set_option("w4", 0): the packed bf16 bytes of W' (same bits)
+    bool w4 = true;                  // ... their int4 stream (GemmW::w4) where the weight has one, and so do QKV, gate/up and down_proj of the 3-16-row family; rdx_set_option("w4", 0): the packed bf16 bytes of W' (same bits)
     int* w4_bad = nullptr;           // device flag of the int4 quantiser: the weight held an Inf / NaN
     bool has_fp8_w = false, has_w4_w = false;     // kinds of GEMM weights set so far (RDX_W_GEMM_FP8 and RDX_W_GEMM_W4 do not mix)
     long long n_w4_gemv = 0, n_w4_chain = 0;      // launches of skinny_gemm_w4_k / decode_chain_w4_k (a captured graph counts once): rdx_w4_stats
+    long long n_w4_xstat16 = 0, n_w4_xrow16 = 0;  // launches of xstat16_w4_k / xrow16_w4_k by the 3-16-row step (likewise): rdx_w4_rows_stats
     long long n_wc_gemv = 0, n_wc_chain = 0;      // launches of skinny_gemm_wc_k / decode_chain_wc_k issued by this context (a captured graph counts once): rdx_wcode_stats
     int chain_naps = 1;             // poll back-off of the chained launch (x s_sleep(8) between polls)
     long long* chain_trace = nullptr; int chain_trace_layer = -1;     // rdx_gemv_trace(7): device timeline buffer of ONE chained launch of the next step
@@ -229,6 +230,7 @@ GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);
 // ... and in the layout of a family (what its probe checks IS what its step function launches):
 GemmArgs coded_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B);         // batch <= 2 chained family, "wcode" on: the GEMV streams W's coded bf16 copy
 GemmArgs w4_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B);            // ... "w4" on: W's int4 stream, where it has one
+GemmArgs w4_rows_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B);       // 3-16-row family, bf16, "w4" on: likewise (xstat16_w4_k / xrow16_w4_k)
 GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);      // one row tile: gate/up writes, o_proj / down_proj read the fragment-packed block
 GemmArgs blk_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);       // row blocks: fragment-packed row tiles of 16 in and (gate/up) out
 GemmArgs blk8_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);      // ... fp8 weights: e4m3 blocks + xscale in; 64-deep model-dtype blocks into the K-split o_proj / down_proj

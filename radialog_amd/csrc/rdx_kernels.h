@@ -66,7 +66,8 @@ inline size_t w4_bytes(int npad, int k) { return (size_t)(npad / 16) * (size_t)(
 // writes the packed bf16 copy of W' (the order of launch_pack_weight, rows padded to npad with zeros), the stream and hdr[npad / 16] = raw << 8.
 // *bad (device, zeroed by the caller) is set when W holds an Inf or a NaN. K % 128 == 0
 void launch_quant_w4(const float* W, void* packed, void* stream, unsigned* hdr, int* bad, int N, int K, int npad, int raw_lo, int raw_hi, hipStream_t s);
-// the batch <= 2 GEMV has an int4 form for these arguments (a.W4 set, bf16, LDS-staged activations, K % 128 == 0)
+// the batch <= 2 GEMV has an int4 form for these arguments (a.W4 set, bf16, LDS-staged activations, K % 128 == 0); the 3-16-row kernels' int4 forms
+// are xstat16_w4_supported / xrow16_w4_supported below
 bool skinny_w4_supported(int dtype, const GemmArgs& a, int epi);
 
 // coded bf16 weights: 128 k-values per chunk; per (tile, chunk) three planes of whole-wave contiguous loads (rdx_common.h)
@@ -150,6 +151,12 @@ bool xstat16_supported(const GemmArgs& a, int epi);
 void launch_xstat16(int dtype, const GemmArgs& a, int epi, hipStream_t s);
 bool xrow16_supported(const GemmArgs& a);
 void launch_xrow16(int dtype, const GemmArgs& a, hipStream_t s);
+// ... their int4 forms (bf16; a.W4 / a.w4hdr set, a.W the packed copy of W' that raw-flagged tiles stream): xstat16_w4_k for EPI_NONE / EPI_SILU_MUL,
+// xrow16_w4_k for K % 128 == 0. The weight fragments are decoded in registers to exactly the bits of W', in the bf16 kernels' MFMA order: same output bits
+bool xstat16_w4_supported(int dtype, const GemmArgs& a, int epi);
+void launch_xstat16_w4(const GemmArgs& a, int epi, hipStream_t s);
+bool xrow16_w4_supported(int dtype, const GemmArgs& a);
+void launch_xrow16_w4(const GemmArgs& a, hipStream_t s);
 void launch_tiled_gemm(int dtype, const GemmArgs& a, const ConvGeom& cg, int epi, hipStream_t s);
 // LDS-DMA GEMM for plain row-major activations (M > 32, K % 64 == 0); `ws` = fp32 split-K workspace (nullable)
 bool gemm_dma_supported(const GemmArgs& a);

@@ -100,7 +100,8 @@ class RdxEngine:
         self.device = torch.device("cuda", device)
         self.lora = lora
         self.weights_fp8 = weights_fp8               # decoder GEMM weights also quantised to e4m3 + per-row scale (configs[4])
-        self.weights_w4 = weights_w4                 # the decoder's seven projections int4 group-quantised (RDX_W_GEMM_W4, radialog_amd/w4.py)
+        self.weights_w4 = weights_w4                 # the decoder's seven projections int4 group-quantised (RDX_W_GEMM_W4, radialog_amd/w4.py): the decode step streams
+                                                     # the nibbles of QKV, gate/up and down_proj at 1-16 rows; everything else reads the packed dequantised copy
         l, q, v = cfg.llama, cfg.qformer, cfg.vision
         rc = RdxConfig()
         rc.dtype = _RDX_DT[dtype]
@@ -507,7 +508,7 @@ class RdxEngine:
 
     def set_option(self, name: str, value: int):
         """rdx_set_option: "flash_min" (batched prefill attention kernel choice), "pconv" (packed / row-major encoder kernels), "xs16", "prompt_blk",
-        "wcode" (the batch <= 2 step streams the coded bf16 weights: on by default; 0 = the raw packed ones, same bits), "w4" (likewise for the int4 streams of a weights_w4 engine), "score_chunk" (logits rows per lm_head launch of score(); default 2048, 0 = all at once)."""
+        "wcode" (the batch <= 2 step streams the coded bf16 weights: on by default; 0 = the raw packed ones, same bits), "w4" (likewise for the int4 streams of a weights_w4 engine, which QKV, gate/up and down_proj stream at 1-16 rows), "score_chunk" (logits rows per lm_head launch of score(); default 2048, 0 = all at once)."""
         check(self.ctx, self.lib.rdx_set_option(self.ctx, name.encode(), int(value)), "rdx_set_option")
 
     def conv_test(self, x, w, bias=None, resid=None, ksize=1, stride=1, epi=0, path=0, iters=0):
@@ -701,6 +702,37 @@ class RdxEngine:
         out = (C.c_longlong * 5)()
         check(self.ctx, self.lib.rdx_w4_stats(self.ctx, out), "rdx_w4_stats")
         return tuple(int(v) for v in out)
+
+    def w4_rows_stats(self):
+        """(int4 xstat16 launches, int4 xrow16 launches) the 3-16-row step of this engine has issued (rdx_w4_rows_stats; a captured graph counts once):
+        QKV and gate/up on xstat16_w4_k, down_proj on xrow16_w4_k."""
+        out = (C.c_longlong * 2)()
+        check(self.ctx, self.lib.rdx_w4_rows_stats(self.ctx, out), "rdx_w4_rows_stats")
+        return tuple(int(v) for v in out)
+
+    def xstat16_w4_test(self, x, norm_w, w, epi=0, eps=1e-6, ldo=None, out_packed=0, raw_lo=None):
+        """xstat16_w4_k (rdx_xstat16_w4_test): xstat16_test's arguments for epi 0 / 4; w fp32 [N, 4096] is quantised on the device (radialog_amd/w4.py),
+        the tiles of rows >= raw_lo stay raw bf16 (raw_lo < 0: only the tile of rows [-raw_lo, -raw_lo + 16))."""
+        M, N = x.shape[0], w.shape[0]
+        x, nw, w = self._dev(x), self._dev(norm_w), self._dev(w, torch.float32)
+        ldo = ldo or ((N + 15) // 16 * 8 if epi == 4 else N)          # N need not fill its last tile (epi 4 writes whole tiles of 8 columns)
+        out = self._nan(N // 64, 2, 64, 8) if out_packed else self._nan(M + 2, ldo)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_xstat16_w4_test(self.ctx, _ptr(x), _ptr(nw), eps, _ptr(w), M, N, epi, _ptr(out), ldo, out_packed,
+                                                     N if raw_lo is None else raw_lo), "rdx_xstat16_w4_test")
+        return out
+
+    def xrow16_w4_test(self, x, w, resid, M=None, ldo=None):
+        """xrow16_w4_k (rdx_xrow16_w4_test): xrow16_test's arguments, K % 128 == 0; w is quantised on the device, every tile int4."""
+        packed = x.dim() == 4
+        M = M if packed else x.shape[0]
+        N, K = w.shape
+        x, w, r = self._dev(x), self._dev(w, torch.float32), self._dev(resid)
+        ldo = ldo or N
+        out = self._nan(M + 2, ldo)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_xrow16_w4_test(self.ctx, _ptr(x), int(packed), _ptr(w), _ptr(r), M, N, K, _ptr(out), ldo), "rdx_xrow16_w4_test")
+        return out
 
     def xrow16_test(self, x, w, resid, M=None, ldo=None):
         """xrow16_k (rdx_xrow16_test): out [M + 2, ldo] = resid [M, N] + T(x w^T). x [M, K] row-major, or (4-d) the packed block [K / 32, 2, 64, 8]

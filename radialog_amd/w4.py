@@ -1,9 +1,11 @@
-"""int4 group-quantised weights ("W4", W4A16): the definition of the 4.125-bit format the batch <= 2 GEMV streams instead of the packed bf16 bytes, as a
+"""int4 group-quantised weights ("W4", W4A16): the definition of the 4.125-bit format the decode step streams at 1-16 rows instead of the packed bf16 bytes (batch <= 2:
+the GEMV and the chained launch; 3-16 rows: xstat16_w4_k / xrow16_w4_k for QKV, gate/up and down_proj), as a
 NumPy quantiser, dequantiser, packer and unpacker. The device quantiser (csrc/gemm.hip quant_w4_k) and the in-register decode (csrc/rdx_common.h
 w4_frag) are compared with this file byte for byte and bit for bit.
 
 int4 is a STORAGE format of one weight stream, not an arithmetic: a quantised weight is defined by its dequantised bf16 value W'. Everything but the
-batch <= 2 step multiplies a packed bf16 copy of W'; the batch <= 2 step decodes the nibbles to exactly W' in registers.
+1-16-row decode steps (o_proj and the lm_head there too, every kernel from 17 rows, the prefill, score()) multiplies a packed bf16 copy of W'; those
+steps decode the nibbles to exactly W' in registers.
 
 For W [N][K] fp32, K % 128 == 0, groups of GROUP = 128 consecutive k of one row (every op below is a NumPy float32 op: IEEE, round to nearest even):
     a  = max |w| over the group

@@ -3,7 +3,7 @@
 (a) the hipGraph step replayed at context ~168 (rdx_time unit 0), (b) the mean step of a 256-token greedy decode (contexts 160 .. 415, what
 bench.py averages), with the HBM fraction (weights + KV of SURVEY 8d over 8 TB/s). `--ab` repeats every batch with the one-row-tile family
 off (rdx_set_option xs16 0: the 32-row kernels of xstat32.hip). python tools/step_time.py [--batches 1,2,4,8,12,16,32] [--ab] [--fp8 | --w4]
-(--w4: int4 group-quantised projections, RdxEngine(weights_w4=True); the HBM fraction then prices the int4 units at 4.125 bits, o_proj and the lm_head at 16)."""
+(--w4: int4 group-quantised projections, RdxEngine(weights_w4=True); the HBM fraction then prices the int4 units at 4.125 bits at 1-16 rows, o_proj and the lm_head at 16, and everything at 16 from 17 rows)."""
 import argparse
 import os
 import sys
@@ -30,9 +30,10 @@ def main():
     cfg = full_cfg()
     lc = cfg.llama
     T, N = 160, a.new
-    wb = bench.llama_param_bytes(lc, lambda n, k: 1 if a.fp8 else 2)
-    if a.w4:        # QKV, gate/up and down_proj stream 4.125 bits per weight at batch <= 2 (the LoRA-A rows, o_proj and the lm_head their bf16 bytes)
-        wb -= lc.layers * (3 * lc.hidden * lc.hidden + 3 * lc.hidden * lc.inter) * (2 - 4.125 / 8)
+    wb16 = bench.llama_param_bytes(lc, lambda n, k: 1 if a.fp8 else 2)
+    # int4: QKV, gate/up and down_proj stream 4.125 bits per weight at 1-16 rows (the LoRA-A rows, o_proj and the lm_head their bf16 bytes); from 17 rows
+    # every kernel reads the packed bf16 copy of the dequantised weight
+    wb4 = wb16 - lc.layers * (3 * lc.hidden * lc.hidden + 3 * lc.hidden * lc.inter) * (2 - 4.125 / 8)
     print(f"| batch | family | step at ctx {T + 8} (ms) | mean step over {N} tokens (ms) | HBM frac (weights + KV) | prefill ms |")
     print("|---|---|---|---|---|---|")
     for B in [int(x) for x in a.batches.split(",")]:
@@ -58,6 +59,7 @@ def main():
             torch.cuda.synchronize()
             avg = ((time.perf_counter() - t0) / 2 - pre) / (N - 1) * 1e3
             kv = B * (T + N / 2.0) * 524288 + B * 524288
+            wb = wb4 if (a.w4 and B <= 16 and (fam or B <= 2)) else wb16
             frac = (wb + kv) / (avg * 1e-3) / 1e9 / bench.HBM_PEAK_GBS
             name = ("fp8 x fp8: " if a.fp8 else "int4: " if a.w4 else "") + ("xs16 (5 launches / layer)" if (fam and not a.fp8 and 3 <= B <= 16) else "chained (3 / layer)" if B <= 2 else
                     "row blocks (33-128 rows, 7 / layer)" if B > 32 else "xstat32 (7 launches / layer)")
