@@ -8,7 +8,9 @@
 //                    With one workgroup per CU a QKV workgroup becomes resident when a down_proj workgroup has retired; its dispatch and
 //                    first byte (~1.8 us) hide behind the wait for the LAST arrival (~3 us: poll 2 us behind the slowest down_proj tile),
 //                    then the row is loaded, normalised and staged (~2 us). A ring of 8 fragments per wave (25 MB over the chip, 4 us of
-//                    HBM time) left ~2 us of that with nothing in flight; the QKV role now holds 16 (half of a wave's K slice);
+//                    HBM time) left ~2 us of that with nothing in flight; the QKV role now holds 16 (half of a wave's K slice). On coded
+//                    weights (decode_chain_wc_k) the ring is 4 coded chunks; the first is decoded into LDS while the wave waits, and its slot
+//                    is refilled only behind the row: loads return in order, and nothing but the ring stands in front of the row;
 //   attn_oproj16_k   decode attention (attn_body.h) -> o_proj (+ residual): 32 attention workgroups + 128 two-tile o_proj workgroups
 //                    whose whole K slice sits in registers while attention runs. Its hand-off is DATA-TAGGED (handoff.h: WaitTagged): the
 //                    attention output travels as 8-byte {two elements, tag} granules in one buffer shared by all layers, the producer neither
@@ -34,9 +36,13 @@ namespace rdx {
 constexpr int CH_WAVES = 16;
 constexpr int CH_THREADS = CH_WAVES * 64;
 constexpr int CH_MAXM = 2;                       // batch rows supported (LDS staging of [M][inter] activations)
-// coded chunks a wave decodes ahead of its role's seam (chain_tile PRE) in decode_chain_wc_k; at most the role's ring (4 and 2), 0 = none. Chosen by
-// measurement (profiles/r13_chain_predecode.md): the QKV role is faster with 1 and slower than without any with 2 or 3; down_proj with 2
-constexpr int CH_PRE_QKV = 1, CH_PRE_DOWN = 2;
+// coded chunks a wave decodes ahead of its role's seam in decode_chain_wc_k, 0 = none; at most the role's ring (4 and 2). Chosen by measurement.
+// CH_PRE_*: into registers (chain_tile PRE; profiles/r13_chain_predecode.md: down_proj is fastest with 2). CH_PARK_QKV: into LDS, refilled behind
+// the hand-off (chain_tile PARK; 64 KiB per chunk: 16 waves x 4 fragments x 1 KiB), in front of the CH_PRE_QKV register chunks. The QKV role is
+// fastest with one parked chunk and none in registers; a second chunk, parked or in registers, is slower than the one (profiles/r17_chain_park.md)
+constexpr int CH_PRE_QKV = 0, CH_PRE_DOWN = 2;
+constexpr int CH_PARK_QKV = 1;
+constexpr size_t CH_PARK_BYTES = (size_t)CH_WAVES * 4 * 64 * 16;
 
 // One weight-streaming unit, WITHOUT what its ring needs: the weight base (model dtype, or the e4m3 bytes of a W8 instantiation) and K reach
 // chain_tile as values of their own -- leading kernel arguments, which the command processor preloads into SGPRs (rdx_kernels.h), so the ring
@@ -59,14 +65,20 @@ template <typename WaitFn> struct ChainLate { ChainGemm a; WaitFn wait; long lon
 // PRE (WC = 1 only): the first PRE coded chunks of the ring are decoded, and their slots refilled, BEFORE the role's dead time ends instead of behind
 // it -- PRE_POLL: in front of wait_inputs(), by every wave but the polling one (wave 0); otherwise between the issue of the activation loads and
 // their staging, by every wave. Same fragments into the same MFMAs in the same order (profiles/r13_chain_predecode.md).
+// PARK (WC = 1 with PRE_POLL only): the first PARK chunks of the ring are decoded ahead of the seam into a wave-private LDS region behind the zero line,
+// park[wave][4 PARK][64 lanes] x 16 bytes, and NO slot is refilled there: the refills of the PARK + PRE decoded slots stand behind the first barrier of
+// the norm statistics, so no weight load stands between the ring and the row. The polling wave decodes behind the wait, in front of its row loads,
+// through the same code. The first trip takes the parked fragments from LDS, then the PRE register fragments, then the rest of the ring. `red` lies over the park region (a wave's slice over
+// its own slots, consumed by then): the role needs 208 B + the staged rows + PARK x 64 KiB (profiles/r17_chain_park.md).
 template <typename T, int EPI, bool NORM, int SUB, int XL, typename WaitFn, int U = 4, bool RESID_EARLY = false, bool W8 = false, int WC = 0, int PRE = 0,
-          bool PRE_POLL = false, typename Late>
+          bool PRE_POLL = false, int PARK = 0, typename Late>
 __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const int K, const int wg, const int ntiles, unsigned char* smem, Late late) {
     typedef typename Vec8<T>::type V8;
     constexpr int WPS = CH_WAVES / SUB;           // waves per tile
     // U chunks per register batch, two batches in flight (a ring of 2 U fragments): 32 VGPRs at U = 4, 64 at U = 8; every role stays <= 128
-    float* red = reinterpret_cast<float*>(smem);                        // [CH_WAVES][256]
-    float* ssq = red + CH_WAVES * 256;                                  // [CH_WAVES][CH_MAXM]
+    constexpr int RED_LD = PARK > 0 ? 4 * PARK * 256 : 256;             // floats from one wave's `red` slice to the next (PARK: a wave's park slots)
+    float* red = reinterpret_cast<float*>(smem);                        // [CH_WAVES][256] (PARK: over the park region, set behind late())
+    float* ssq = red + (PARK > 0 ? 0 : CH_WAVES * 256);                 // [CH_WAVES][CH_MAXM]
     float* rstd_s = ssq + CH_WAVES * CH_MAXM;                           // [CH_MAXM] (+pad)
     T* xs = reinterpret_cast<T*>(rstd_s + 16);                          // [M][K] x-hat
 
@@ -149,7 +161,8 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
     // to a SIMD; the refills are in flight that much earlier. No barrier and no wait on another workgroup in here. Wave 0 polls (PRE_POLL): loads
     // return in order, so its first poll must not stand behind a refill -- it decodes nothing here and runs the same code once the row is staged, in
     // front of its first MFMA (one path behind the seam for all waves; a wave-0 path of its own cost 20 bytes of scratch).
-    static_assert(PRE == 0 || (WC == 1 && PRE <= RC), "pre-decode: coded bf16 weights, at most the ring");
+    static_assert(PRE == 0 || (WC == 1 && PARK + PRE <= RC), "pre-decode: coded bf16 weights, at most the ring");
+    static_assert(PARK == 0 || (WC == 1 && PRE_POLL && !WaitFn::TAGGED && NORM), "parked pre-decode: the polling role of the coded launch");
     static_assert(PRE == 0 || PRE_POLL || !WaitFn::TAGGED, "pre-decode without a poll stands behind the plain activation loads: a tagged sweep has no such site");
     u4 pre[PRE ? 4 * PRE : 1];
     const bool predec = PRE > 0 && !(wc_hdr & 0x100u);        // wave-uniform
@@ -173,6 +186,74 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             if (form_g()) predecode_as(std::false_type());
         }
     };
+    // PARK: decode only, chunks 0 .. PARK - 1 into the wave's park slots (one 16-byte LDS store per fragment, lane-contiguous), PARK .. PARK + PRE - 1
+    // into `pre`; the chunks of the first trip go into all of these slots behind the row (below, in the norm statistics)
+    u4* const parkw = reinterpret_cast<u4*>(xs + (size_t)a.M * K + 8) + wa * (4 * (PARK > 0 ? PARK : 1) * 64) + lane;
+    if constexpr (PARK > 0) red = reinterpret_cast<float*>(xs + (size_t)a.M * K + 8);
+    auto ahead_as = [&](auto dn) {
+        if constexpr (PARK > 0) {
+            constexpr bool DN = decltype(dn)::value;
+            const unsigned base4 = (wc_hdr & 0xffu) * 0x01010101u;
+#pragma unroll
+            for (int u = 0; u < PARK + PRE; ++u)      // opaque: the decode below stands in the two-pass loop and is not hoisted out of it (for all waves, both forms)
+                asm volatile("" : "+v"(cring[u].lo0), "+v"(cring[u].lo1), "+v"(cring[u].ix), "+v"(cring[u].sg));
+#pragma unroll
+            for (int u = 0; u < PARK; ++u) {
+                parkw[(4 * u) * 64] = CD::template frag<0, DN>(cring[u], base4); parkw[(4 * u + 1) * 64] = CD::template frag<1, DN>(cring[u], base4);
+                parkw[(4 * u + 2) * 64] = CD::template frag<2, DN>(cring[u], base4); parkw[(4 * u + 3) * 64] = CD::template frag<3, DN>(cring[u], base4);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+            for (int u = 0; u < PRE; ++u) {
+                pre[4 * u] = CD::template frag<0, DN>(cring[PARK + u], base4); pre[4 * u + 1] = CD::template frag<1, DN>(cring[PARK + u], base4);
+                pre[4 * u + 2] = CD::template frag<2, DN>(cring[PARK + u], base4); pre[4 * u + 3] = CD::template frag<3, DN>(cring[PARK + u], base4);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        }
+    };
+    auto ahead = [&] {
+        if (!(wc_hdr & 0x100u)) {             // wave-uniform; a flagged raw tile parks nothing
+            if (form_d()) ahead_as(std::true_type());
+            if (form_g()) ahead_as(std::false_type());
+        }
+    };
+    // activations: published write-through by other workgroups of this launch -> agent-scope 8-byte loads (L1 bypass),
+    // each chunk loaded ONCE and kept in registers across the RMSNorm statistics
+    // XL = chunks of 4 elements per thread: M*K/4 <= XL*1024 (checked by chain_supported)
+    const int K4 = K >> 2, total4 = a.M * K4;
+    unsigned long long xr[XL];
+    unsigned long long nwr[PARK > 0 ? XL : 1];       // PARK: the norm weights, loaded next to the row
+    if constexpr (PARK > 0) {
+        // ahead() stands ONCE in the kernel's text, in a loop of two passes: fifteen waves run it in pass 0, in front of the hand-off wait, the polling
+        // wave in pass 1, behind it and in front of its row loads: one path for all waves, no twin. (A second inlined copy for the polling wave,
+        // under the flight of its row, is code that one wave runs once per workgroup with the other fifteen waiting at the barrier of the norm
+        // statistics; measured 1.4 ms per report behind this form, profiles/r17_chain_park.md forms 3 and 4.) No load
+        // stands in the loop: a loaded value carried round it is copied in the loop's header behind vmcnt(0), in front of the first poll. `pass`
+        // is opaque so that the loop is neither unrolled nor peeled.
+        unsigned pass = 0;
+#pragma nounroll
+        for (;;) {
+            asm volatile("" : "+s"(pass));
+            if ((pass == 0) == (wa != 0)) ahead();
+            if (pass) break;
+            wait_inputs();
+            CH_T(3);
+            pass = 1;
+        }
+#pragma unroll
+        for (int i = 0; i < XL; ++i) {
+            const int c = threadIdx.x + i * CH_THREADS;
+            xr[i] = 0ull; nwr[i] = 0ull;
+            if (c < total4) {
+                const int m = c / K4, k4 = c - m * K4;
+                xr[i] = ld8_agent(X + (size_t)m * a.ldx + (size_t)k4 * 4);
+                // the norm weights predate the launch: loaded here, behind the row, they are back with it; where the staging loads them without
+                // PARK they would return behind the refills (loads return in order)
+                nwr[i] = *reinterpret_cast<const unsigned long long*>(reinterpret_cast<const T*>(a.norm_w) + (size_t)k4 * 4);
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    } else {
     if constexpr (PRE > 0 && PRE_POLL) {
         if (wa != 0) predecode();
     }
@@ -180,11 +261,6 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
     wait_inputs();
     if (!WaitFn::TAGGED) CH_T(3);
 
-    // activations: published write-through by other workgroups of this launch -> agent-scope 8-byte loads (L1 bypass),
-    // each chunk loaded ONCE and kept in registers across the RMSNorm statistics
-    // XL = chunks of 4 elements per thread: M*K/4 <= XL*1024 (checked by chain_supported)
-    const int K4 = K >> 2, total4 = a.M * K4;
-    unsigned long long xr[XL];
     if constexpr (WaitFn::TAGGED) {              // tagged granules (handoff.h): the loads are the wait; same chunks in the same registers
         wait_inputs.template sweep<XL>(xr, a.X, a.ldx, K4, total4, CH_THREADS);
         if (trace) __syncthreads();              // traced launches only: "inputs ready" = EVERY wave has its granules (a product launch meets at the staging barrier below)
@@ -200,6 +276,7 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             __builtin_amdgcn_sched_barrier(0);
             predecode();
         }
+    }
     }
     if (NORM) {
         float ss[CH_MAXM];
@@ -221,6 +298,15 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             if (lane == 0) ssq[wa * CH_MAXM + m] = t;
         }
         __syncthreads();
+        if constexpr (PARK > 0) {
+            // The refills of the decoded slots, behind the barrier that every wave reaches with its row in registers: right behind a wave's own row
+            // loads they stand in front of the rows of the workgroup's later waves ("inputs ready -> first MFMA" 2.5 us there, 2.1 here at depth 1;
+            // profiles/r17_chain_park.md forms 2 and 3). UNCONDITIONAL, a flagged raw tile included (it drops the ring, as it drops the ring
+            // of the entry): behind a conditional load every later wait is vmcnt(0).
+#pragma unroll
+            for (int u = 0; u < PARK + PRE; ++u) { const size_t o = (size_t)min(q0 + RC + u, qlast) * CD::BYTES; cring[u] = CD::load(cb16 + o, cb4 + o); }
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (threadIdx.x < CH_MAXM) {
             float t = 0.f;
 #pragma unroll
@@ -239,7 +325,9 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
                 unsigned long long v = xr[i];
                 if (NORM) {
                     const float rs = rstd_s[m];
-                    const unsigned long long nw = *reinterpret_cast<const unsigned long long*>(NW + (size_t)k4 * 4);
+                    unsigned long long nw;
+                    if constexpr (PARK > 0) nw = nwr[i];
+                    else nw = *reinterpret_cast<const unsigned long long*>(NW + (size_t)k4 * 4);
                     v = 0ull;
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
@@ -360,18 +448,29 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
                     __builtin_amdgcn_sched_barrier(0);
                 }
             };
+            if constexpr (PARK > 0) {
+                // The first trip, unconditional as below: chunks q0 .. q0 + PARK - 1 are in the wave's park slots and take an LDS read and an MFMA each
+#pragma unroll
+                for (int u = 0; u < PARK; ++u) {
+                    const u4 x0 = *xsel(4 * (q0 + u), true), x1 = *xsel(4 * (q0 + u) + 1, true), x2 = *xsel(4 * (q0 + u) + 2, true), x3 = *xsel(4 * (q0 + u) + 3, true);
+                    const u4 w0 = parkw[(4 * u) * 64], w1 = parkw[(4 * u + 1) * 64], w2 = parkw[(4 * u + 2) * 64], w3 = parkw[(4 * u + 3) * 64];
+                    acc = mfma16(as_vec8<T>(w0), as_vec8<T>(x0), acc); acc = mfma16(as_vec8<T>(w1), as_vec8<T>(x1), acc);
+                    acc = mfma16(as_vec8<T>(w2), as_vec8<T>(x2), acc); acc = mfma16(as_vec8<T>(w3), as_vec8<T>(x3), acc);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
             if constexpr (PRE > 0) {
                 // The first trip, unconditional (a slice of at most RC chunks refills from its clamped last chunk, and the guard sends what lies past
                 // c1 to the zero line): chunks q0 .. q0 + PRE - 1 are in `pre`, decoded and their slots refilled ahead of the seam -- by the polling
                 // wave only now -- and take MFMAs only, same guard; the rest of the ring follows as in any trip, in the tile's form. The ring is then
                 // that of a first trip taken: nothing is fetched twice that the loop without pre-decode fetches once. The MFMAs on `pre` stand in
                 // front of both forms: its 16 PRE registers are dead where the forms' loops begin.
-                if constexpr (PRE_POLL) {
+                if constexpr (PRE_POLL && PARK == 0) {
                     if (wa == 0) predecode();
                 }
 #pragma unroll
                 for (int u = 0; u < 4 * PRE; ++u) {
-                    acc = mfma16(as_vec8<T>(pre[u]), as_vec8<T>(*xsel(4 * q0 + u, true)), acc);
+                    acc = mfma16(as_vec8<T>(pre[u]), as_vec8<T>(*xsel(4 * (q0 + PARK) + u, true)), acc);
                     if (u % 4 == 3) __builtin_amdgcn_sched_barrier(0);      // a chunk's four operand reads at a time (16 VGPRs)
                 }
             }
@@ -380,10 +479,10 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
                 // tile takes the other.
                 auto coded_loop = [&](auto dn) {
                     int q = q0;
-                    if constexpr (PRE > 0) {
-                        // the rest of the first trip (above): the ring's chunks PRE .. RC - 1 as in any trip, guarded
+                    if constexpr (PARK + PRE > 0) {
+                        // the rest of the first trip (above): the ring's chunks PARK + PRE .. RC - 1 as in any trip, guarded
 #pragma unroll
-                        for (int u = PRE; u < RC; ++u) {
+                        for (int u = PARK + PRE; u < RC; ++u) {
                             consumeC(dn, cring[u], q0 + u, true);
                             const size_t o = (size_t)min(q0 + RC + u, qlast) * CD::BYTES;
                             cring[u] = CD::load(cb16 + o, cb4 + o);
@@ -425,7 +524,7 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
     }
     CH_T(1);
     // D[n_local = g*4+reg][m_local = r] -> red[wave][m_local*16 + n_local]
-    *reinterpret_cast<float4*>(&red[wa * 256 + r * 16 + g * 4]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+    *reinterpret_cast<float4*>(&red[wa * RED_LD + r * 16 + g * 4]) = make_float4(acc[0], acc[1], acc[2], acc[3]);
     __syncthreads();
 
     // epilogue: one thread per 4 consecutive output columns (one write-through 8-byte store each)
@@ -443,7 +542,7 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
         for (int j = 0; j < 4; ++j) {
             v[j] = 0.f;
 #pragma unroll
-            for (int i = 0; i < WPS; ++i) v[j] += red[(so * WPS + i) * 256 + m * 16 + q * 4 + j];
+            for (int i = 0; i < WPS; ++i) v[j] += red[(so * WPS + i) * RED_LD + m * 16 + q * 4 + j];
             if (W8) v[j] *= a.wscale[t_o * 16 + q * 4 + j];
         }
         unsigned long long pk = 0ull;
@@ -466,7 +565,7 @@ __device__ __forceinline__ ChainLate<WaitFn> chain_tile(const void* Wb, const in
             for (int j = 0; j < 4; ++j) {
                 float u = 0.f;
 #pragma unroll
-                for (int i = 0; i < WPS; ++i) u += red[(so * WPS + i) * 256 + m * 16 + 8 + q * 4 + j];
+                for (int i = 0; i < WPS; ++i) u += red[(so * WPS + i) * RED_LD + m * 16 + 8 + q * 4 + j];
                 if (W8) u *= a.wscale[t_o * 16 + 8 + q * 4 + j];
                 pk |= (unsigned long long)bits16<T>(fromf<T>(swiglu<T>(v[j], u))) << (16 * j);
             }
@@ -530,7 +629,7 @@ __device__ __forceinline__ void chain_coded(const void* cdown, const void* cqkv,
         if (lt.trace && threadIdx.x == 0) lt.trace[2] = (long long)__builtin_amdgcn_s_memrealtime();      // arrival
         return;
     }
-    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, 8, false, false, WC, WC == 1 ? CH_PRE_QKV : 0, true>(cqkv, H, blockIdx.x - nwg_down, (qkv_n + 15) / 16, msm, [&] {
+    chain_tile<T, EPI_NONE, true, 4, 2, WaitSharded, 8, false, false, WC, WC == 1 ? CH_PRE_QKV : 0, true, WC == 1 ? CH_PARK_QKV : 0>(cqkv, H, blockIdx.x - nwg_down, (qkv_n + 15) / 16, msm, [&] {
         const ChainArgs ca = args();
         int* ctr = ca.ctr + (size_t)ca.layer * HO_CTR_INTS;
         return ChainLate<WaitSharded>{ChainGemm{ca.dx, H, nullptr, 0, ca.dqkv, ca.qkv_ld, ca.B, qkv_n, ca.attn_norm, ca.eps, nullptr},
@@ -642,9 +741,13 @@ void launch_decode_chain(int dtype, ChainArgs ca, bool with_next_qkv, hipStream_
             if (w4_attr_set.first()) hipFuncSetAttribute((const void*)decode_chain_w4_k, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
             hipLaunchKernelGGL(decode_chain_w4_k, grid, block, smem, s, ca.cdown, with_next_qkv ? ca.cqkv : ca.cdown, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
         } else if (ca.wc && dtype == DT_BF16 && !ca.w8) {        // coded bf16 weights (api_llama.hip sets wc only where every copy of the launch exists)
+            // the larger of the two roles' needs: the QKV role's `red` lies over its park region (chain_tile PARK), down_proj's carve-up is sm_gemm.
+            // B * hidden <= 8192 (chain_supported): 208 B + at most 16 KiB of rows + 64 KiB per parked chunk, 147,664 B at depth 2 of the CU's 160 KiB
+            const size_t sm_qkv = (size_t)(CH_WAVES * CH_MAXM + 16) * 4 + (size_t)ca.B * ca.hidden * 2 + 16 + CH_PARK_QKV * CH_PARK_BYTES;
+            const size_t smem_wc = smem > sm_qkv ? smem : sm_qkv;
             static DevOnce wc_attr_set;
-            if (wc_attr_set.first()) hipFuncSetAttribute((const void*)decode_chain_wc_k, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);
-            hipLaunchKernelGGL(decode_chain_wc_k, grid, block, smem, s, ca.cdown, with_next_qkv ? ca.cqkv : ca.cdown, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
+            if (wc_attr_set.first()) hipFuncSetAttribute((const void*)decode_chain_wc_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            hipLaunchKernelGGL(decode_chain_wc_k, grid, block, smem_wc, s, ca.cdown, with_next_qkv ? ca.cqkv : ca.cdown, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
         } else if (ca.w8) hipLaunchKernelGGL((decode_chain_k<T, true>), grid, block, smem, s, ca.wdown8, ca.wqkv8, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
         else hipLaunchKernelGGL((decode_chain_k<T, false>), grid, block, smem, s, ca.wdown, ca.wqkv, ca.hidden, ca.inter, ca.qkv_n, nwg_down, ca);
     });
