@@ -38,6 +38,8 @@ def parse_args(argv=None):
     p.add_argument("--min_new_tokens", type=int, default=0, help="greedy decode: no EOS before this many generated tokens (0 = off)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     p.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: decoder GEMMs in OCP e4m3 on the fp8 MFMA (weights_fp8=True)")
+    p.add_argument("--kv_fp8", action="store_true", help="the decoder's KV cache as e4m3 codes + one exponent byte per row (kv_fp8=True): half the cache bytes; "
+                   "every chat turn then prefills the whole conversation (reuse_prefix_kv is not built on it)")
     p.add_argument("--synthetic", action="store_true", help="run on the deterministic random-init weights (no checkpoints are "
                    "reachable without a network); without it every missing weight file is an error")
     args = p.parse_args(argv)
@@ -63,10 +65,10 @@ def init_vicuna(args):
     tok = load_tokenizer(args.vicuna)
     dt = torch.float16 if args.dtype == "f16" else torch.bfloat16
     lang_model = LlamaForCausalLM.from_pretrained(args.vicuna, torch_dtype=dt, device_map="auto", max_batch=1, max_len=1024,
-                                                  synthetic=args.synthetic, weights_fp8=args.fp8)
+                                                  synthetic=args.synthetic, weights_fp8=args.fp8, kv_fp8=args.kv_fp8)
     if args.lora_model:
         lang_model = PeftModelForCausalLM.from_pretrained(lang_model, args.lora_model, torch_dtype=dt)
-    lang_model.reuse_prefix_kv = True       # chat turns re-send the whole conversation: keep the KV rows of the shared token prefix
+    lang_model.reuse_prefix_kv = not args.kv_fp8       # chat turns re-send the whole conversation: keep the KV rows of the shared token prefix
     return lang_model.eval(), tok
 
 

@@ -281,6 +281,11 @@ int rdx_comm_world(rdx_ctx* ctx);                  /* ranks of the initialised c
  * librdx_hooks.so, loaded under RDX_DEBUG_HOOKS=1 only) */
 int rdx_kv_read(rdx_ctx* ctx, int layer, int which /*0=K,1=V*/, void* dst /*model dtype [B][heads][max_len][D]*/);
 int rdx_hidden_read(rdx_ctx* ctx, void* dst /*model dtype [B][hidden]: decoder output rows of the last call*/);
+/* fp8 KV cache ("kv_fp8"): rdx_kv_read returns the stored values x' in the model dtype; rdx_kv_read_codes the e4m3 codes [B][heads][max_len][D] bytes and
+ * the row exponents [B][heads][max_len] int8 of one layer, both in logical order (device pointers; -1 on a context without the option).
+ * rdx_kv_bytes: bytes of the context's KV allocation (caches and, fp8, exponents; < 0 without llama state). */
+int rdx_kv_read_codes(rdx_ctx* ctx, int layer, int which /*0=K,1=V*/, void* codes, void* exps);
+long long rdx_kv_bytes(rdx_ctx* ctx);
 /* average duration (ms) of one hot-path unit, measured with HIP events on the context's stream:
  *   what = 0: one decode step (whole graph) at the current state, `iters` replays
  *   what = 1: the gate/up SwiGLU weight-streaming GEMV of every layer in turn, `iters` sweeps -> ms per launch
@@ -299,7 +304,15 @@ int rdx_time(rdx_ctx* ctx, int what, int iters, float* ms_host);
  * QKV and lm_head weights (1, default) or the raw packed ones (0); the results are the same bits either way, a captured step graph is dropped (no
  * environment variable), "w4" = likewise for RDX_W_GEMM_W4 weights: the batch <= 2 step streams the int4 copies of gate/up, down_proj and QKV (1, default) or
  * the packed bytes of their dequantised values (0); the same bits, a captured step graph is dropped, "score_chunk" = logits rows per lm_head launch of the scoring pass (default 2048, the fastest of 128 / 512 / 2048 / all on 3382 rows: profiles/r11_score.md; 0 = all rows of a call at once; negative values
- * return -1). Unknown names return -1. No reference counterpart.
+ * return -1), "kv_fp8" = the decoder's KV cache as an fp8 storage format (0, default: the model dtype; 1: OCP e4m3 codes with one power-of-two exponent
+ * byte per cache row of 128 values, radialog_amd/kv8.py). Valid only BEFORE rdx_finalize_weights, which then allocates codes, exponents and one layer of
+ * staging rows instead of the 2-byte caches (afterwards: -1 with a message). A stored row IS its dequantised value x' = code 2^e, exactly a value of the
+ * model dtype: decode attention over the fp8 cache gives the bits it gives over a model-dtype cache holding x'. The prompt's own attention sees its
+ * unquantised K / V (the prompt's logits, token 0 and rdx_score are those of a plain context), a decode step's new token takes part in its own step
+ * unquantised and is stored quantised. Rows 1-2 run the generic kernel family (no fused attention + o_proj, no chained launch). Not built on an fp8
+ * cache, -1 with a message naming "kv_fp8": rdx_prefill_append / rdx_generate_append (the kept prefix is not held in the model dtype), rdx_beam_search,
+ * rdx_rows_begin. Without the option every launch and every output bit is unchanged.
+ * Unknown names return -1. No reference counterpart.
  * At batch 3-16 on the xs16 family rdx_time units 1-5 time THOSE kernels (the RMSNorm is their prologue); max_batch > 32 needs the Vicuna-7B widths
  * (hidden 4096, inter 11008): rdx_finalize_weights refuses other models with more than 32 rows. */
 int rdx_set_option(rdx_ctx* ctx, const char* name, int value);

@@ -79,6 +79,23 @@ int rdx_decode_attn_test(rdx_ctx* ctx, int heads, int B, int max_len, int k_perm
                          const void* cur_rope, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos, const int32_t* slot,
                          const uint8_t* key_mask, void* kcache, void* vcache, void* out, long long out_bytes, int out_packed, int out_mt);
 
+/* launch_decode_attention_kv8 alone (the same three builds on the fp8 KV cache; the format: radialog_amd/kv8.py): rdx_decode_attn_test's arguments, with the
+ * caches as kcodes / vcodes [B][heads][max_len][128] e4m3 bytes (K in the kernels' storage order, kv8.k_store; V row-major) and kexp / vexp [B][heads][max_len]
+ * int8 row exponents, all updated in place: the new token's code rows and exponents at each row's slot. The output bits are those of rdx_decode_attn_test
+ * on model-dtype caches holding the stored values. Same refusals. */
+int rdx_decode_attn_kv8_test(rdx_ctx* ctx, int heads, int B, int max_len, int lora_r, float lora_scale, const void* qkv, const void* lbq, const void* lbv,
+                             const void* cur_rope, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos, const int32_t* slot,
+                             const uint8_t* key_mask, void* kcodes, void* kexp, void* vcodes, void* vexp, void* out, long long out_bytes, int out_packed,
+                             int out_mt);
+/* launch_kv8_quant_rows alone (attn.hip kv8_quant_rows_k: the prompt's staged rows into the fp8 cache): krows / vrows [B][heads][stage_len][128] model dtype,
+ * row-major; rows t < T of every (row, head) go to positions slot0 + t of kcodes / kexp / vcodes / vexp (shapes as above, K in the storage order); every other
+ * byte is left alone. Refused: stage_len < T, max_len not a multiple of 16, slots outside the cache. */
+int rdx_kv8_quant_test(rdx_ctx* ctx, int heads, int B, int T, int stage_len, int max_len, int slot0, const void* krows, const void* vrows, void* kcodes, void* kexp,
+                       void* vcodes, void* vexp);
+/* Overwrites one layer's K (which 0) or V (1) cache of a finalized PLAIN context with src [max_batch][heads][max_len][128], model dtype, logical order (K is
+ * stored in the order the context keeps it). How a test gives a plain engine the values an fp8-cache engine holds. Refused on a kv_fp8 context. */
+int rdx_kv_write_test(rdx_ctx* ctx, int layer, int which, const void* src);
+
 /* launch_rope_kv_prefill alone (attn.hip: the prompt's LoRA-B add, RoPE and KV-cache write), same dims: qkv [B][T][qkv_ld], pos_ids [B][T] (device), cos_t /
  * sin_t [max_pos][128]; token t of row b lands in cache slot slot0 + t; qout [B T][hidden] is filled with 0xff bytes, then written. Refused before anything is
  * written: slot0 < 0, slot0 + T > max_len, a position id outside the tables. */

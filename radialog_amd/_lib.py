@@ -100,6 +100,8 @@ SYMBOLS = {
     "rdx_allgather_tokens": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     "rdx_comm_world": (C.c_int, [_P]),
     "rdx_kv_read": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "rdx_kv_read_codes": (C.c_int, [_P, C.c_int, C.c_int, _P, _P]),
+    "rdx_kv_bytes": (C.c_longlong, [_P]),
     "rdx_hidden_read": (C.c_int, [_P, _P]),
     "rdx_time": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "rdx_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),
@@ -145,6 +147,10 @@ DEC_HOOK_SYMBOLS = {
     "rdx_decode_attn_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_longlong,
                                        C.c_int, C.c_int]),
     "rdx_rope_kv_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "rdx_decode_attn_kv8_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_longlong,
+                                           C.c_int, C.c_int]),
+    "rdx_kv8_quant_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "rdx_kv_write_test": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "rdx_wcode_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_wcode_stats": (C.c_int, [_P, C.POINTER(C.c_longlong)]),
     "rdx_wcode_dense_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),

@@ -303,11 +303,22 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
         c->ld.k_perm = (getenv("RDX_KPERM") ? atoi(getenv("RDX_KPERM")) : (f.max_batch * f.heads <= 256)) ? 1 : 0;
         const int B = f.max_batch;
         c->kv_layer_elems = (size_t)B * f.heads * f.max_len * 128;
-        ALLOC(c, c->kcache, c->kv_layer_elems * f.layers * 2);
-        ALLOC(c, c->vcache, c->kv_layer_elems * f.layers * 2);
+        c->ld.kv_fp8 = c->kv_fp8 ? 1 : 0;
+        // fp8 KV cache: one code byte per element, one exponent byte per row of 128, and the prompt's rows of ONE layer in the model dtype
+        const size_t kvb = c->kv_layer_elems * f.layers * (c->kv_fp8 ? 1 : 2), kxb = c->kv_fp8 ? c->kv_layer_elems / 128 * f.layers : 0;
+        ALLOC(c, c->kcache, kvb);
+        ALLOC(c, c->vcache, kvb);
         // zero-initialised: decode attention multiplies never-written rows by P = 0 (any finite value is fine, NaN bits are not)
-        HIPCHK(c, hipMemset(c->kcache, 0, c->kv_layer_elems * f.layers * 2));
-        HIPCHK(c, hipMemset(c->vcache, 0, c->kv_layer_elems * f.layers * 2));
+        HIPCHK(c, hipMemset(c->kcache, 0, kvb));
+        HIPCHK(c, hipMemset(c->vcache, 0, kvb));
+        if (c->kv_fp8) {
+            ALLOC(c, c->kexp, kxb); ALLOC(c, c->vexp, kxb);
+            HIPCHK(c, hipMemset(c->kexp, 0, kxb));
+            HIPCHK(c, hipMemset(c->vexp, 0, kxb));
+            const size_t stb = (size_t)B * f.heads * ((f.max_len + 15) / 16 * 16) * 128 * 2;      // a prompt's rows at a stride of ceil16(T) <= ceil16(max_len)
+            ALLOC(c, c->kv_kstage, stb); ALLOC(c, c->kv_vstage, stb);
+        }
+        c->kv_alloc_bytes = 2 * (kvb + kxb);
         ALLOC(c, c->key_mask, (size_t)B * f.max_len);
         HIPCHK(c, hipMemset(c->key_mask, 0, (size_t)B * f.max_len));
         ALLOC(c, c->d_img_pos, B * sizeof(int)); ALLOC(c, c->d_pos, B * sizeof(int)); ALLOC(c, c->d_slot, B * sizeof(int));
@@ -444,6 +455,11 @@ extern "C" int rdx_set_option(rdx_ctx* c, const char* name, int value) {
     if (!strcmp(name, "wcode")) {         // the batch <= 2 step's GEMVs and chained launches on the coded bf16 weights (on) or on the raw packed ones (the A/B leg); same bits either way
         c->wcode = value != 0;
         if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; c->gkey = GraphKey(); }
+        return 0;
+    }
+    if (!strcmp(name, "kv_fp8")) {        // the decoder's KV cache as e4m3 codes + one power-of-two exponent per row (radialog_amd/kv8.py): decides what rdx_finalize_weights allocates
+        if (c->finalized) return fail(c, -1, "rdx_set_option: kv_fp8 decides what rdx_finalize_weights allocates; set it before that call");
+        c->kv_fp8 = value != 0;
         return 0;
     }
     if (!strcmp(name, "score_chunk")) {   // rdx_score: logits rows per lm_head launch (0 = all rows of a call at once)

@@ -15,7 +15,7 @@ extern "C" int rdx_attn_trace(rdx_ctx* c, int layer, long long* host) {
     HIPCHK(c, hipMemsetAsync(dtr, 0, 8 * sizeof(long long), c->stream));
     DecAttnArgs at = dec_attn_args(c, layer);
     at.trace = dtr;
-    launch_decode_attention(c->cfg.dtype, at, c->cur_B, c->stream);
+    run_decode_attention(c, at, layer, c->cur_B);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(host, dtr, 8 * sizeof(long long), hipMemcpyDeviceToHost);
     hipFree(dtr);

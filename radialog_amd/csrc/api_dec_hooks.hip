@@ -329,18 +329,21 @@ bool attn_dims(LlamaDims& d, int heads, int max_len, int k_perm, int lora_r, flo
 
 }  // namespace
 
-extern "C" int rdx_decode_attn_test(rdx_ctx* c, int heads, int B, int max_len, int k_perm, int lora_r, float lora_scale, const void* qkv, const void* lbq,
-                                    const void* lbv, const void* cur_rope, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos,
-                                    const int32_t* slot, const uint8_t* key_mask, void* kcache, void* vcache, void* out, long long out_bytes, int out_packed,
-                                    int out_mt) {
-    if (!c || !qkv || !slot || !key_mask || !kcache || !vcache || !out || B <= 0 || B > 4096) return fail(c, -1, "rdx_decode_attn_test: bad arguments");
+namespace {
+
+// both decode-attention hooks: the checks, then the launch on the model-dtype caches or (kexp / vexp given) on the fp8 codes and exponents
+int decode_attn_hook(rdx_ctx* c, const char* who, int heads, int B, int max_len, int k_perm, int lora_r, float lora_scale, const void* qkv, const void* lbq,
+                     const void* lbv, const void* cur_rope, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos, const int32_t* slot,
+                     const uint8_t* key_mask, void* kcache, void* vcache, signed char* kexp, signed char* vexp, void* out, long long out_bytes, int out_packed,
+                     int out_mt) {
+    if (!c || !qkv || !slot || !key_mask || !kcache || !vcache || !out || B <= 0 || B > 4096) return fail(c, -1, "%s: bad arguments", who);
     DecAttnArgs a;
     if (!attn_dims(a.d, heads, max_len, k_perm, lora_r, lora_scale, max_pos))
-        return fail(c, -1, "rdx_decode_attn_test: heads %d, max_len %d (a multiple of 32 in (0, 1536]), lora_r %d (0 or 8)", heads, max_len, lora_r);
-    if (lora_r && (!lbq || !lbv)) return fail(c, -1, "rdx_decode_attn_test: lora_r 8 needs lbq and lbv");
+        return fail(c, -1, "%s: heads %d, max_len %d (a multiple of 32 in (0, 1536]), lora_r %d (0 or 8)", who, heads, max_len, lora_r);
+    if (lora_r && (!lbq || !lbv)) return fail(c, -1, "%s: lora_r 8 needs lbq and lbv", who);
     const bool tables = cos_t && sin_t && pos && max_pos > 0;
     if ((cur_rope != nullptr) == tables || (!cur_rope && (cos_t || sin_t || pos) && !tables))
-        return fail(c, -1, "rdx_decode_attn_test: either cur_rope, or cos_t / sin_t / pos with max_pos > 0");
+        return fail(c, -1, "%s: either cur_rope, or cos_t / sin_t / pos with max_pos > 0", who);
     const size_t H = a.d.hidden;
     size_t extent = 0;      // bytes the layout holds; 0: it does not hold B rows
     switch (out_packed) {
@@ -351,7 +354,7 @@ extern "C" int rdx_decode_attn_test(rdx_ctx* c, int heads, int B, int max_len, i
     default: break;
     }
     if (!extent || out_bytes < (long long)extent)
-        return fail(c, -1, "rdx_decode_attn_test: out_packed %d (out_mt %d, %lld bytes) does not hold %d rows", out_packed, out_mt, out_bytes, B);
+        return fail(c, -1, "%s: out_packed %d (out_mt %d, %lld bytes) does not hold %d rows", who, out_packed, out_mt, out_bytes, B);
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::vector<int32_t> hs(B), hp(B);
@@ -360,14 +363,68 @@ extern "C" int rdx_decode_attn_test(rdx_ctx* c, int heads, int B, int max_len, i
     HIPCHK(c, hipMemcpy(hm.data(), key_mask, hm.size(), hipMemcpyDeviceToHost));
     if (tables) HIPCHK(c, hipMemcpy(hp.data(), pos, (size_t)B * 4, hipMemcpyDeviceToHost));
     for (int b = 0; b < B; ++b) {
-        if (hs[b] < 1 || hs[b] > max_len - 1) return fail(c, -1, "rdx_decode_attn_test: row %d: slot %d outside [1, %d]", b, hs[b], max_len - 1);
-        if (!hm[(size_t)b * max_len + hs[b]]) return fail(c, -1, "rdx_decode_attn_test: row %d: the mask byte of its own slot %d is zero", b, hs[b]);
-        if (tables && (hp[b] < 0 || hp[b] >= max_pos)) return fail(c, -1, "rdx_decode_attn_test: row %d: position %d outside the tables [0, %d)", b, hp[b], max_pos);
+        if (hs[b] < 1 || hs[b] > max_len - 1) return fail(c, -1, "%s: row %d: slot %d outside [1, %d]", who, b, hs[b], max_len - 1);
+        if (!hm[(size_t)b * max_len + hs[b]]) return fail(c, -1, "%s: row %d: the mask byte of its own slot %d is zero", who, b, hs[b]);
+        if (tables && (hp[b] < 0 || hp[b] >= max_pos)) return fail(c, -1, "%s: row %d: position %d outside the tables [0, %d)", who, b, hp[b], max_pos);
     }
     a.qkv = qkv; a.lbq = lbq; a.lbv = lbv; a.cos_t = cos_t; a.sin_t = sin_t; a.cur_rope = cur_rope; a.pos = pos; a.slot_b = slot; a.key_mask = key_mask;
     a.kcache = kcache; a.vcache = vcache; a.out = out; a.out_packed = (ActLayout)out_packed; a.out_mt = out_mt;
     HIPCHK(c, hipMemsetAsync(out, 0xff, (size_t)out_bytes, c->stream));
-    launch_decode_attention(c->cfg.dtype, a, B, c->stream);
+    if (kexp) { a.d.kv_fp8 = 1; launch_decode_attention_kv8(c->cfg.dtype, a, kexp, vexp, B, c->stream); }
+    else launch_decode_attention(c->cfg.dtype, a, B, c->stream);
+    return finish(c);
+}
+
+}  // namespace
+
+extern "C" int rdx_decode_attn_test(rdx_ctx* c, int heads, int B, int max_len, int k_perm, int lora_r, float lora_scale, const void* qkv, const void* lbq,
+                                    const void* lbv, const void* cur_rope, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos,
+                                    const int32_t* slot, const uint8_t* key_mask, void* kcache, void* vcache, void* out, long long out_bytes, int out_packed,
+                                    int out_mt) {
+    return decode_attn_hook(c, "rdx_decode_attn_test", heads, B, max_len, k_perm, lora_r, lora_scale, qkv, lbq, lbv, cur_rope, cos_t, sin_t, max_pos, pos, slot, key_mask,
+                            kcache, vcache, nullptr, nullptr, out, out_bytes, out_packed, out_mt);
+}
+
+extern "C" int rdx_decode_attn_kv8_test(rdx_ctx* c, int heads, int B, int max_len, int lora_r, float lora_scale, const void* qkv, const void* lbq, const void* lbv,
+                                        const void* cur_rope, const void* cos_t, const void* sin_t, int max_pos, const int32_t* pos, const int32_t* slot,
+                                        const uint8_t* key_mask, void* kcodes, void* kexp, void* vcodes, void* vexp, void* out, long long out_bytes, int out_packed,
+                                        int out_mt) {
+    if (!kexp || !vexp) return fail(c, -1, "rdx_decode_attn_kv8_test: bad arguments");
+    return decode_attn_hook(c, "rdx_decode_attn_kv8_test", heads, B, max_len, 0, lora_r, lora_scale, qkv, lbq, lbv, cur_rope, cos_t, sin_t, max_pos, pos, slot, key_mask,
+                            kcodes, vcodes, (signed char*)kexp, (signed char*)vexp, out, out_bytes, out_packed, out_mt);
+}
+
+extern "C" int rdx_kv8_quant_test(rdx_ctx* c, int heads, int B, int T, int stage_len, int max_len, int slot0, const void* krows, const void* vrows, void* kcodes,
+                                  void* kexp, void* vcodes, void* vexp) {
+    if (!c || !krows || !vrows || !kcodes || !kexp || !vcodes || !vexp || heads <= 0 || B <= 0 || T <= 0) return fail(c, -1, "rdx_kv8_quant_test: bad arguments");
+    if (stage_len < T || max_len % 16 || slot0 < 0 || T > max_len || slot0 > max_len - T)
+        return fail(c, -1, "rdx_kv8_quant_test: %d staged rows of stride %d into slots [%d, %d + %d) of max_len %d (a multiple of 16)", T, stage_len, slot0, slot0, T, max_len);
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_kv8_quant_rows(c->cfg.dtype, krows, vrows, stage_len, kcodes, (signed char*)kexp, vcodes, (signed char*)vexp, (size_t)B * heads, max_len, T, slot0, c->stream);
+    return finish(c);
+}
+
+// logical model-dtype rows [B][heads][max_len][128] into a PLAIN context's cache of one layer (K in the order the context keeps it)
+extern "C" int rdx_kv_write_test(rdx_ctx* c, int layer, int which, const void* src) {
+    if (!c || !c->finalized || !c->cfg.enable_llama || !src || layer < 0 || layer >= c->cfg.layers) return fail(c, -1, "rdx_kv_write_test: bad arguments");
+    if (c->kv_fp8) return fail(c, -1, "rdx_kv_write_test: a plain (model-dtype) KV cache is needed, this context's is fp8 (kv_fp8)");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bytes = c->kv_layer_elems * 2;
+    if (which || !c->ld.k_perm) {
+        HIPCHK(c, hipMemcpyAsync(kv_ptr(c, which ? c->vcache : c->kcache, layer), src, bytes, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        // the fragment order on the host: element offsets from kperm() itself
+        const int L = c->cfg.max_len;
+        const size_t slabs = c->kv_layer_elems / ((size_t)L * 128);
+        std::vector<unsigned short> in(c->kv_layer_elems), outv(c->kv_layer_elems);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipMemcpy(in.data(), src, bytes, hipMemcpyDeviceToHost));
+        for (size_t sl = 0; sl < slabs; ++sl)
+            for (int p = 0; p < L; ++p)
+                for (int d8 = 0; d8 < 128; d8 += 8)
+                    memcpy(&outv[sl * L * 128 + kperm(p, d8, 1)], &in[sl * L * 128 + (size_t)p * 128 + d8], 16);
+        HIPCHK(c, hipMemcpy(kv_ptr(c, c->kcache, layer), outv.data(), bytes, hipMemcpyHostToDevice));
+    }
     return finish(c);
 }
 

@@ -20,6 +20,11 @@ DecAttnArgs dec_attn_args(rdx_ctx* c, int layer) {
     return at;
 }
 
+void run_decode_attention(rdx_ctx* c, const DecAttnArgs& at, int layer, int B) {
+    if (c->kv_fp8) launch_decode_attention_kv8(c->cfg.dtype, at, kvx_ptr(c, c->kexp, layer), kvx_ptr(c, c->vexp, layer), B, c->stream);
+    else launch_decode_attention(c->cfg.dtype, at, B, c->stream);
+}
+
 AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer, int row0) {
     const rdx_config& f = c->cfg;
     const int H = f.hidden;

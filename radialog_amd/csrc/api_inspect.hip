@@ -9,9 +9,29 @@
 extern "C" int rdx_kv_read(rdx_ctx* c, int layer, int which, void* dst) {
     if (!c || !c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_kv_read: no llama state");
     if (layer < 0 || layer >= c->cfg.layers || !dst) return fail(c, -1, "rdx_kv_read: bad arguments");
+    if (c->kv_fp8) {        // the stored values x' = code 2^e in the model dtype, logical order
+        launch_kv8_read(c->cfg.dtype, kv_ptr(c, which ? c->vcache : c->kcache, layer), kvx_ptr(c, which ? c->vexp : c->kexp, layer), which ? 0 : 1,
+                        c->kv_layer_elems / ((size_t)c->cfg.max_len * 128), c->cfg.max_len, nullptr, dst, c->stream);
+        return 0;
+    }
     if (which) HIPCHK(c, hipMemcpyAsync(dst, kv_ptr(c, c->vcache, layer), c->kv_layer_elems * 2, hipMemcpyDeviceToDevice, c->stream));
     else launch_k_unperm(kv_ptr(c, c->kcache, layer), dst, c->kv_layer_elems / ((size_t)c->cfg.max_len * 128), c->cfg.max_len, c->ld.k_perm, c->stream);   // K: back from the fragment order
     return 0;
+}
+
+extern "C" int rdx_kv_read_codes(rdx_ctx* c, int layer, int which, void* codes, void* exps) {
+    if (!c || !c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_kv_read_codes: no llama state");
+    if (!c->kv_fp8) return fail(c, -1, "rdx_kv_read_codes: the context's KV cache is not fp8 (rdx_set_option kv_fp8)");
+    if (layer < 0 || layer >= c->cfg.layers || !codes || !exps) return fail(c, -1, "rdx_kv_read_codes: bad arguments");
+    launch_kv8_read(c->cfg.dtype, kv_ptr(c, which ? c->vcache : c->kcache, layer), nullptr, which ? 0 : 1, c->kv_layer_elems / ((size_t)c->cfg.max_len * 128),
+                    c->cfg.max_len, codes, nullptr, c->stream);
+    HIPCHK(c, hipMemcpyAsync(exps, kvx_ptr(c, which ? c->vexp : c->kexp, layer), c->kv_layer_elems / 128, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+extern "C" long long rdx_kv_bytes(rdx_ctx* c) {
+    if (!c || !c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_kv_bytes: no llama state");
+    return (long long)c->kv_alloc_bytes;
 }
 
 extern "C" int rdx_hidden_read(rdx_ctx* c, void* dst) {
@@ -103,7 +123,7 @@ extern "C" int rdx_time(rdx_ctx* c, int what, int iters, float* ms_host) {
                 const int li = same_layer ? 0 : l;
                 const LlamaLayer* L = &c->ll[li];
                 if (what == 6) {        // decode attention at the current slot (re-appends the same KV row: idempotent)
-                    launch_decode_attention(dt, dec_attn_args(c, li), B, c->stream);
+                    run_decode_attention(c, dec_attn_args(c, li), li, B);
                 } else if (x16) {
                     GemmArgs a = xs16_unit(c, L, u, B);
                     if (resid_unit) { a.out = c->dqkv; launch_xrow16(dt, a, c->stream); }

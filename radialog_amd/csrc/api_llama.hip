@@ -204,6 +204,23 @@ static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
 
     const bool fp8 = fp8_weights(c->ll[0].wqkv);
     const size_t kv_row = (size_t)row0 * f.heads * f.max_len * 128 * 2;        // bytes of row0 cache rows of one layer
+    // fp8 KV cache: the prompt's K / V rows of a layer go to the one-layer staging buffer in the model dtype ([B][heads][ceil16(T)][128], row-major K), which
+    // is what the prompt's own attention reads -- unquantised, so the prompt computes what a plain context computes -- and are then quantised into the cache.
+    // Both kernels run unchanged on dims and strides that describe the staging buffer. keep == 0 and row0 == 0 (the append calls and row sessions refuse).
+    const bool kv8 = c->kv_fp8;
+    const int stage_len = (T + 15) / 16 * 16;
+    LlamaDims sd = c->ld;
+    sd.max_len = stage_len; sd.k_perm = 0;
+    auto stage_attn = [&](AttnArgs at) {
+        at.K = c->kv_kstage; at.V = c->kv_vstage; at.k_perm = 0;
+        at.k_bs = at.v_bs = (long)f.heads * stage_len * 128; at.k_hs = at.v_hs = (long)stage_len * 128;
+        return at;
+    };
+    auto quant_stage = [&](int l) {
+        launch_kv8_quant_rows(dt, c->kv_kstage, c->kv_vstage, stage_len, kv_ptr(c, c->kcache, l), kvx_ptr(c, c->kexp, l), kv_ptr(c, c->vcache, l),
+                              kvx_ptr(c, c->vexp, l), (size_t)B * f.heads, f.max_len, T, 0, s);
+    };
+    if (kv8 && (keep > 0 || row0 > 0)) return fail(c, -1, "the prompt path on the fp8 KV cache (kv_fp8) starts at slot 0 of row 0");
     // the RMSNorm of the residual stream px in the layout the projection behind it reads; `pend` slab groups of a K-split down_proj are folded in first
     auto prompt_norm = [&](const void* w, void* out, ActLayout layout, int mtiles, int pend) {
         run_rmsnorm(c, NormArgs{c->px, w, out, c->pxs, (int)M, H, f.rms_eps, layout, mtiles, pend ? c->pslab : nullptr, pend});
@@ -225,8 +242,11 @@ static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
             };
             prompt_norm(L.attn_norm, c->pxq, ACT_ROWS_E4M3, 0, 0);
             g8(L.wqkv, H, 1, c->pqkv, c->ld.qkv_ld, nullptr, EPI_NONE);
-            launch_rope_kv_prefill(dt, c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq, kc, vc, B, T, keep, s);
-            launch_attention(dt, 128, prefill_attn_args(c, B, T, keep, l, row0), s);
+            launch_rope_kv_prefill(dt, kv8 ? sd : c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq, kv8 ? c->kv_kstage : kc,
+                                   kv8 ? c->kv_vstage : vc, B, T, keep, s);
+            const AttnArgs at = prefill_attn_args(c, B, T, keep, l, row0);
+            launch_attention(dt, 128, kv8 ? stage_attn(at) : at, s);
+            if (kv8) quant_stage(l);
             launch_quant_rows(dt, c->patt, H, c->pxq, c->pxs, (int)M, H, 2, s);
             g8(L.wo, H, 2, c->px, H, c->px, EPI_RESID);
             prompt_norm(L.mlp_norm, c->pxq, ACT_ROWS_E4M3, 0, 0);
@@ -270,11 +290,13 @@ static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
         pend = 0;
         { GemmArgs a = gargs(c->pxn, H, L.wqkv, nullptr, c->pqkv, c->ld.qkv_ld, (int)M); a.N = L.wqkv.Npad; prompt_gemm(a, EPI_NONE, false); }
         // new K/V rows land behind the kept slots
-        launch_rope_kv_prefill(dt, c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq,
-                               kc, vc, B, T, keep, s);
+        launch_rope_kv_prefill(dt, kv8 ? sd : c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq,
+                               kv8 ? c->kv_kstage : kc, kv8 ? c->kv_vstage : vc, B, T, keep, s);
         AttnArgs at = prefill_attn_args(c, B, T, keep, l, row0);
+        if (kv8) at = stage_attn(at);
         at.o_packed_mt = ws ? mtl : 0;
         launch_attention(dt, 128, at, s);
+        if (kv8) quant_stage(l);
         { GemmArgs a = gargs(c->patt, H, L.wo, nullptr, c->px, H, (int)M); a.resid = c->px; a.ldr = H; prompt_gemm(a, EPI_RESID, false); }
         prompt_norm(L.mlp_norm, c->pxn, xl, mtl, 0);
         { GemmArgs a = gargs(c->pxn, H, L.wgu, nullptr, c->pgu, f.inter, (int)M); prompt_gemm(a, EPI_SILU_MUL, true); }
@@ -308,6 +330,7 @@ extern "C" int rdx_prefill(rdx_ctx* c, const int32_t* ids, const int32_t* mask, 
 extern "C" int rdx_prefill_append(rdx_ctx* c, const int32_t* ids_tail, int B, int T_tail, int keep_len, int max_new, int eos_id,
                                   int pad_id, int32_t* out_tokens, void* logits) {
     if (!c) return -1;
+    if (int krc = kv8_refuse(c, "rdx_prefill_append", "the kept prefix is not held in the model dtype")) return krc;
     if (c->rules_on) return fail(c, -1, "rdx_prefill_append: not available under logits rules (the token history is not carried across calls); rdx_set_logits_rules(ctx, NULL) first");
     if (keep_len <= 0 || c->cur_B <= 0) return fail(c, -1, "rdx_prefill_append: no cached conversation to continue (keep_len %d)", keep_len);
     return prefill_impl(c, ids_tail, nullptr, B, T_tail, nullptr, keep_len, max_new, eos_id, pad_id, out_tokens, logits);
@@ -413,7 +436,7 @@ static void step_blk(rdx_ctx* c, int B) {
         launch_xstat_blk(dt, norm_in_front(c, blk_unit(c, L, UNIT_QKV, B)), EPI_NONE, s);
         DecAttnArgs at = dec_attn_args(c, l);
         at.out_packed = ACT_TILES32; at.out_mt = (B + 15) / 16;
-        launch_decode_attention(dt, at, B, s);
+        run_decode_attention(c, at, l, B);
         launch_xstat_blk(dt, blk_unit(c, L, UNIT_O, B), EPI_RESID, s);
         launch_xstat_blk(dt, norm_in_front(c, blk_unit(c, L, UNIT_GATE_UP, B)), EPI_SILU_MUL, s);
         // down_proj: K-split over 4 workgroups per tile into fp32 slabs, combined (+ residual) by the next RMSNorm (xsplit32_k<.., BLK>: 21 us against
@@ -435,7 +458,7 @@ static void step_blk8(rdx_ctx* c, int B) {
         launch_xstat_blk8(dt, norm_in_front(c, blk8_unit(c, L, UNIT_QKV, B)), EPI_NONE, s);
         DecAttnArgs at = dec_attn_args(c, l);
         at.out_packed = ACT_BLK64;
-        launch_decode_attention(dt, at, B, s);
+        run_decode_attention(c, at, l, B);
         ksplit(blk8_unit(c, L, UNIT_O, B));
         launch_xstat_blk8(dt, norm_in_front(c, blk8_unit(c, L, UNIT_GATE_UP, B)), EPI_SILU_MUL, s);
         ksplit(blk8_unit(c, L, UNIT_DOWN, B));
@@ -458,7 +481,7 @@ static void step_xs16(rdx_ctx* c, int B) {
         xstat(w4_rows_unit(c, xs16_unit(c, L, UNIT_QKV, B), L->wqkv, B), EPI_NONE);
         DecAttnArgs at = dec_attn_args(c, l);
         at.out_packed = ACT_BLK32;
-        launch_decode_attention(dt, at, B, s);
+        run_decode_attention(c, at, l, B);
         launch_xrow16(dt, xs16_unit(c, L, UNIT_O, B), s);
         xstat(w4_rows_unit(c, xs16_unit(c, L, UNIT_GATE_UP, B), L->wgu, B), EPI_SILU_MUL);
         const GemmArgs dn = w4_rows_unit(c, xs16_unit(c, L, UNIT_DOWN, B), L->wdown, B);
@@ -486,7 +509,7 @@ static void attn_oproj(rdx_ctx* c, int l, int B) {
     const GemmArgs ap = ksplit_args(ao);
     const int kg = (B >= xs_min_rows() && c->kslab) ? xsplit32_groups(ap) : 0;
     at.out_packed = kg > 0 ? ap.xpacked : ACT_ROWS;
-    launch_decode_attention(dt, at, B, c->stream);
+    run_decode_attention(c, at, l, B);
     if (kg) launch_ksplit(c, ap);
     else skinny(c, ao, EPI_RESID);
 }
@@ -641,6 +664,7 @@ extern "C" int rdx_generate_append(rdx_ctx* c, const int32_t* ids_tail, int B, i
                                    int pad_id, int32_t* out_tokens, void* scores, int* n_steps_host, int use_graph) {
     if (!c) return -1;
     if (max_new <= 0) return fail(c, -1, "rdx_generate_append: max_new must be positive");
+    if (int krc = kv8_refuse(c, "rdx_generate_append", "the kept prefix is not held in the model dtype")) return krc;
     if (c->rules_on) return fail(c, -1, "rdx_generate_append: not available under logits rules (the token history is not carried across calls); rdx_set_logits_rules(ctx, NULL) first");
     int rc = rdx_prefill_append(c, ids_tail, B, T_tail, keep_len, max_new, eos_id, pad_id, out_tokens, scores);
     if (rc) return rc;
@@ -732,6 +756,7 @@ extern "C" int rdx_beam_search(rdx_ctx* c, const int32_t* ids, const int32_t* ma
                                void* step_scores, int* n_steps_host) {
     if (!c) return -1;
     if (int src = rows_refuse(c, "rdx_beam_search")) return src;
+    if (int krc = kv8_refuse(c, "rdx_beam_search", "the beam reorder moves model-dtype cache rows")) return krc;
     if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_beam_search: llama weights not finalized");
     const rdx_config& f = c->cfg;
     if (c->sampling.do_sample) return fail(c, -1, "rdx_beam_search: not available while sampling is on (beam-sample is not built); rdx_set_sampling(ctx, NULL) first");

@@ -31,6 +31,7 @@ extern "C" int rdx_rows_begin(rdx_ctx* c, int rows, int stage, int cap, int eos_
     if (!c) return -1;
     if (c->rs_on) return fail(c, -1, "rdx_rows_begin: a row session is already open on this context; rdx_rows_end first");
     if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_rows_begin: llama weights not finalized");
+    if (int krc = kv8_refuse(c, "rdx_rows_begin", "the row moves copy model-dtype cache rows")) return krc;
     const rdx_config& f = c->cfg;
     if (c->rules_on) return fail(c, -1, "rdx_rows_begin: not available under logits rules (a moved row's token history would have to move too); rdx_set_logits_rules(ctx, NULL) first");
     if (c->sampling.do_sample) return fail(c, -1, "rdx_rows_begin: not available while sampling is on (a moved row's draw index would have to move too); rdx_set_sampling(ctx, NULL) first");

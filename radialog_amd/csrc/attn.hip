@@ -384,15 +384,101 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 16 ? 1 : 4)) void decode_atte
     else decode_attention_body<T, WAVES, false>(a, blockIdx.x, blockIdx.y, dsm);
 }
 
-void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, hipStream_t s) {
-    dim3 grid(a.d.heads, B);
+// the same three builds on the fp8 KV cache (attn_body.h KV8): wave counts, row sweeps and register windows of their T twins
+template <typename T, int WAVES>
+__global__ __launch_bounds__(WAVES * 64, (WAVES == 16 ? 1 : 4)) void decode_attention_kv8_k(DecAttnArgs a, signed char* kexp, signed char* vexp) {
+    extern __shared__ __attribute__((aligned(16))) float dsm[];
+    if (WAVES == 16) decode_attention_kv8_body<T, WAVES, true, true>(a, kexp, vexp, blockIdx.x, blockIdx.y, dsm);
+    else if (WAVES == 8) decode_attention_kv8_body<T, WAVES, true, false, 3>(a, kexp, vexp, blockIdx.x, blockIdx.y, dsm);
+    else decode_attention_kv8_body<T, WAVES, false>(a, kexp, vexp, blockIdx.x, blockIdx.y, dsm);
+}
+
+// which build a launch of heads x B pairs takes (both caches): 16, 8 or 4 waves
+static int decode_attention_waves(const DecAttnArgs& a, int B) {
     const char* tp_env = getenv("RDX_ATT_TP");                       // tests: 1 forces the throughput variant, 2 the 8-wave one (re-read per launch: the tests flip it between engines)
     const int force_tp = tp_env ? atoi(tp_env) : 0;
     static const bool att_mid = !(getenv("RDX_ATT_MID") && atoi(getenv("RDX_ATT_MID")) == 0);      // A/B switch, read once
-    if (a.d.heads * B <= 256 && !force_tp) {
+    if (a.d.heads * B <= 256 && !force_tp) return DA_WAVES;
+    if (force_tp == 2 || (a.d.heads * B <= 512 && !force_tp && att_mid)) return DA_WAVES_MID;
+    return DA_WAVES_TP;
+}
+
+void launch_decode_attention_kv8(int dtype, const DecAttnArgs& a, signed char* kexp, signed char* vexp, int B, hipStream_t s) {
+    dim3 grid(a.d.heads, B);
+    const int waves = decode_attention_waves(a, B);
+    const size_t smem = decode_attention_smem_floats(waves, a.d.max_len) * sizeof(float);
+    if (waves == DA_WAVES) {
+        RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((decode_attention_kv8_k<T, DA_WAVES>), grid, dim3(DA_WAVES * 64), smem, s, a, kexp, vexp));
+    } else if (waves == DA_WAVES_MID) {
+        RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((decode_attention_kv8_k<T, DA_WAVES_MID>), grid, dim3(DA_WAVES_MID * 64), smem, s, a, kexp, vexp));
+    } else {
+        RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((decode_attention_kv8_k<T, DA_WAVES_TP>), grid, dim3(DA_WAVES_TP * 64), smem, s, a, kexp, vexp));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// fp8 KV cache: the prompt's rows into the cache, and the cache back in logical order
+// ------------------------------------------------------------------------------------------------------------------
+// staged T rows [B][heads][stage_len][128] (row-major K and V: what rope_kv_prefill_k wrote with k_perm 0) -> codes and exponents of positions
+// [slot0, slot0 + Tn). 16 lanes = one row (8 dims each), which = blockIdx.y: K or V.
+template <typename T>
+__global__ __launch_bounds__(256) void kv8_quant_rows_k(const T* __restrict__ kst, const T* __restrict__ vst, int stage_len, unsigned char* __restrict__ kcodes,
+                                                        signed char* __restrict__ kexp, unsigned char* __restrict__ vcodes, signed char* __restrict__ vexp,
+                                                        int max_len, int Tn, int slot0, size_t rows) {
+    typedef typename Vec8<T>::type V8;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;         // rows is a multiple of nothing, but 16 lanes of a row leave together
+    const size_t row = i >> 4;
+    if (row >= rows) return;
+    const int doct = (int)(i & 15), isv = blockIdx.y;
+    const size_t slab = row / Tn;
+    const int t = (int)(row - slab * Tn), pos = slot0 + t;
+    const V8 v = as_vec8<T>(ldg16((isv ? vst : kst) + (slab * stage_len + t) * 128 + doct * 8));
+    float x[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) x[e] = tof<T>(v[e]);
+    float am = 0.f;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) am = fmaxf(am, fabsf(x[e]));
+    const int ex = kv8_exp(row16_max(am));
+    const u2 c = kv8_quant8(x, ex);
+    if (isv) stg8(vcodes + slab * max_len * 128 + (size_t)pos * 128 + doct * 8, c);
+    else stg8(kcodes + slab * max_len * 128 + kperm8(pos, doct * 8), c);
+    if (doct == 0) stg1s((isv ? vexp : kexp) + slab * max_len + pos, ex);
+}
+void launch_kv8_quant_rows(int dtype, const void* kstage, const void* vstage, int stage_len, void* kcodes, signed char* kexp, void* vcodes, signed char* vexp,
+                           size_t slabs, int max_len, int T_, int slot0, hipStream_t s) {
+    const size_t rows = slabs * T_;
+    dim3 grid((unsigned)((rows * 16 + 255) / 256), 2);
+    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((kv8_quant_rows_k<T>), grid, dim3(256), 0, s, (const T*)kstage, (const T*)vstage, stage_len, (unsigned char*)kcodes,
+                                                kexp, (unsigned char*)vcodes, vexp, max_len, T_, slot0, rows));
+}
+
+// read-back: slabs of codes (is_k: the kperm8 order, else row-major) -> the codes in logical order [slab][max_len][128] (codes_out, nullable) and the
+// stored values x' = code 2^e in T (t_out, nullable). One thread = 8 dims of one position.
+template <typename T>
+__global__ __launch_bounds__(256) void kv8_read_k(const unsigned char* __restrict__ codes, const signed char* __restrict__ exps, int is_k, int max_len, size_t total8,
+                                                  unsigned char* __restrict__ codes_out, T* __restrict__ t_out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= total8) return;
+    const size_t slab = i / ((size_t)max_len * 16), rem = i - slab * (size_t)max_len * 16;
+    const int pos = (int)(rem >> 4), dim = (int)(rem & 15) * 8;
+    const u2 c = ldg8(codes + slab * max_len * 128 + (is_k ? kperm8(pos, dim) : (size_t)pos * 128 + dim));
+    if (codes_out) stg8(codes_out + i * 8, c);
+    if (t_out) stg16(t_out + i * 8, kv8_expand<T>(c.x, c.y, kv8_scale(ldg1s(exps + slab * max_len + pos))));
+}
+void launch_kv8_read(int dtype, const void* codes, const signed char* exps, int is_k, size_t slabs, int max_len, void* codes_out, void* t_out, hipStream_t s) {
+    const size_t total8 = slabs * max_len * 16;
+    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((kv8_read_k<T>), dim3((unsigned)((total8 + 255) / 256)), dim3(256), 0, s, (const unsigned char*)codes, exps, is_k,
+                                                max_len, total8, (unsigned char*)codes_out, (T*)t_out));
+}
+
+void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, hipStream_t s) {
+    dim3 grid(a.d.heads, B);
+    const int waves = decode_attention_waves(a, B);
+    if (waves == DA_WAVES) {
         const size_t smem = decode_attention_smem_floats(DA_WAVES, a.d.max_len) * sizeof(float);
         RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((decode_attention_k<T, DA_WAVES>), grid, dim3(DA_WAVES * 64), smem, s, a));
-    } else if (force_tp == 2 || (a.d.heads * B <= 512 && !force_tp && att_mid)) {
+    } else if (waves == DA_WAVES_MID) {
         // 9-16 rows at 32 heads (round 5; RDX_ATT_MID=0: the 4-wave form, the A/B leg; RDX_ATT_TP=2: forced, tests): batch 12 3.162 -> 3.098 ms per step, 16: 3.222 -> 3.178
         const size_t smem = decode_attention_smem_floats(DA_WAVES_MID, a.d.max_len) * sizeof(float);
         RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((decode_attention_k<T, DA_WAVES_MID>), grid, dim3(DA_WAVES_MID * 64), smem, s, a));

@@ -55,10 +55,17 @@ struct AttnNow {
     __device__ __forceinline__ const DecAttnArgs& operator()() const { return a; }
     __device__ __forceinline__ int* hint() const { return nullptr; }
 };
+// ... on the fp8 KV cache (KV8; the format: radialog_amd/kv8.py): a.kcache / a.vcache are the code slabs (K in the kperm8 order of rdx_common.h, V row-major),
+// ke / ve the row exponents [rows][heads][max_len], one signed byte each
+struct AttnNowKv8 : AttnNow { signed char *ke, *ve; };
 
 // COH: the OUTPUT is in-launch traffic (tagged granules + hint of the fused attention + o_proj launch, tag from a.epoch). COHX: the qkv row was
 // published by other workgroups of THIS launch and is read with agent-scope loads; in the fused launch the row predates the launch (COHX = false)
-template <typename T, int WAVES, bool DED, typename WaitFn, bool V_EARLY_, int KG_, bool COH, bool COHX, typename Late>
+// KV8: the cache holds e4m3 codes and one power-of-two exponent per row (late.ke / late.ve). Codes and exponents are loaded where the T fragments and rows
+// are, from addresses clamped the same way, and expanded to the T values x' = code 2^e (exact) in front of the same MFMAs and dot2s, in the same order: the
+// output bits are those of the T build on a cache holding x'. The new token takes part in its own step unquantised (s_new, part[]), as in the T build,
+// and wave 0 stores it quantised: its code row and exponent.
+template <typename T, int WAVES, bool DED, typename WaitFn, bool V_EARLY_, int KG_, bool COH, bool COHX, typename Late, bool KV8 = false>
 __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late late, const int h, const int b, float* dsm, WaitFn wait_inputs) {
     typedef typename Vec8<T>::type V8;
     constexpr int D = 128;
@@ -87,6 +94,12 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
     const T* x = qkv + (size_t)b * d.qkv_ld;
     T* kc = reinterpret_cast<T*>(e.kcache) + ((size_t)b * d.heads + h) * d.max_len * D;
     T* vc = reinterpret_cast<T*>(e.vcache) + ((size_t)b * d.heads + h) * d.max_len * D;
+    static_assert(!KV8 || !COH, "the fp8 cache is read by the stand-alone launches only");
+    // KV8: the same slabs in bytes, and this pair's exponent rows
+    unsigned char* const kc8 = reinterpret_cast<unsigned char*>(e.kcache) + ((size_t)b * d.heads + h) * d.max_len * D;
+    unsigned char* const vc8 = reinterpret_cast<unsigned char*>(e.vcache) + ((size_t)b * d.heads + h) * d.max_len * D;
+    signed char *ke = nullptr, *ve = nullptr;
+    if constexpr (KV8) { ke = late.ke + ((size_t)b * d.heads + h) * d.max_len; ve = late.ve + ((size_t)b * d.heads + h) * d.max_len; }
 
     // debug timeline (null in every product launch), 100 MHz ticks, thread 0. Stand-alone launches: workgroup (0, 0) alone, slots as rdx_attn_trace
     // documents them. COH (the fused launch, rdx_gemv_trace 8): one record per workgroup at trace[(b heads + h) * 8]: [0] entry, [1] qkv row loaded (new
@@ -101,7 +114,21 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
     // ---- cache loads of this lane in flight first ------------------------------------------------------------------
     const int cw = DED ? w - 1 : w;              // cache-wave index (-1: the dedicated new-token wave)
     const bool owns_rows = !DED || w > 0;        // wave-uniform
-    u4 kr[KG][4], vr[VR];
+    u4 kr[KV8 ? 1 : KG][4], vr[KV8 ? 1 : VR];
+    u4 kr8[KV8 ? KG : 1][2];                     // KV8: the lane's 32 code bytes of a group (its four fragments' pieces), the exponent of its position
+    u2 vr8[KV8 ? VR : 1];                        //      8 codes of a V row, the row's exponent
+    int kex[KV8 ? KG : 1], vex[KV8 ? VR : 1];
+    // a lane's fragment pieces / V dims as T values
+    auto k8_load = [&](int j, u4 (&c)[2], int& ex) {
+        const unsigned char* p = kc8 + kperm8(j, g * 8);
+        c[0] = ldg16(p); c[1] = ldg16(p + 16);
+        ex = ldg1s(ke + j);
+    };
+    auto k8_frags = [&](const u4 (&c)[2], int ex, u4 (&kf)[4]) {
+        const float s = kv8_scale(ex);
+        kf[0] = kv8_expand<T>(c[0].x, c[0].y, s); kf[1] = kv8_expand<T>(c[0].z, c[0].w, s);
+        kf[2] = kv8_expand<T>(c[1].x, c[1].y, s); kf[3] = kv8_expand<T>(c[1].z, c[1].w, s);
+    };
     unsigned kmw[KG];                            // key-mask bytes of positions gb + 4g .. +3
     // The lower half of the register window is loaded unconditionally at kernel entry; the upper half only once `slot`
     // is known and only by the waves whose rows exist (all of a head's cache traffic funnels through ONE CU's L1 at
@@ -114,8 +141,11 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
             const int gb = (u * CW + cw) * 16;
             if (u >= u0 && u < u1 && gb < limit) {
                 const int j = min(gb + r, d.max_len - 1);
+                if constexpr (KV8) k8_load(j, kr8[u], kex[u]);
+                else {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) kr[u][c] = ldg16(kc + kperm(j, c * 32 + g * 8, d.k_perm));
+                    for (int c = 0; c < 4; ++c) kr[u][c] = ldg16(kc + kperm(j, c * 32 + g * 8, d.k_perm));
+                }
                 kmw[u] = *reinterpret_cast<const unsigned*>(mask() + min(gb + 4 * g, d.max_len - 4));
             }
         }
@@ -127,7 +157,8 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
             // a pair is loaded with its even partner (clamped address, P = 0) -- an unloaded register may hold a NaN pattern
             if (u >= u0 && u < u1 && (u & ~1) * SPAN + cw * 4 < limit) {
                 const int j = min(u * SPAN + cw * 4 + jsub, d.max_len - 1);
-                vr[u] = ldg16(vc + (size_t)j * D + doct * 8);
+                if constexpr (KV8) { vr8[u] = ldg8(vc8 + (size_t)j * D + doct * 8); vex[u] = ldg1s(ve + j); }
+                else vr[u] = ldg16(vc + (size_t)j * D + doct * 8);
             }
         }
     };
@@ -231,12 +262,26 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
 #pragma unroll
             for (int e = 0; e < 8; ++e) { qo[e] = fromf<T>(q8n[e]); ko[e] = fromf<T>(k8[e]); vo[e] = fromf<T>(v8[e]); }
             *reinterpret_cast<u4*>(qT + doct * 8) = as_u4<T>(qo);
-            stg16(kc + kperm(slot, doct * 8, d.k_perm), as_u4<T>(ko));      // K rows live in the 16-position fragment order (rdx_common.h)
-            stg16(vc + (size_t)slot * D + doct * 8, as_u4<T>(vo));
+            if constexpr (!KV8) {                                               // (KV8: stored quantised, below)
+                stg16(kc + kperm(slot, doct * 8, d.k_perm), as_u4<T>(ko));      // K rows live in the 16-position fragment order (rdx_common.h)
+                stg16(vc + (size_t)slot * D + doct * 8, as_u4<T>(vo));
+            }
             // the new row's V (fp32) waits in wave 0's own slice of `part` until P.V: the same lanes read it back, and only then does wave 0
             // overwrite the slice with its partial output -- LDS serves a wave's operations in order, no barrier involved
 #pragma unroll
             for (int e = 0; e < 8; ++e) part[doct * 8 + e] = v8[e];
+        }
+        if constexpr (KV8) {
+            // the new row stored quantised (kv8.py): absmax over the head's 16 lanes by DPP, the exponent, one rounding to e4m3 of the exactly scaled values
+            float ka = 0.f, va = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { ka = fmaxf(ka, fabsf(k8[e])); va = fmaxf(va, fabsf(v8[e])); }
+            const int kx = kv8_exp(row16_max(ka)), vx = kv8_exp(row16_max(va));
+            if (jsub == 0) {
+                stg8(kc8 + kperm8(slot, doct * 8), kv8_quant8(k8, kx));
+                stg8(vc8 + (size_t)slot * D + doct * 8, kv8_quant8(v8, vx));
+                if (doct == 0) { stg1s(ke + slot, kx); stg1s(ve + slot, vx); }
+            }
         }
         // q . k of the new position, finished HERE: q8n / k8 / v8 (24 registers in every wave of the launch, used by wave 0 only) are dead
         // before the cache phases start -- they used to stay live through scores, softmax and P.V, and at the 128-register cap of the
@@ -277,7 +322,10 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
     if (owns_rows) {
 #pragma unroll
         for (int u = 0; u < KG; ++u)
-            if (u < KG_LO || (u * CW + cw) * 16 < slot) score_group(kr[u], kmw[u], (u * CW + cw) * 16);   // wave-uniform
+            if (u < KG_LO || (u * CW + cw) * 16 < slot) {                                                  // wave-uniform
+                if constexpr (KV8) { u4 kf[4]; k8_frags(kr8[u], kex[u], kf); score_group(kf, kmw[u], (u * CW + cw) * 16); }
+                else score_group(kr[u], kmw[u], (u * CW + cw) * 16);
+            }
         if (!V_EARLY) { load_v(0, VR_LO, 0x7fffffff); load_v(VR_LO, VR, slot); }     // K registers are free now
         // contexts beyond the register window: two groups per trip, all eight fragment loads issued before the first MFMA
         // (the register window is dead by now); a group past the context is loaded from a clamped row and stores nothing
@@ -285,19 +333,27 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
         // loads are real HBM traffic: at batch 32 the clamped rows were a fifth of the kernel's bytes)
         for (int gi = KG * CW + cw; gi * 16 < slot; gi += KT * CW) {
             u4 kf[KT][4];
+            u4 kf8[KT][2];
+            int kfx[KT];
             unsigned mw[KT];
 #pragma unroll
             for (int t = 0; t < KT; ++t) {
                 if (t > 0 && !((gi + t * CW) * 16 < slot)) break;       // wave-uniform: a group past the context would store nothing, and its loads are real HBM traffic
                 const int gb = (gi + t * CW) * 16;
                 const int j = min(gb + r, d.max_len - 1);
+                if constexpr (KV8) k8_load(j, kf8[t], kfx[t]);
+                else {
 #pragma unroll
-                for (int c = 0; c < 4; ++c) kf[t][c] = ldg16(kc + kperm(j, c * 32 + g * 8, d.k_perm));
+                    for (int c = 0; c < 4; ++c) kf[t][c] = ldg16(kc + kperm(j, c * 32 + g * 8, d.k_perm));
+                }
                 mw[t] = *reinterpret_cast<const unsigned*>(km + min(gb + 4 * g, d.max_len - 4));
             }
 #pragma unroll
             for (int t = 0; t < KT; ++t)
-                if (t == 0 || (gi + t * CW) * 16 < slot) score_group(kf[t], mw[t], (gi + t * CW) * 16);      // positions >= slot are not stored
+                if (t == 0 || (gi + t * CW) * 16 < slot) {                                                  // positions >= slot are not stored
+                    if constexpr (KV8) k8_frags(kf8[t], kfx[t], kf[t]);
+                    score_group(kf[t], mw[t], (gi + t * CW) * 16);
+                }
         }
     }
     if (w == 0 && lane == 0) S[slot] = km_new ? rnd<T>(rnd<T>(s_new) / div) : -INFINITY;      // the new position itself
@@ -337,8 +393,11 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
             // rows u, u+1 of this lane: (v_u[d], v_u+1[d]) . (p_u, p_u+1) for its 8 dims; rows >= slot have p = 0
             // (the cache is zero-initialised, so unused rows hold finite values)
             const unsigned pp = (unsigned)bits16<T>(fromf<T>(pu[u])) | ((unsigned)bits16<T>(fromf<T>(pu[u + 1])) << 16);
-            const unsigned a0[4] = {vr[u].x, vr[u].y, vr[u].z, vr[u].w};
-            const unsigned a1[4] = {vr[u + 1].x, vr[u + 1].y, vr[u + 1].z, vr[u + 1].w};
+            u4 x0, x1;
+            if constexpr (KV8) { x0 = kv8_expand<T>(vr8[u].x, vr8[u].y, kv8_scale(vex[u])); x1 = kv8_expand<T>(vr8[u + 1].x, vr8[u + 1].y, kv8_scale(vex[u + 1])); }
+            else { x0 = vr[u]; x1 = vr[u + 1]; }
+            const unsigned a0[4] = {x0.x, x0.y, x0.z, x0.w};
+            const unsigned a1[4] = {x1.x, x1.y, x1.z, x1.w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const unsigned lo = __builtin_amdgcn_perm(a1[e], a0[e], 0x05040100u);    // (v_u[2e],   v_u+1[2e])
@@ -350,16 +409,24 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
         // contexts beyond the register window: four rows per trip, loads first (clamped rows get P = 0)
         for (int j0 = VR * SPAN; j0 < slot; j0 += VT * SPAN) {
             u4 vt[VT];
+            u2 vt8[VT];
+            int vtx[VT];
             float pt[VT];
 #pragma unroll
             for (int t = 0; t < VT; ++t) {
                 const int j = j0 + t * SPAN + cw * 4 + jsub;
                 // rows of a whole wave past the context (wave-uniform test) are not fetched: zero row, P = 0
+                if constexpr (KV8) {
+                    const bool in = j0 + t * SPAN + cw * 4 < slot;
+                    vt8[t] = in ? ldg8(vc8 + (size_t)min(j, d.max_len - 1) * D + doct * 8) : (u2){0u, 0u};
+                    vtx[t] = in ? ldg1s(ve + min(j, d.max_len - 1)) : 0;
+                } else
                 vt[t] = (j0 + t * SPAN + cw * 4 < slot) ? ldg16(vc + (size_t)min(j, d.max_len - 1) * D + doct * 8) : (u4){0u, 0u, 0u, 0u};
                 pt[t] = j < slot ? rnd<T>(expf(S[j] - mx) / sum) : 0.f;
             }
 #pragma unroll
             for (int t = 0; t < VT; t += 2) {
+                if constexpr (KV8) { vt[t] = kv8_expand<T>(vt8[t].x, vt8[t].y, kv8_scale(vtx[t])); vt[t + 1] = kv8_expand<T>(vt8[t + 1].x, vt8[t + 1].y, kv8_scale(vtx[t + 1])); }
                 const unsigned pp = (unsigned)bits16<T>(fromf<T>(pt[t])) | ((unsigned)bits16<T>(fromf<T>(pt[t + 1])) << 16);
                 const unsigned a0[4] = {vt[t].x, vt[t].y, vt[t].z, vt[t].w};
                 const unsigned a1[4] = {vt[t + 1].x, vt[t + 1].y, vt[t + 1].z, vt[t + 1].w};
@@ -419,6 +486,12 @@ __device__ __forceinline__ void decode_attention_core(const AttnEarly& e, Late l
 template <typename T, int WAVES, bool DED = (WAVES == 8), typename WaitFn = NoWait, bool V_EARLY_ = !DED, int KG_ = 0>
 __device__ __forceinline__ void decode_attention_body(const DecAttnArgs& a, const int h, const int b, float* dsm, WaitFn wait_inputs = WaitFn()) {
     decode_attention_core<T, WAVES, DED, WaitFn, V_EARLY_, KG_, false, false>(AttnEarly{a.qkv, a.kcache, a.vcache, a.d}, AttnNow{a}, h, b, dsm, wait_inputs);
+}
+// ... on the fp8 KV cache: the same variants (wave count, row sweep, register window), codes and exponents in place of the T rows
+template <typename T, int WAVES, bool DED = (WAVES == 8), bool V_EARLY_ = !DED, int KG_ = 0>
+__device__ __forceinline__ void decode_attention_kv8_body(const DecAttnArgs& a, signed char* kexp, signed char* vexp, const int h, const int b, float* dsm) {
+    AttnNowKv8 now{{a}, kexp, vexp};
+    decode_attention_core<T, WAVES, DED, NoWait, V_EARLY_, KG_, false, false, AttnNowKv8, true>(AttnEarly{a.qkv, a.kcache, a.vcache, a.d}, now, h, b, dsm, NoWait());
 }
 
 }  // namespace rdx

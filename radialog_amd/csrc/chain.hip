@@ -692,6 +692,7 @@ __global__ __launch_bounds__(CH_THREADS, 4) void attn_oproj16_k(const void* wo, 
 
 bool attn_oproj16_supported(const LlamaDims& d, int N, int K, int B) {
     const int ntiles = (N + 15) / 16;
+    if (d.kv_fp8) return false;      // the fp8 KV cache is read by the stand-alone attention builds only
     return B <= CH_MAXM && d.head_dim == 128 && K == d.heads * 128 && K == d.hidden && K % 32 == 0 && N % 4 == 0 && (size_t)B * K <= 8192 &&
            d.heads * B + (ntiles + 1) / 2 <= 256;
 }

@@ -91,6 +91,48 @@ template <> __device__ __forceinline__ u4 dequant8<f16>(unsigned lo, unsigned hi
                 __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(c[0], c[1])), __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(d[0], d[1]))};
 }
 
+// ---- fp8 KV cache ("kv8": e4m3 codes with one power-of-two exponent per cache row of 128; the format's definition is radialog_amd/kv8.py) ----
+// The stored row IS x' = code * 2^e, exactly a bf16 and an f16 value (e >= -15), so the expansion below is exact and the cache reads as a T cache
+// holding x'. Two codes times the scale become a packed T pair in one VALU instruction (v_cvt_scalef32_pk_{bf16,f16}_fp8).
+constexpr int KV8_EMIN = -15;
+__device__ __forceinline__ float kv8_scale(int e) { return __builtin_bit_cast(float, (unsigned)(e + 127) << 23); }       // 2^e, e in [-126, 127]
+template <typename T, bool HI> __device__ __forceinline__ unsigned kv8_pk(unsigned w, float s);       // codes 2 HI, 2 HI + 1 of w, times s
+template <> __device__ __forceinline__ unsigned kv8_pk<bf16, false>(unsigned w, float s) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, s, false)); }
+template <> __device__ __forceinline__ unsigned kv8_pk<bf16, true>(unsigned w, float s) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w, s, true)); }
+template <> __device__ __forceinline__ unsigned kv8_pk<f16, false>(unsigned w, float s) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, s, false)); }
+template <> __device__ __forceinline__ unsigned kv8_pk<f16, true>(unsigned w, float s) { return __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w, s, true)); }
+// two dwords = 8 codes -> 8 T values x' in one 16-byte register quad (an MFMA A-operand chunk, or 8 dims of a V row)
+template <typename T> __device__ __forceinline__ u4 kv8_expand(unsigned lo, unsigned hi, float s) {
+    return (u4){kv8_pk<T, false>(lo, s), kv8_pk<T, true>(lo, s), kv8_pk<T, false>(hi, s), kv8_pk<T, true>(hi, s)};
+}
+// the row exponent of radialog_amd/kv8.py from the row's absmax (a T value held in fp32, finite): the smallest e >= -15 with amax 2^-e <= 448. With
+// frexp(amax) = (m, ex), ex = E - 126 and m <= 0.875 <=> mantissa field <= 0x600000. Zero and fp32-subnormal rows (E = 0) clamp to -15.
+__device__ __forceinline__ int kv8_exp(float amax) {
+    const unsigned u = __builtin_bit_cast(unsigned, amax);
+    const int E = (int)((u >> 23) & 0xffu);
+    return max(E - 135 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0), KV8_EMIN);
+}
+// 8 values of a row (fp32 copies of T values) -> 8 codes RNE_e4m3(x 2^-e): the scaling is exact (or underflows below half the smallest code), one rounding
+__device__ __forceinline__ u2 kv8_quant8(const float (&x)[8], int e) {
+    const float inv = kv8_scale(-e);
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[0] * inv, x[1] * inv, lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(x[2] * inv, x[3] * inv, lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[4] * inv, x[5] * inv, hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(x[6] * inv, x[7] * inv, hi, true);
+    return (u2){(unsigned)lo, (unsigned)hi};
+}
+// K codes inside one (row, head) slab [max_len][128] bytes: every group of 16 positions is stored [g = (dim % 32) / 8][r = pos % 16][dim / 32][8], so
+// the 32 bytes of an MFMA A-fragment lane (g, r) -- its four 8-dim pieces -- are contiguous and a wave's group is ONE contiguous 2 KiB. V codes are row-major.
+__host__ __device__ __forceinline__ size_t kperm8(int pos, int dim) {
+    return (size_t)(pos >> 4) * 2048 + (size_t)((((dim & 31) >> 3) * 16 + (pos & 15)) * 32 + (dim >> 5) * 8 + (dim & 7));
+}
+typedef __attribute__((address_space(1))) u2 g_u2;
+__device__ __forceinline__ u2 ldg8(const void* p) { return *(const g_u2*)p; }
+__device__ __forceinline__ void stg8(void* p, u2 v) { *(g_u2*)p = v; }
+__device__ __forceinline__ int ldg1s(const void* p) { return *(const __attribute__((address_space(1))) signed char*)p; }
+__device__ __forceinline__ void stg1s(void* p, int v) { *(__attribute__((address_space(1))) signed char*)p = (signed char)v; }
+
 // ---- coded bf16 weights ("WC", 13 bits per weight, exact; the format's definition is radialog_amd/wcode.py) ------------------------------
 // A coded chunk is 128 k-values of one 16-row tile = four of the packed 32-k chunks, WC_CHUNK_BYTES bytes in three planes, each a run of whole-wave
 // contiguous loads: [lo0: 64 lanes x 16 B][lo1: 64 x 16 B][idx: 64 x 16 B][sign: 64 x 4 B]. Lane (g, r) holds the 32 weights of ITS four MFMA A

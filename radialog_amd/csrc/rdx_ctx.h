@@ -86,6 +86,13 @@ struct rdx_ctx {
     LlamaDims ld;
     void *kcache = nullptr, *vcache = nullptr;     // [layers][B][heads][max_len][D]
     size_t kv_layer_elems = 0;
+    // fp8 KV cache (rdx_set_option("kv_fp8", 1) before rdx_finalize_weights; the format: radialog_amd/kv8.py): kcache / vcache then hold the e4m3 codes, one BYTE
+    // per element (K in the kperm8 order of rdx_common.h, V row-major), kexp / vexp the row exponents [layers][B][heads][max_len]; kv_kstage / kv_vstage:
+    // the prompt's K / V rows of ONE layer in the model dtype, [B][heads][ceil16(T)][128] row-major -- what the prompt's own attention reads
+    bool kv_fp8 = false;
+    signed char *kexp = nullptr, *vexp = nullptr;
+    void *kv_kstage = nullptr, *kv_vstage = nullptr;
+    size_t kv_alloc_bytes = 0;                     // bytes of the KV allocation (caches, exponents; the staging buffer is not part of it): rdx_kv_bytes
     uint8_t* key_mask = nullptr;                   // [B][max_len]
     int *d_img_pos = nullptr, *d_pos_ids = nullptr, *d_pos = nullptr, *d_slot = nullptr, *d_step = nullptr, *d_unf = nullptr;
     float* part_val = nullptr; int* part_idx = nullptr; int n_vtiles = 0;
@@ -255,7 +262,14 @@ inline bool fp8_weights(const GemmW& W) { return W.w8 && W.scale && !W.w; }     
 int take_unsupported(rdx_ctx* c);     // nonzero (and rdx_last_error set) when a launch since the last call had no kernel for its shape
 
 // ---- decoder (api_llama.hip) ----
-inline void* kv_ptr(rdx_ctx* c, void* base, int layer) { return (char*)base + (size_t)layer * c->kv_layer_elems * 2; }
+inline void* kv_ptr(rdx_ctx* c, void* base, int layer) { return (char*)base + (size_t)layer * c->kv_layer_elems * (c->kv_fp8 ? 1 : 2); }
+inline signed char* kvx_ptr(rdx_ctx* c, signed char* base, int layer) { return base + (size_t)layer * (c->kv_layer_elems / 128); }      // fp8 KV cache: a layer's row exponents
+// decode attention of one layer on whichever cache the context holds (at from dec_attn_args)
+void run_decode_attention(rdx_ctx* c, const DecAttnArgs& at, int layer, int B);
+// every entry point that needs the cached rows in the model dtype refuses on an fp8 KV cache (-1, a message naming "kv_fp8")
+inline int kv8_refuse(rdx_ctx* c, const char* who, const char* why) {
+    return c->kv_fp8 ? fail(c, -1, "%s: not built for the fp8 KV cache (kv_fp8): %s", who, why) : 0;
+}
 int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep,
                  int max_new, int eos_id, int pad_id, int32_t* out_tokens, void* logits);
 // evs (timing only, eager launches): a pair of events recorded around every chained down(l) -> QKV(l+1) launch of this step

@@ -123,6 +123,8 @@ struct LlamaDims {
     int max_len;         // KV slots per (b, head)
     int max_pos;
     int k_perm;          // K cache slabs in the 16-position fragment order (rdx_common.h kperm) instead of row-major
+    int kv_fp8 = 0;      // the context's KV cache holds e4m3 codes + row exponents (radialog_amd/kv8.py): decode attention through launch_decode_attention_kv8,
+                         // never inside the fused attention + o_proj launch
 };
 
 void launch_pack_weight(int dtype, const float* src, void* dst, int N, int K, int Npad, const int* rowmap, hipStream_t s);
@@ -232,6 +234,15 @@ struct DecAttnArgs {
     int layers = 0, layer = 0;
 };
 void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, hipStream_t s);
+// fp8 KV cache (the format: radialog_amd/kv8.py; device side: rdx_common.h "kv8"). a.kcache / a.vcache are the code slabs [B][heads][max_len][128] bytes (K in
+// the kperm8 order, V row-major; a.d.k_perm is not looked at), kexp / vexp the row exponents [B][heads][max_len]. Same variants and output bits as
+// launch_decode_attention on a T cache holding the stored values.
+void launch_decode_attention_kv8(int dtype, const DecAttnArgs& a, signed char* kexp, signed char* vexp, int B, hipStream_t s);
+// staged T rows [slabs][stage_len][128] (row-major K and V) -> codes and exponents of cache positions [slot0, slot0 + T) of every slab
+void launch_kv8_quant_rows(int dtype, const void* kstage, const void* vstage, int stage_len, void* kcodes, signed char* kexp, void* vcodes, signed char* vexp,
+                           size_t slabs, int max_len, int T, int slot0, hipStream_t s);
+// code slabs (is_k: the kperm8 order) -> the codes in logical order (codes_out, nullable) and the stored values in T (t_out, nullable), [slabs][max_len][128]
+void launch_kv8_read(int dtype, const void* codes, const signed char* exps, int is_k, size_t slabs, int max_len, void* codes_out, void* t_out, hipStream_t s);
 // Chained decode launches of the batch <= 2 step (chain.hip): units run as roles of one launch, chained by a fence-free counter
 // hand-off (handoff.h) instead of a kernel boundary.
 // Every launch is a graph node of ONE layer, so the layer's pointers travel by value (no device table, no dependent read in front of the weight

@@ -86,13 +86,15 @@ class Sampling:
 class RdxEngine:
     def __init__(self, cfg: RaDialogCfg, dtype: str = "bf16", device: int = 0, max_batch: int = 1, max_len: int = 512,
                  lora: bool = True, vision: bool = True, llama: bool = True, classifier: bool = False,
-                 weights_fp8: bool = False, weights_w4: bool = False):
+                 weights_fp8: bool = False, weights_w4: bool = False, kv_fp8: bool = False):
         if dtype not in _RDX_DT:
             raise ValueError(f"dtype must be 'f16' or 'bf16', got {dtype!r}")
         if weights_w4 and weights_fp8:
             raise ValueError("weights_w4 and weights_fp8 do not mix: one weight format per context")
         if weights_w4 and dtype == "f16":
             raise ValueError("weights_w4 needs dtype='bf16' (int4 weights are not built for f16)")
+        if kv_fp8 and (classifier or not llama):
+            raise ValueError("kv_fp8 is an option of the decoder's KV cache: it needs llama=True")
         self.lib = _lib.load()                       # raises RdxLibraryError when the HIP library is absent
         if not torch.cuda.is_available():
             raise _lib.RdxError("RdxEngine needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU path")
@@ -129,6 +131,10 @@ class RdxEngine:
             raise _lib.RdxError(f"rdx_create failed ({rcode}): {msg.decode() if msg else '?'}")
         self._finalized = False
         self._keep = {}
+        # the decoder's KV cache as e4m3 codes + one power-of-two exponent per row (radialog_amd/kv8.py): half the cache bytes; decides what finalize allocates
+        self.kv_fp8 = bool(kv_fp8)
+        if self.kv_fp8:
+            self.set_option("kv_fp8", 1)
         self._rules = LogitsRules()                  # what the context holds (set_logits_rules is the one place that changes it)
         self._sampling = None                        # likewise (set_sampling); None = greedy
 
@@ -303,6 +309,8 @@ class RdxEngine:
         (HF's .scores). An active rule prefills the whole prompt: the token history is not carried across calls.
         sampling: Sampling or (temperature, top_k, top_p, seed): rules, then the warpers, then one draw per row and step; the scores are the warped ones."""
         B, T = ids.shape
+        if reuse_prefix and self.kv_fp8:
+            raise ValueError("reuse_prefix is not built on the fp8 KV cache (kv_fp8): the kept prefix is not held in the model dtype")
         self.set_sampling(sampling)
         if self.set_logits_rules(logits_rules).active:
             reuse_prefix = False
@@ -477,6 +485,32 @@ class RdxEngine:
         check(self.ctx, self.lib.rdx_kv_read(self.ctx, layer, which, _ptr(out)), "rdx_kv_read")
         self.sync()
         return out[:batch]
+
+    def kv_read_codes(self, layer: int, which: int, batch: int):
+        """An fp8 KV cache (kv_fp8=True) as stored, in logical order: (codes uint8 [batch, heads, max_len, 128], exponents int8 [batch, heads, max_len]) of
+        one layer's K (which 0) or V (1); kv_read() returns the same rows dequantised (radialog_amd/kv8.py dequant)."""
+        l = self.cfg.llama
+        codes = torch.empty(self.max_batch, l.heads, self.max_len, l.head_dim, dtype=torch.uint8, device=self.device)
+        exps = torch.empty(self.max_batch, l.heads, self.max_len, dtype=torch.int8, device=self.device)
+        check(self.ctx, self.lib.rdx_kv_read_codes(self.ctx, layer, which, _ptr(codes), _ptr(exps)), "rdx_kv_read_codes")
+        self.sync()
+        return codes[:batch], exps[:batch]
+
+    def kv_cache_bytes(self) -> int:
+        """Bytes of the context's KV allocation (rdx_kv_bytes): K and V caches of every layer and, fp8, their row exponents."""
+        n = self.lib.rdx_kv_bytes(self.ctx)
+        if n < 0:
+            raise _lib.RdxError(f"rdx_kv_bytes failed: {self._last_error()}")
+        return int(n)
+
+    def kv_write_test(self, layer: int, which: int, rows: torch.Tensor):
+        """rdx_kv_write_test: overwrite one layer's K (0) or V (1) cache of a plain engine with rows [batch <= max_batch, heads, max_len, 128] in logical
+        order (rows past `batch` become zeros)."""
+        l = self.cfg.llama
+        full = torch.zeros(self.max_batch, l.heads, self.max_len, l.head_dim, dtype=self.tdtype, device=self.device)
+        full[:rows.shape[0]] = rows.to(self.device, self.tdtype)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_kv_write_test(self.ctx, layer, which, _ptr(full)), "rdx_kv_write_test")
 
     def gemm_test(self, x, w, bias=None, resid=None, epi=0, norm_w=None, eps=1e-6, force=0):
         """out = epilogue(x @ w.T) through the production GEMM kernels. x [M,K] model dtype, w [N,K] fp32."""
@@ -856,6 +890,55 @@ class RdxEngine:
                                            0 if ct is None else ct.shape[0], _ptr(ps), _ptr(sl), _ptr(km), _ptr(kc), _ptr(vc), _ptr(out), out.numel(), int(out_packed),
                                            int(out_mt))
         return (None if rc == 0 else self._last_error()), out, kc, vc
+
+    def decode_attn_kv8_test(self, qkv, kcodes, kexp, vcodes, vexp, slot, key_mask, cur_rope=None, cos=None, sin=None, pos=None, lbq=None, lbv=None, lora_scale=1.0,
+                             out_packed=0, out_mt=2, out_bytes=None, guard=0):
+        """launch_decode_attention_kv8 alone (rdx_decode_attn_kv8_test): decode_attn_test's arguments with the caches as kcodes / vcodes uint8 [B, heads, max_len,
+        128] (K in the kernels' storage order: kv8.k_store) and kexp / vexp int8 [B, heads, max_len]. Returns (error or None, raw output uint8, kcodes, kexp,
+        vcodes, vexp after the launch); each of the four is followed by `guard` bytes that were 0xff before the launch (flat uint8 tensors, the buffer first)."""
+        B, heads, max_len = kcodes.shape[:3]
+        H = 128 * heads
+        x = self._dev(qkv)
+
+        def guarded(t, dt):
+            t = self._dev(t, dt).contiguous()
+            buf = torch.full((t.numel() + guard,), 0xff, dtype=torch.uint8, device=self.device)
+            buf[:t.numel()] = t.view(torch.uint8).reshape(-1)
+            return buf
+        kc, vc, ke, ve = guarded(kcodes, torch.uint8), guarded(vcodes, torch.uint8), guarded(kexp, torch.int8), guarded(vexp, torch.int8)
+        sl, km = self._dev(slot, torch.int32), self._dev(key_mask, torch.uint8)
+        cr, ct, st, ps = self._dev(cur_rope), self._dev(cos), self._dev(sin), self._dev(pos, torch.int32)
+        bq, bv = self._dev(lbq), self._dev(lbv)
+        lora_r = 0 if lbq is None else 8
+        if tuple(x.shape) != (B, (3 * H + 2 * lora_r + 15) // 16 * 16) or vcodes.shape != kcodes.shape or kcodes.shape[3] != 128 or tuple(kexp.shape) != (B, heads, max_len) \
+                or vexp.shape != kexp.shape or sl.numel() != B or tuple(km.shape) != (B, max_len):
+            raise ValueError("decode_attn_kv8_test: qkv [B, qkv_ld], codes [B, heads, max_len, 128], exponents [B, heads, max_len], slot [B], key_mask [B, max_len]")
+        out = torch.full((B * H * 2 if out_bytes is None else out_bytes,), 0xff, dtype=torch.uint8, device=self.device)
+        torch.cuda.synchronize(self.device)
+        rc = self.lib.rdx_decode_attn_kv8_test(self.ctx, heads, B, max_len, lora_r, float(lora_scale), _ptr(x), _ptr(bq), _ptr(bv), _ptr(cr), _ptr(ct), _ptr(st),
+                                               0 if ct is None else ct.shape[0], _ptr(ps), _ptr(sl), _ptr(km), _ptr(kc), _ptr(ke), _ptr(vc), _ptr(ve), _ptr(out),
+                                               out.numel(), int(out_packed), int(out_mt))
+        return (None if rc == 0 else self._last_error()), out, kc, ke, vc, ve
+
+    def kv8_quant_test(self, krows, vrows, T, max_len, slot0, kcodes, kexp, vcodes, vexp, guard=0):
+        """launch_kv8_quant_rows alone (rdx_kv8_quant_test): krows / vrows [B, heads, stage_len, 128] model dtype; rows t < T go to positions slot0 + t of the
+        codes [B, heads, max_len, 128] uint8 (K in the storage order) and exponents [B, heads, max_len] int8. Returns (error or None, kcodes, kexp, vcodes,
+        vexp) as flat uint8 tensors, each followed by `guard` bytes that were 0xff before the launch."""
+        B, heads, stage_len = krows.shape[:3]
+        kr, vr = self._dev(krows), self._dev(vrows)
+
+        def guarded(t, dt):
+            t = self._dev(t, dt).contiguous()
+            buf = torch.full((t.numel() + guard,), 0xff, dtype=torch.uint8, device=self.device)
+            buf[:t.numel()] = t.view(torch.uint8).reshape(-1)
+            return buf
+        kc, vc, ke, ve = guarded(kcodes, torch.uint8), guarded(vcodes, torch.uint8), guarded(kexp, torch.int8), guarded(vexp, torch.int8)
+        if vr.shape != kr.shape or kr.shape[3] != 128 or tuple(kcodes.shape) != (B, heads, max_len, 128) or vcodes.shape != kcodes.shape \
+                or tuple(kexp.shape) != (B, heads, max_len) or vexp.shape != kexp.shape:
+            raise ValueError("kv8_quant_test: rows [B, heads, stage_len, 128], codes [B, heads, max_len, 128], exponents [B, heads, max_len]")
+        torch.cuda.synchronize(self.device)
+        rc = self.lib.rdx_kv8_quant_test(self.ctx, heads, B, int(T), stage_len, int(max_len), int(slot0), _ptr(kr), _ptr(vr), _ptr(kc), _ptr(ke), _ptr(vc), _ptr(ve))
+        return (None if rc == 0 else self._last_error()), kc, ke, vc, ve
 
     def rope_kv_test(self, qkv, pos_ids, cos, sin, slot0, kcache, vcache, k_perm, lbq=None, lbv=None, lora_scale=1.0):
         """launch_rope_kv_prefill alone (rdx_rope_kv_test): qkv [B, T, qkv_ld], pos_ids int [B, T], cos / sin [max_pos, 128], caches [B, heads, max_len, 128].

@@ -57,7 +57,8 @@ class _BaseModel:
 
 class LlamaForCausalLM:
     def __init__(self, cfg: Optional[LlamaCfg] = None, dtype: str = "bf16", max_batch: int = 12, max_len: int = 1024,
-                 lora: bool = True, device: int = 0, weights_fp8: bool = False, weights_w4: bool = False):
+                 lora: bool = True, device: int = 0, weights_fp8: bool = False, weights_w4: bool = False,
+                 kv_fp8: bool = False):
         self.lcfg = cfg or LlamaCfg()
         self.config = SimpleNamespace(hidden_size=self.lcfg.hidden, vocab_size=self.lcfg.vocab,
                                       num_hidden_layers=self.lcfg.layers, pad_token_id=0, eos_token_id=2)
@@ -73,6 +74,9 @@ class LlamaForCausalLM:
         self.weights_fp8 = bool(weights_fp8)
         # int4 group-quantised projections (RdxEngine(weights_w4=True), radialog_amd/w4.py): `from_pretrained(..., weights_w4=True)`, next to weights_fp8
         self.weights_w4 = bool(weights_w4)
+        # the KV cache as e4m3 codes + one power-of-two exponent per row (RdxEngine(kv_fp8=True), radialog_amd/kv8.py): `from_pretrained(..., kv_fp8=True)`.
+        # Greedy / sampled generate and scoring only: beams, reuse_prefix_kv and generate_many are not built on it
+        self.kv_fp8 = bool(kv_fp8)
         self.device = torch.device("cuda", device)
         self._engine = None
         self._state = None            # reference-named tensors (dict, stored dtype); with _synthetic they overlay the random-init generator
@@ -166,7 +170,7 @@ class LlamaForCausalLM:
         from .engine import RdxEngine, synth_getter
         cfg = RaDialogCfg(llama=self.lcfg)
         eng = RdxEngine(cfg, dtype=self.dtype, device=self.device.index or 0, max_batch=self.max_batch, max_len=self.max_len,
-                        lora=self.lora, vision=False, llama=True, weights_fp8=self.weights_fp8, weights_w4=self.weights_w4)
+                        lora=self.lora, vision=False, llama=True, weights_fp8=self.weights_fp8, weights_w4=self.weights_w4, kv_fp8=self.kv_fp8)
         if self._state is None and not self._synthetic:
             eng.close()
             raise RuntimeError("LlamaForCausalLM has no weights: build it with from_pretrained(local_dir) or from_pretrained(synthetic=True)")
@@ -239,6 +243,10 @@ class LlamaForCausalLM:
         if rules.active and num_beams > 1:
             raise ValueError("repetition_penalty / no_repeat_ngram_size / min_new_tokens apply to greedy search only (num_beams=1): beam search "
                              "under logits rules is not built")
+        if self.kv_fp8 and num_beams > 1:
+            raise ValueError("kv_fp8: beam search is not built on the fp8 KV cache (the beam reorder moves model-dtype rows); num_beams=1 only")
+        if self.kv_fp8 and getattr(self, "reuse_prefix_kv", False):
+            raise ValueError("kv_fp8: reuse_prefix_kv is not built on the fp8 KV cache (the kept prefix is not held in the model dtype)")
         if input_ids.dim() != 2:
             raise ValueError("You have to specify decoder_input_ids of shape [batch, seq]")
         B, T = input_ids.shape
@@ -283,6 +291,8 @@ class LlamaForCausalLM:
         sequence per prompt, in order: the prompt, then what was generated up to and including EOS or up to the prompt's max_new_tokens.
         Greedy search only: num_beams > 1, do_sample and active logits rules raise ValueError."""
         from .engine import LogitsRules, QUEUE_STAGE
+        if self.kv_fp8:
+            raise ValueError("kv_fp8: generate_many is not built on the fp8 KV cache (a row session moves model-dtype cache rows)")
         if num_beams != 1:
             raise ValueError("generate_many runs greedy search only (num_beams=1): beams in a row session are not built")
         if do_sample:

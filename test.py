@@ -66,6 +66,8 @@ def main(argv=None):
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     p.add_argument("--synthetic", action="store_true", help="deterministic random-init weights (no checkpoints reachable offline)")
     p.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: decoder GEMMs in OCP e4m3 on the fp8 MFMA (weights_fp8=True)")
+    p.add_argument("--kv_fp8", action="store_true", help="the decoder's KV cache as e4m3 codes + one exponent byte per row (kv_fp8=True): half the cache bytes; "
+                   "greedy / sampled search only (no --num_beams > 1, no --queue_rows)")
     p.add_argument("--queue_rows", type=int, default=0, help="report loop through a queue (generate_many): this many rows decode at a time and a finished "
                    "row takes the next waiting prompt (0 = off: the batched loop; greedy search only)")
     p.add_argument("--do_corr", action="store_true", help="automatic prompt correction on top of the reports (test.py:437-500)")
@@ -90,6 +92,8 @@ def main(argv=None):
     except ValueError as e:
         p.error(str(e))
     beams = max(args.num_beams, 1)
+    if args.kv_fp8 and (beams > 1 or args.queue_rows > 0):
+        p.error("--kv_fp8 runs greedy / sampled search only: beam search and the row queue are not built on the fp8 KV cache")
     queue_stage = 0
     if args.queue_rows > 0:
         if beams > 1 or args.do_sample or args.repetition_penalty != 1.0 or args.no_repeat_ngram_size or args.min_new_tokens:
@@ -100,7 +104,7 @@ def main(argv=None):
             p.error(f"--queue_rows {args.queue_rows} + {queue_stage} staging rows exceed the engine's rows")
         max_batch = max(max_batch, args.queue_rows + queue_stage)
     lang_model = LlamaForCausalLM.from_pretrained(args.vicuna, torch_dtype=dt, device_map="auto", max_batch=max_batch,
-                                                  max_len=1024, device=local, synthetic=args.synthetic, weights_fp8=args.fp8)
+                                                  max_len=1024, device=local, synthetic=args.synthetic, weights_fp8=args.fp8, kv_fp8=args.kv_fp8)
     if args.lora_model:
         lang_model = PeftModelForCausalLM.from_pretrained(lang_model, args.lora_model, torch_dtype=dt, use_ram_optimized_load=False).half()
     lang_model.eval()

@@ -2,7 +2,8 @@
 """Decode-step time per batch size (README's batch table, VERDICT r4 "next" 4): Vicuna-7B shapes, bf16 (or --dtype f16), prompt 160 tokens,
 (a) the hipGraph step replayed at context ~168 (rdx_time unit 0), (b) the mean step of a 256-token greedy decode (contexts 160 .. 415, what
 bench.py averages), with the HBM fraction (weights + KV of SURVEY 8d over 8 TB/s). `--ab` repeats every batch with the one-row-tile family
-off (rdx_set_option xs16 0: the 32-row kernels of xstat32.hip). python tools/step_time.py [--batches 1,2,4,8,12,16,32] [--ab] [--fp8 | --w4]
+off (rdx_set_option xs16 0: the 32-row kernels of xstat32.hip). python tools/step_time.py [--batches 1,2,4,8,12,16,32] [--ab] [--fp8 | --w4] [--kv8]
+(--kv8: the fp8 KV cache, RdxEngine(kv_fp8=True); the HBM fraction then prices KV at 1 + 1/128 bytes per element instead of 2, and 1-2 rows run the generic family)
 (--w4: int4 group-quantised projections, RdxEngine(weights_w4=True); the HBM fraction then prices the int4 units at 4.125 bits at 1-16 rows, o_proj and the lm_head at 16, and everything at 16 from 17 rows)."""
 import argparse
 import os
@@ -25,6 +26,7 @@ def main():
     ap.add_argument("--ab", action="store_true")
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--w4", action="store_true")
+    ap.add_argument("--kv8", action="store_true")
     ap.add_argument("--new", type=int, default=256)
     a = ap.parse_args()
     cfg = full_cfg()
@@ -37,7 +39,7 @@ def main():
     print(f"| batch | family | step at ctx {T + 8} (ms) | mean step over {N} tokens (ms) | HBM frac (weights + KV) | prefill ms |")
     print("|---|---|---|---|---|---|")
     for B in [int(x) for x in a.batches.split(",")]:
-        eng = RdxEngine(cfg, dtype=a.dtype, device=0, max_batch=B, max_len=(T + N + 64 + 31) // 32 * 32, lora=True, vision=False, weights_fp8=a.fp8, weights_w4=a.w4)
+        eng = RdxEngine(cfg, dtype=a.dtype, device=0, max_batch=B, max_len=(T + N + 64 + 31) // 32 * 32, lora=True, vision=False, weights_fp8=a.fp8, weights_w4=a.w4, kv_fp8=a.kv8)
         eng.load_weights(synth_getter(cfg, eng.device, lora=True), vision=False)
         ids = synth.synth_prompt_ids(B, T, vocab=lc.vocab, pad_rows=(B > 1), seed=7).to(eng.device)
         qf = synth.synth("t.qf_step", (B, 32, lc.qformer_dim), -1.0, 1.0).to(eng.device)
@@ -58,10 +60,11 @@ def main():
                 toks, _, n = eng.generate(ids, qf, max_new=N, eos_id=-1, pad_id=0)
             torch.cuda.synchronize()
             avg = ((time.perf_counter() - t0) / 2 - pre) / (N - 1) * 1e3
-            kv = B * (T + N / 2.0) * 524288 + B * 524288
+            kv_pos = 524288 * ((1 + 1 / 128) / 2 if a.kv8 else 1)         # bytes of one cached position of one row: K and V, 32 layers x 4096 elements
+            kv = B * (T + N / 2.0) * kv_pos + B * kv_pos
             wb = wb4 if (a.w4 and B <= 16 and (fam or B <= 2)) else wb16
             frac = (wb + kv) / (avg * 1e-3) / 1e9 / bench.HBM_PEAK_GBS
-            name = ("fp8 x fp8: " if a.fp8 else "int4: " if a.w4 else "") + ("xs16 (5 launches / layer)" if (fam and not a.fp8 and 3 <= B <= 16) else "chained (3 / layer)" if B <= 2 else
+            name = ("kv8, " if a.kv8 else "") + ("fp8 x fp8: " if a.fp8 else "int4: " if a.w4 else "") + ("xs16 (5 launches / layer)" if (fam and not a.fp8 and 3 <= B <= 16) else "generic (GEMV, 5 / layer)" if (B <= 2 and a.kv8) else "chained (3 / layer)" if B <= 2 else
                     "row blocks (33-128 rows, 7 / layer)" if B > 32 else "xstat32 (7 launches / layer)")
             print(f"| {B} | {name} | {step:.3f} | {avg:.3f} | {frac * 100:.1f} % | {pre * 1e3:.1f} |", flush=True)
         eng.close()
