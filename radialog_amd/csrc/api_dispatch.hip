@@ -25,25 +25,6 @@ void run_decode_attention(rdx_ctx* c, const DecAttnArgs& at, int layer, int B) {
     else launch_decode_attention(c->cfg.dtype, at, B, c->stream);
 }
 
-AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer, int row0) {
-    const rdx_config& f = c->cfg;
-    const int H = f.hidden;
-    AttnArgs at;
-    memset(&at, 0, sizeof(at));
-    at.Q = c->pq; at.q_bs = (long)T * H; at.q_ts = H; at.q_hs = 128;
-    at.K = kv_ptr(c, c->kcache, layer); at.V = kv_ptr(c, c->vcache, layer);
-    at.key_mask = c->key_mask;
-    if (row0) {
-        const size_t kv_row = (size_t)row0 * f.heads * f.max_len * 128 * 2;
-        at.K = (const char*)at.K + kv_row; at.V = (const char*)at.V + kv_row; at.key_mask = c->key_mask + (size_t)row0 * f.max_len;
-    }
-    at.k_bs = at.v_bs = (long)f.heads * f.max_len * 128; at.k_ts = at.v_ts = 128; at.k_hs = at.v_hs = (long)f.max_len * 128;
-    at.O = c->patt; at.o_bs = (long)T * H; at.o_ts = H; at.o_hs = 128;
-    at.B = B; at.H = f.heads; at.Tq = T; at.Tk = keep + T; at.causal = 1; at.k_perm = c->ld.k_perm; at.km_bs = f.max_len;
-    at.flash_min = c->flash_min;
-    return at;
-}
-
 GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     const rdx_config& f = c->cfg;
     const int H = f.hidden;
@@ -133,6 +114,95 @@ DecFamily decode_family(rdx_ctx* c, int B) {
     if (c->chain_mlp && c->fuse_attn_oproj && chain_supported(c->ld, c->cfg.inter, B) && attn_oproj16_supported(c->ld, c->cfg.hidden, c->cfg.hidden, B))
         return DEC_CHAINED;
     return xs16_ok(c, B) ? DEC_XS16 : DEC_GENERIC;
+}
+
+// ---- the prompt's units (rdx_ctx.h): the family is decided once, every unit's arguments come from one builder in that family's layout ----
+PromptPlan prompt_plan(rdx_ctx* c, int B, int T) {
+    PromptPlan p;
+    p.family = PROMPT_ROWS; p.M = B * T; p.mtiles = (p.M + 15) / 16; p.blk = p.down_split = false;
+    const LlamaLayer* L = &c->ll[0];
+    if (fp8_weights(L->wqkv)) { p.family = PROMPT_FP8; return p; }
+    // few rows (one or two prompts): the projections are weight-stream bound -> weight-stationary kernels over fragment-packed
+    // activations (wstat.hip); the producers (RMSNorm, attention, the SwiGLU epilogue) write that order directly
+    constexpr int ws_maxm = 384;
+    // measured (tools/prefill_only.py, 32 layers): wstat's time grows with the row tiles of 16, the 128-row tile GEMMs' with the row tiles of 128 --
+    // M = 64: 4.84 vs 5.34 ms, 100: 6.06 / 6.26, 160: 7.30 / 7.64, 320: 11.43 / 11.92, but 250: 9.56 / 8.86. Take wstat when the 128-row
+    // tiling would pad by 24 rows or more.
+    constexpr int ws_minpad = 24;
+    if (p.M <= 32 || p.M > ws_maxm || (p.M + 127) / 128 * 128 - p.M < ws_minpad) return p;
+    p.family = PROMPT_TILES;
+    const GemmArgs qkv = prompt_unit(c, p, L, UNIT_QKV), down = prompt_unit(c, p, L, UNIT_DOWN);
+    if (!wstat_supported(qkv, EPI_NONE) || !wstat_supported(down, EPI_RESID)) { p.family = PROMPT_ROWS; return p; }
+    // up to 192 rows the K = 4096 projections run activation-stationary in row blocks of 32 whose workgroups share an XCD's L2
+    // (xstat32_k<.., BLK>: the weights cross each CU once per row block instead of the activations once per 32 columns); down_proj
+    // (K = 11008) and longer prompts keep the weight-stationary kernel
+    p.blk = c->prompt_blk && xstat_blk_supported(qkv, EPI_NONE) && xstat_blk_supported(prompt_unit(c, p, L, UNIT_O), EPI_RESID) &&
+            xstat_blk_supported(prompt_unit(c, p, L, UNIT_GATE_UP), EPI_SILU_MUL);
+    // down_proj of a prompt of <= 128 rows (<= 4 row blocks: 160 rows measured 55.9 us against wstat_k 49.5; 64 rows 3.96 -> 3.69 ms per prefill) K-split over
+    // 4 workgroups per tile into fp32 slabs (xsplit32_k<.., BLK>), combined (+ residual) by the next layer's RMSNorm -- after the last layer by one more norm
+    // launch whose packed output nobody reads
+    p.down_split = c->prompt_blk && p.M <= 128 && xsplit_blk_supported(down);
+    return p;
+}
+
+GemmArgs prompt_unit(rdx_ctx* c, const PromptPlan& p, const LlamaLayer* L, DecUnit u) {
+    const rdx_config& f = c->cfg;
+    const int H = f.hidden;
+    const GemmW& W = u == UNIT_QKV ? L->wqkv : u == UNIT_O ? L->wo : u == UNIT_GATE_UP ? L->wgu : L->wdown;
+    GemmArgs a;
+    switch (u) {
+    case UNIT_QKV: a = gargs(c->pxn, H, W, nullptr, c->pqkv, c->ld.qkv_ld, p.M); a.N = W.Npad; break;
+    case UNIT_O: a = gargs(c->patt, H, W, nullptr, c->px, H, p.M); a.resid = c->px; a.ldr = H; break;
+    case UNIT_GATE_UP: a = gargs(c->pxn, H, W, nullptr, c->pgu, f.inter, p.M); break;
+    default: a = gargs(c->pgu, f.inter, W, nullptr, c->px, H, p.M); a.resid = c->px; a.ldr = H;
+    }
+    switch (p.family) {
+    case PROMPT_ROWS: break;
+    case PROMPT_TILES: a.xpacked = ACT_TILES32; a.mtiles = p.mtiles; a.out_packed = u == UNIT_GATE_UP ? ACT_TILES32 : ACT_ROWS; break;
+    case PROMPT_FP8:        // gemm8 over the e4m3 rows in pxq and whole weight tiles; the rows' scales: 1 K group behind an RMSNorm, 2 for o_proj, 4 for down_proj
+        a.X = c->pxq; a.N = W.Npad; a.xscale = c->pxs; a.xgroups = u == UNIT_O ? 2 : u == UNIT_DOWN ? 4 : 1; a.ldr = H;
+    }
+    return a;
+}
+
+void prompt_norm(rdx_ctx* c, const PromptPlan& p, const void* w, int pend) {
+    const bool fp8 = p.family == PROMPT_FP8;        // quantised to e4m3 in the norm's epilogue
+    run_rmsnorm(c, NormArgs{c->px, w, fp8 ? c->pxq : c->pxn, c->pxs, p.M, c->cfg.hidden, c->cfg.rms_eps,
+                            fp8 ? ACT_ROWS_E4M3 : p.family == PROMPT_TILES ? ACT_TILES32 : ACT_ROWS, fp8 ? 0 : p.mtiles, pend ? c->pslab : nullptr, pend});
+}
+
+void prompt_attention(rdx_ctx* c, const PromptPlan& p, int l, int B, int T, int keep, int row0) {
+    const rdx_config& f = c->cfg;
+    const LlamaLayer& L = c->ll[l];
+    const int H = f.hidden;
+    hipStream_t s = c->stream;
+    // where the layer's new K / V rows land (behind the kept slots) and what the attention reads: cache rows row0 .. of layer l ...
+    LlamaDims d = c->ld;
+    void *K = nullptr, *V = nullptr;
+    if (!c->kv_fp8) {
+        const size_t kv_row = (size_t)row0 * f.heads * f.max_len * 128 * 2;
+        K = (char*)kv_ptr(c, c->kcache, l) + kv_row; V = (char*)kv_ptr(c, c->vcache, l) + kv_row;
+    } else {
+        // ... fp8 KV cache: the one-layer staging buffer in the model dtype ([B][heads][ceil16(T)][128], row-major K), which is what the prompt's own attention
+        // reads -- unquantised, so the prompt computes what a plain context computes -- and which is then quantised into the cache. Both kernels run unchanged
+        // on dims and strides that describe the staging buffer. keep == 0 and row0 == 0 (prompt_refuse).
+        K = c->kv_kstage; V = c->kv_vstage;
+        d.max_len = (T + 15) / 16 * 16; d.k_perm = 0;
+    }
+    launch_rope_kv_prefill(f.dtype, d, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq, K, V, B, T, keep, s);
+    AttnArgs at;
+    memset(&at, 0, sizeof(at));
+    at.Q = c->pq; at.q_bs = (long)T * H; at.q_ts = H; at.q_hs = 128;
+    at.K = K; at.V = V; at.key_mask = c->key_mask + (size_t)row0 * f.max_len;
+    at.k_bs = at.v_bs = (long)f.heads * d.max_len * 128; at.k_ts = at.v_ts = 128; at.k_hs = at.v_hs = (long)d.max_len * 128;
+    at.O = c->patt; at.o_bs = (long)T * H; at.o_ts = H; at.o_hs = 128;
+    at.B = B; at.H = f.heads; at.Tq = T; at.Tk = keep + T; at.causal = 1; at.k_perm = d.k_perm; at.km_bs = f.max_len;
+    at.flash_min = c->flash_min;
+    at.o_packed_mt = p.family == PROMPT_TILES ? p.mtiles : 0;
+    launch_attention(f.dtype, 128, at, s);
+    if (c->kv_fp8)
+        launch_kv8_quant_rows(f.dtype, K, V, d.max_len, kv_ptr(c, c->kcache, l), kvx_ptr(c, c->kexp, l), kv_ptr(c, c->vcache, l), kvx_ptr(c, c->vexp, l),
+                              (size_t)B * f.heads, f.max_len, T, 0, s);
 }
 
 // Skinny GEMM with an optional fused RMSNorm: fused when the activations fit the GEMV's LDS stage; otherwise the RMSNorm runs as its own launch

@@ -138,7 +138,123 @@ static int rules_need_prefill(rdx_ctx* c, const char* who) {
     return 0;
 }
 
-static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep, int pad_id, bool hist, int row0 = 0);
+// ---- the prompt: one layer loop per kernel family (prompt_plan), every unit's arguments from the builders of api_dispatch.hip ----
+// What the prompt path refuses, decided from the arguments and the context alone. Its entry points ask before their first effect: before the workspace
+// grows, before cur_* / hist_ready change and before the first launch, so that a refused call leaves the conversation it would have replaced as it was.
+static int prompt_refuse(rdx_ctx* c, int B, int keep, int row0) {
+    if (c->kv_fp8 && (keep > 0 || row0 > 0)) return fail(c, -1, "the prompt path on the fp8 KV cache (kv_fp8) starts at slot 0 of row 0");
+    if (B > 32 && !blk64_ok(c, B)) return fail(c, -8, "rdx_prefill: more than 32 rows per context need the Vicuna-7B widths (hidden 4096, inter 11008: the row-block decode family)");
+    return 0;
+}
+
+// row-major rows: the <= 32-row kernels or the 128-row tile GEMMs, run_gemm picks per projection
+static void prompt_rows(rdx_ctx* c, const PromptPlan& p, int B, int T, int keep, int row0) {
+    for (int l = 0; l < c->cfg.layers; ++l) {
+        const LlamaLayer* L = &c->ll[l];
+        prompt_norm(c, p, L->attn_norm, 0);
+        run_gemm(c, prompt_unit(c, p, L, UNIT_QKV), EPI_NONE);
+        prompt_attention(c, p, l, B, T, keep, row0);
+        run_gemm(c, prompt_unit(c, p, L, UNIT_O), EPI_RESID);
+        prompt_norm(c, p, L->mlp_norm, 0);
+        run_gemm(c, prompt_unit(c, p, L, UNIT_GATE_UP), EPI_SILU_MUL);
+        run_gemm(c, prompt_unit(c, p, L, UNIT_DOWN), EPI_RESID);
+    }
+}
+
+// one or two prompts (33-384 rows) on fragment-packed row tiles: the norms, the attention and the SwiGLU epilogue write the order the projections read
+static void prompt_tiles(rdx_ctx* c, const PromptPlan& p, int B, int T, int keep, int row0) {
+    const int dt = c->cfg.dtype;
+    hipStream_t s = c->stream;
+    auto proj = [&](const GemmArgs& a, int epi) {
+        if (p.blk) launch_xstat_blk(dt, a, epi, s);
+        else launch_wstat(dt, a, epi, s);
+    };
+    int pend = 0;       // slab groups a K-split down_proj left for the next RMSNorm
+    for (int l = 0; l < c->cfg.layers; ++l) {
+        const LlamaLayer* L = &c->ll[l];
+        prompt_norm(c, p, L->attn_norm, pend);
+        pend = 0;
+        proj(prompt_unit(c, p, L, UNIT_QKV), EPI_NONE);
+        prompt_attention(c, p, l, B, T, keep, row0);
+        proj(prompt_unit(c, p, L, UNIT_O), EPI_RESID);
+        prompt_norm(c, p, L->mlp_norm, 0);
+        proj(prompt_unit(c, p, L, UNIT_GATE_UP), EPI_SILU_MUL);
+        const GemmArgs d = prompt_unit(c, p, L, UNIT_DOWN);
+        if (p.down_split) { launch_xsplit_blk(dt, d, c->pslab, s); pend = 4; }
+        else launch_wstat(dt, d, EPI_RESID, s);
+    }
+    if (pend) prompt_norm(c, p, c->ll[0].attn_norm, pend);       // its packed output is read by nobody
+}
+
+// fp8 weights (BASELINE configs[4]): every projection of the prompt is an fp8 x fp8 MFMA GEMM (gemm8.hip) over e4m3 activations with one scale per row and
+// K group -- quantised in the RMSNorm's epilogue, or by quant_rows_k on the attention / SwiGLU output; LoRA-B, RoPE, attention, SwiGLU and the residual adds
+// stay in the model dtype
+static void prompt_fp8(rdx_ctx* c, const PromptPlan& p, int B, int T, int keep, int row0) {
+    const rdx_config& f = c->cfg;
+    const int dt = f.dtype;
+    hipStream_t s = c->stream;
+    auto gemm8 = [&](const GemmArgs& a, int epi) {
+        if (gemm8_supported(a, epi)) launch_gemm8(dt, a, epi, s);
+        else c->unsupported = "fp8 weights: prefill projection shape not supported by gemm8 (N % 16, K % 64)";
+    };
+    for (int l = 0; l < f.layers; ++l) {
+        const LlamaLayer* L = &c->ll[l];
+        prompt_norm(c, p, L->attn_norm, 0);
+        gemm8(prompt_unit(c, p, L, UNIT_QKV), EPI_NONE);
+        prompt_attention(c, p, l, B, T, keep, row0);
+        const GemmArgs o = prompt_unit(c, p, L, UNIT_O);
+        launch_quant_rows(dt, c->patt, f.hidden, c->pxq, c->pxs, p.M, f.hidden, o.xgroups, s);
+        gemm8(o, EPI_RESID);
+        prompt_norm(c, p, L->mlp_norm, 0);
+        gemm8(prompt_unit(c, p, L, UNIT_GATE_UP), EPI_SILU_MUL);
+        const GemmArgs d = prompt_unit(c, p, L, UNIT_DOWN);
+        launch_quant_rows(dt, c->pgu, f.inter, c->pxq, c->pxs, p.M, f.inter, d.xgroups, s);
+        gemm8(d, EPI_RESID);
+    }
+}
+
+// The prompt through every layer: the residual stream of all B x T positions ends in c->px (row-major [B T][hidden]), K / V in the cache behind `keep` kept
+// slots (keep > 0: `T` further tokens of a cached conversation, no image splice), the per-row decode state (d_pos / d_slot / d_step / d_unf, the key mask) is
+// that of a prompt of T tokens. What the callers do with px is theirs: the prefill gathers the last row of each prompt for token 0, the scoring pass the rows
+// whose successor is scored. The callers have asked prompt_refuse and sized the workspace (ensure_prefill_ws) for B x T rows. hist: start the token history
+// of the logits rules from `ids`.
+// row0 (a row session's refill; keep == 0, no history): the B prompts fill rows row0 .. row0 + B - 1 of the KV cache, the key mask and the decode state; the
+// workspaces (px .., the splice rows, img_pos / pos_ids) are prompt-local and stay at base 0. The launches are those of row0 == 0.
+static void prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep, int pad_id, bool hist, int row0 = 0) {
+    const rdx_config& f = c->cfg;
+    const int dt = f.dtype, H = f.hidden;
+    hipStream_t s = c->stream;
+    if (keep > 0) {
+        launch_prep_append(B, T, keep, c->d_img_pos, c->d_pos_ids, c->d_pos, c->d_slot, c->d_step, c->d_unf, s);
+        qformer_embs = nullptr;
+    } else {
+        launch_prep_prompt(ids, mask, B, T, 32000, pad_id, c->d_img_pos, c->d_pos_ids, c->key_mask + (size_t)row0 * f.max_len, f.max_len, c->d_pos + row0,
+                           c->d_slot + row0, c->d_step + row0, c->d_unf + row0, s);
+    }
+    c->hist_ready = hist;
+    if (hist) launch_hist_init(ids, B, T, c->d_hist, c->d_hist_len, f.max_len, s);
+    if (qformer_embs) {
+        // a8: img_proj_layer on the model-dtype copy of the Q-Former output (".half()", modeling_llama_imgemb.py:576-579)
+        launch_from_f32(dt, qformer_embs, c->pqe, (size_t)B * 32 * f.qformer_dim, s);
+        run_gemm(c, gargs(c->pqe, f.qformer_dim, c->img_proj_w, c->img_proj_b, c->pimg, H, B * 32), EPI_NONE);
+    }
+    launch_embed_splice(dt, ids, c->d_img_pos, c->embed, f.vocab, c->pimg, 32, c->px, B, T, H, qformer_embs ? 1 : 0, s);
+    const PromptPlan p = prompt_plan(c, B, T);
+    switch (p.family) {
+    case PROMPT_ROWS: prompt_rows(c, p, B, T, keep, row0); break;
+    case PROMPT_TILES: prompt_tiles(c, p, B, T, keep, row0); break;
+    case PROMPT_FP8: prompt_fp8(c, p, B, T, keep, row0); break;
+    }
+}
+
+// token 0 of B prompts whose layers have run: the last row of each (datt doubles as the [B][H] last-position buffer) through the lm_head and the selection
+// (row0 / tokens: lm_head_and_greedy)
+static int prompt_token0(rdx_ctx* c, int B, int T, void* logits, int row0 = 0, int32_t* tokens = nullptr) {
+    launch_gather_last(c->cfg.dtype, c->px, c->datt, B, T, c->cfg.hidden, c->stream);
+    lm_head_and_greedy(c, c->datt, B, logits, nullptr, 0, /*advance=*/0, row0, tokens);
+    HIPCHK(c, hipGetLastError());
+    return take_unsupported(c);
+}
 
 // keep == 0: a fresh prompt. keep > 0: `T` further prompt tokens behind the first `keep` cache slots of the previous call(s)
 // (the shared prefix of a multi-turn conversation is not recomputed; no image splice in the continuation).
@@ -152,6 +268,7 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
     if (T <= 0 || keep + T + max_new > f.max_len) return fail(c, -1, "rdx_prefill: T (%d) + max_new (%d) exceeds max_len %d", keep + T, max_new, f.max_len);
     if (keep + T + max_new > f.max_pos) return fail(c, -1, "rdx_prefill: sequence exceeds max_position_embeddings %d", f.max_pos);
     if (qformer_embs && T < 32) return fail(c, -1, "rdx_prefill: image splice needs T >= 32");
+    if (int prc = prompt_refuse(c, B, keep, 0)) return prc;
     HIPCHK(c, hipSetDevice(c->device));
     if (keep > 0) {
         if (B != c->cur_B) return fail(c, -1, "rdx_prefill_append: batch %d differs from the cached conversation's %d", B, c->cur_B);
@@ -165,161 +282,16 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
     if (rc) return rc;
     c->cur_B = B; c->cur_T = keep + T; c->cur_max_new = max_new; c->cur_eos = eos_id; c->cur_pad = pad_id; c->cur_tokens = out_tokens;
     c->cur_steps = 1;
-    rc = prompt_layers(c, ids, mask, B, T, qformer_embs, keep, pad_id, c->rules_on);
-    if (rc) return rc;
-    launch_gather_last(f.dtype, c->px, c->datt, B, T, f.hidden, c->stream);      // datt doubles as the [B][H] last-position buffer
-    lm_head_and_greedy(c, c->datt, B, logits, nullptr, 0, /*advance=*/0);
-    HIPCHK(c, hipGetLastError());
-    return take_unsupported(c);
-}
-
-// The prompt through every layer: the residual stream of all B x T positions ends in c->px (row-major [B T][hidden]), K / V in the cache behind `keep` kept
-// slots, the per-row decode state (d_pos / d_slot / d_step / d_unf, the key mask) is that of a prompt of T tokens. What the callers do with px is theirs: the
-// prefill gathers the last row of each prompt for token 0, the scoring pass the rows whose successor is scored. The workspace (ensure_prefill_ws) holds B x T
-// rows. hist: start the token history of the logits rules from `ids`.
-// row0 (a row session's refill; keep == 0, no history): the B prompts fill rows row0 .. row0 + B - 1 of the KV cache, the key mask and the decode state; the
-// workspaces (px .., the splice rows, img_pos / pos_ids) are prompt-local and stay at base 0. The launches are those of row0 == 0.
-static int prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep, int pad_id, bool hist, int row0) {
-    const rdx_config& f = c->cfg;
-    const size_t M = (size_t)B * T;
-    const int dt = f.dtype, H = f.hidden;
-    hipStream_t s = c->stream;
-
-    if (keep > 0) {
-        launch_prep_append(B, T, keep, c->d_img_pos, c->d_pos_ids, c->d_pos, c->d_slot, c->d_step, c->d_unf, s);
-        qformer_embs = nullptr;
-    } else {
-        launch_prep_prompt(ids, mask, B, T, 32000, pad_id, c->d_img_pos, c->d_pos_ids, c->key_mask + (size_t)row0 * f.max_len, f.max_len, c->d_pos + row0,
-                           c->d_slot + row0, c->d_step + row0, c->d_unf + row0, s);
-    }
-    c->hist_ready = hist;
-    if (hist) launch_hist_init(ids, B, T, c->d_hist, c->d_hist_len, f.max_len, s);
-    if (qformer_embs) {
-        // a8: img_proj_layer on the model-dtype copy of the Q-Former output (".half()", modeling_llama_imgemb.py:576-579)
-        launch_from_f32(dt, qformer_embs, c->pqe, (size_t)B * 32 * f.qformer_dim, s);
-        GemmArgs a = gargs(c->pqe, f.qformer_dim, c->img_proj_w, c->img_proj_b, c->pimg, H, B * 32);
-        run_gemm(c, a, EPI_NONE);
-    }
-    launch_embed_splice(dt, ids, c->d_img_pos, c->embed, f.vocab, c->pimg, 32, c->px, B, T, H, qformer_embs ? 1 : 0, s);
-
-    const bool fp8 = fp8_weights(c->ll[0].wqkv);
-    const size_t kv_row = (size_t)row0 * f.heads * f.max_len * 128 * 2;        // bytes of row0 cache rows of one layer
-    // fp8 KV cache: the prompt's K / V rows of a layer go to the one-layer staging buffer in the model dtype ([B][heads][ceil16(T)][128], row-major K), which
-    // is what the prompt's own attention reads -- unquantised, so the prompt computes what a plain context computes -- and are then quantised into the cache.
-    // Both kernels run unchanged on dims and strides that describe the staging buffer. keep == 0 and row0 == 0 (the append calls and row sessions refuse).
-    const bool kv8 = c->kv_fp8;
-    const int stage_len = (T + 15) / 16 * 16;
-    LlamaDims sd = c->ld;
-    sd.max_len = stage_len; sd.k_perm = 0;
-    auto stage_attn = [&](AttnArgs at) {
-        at.K = c->kv_kstage; at.V = c->kv_vstage; at.k_perm = 0;
-        at.k_bs = at.v_bs = (long)f.heads * stage_len * 128; at.k_hs = at.v_hs = (long)stage_len * 128;
-        return at;
-    };
-    auto quant_stage = [&](int l) {
-        launch_kv8_quant_rows(dt, c->kv_kstage, c->kv_vstage, stage_len, kv_ptr(c, c->kcache, l), kvx_ptr(c, c->kexp, l), kv_ptr(c, c->vcache, l),
-                              kvx_ptr(c, c->vexp, l), (size_t)B * f.heads, f.max_len, T, 0, s);
-    };
-    if (kv8 && (keep > 0 || row0 > 0)) return fail(c, -1, "the prompt path on the fp8 KV cache (kv_fp8) starts at slot 0 of row 0");
-    // the RMSNorm of the residual stream px in the layout the projection behind it reads; `pend` slab groups of a K-split down_proj are folded in first
-    auto prompt_norm = [&](const void* w, void* out, ActLayout layout, int mtiles, int pend) {
-        run_rmsnorm(c, NormArgs{c->px, w, out, c->pxs, (int)M, H, f.rms_eps, layout, mtiles, pend ? c->pslab : nullptr, pend});
-    };
-    if (B > 32 && !blk64_ok(c, B)) return fail(c, -8, "rdx_prefill: more than 32 rows per context need the Vicuna-7B widths (hidden 4096, inter 11008: the row-block decode family)");
-    if (fp8) {
-        // fp8 weights (BASELINE configs[4]): every projection of the prompt is an fp8 x fp8 MFMA GEMM (gemm8.hip) over e4m3 activations with one
-        // scale per row and K group -- 1 group behind an RMSNorm (quantised in its epilogue), 2 for o_proj, 4 for down_proj (quant_rows_k on the
-        // attention / SwiGLU output); LoRA-B, RoPE, attention, SwiGLU and the residual adds stay in the model dtype
-        for (int l = 0; l < f.layers; ++l) {
-            const LlamaLayer& L = c->ll[l];
-            void* kc = (char*)kv_ptr(c, c->kcache, l) + kv_row;
-            void* vc = (char*)kv_ptr(c, c->vcache, l) + kv_row;
-            auto g8 = [&](const GemmW& W, int K, int groups, void* out, int ldo, const void* resid, int epi) {
-                GemmArgs a = gargs(c->pxq, K, W, nullptr, out, ldo, (int)M);
-                a.N = W.Npad; a.xscale = c->pxs; a.xgroups = groups; a.resid = resid; a.ldr = H;
-                if (!gemm8_supported(a, epi)) { c->unsupported = "fp8 weights: prefill projection shape not supported by gemm8 (N % 16, K % 64)"; return; }
-                launch_gemm8(dt, a, epi, s);
-            };
-            prompt_norm(L.attn_norm, c->pxq, ACT_ROWS_E4M3, 0, 0);
-            g8(L.wqkv, H, 1, c->pqkv, c->ld.qkv_ld, nullptr, EPI_NONE);
-            launch_rope_kv_prefill(dt, kv8 ? sd : c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq, kv8 ? c->kv_kstage : kc,
-                                   kv8 ? c->kv_vstage : vc, B, T, keep, s);
-            const AttnArgs at = prefill_attn_args(c, B, T, keep, l, row0);
-            launch_attention(dt, 128, kv8 ? stage_attn(at) : at, s);
-            if (kv8) quant_stage(l);
-            launch_quant_rows(dt, c->patt, H, c->pxq, c->pxs, (int)M, H, 2, s);
-            g8(L.wo, H, 2, c->px, H, c->px, EPI_RESID);
-            prompt_norm(L.mlp_norm, c->pxq, ACT_ROWS_E4M3, 0, 0);
-            g8(L.wgu, H, 1, c->pgu, f.inter, nullptr, EPI_SILU_MUL);
-            launch_quant_rows(dt, c->pgu, f.inter, c->pxq, c->pxs, (int)M, f.inter, 4, s);
-            g8(L.wdown, f.inter, 4, c->px, H, c->px, EPI_RESID);
-        }
-    } else {
-    // few rows (one or two prompts): the projections are weight-stream bound -> weight-stationary kernels over fragment-packed
-    // activations (wstat.hip); the producers (RMSNorm, attention, the SwiGLU epilogue) write that order directly
-    const int mtl = (int)((M + 15) / 16);
-    constexpr int ws_maxm = 384;
-    // measured (tools/prefill_only.py, 32 layers): wstat's time grows with the row tiles of 16, the 128-row tile GEMMs' with the row tiles of 128 --
-    // M = 64: 4.84 vs 5.34 ms, 100: 6.06 / 6.26, 160: 7.30 / 7.64, 320: 11.43 / 11.92, but 250: 9.56 / 8.86. Take wstat when the 128-row
-    // tiling would pad by 24 rows or more.
-    constexpr int ws_minpad = 24;
-    bool ws = (int)M > 32 && (int)M <= ws_maxm && (int)((M + 127) / 128 * 128 - M) >= ws_minpad;
-    if (ws) {
-        GemmArgs p = gargs(c->pxn, H, c->ll[0].wqkv, nullptr, c->pqkv, c->ld.qkv_ld, (int)M); p.xpacked = ACT_TILES32; p.mtiles = mtl;
-        GemmArgs d = gargs(c->pgu, f.inter, c->ll[0].wdown, nullptr, c->px, H, (int)M); d.xpacked = ACT_TILES32; d.mtiles = mtl;
-        ws = wstat_supported(p, EPI_NONE) && wstat_supported(d, EPI_RESID);
-    }
-    auto prompt_gemm = [&](GemmArgs a, int epi, bool packed_out) {
-        if (!ws) { run_gemm(c, a, epi); return; }
-        a.xpacked = ACT_TILES32; a.mtiles = mtl; a.out_packed = packed_out ? ACT_TILES32 : ACT_ROWS;
-        // round 5: up to 192 rows the K = 4096 projections run activation-stationary in row blocks of 32 whose workgroups share an XCD's L2
-        // (xstat32_k<.., BLK>: the weights cross each CU once per row block instead of the activations once per 32 columns); down_proj
-        // (K = 11008) and longer prompts keep the weight-stationary kernel
-        if (c->prompt_blk && xstat_blk_supported(a, epi)) { launch_xstat_blk(dt, a, epi, s); return; }
-        launch_wstat(dt, a, epi, s);
-    };
-    // round 5: down_proj of a prompt of <= 128 rows (<= 4 row blocks: 160 rows measured 55.9 us against wstat_k 49.5; 64 rows 3.96 -> 3.69 ms per prefill) K-split over 4 workgroups per tile into fp32 slabs (xsplit32_k<.., BLK>), combined (+ residual) by the next
-    // layer's RMSNorm -- after the last layer by one more norm launch whose packed output nobody reads
-    int pend = 0;
-    const ActLayout xl = ws ? ACT_TILES32 : ACT_ROWS;       // what the norms write and the projections read
-    for (int l = 0; l < f.layers; ++l) {
-        const LlamaLayer& L = c->ll[l];
-        void* kc = (char*)kv_ptr(c, c->kcache, l) + kv_row;
-        void* vc = (char*)kv_ptr(c, c->vcache, l) + kv_row;
-        prompt_norm(L.attn_norm, c->pxn, xl, mtl, pend);
-        pend = 0;
-        { GemmArgs a = gargs(c->pxn, H, L.wqkv, nullptr, c->pqkv, c->ld.qkv_ld, (int)M); a.N = L.wqkv.Npad; prompt_gemm(a, EPI_NONE, false); }
-        // new K/V rows land behind the kept slots
-        launch_rope_kv_prefill(dt, kv8 ? sd : c->ld, c->pqkv, L.lora_bq, L.lora_bv, c->rope_cos, c->rope_sin, c->d_pos_ids, c->pq,
-                               kv8 ? c->kv_kstage : kc, kv8 ? c->kv_vstage : vc, B, T, keep, s);
-        AttnArgs at = prefill_attn_args(c, B, T, keep, l, row0);
-        if (kv8) at = stage_attn(at);
-        at.o_packed_mt = ws ? mtl : 0;
-        launch_attention(dt, 128, at, s);
-        if (kv8) quant_stage(l);
-        { GemmArgs a = gargs(c->patt, H, L.wo, nullptr, c->px, H, (int)M); a.resid = c->px; a.ldr = H; prompt_gemm(a, EPI_RESID, false); }
-        prompt_norm(L.mlp_norm, c->pxn, xl, mtl, 0);
-        { GemmArgs a = gargs(c->pxn, H, L.wgu, nullptr, c->pgu, f.inter, (int)M); prompt_gemm(a, EPI_SILU_MUL, true); }
-        { GemmArgs a = gargs(c->pgu, f.inter, L.wdown, nullptr, c->px, H, (int)M); a.resid = c->px; a.ldr = H;
-          GemmArgs b = a; b.xpacked = ACT_TILES32; b.mtiles = mtl;
-          if (ws && c->prompt_blk && M <= 128 && xsplit_blk_supported(b)) { launch_xsplit_blk(dt, b, c->pslab, s); pend = 4; }
-          else prompt_gemm(a, EPI_RESID, false); }
-    }
-    if (pend) prompt_norm(c->ll[0].attn_norm, c->pxn, xl, mtl, pend);
-    }
-    return 0;
+    prompt_layers(c, ids, mask, B, T, qformer_embs, keep, pad_id, c->rules_on);
+    return prompt_token0(c, B, T, logits);
 }
 
 int prefill_rows_at(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int R, int T, const float* qformer_embs, int row0, int32_t* tokens, void* logits) {
-    const rdx_config& f = c->cfg;
+    if (int prc = prompt_refuse(c, R, 0, row0)) return prc;
     int rc = ensure_prefill_ws(c, (size_t)R * T);
     if (rc) return rc;
-    rc = prompt_layers(c, ids, mask, R, T, qformer_embs, 0, c->cur_pad, /*hist=*/false, row0);
-    if (rc) return rc;
-    launch_gather_last(f.dtype, c->px, c->datt, R, T, f.hidden, c->stream);
-    lm_head_and_greedy(c, c->datt, R, logits, nullptr, 0, /*advance=*/0, row0, tokens);
-    HIPCHK(c, hipGetLastError());
-    return take_unsupported(c);
+    prompt_layers(c, ids, mask, R, T, qformer_embs, 0, c->cur_pad, /*hist=*/false, row0);
+    return prompt_token0(c, R, T, logits, row0, tokens);
 }
 
 extern "C" int rdx_prefill(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs,
@@ -390,6 +362,7 @@ extern "C" int rdx_score(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
         }
     const size_t n = rows.size();
     const size_t chunk = c->score_chunk > 0 ? std::min<size_t>((size_t)c->score_chunk, n) : n;
+    if (int prc = n ? prompt_refuse(c, B, 0, 0) : 0) return prc;       // (nothing scored: no prompt runs)
     int rc = ensure_prefill_ws(c, (size_t)B * T);
     if (rc) return rc;
     if (n && (rc = ensure_score_ws(c, n, chunk))) return rc;
@@ -400,8 +373,7 @@ extern "C" int rdx_score(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
     HIPCHK(c, hipMemsetAsync(logprob, 0, (size_t)B * T * sizeof(float), s));
     if (top1) HIPCHK(c, hipMemsetAsync(top1, 0xff, (size_t)B * T * sizeof(int32_t), s));       // -1
     if (n) {
-        rc = prompt_layers(c, ids, mask, B, T, qformer_embs, 0, /*pad_id=*/0, /*hist=*/false);
-        if (rc) return rc;
+        prompt_layers(c, ids, mask, B, T, qformer_embs, 0, /*pad_id=*/0, /*hist=*/false);
         int* d_rows = c->sc_idx; int *d_tgt = d_rows + n, *d_dst = d_tgt + n, *d_ldst = d_dst + n;
         HIPCHK(c, hipMemcpyAsync(d_rows, rows.data(), n * sizeof(int), hipMemcpyHostToDevice, s));
         HIPCHK(c, hipMemcpyAsync(d_tgt, tgt.data(), n * sizeof(int), hipMemcpyHostToDevice, s));

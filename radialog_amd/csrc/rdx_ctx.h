@@ -230,7 +230,6 @@ enum DecUnit { UNIT_QKV, UNIT_O, UNIT_GATE_UP, UNIT_DOWN, UNIT_LM_HEAD };
 enum DecFamily { DEC_UNSUPPORTED, DEC_CHAINED, DEC_GENERIC, DEC_XS16, DEC_BLK, DEC_BLK8 };
 DecFamily decode_family(rdx_ctx* c, int B);
 DecAttnArgs dec_attn_args(rdx_ctx* c, int layer);                                  // decode attention; callers set out_packed / out_mt / trace
-AttnArgs prefill_attn_args(rdx_ctx* c, int B, int T, int keep, int layer, int row0 = 0);         // T prompt tokens behind `keep` cached ones; callers set o_packed_mt. row0: the B prompts are cache rows row0 ..
 // a unit in its base form: row-major activations, the RMSNorm in front of QKV / gate-up / lm_head as the kernel's prologue (norm_w), the residual of o_proj /
 // down_proj as its epilogue. L may be null for UNIT_LM_HEAD, whose callers set X (when not dx), out and out_step.
 GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);
@@ -252,6 +251,25 @@ void launch_down(rdx_ctx* c, const LlamaLayer& L, int B, bool split);
 bool blk64_ok(rdx_ctx* c, int B);      // 33-128 rows: the row-block decode family (model-dtype weights, or fp8 weights: blk64_fp8)
 bool blk64_fp8(rdx_ctx* c);            // ... its fp8 form is the one in use (e4m3 decoder weights)
 bool xs16_ok(rdx_ctx* c, int B);       // batch 3-16, model-dtype weights, hidden 4096: the step's projections on xs16.hip (no stand-alone RMSNorm, no K-split slabs)
+// ---- the prompt's units (api_dispatch.hip), the step's idea once more: the family is decided once per prompt, and what a family's layer loop (api_llama.hip)
+// launches is what the builder returned ----
+// PROMPT_FP8: fp8 weights, every projection on gemm8 over e4m3 rows. PROMPT_TILES: one or two prompts on fragment-packed row tiles of 16 (wstat_k, the row-block
+// xstat32_k, the K-split xsplit32_k). PROMPT_ROWS: everything else, row-major rows through run_gemm.
+enum PromptFamily { PROMPT_ROWS, PROMPT_TILES, PROMPT_FP8 };
+struct PromptPlan {
+    PromptFamily family;
+    int M, mtiles;       // rows = B x T, their row tiles of 16
+    bool blk;            // PROMPT_TILES: the K = 4096 projections take the row-block kernel ("prompt_blk" on and xstat_blk_supported), else wstat_k
+    bool down_split;     // PROMPT_TILES: down_proj K-split into fp32 slabs that the next RMSNorm folds in, else wstat_k
+};
+PromptPlan prompt_plan(rdx_ctx* c, int B, int T);
+// QKV, o_proj, gate/up or down_proj of layer L on the prompt buffers (px .. pgu; fp8: pxq / pxs), in the plan's family's layout
+GemmArgs prompt_unit(rdx_ctx* c, const PromptPlan& p, const LlamaLayer* L, DecUnit u);
+// the RMSNorm of the residual stream px by w, in the layout the projection behind it reads; `pend` slab groups of a K-split down_proj are folded in first
+void prompt_norm(rdx_ctx* c, const PromptPlan& p, const void* w, int pend);
+// layer l behind its QKV projection: RoPE + the K / V rows of T prompt tokens into the cache behind `keep` kept slots, rows row0 .. row0 + B - 1, then the causal
+// attention over them into patt (PROMPT_TILES: fragment-packed); an fp8 KV cache goes through its staging buffer and is quantised last
+void prompt_attention(rdx_ctx* c, const PromptPlan& p, int l, int B, int T, int keep, int row0);
 void run_gemm(rdx_ctx* c, GemmArgs a, int epi);
 void conv_gemm(rdx_ctx* c, const void* X, const GemmW& W, const float* bias, const void* resid, void* out, int B,
                int Hin, int Win, int Cin, int KH, int KW, int stride, int pad, int Hout, int Wout, int epi);
