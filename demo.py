@@ -36,6 +36,7 @@ def parse_args(argv=None):
     p.add_argument("--repetition_penalty", type=float, default=1.0, help="greedy decode: divide / multiply the logits of tokens already in the sequence (1.0 = off)")
     p.add_argument("--no_repeat_ngram_size", type=int, default=0, help="greedy decode: no n-gram of this size occurs twice (0 = off)")
     p.add_argument("--min_new_tokens", type=int, default=0, help="greedy decode: no EOS before this many generated tokens (0 = off)")
+    p.add_argument("--logprobs", type=int, default=None, metavar="N", help="print the report's mean token log-prob (and keep the N = 0 .. 8 likeliest tokens of every step)")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     p.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: decoder GEMMs in OCP e4m3 on the fp8 MFMA (weights_fp8=True)")
     p.add_argument("--kv_fp8", action="store_true", help="the decoder's KV cache as e4m3 codes + one exponent byte per row (kv_fp8=True): half the cache bytes; "
@@ -101,7 +102,7 @@ def get_response(blip_model, lang_model, tok, conv, image, findings, max_new_tok
 
 
 def main(argv=None):
-    """Runs one request; returns {"findings", "prediction", "sequences", "n_scores"} (the reference's script returns nothing; the
+    """Runs one request; returns {"findings", "prediction", "sequences", "n_scores"} and, with --logprobs, "mean_logprob" (the reference's script returns nothing; the
     return value exists so that tests/test_gpu_entrypoints.py can assert on what was printed)."""
     args = parse_args(argv)
     cfg = Config(args)
@@ -120,11 +121,18 @@ def main(argv=None):
     findings = findings or "no finding"
     pred, out = get_response(blip_model, lang_model, tok, new_conversation(), image, findings, args.max_new_tokens,
                              repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
-                             min_new_tokens=args.min_new_tokens)
+                             min_new_tokens=args.min_new_tokens,
+                             **({} if args.logprobs is None else {"output_logprobs": True, "top_logprobs": args.logprobs}))
     print(f"generated {out.sequences.shape[1]} ids, {len(out.scores)} steps")
     print("ASSISTANT:", pred[:400])
+    res = {"findings": findings, "prediction": pred, "sequences": out.sequences.cpu(), "n_scores": len(out.scores)}
+    if args.logprobs is not None:
+        from radialog_amd.engine import mean_token_logprob
+        n = out.token_logprobs.shape[1]
+        res["mean_logprob"] = float(mean_token_logprob(out.sequences[:, -n:], lang_model.config.eos_token_id, out.token_logprobs)[0])
+        print(f"mean token log-prob: {res['mean_logprob']:.3f}")
     lang_model.close()
-    return {"findings": findings, "prediction": pred, "sequences": out.sequences.cpu(), "n_scores": len(out.scores)}
+    return res
 
 
 if __name__ == "__main__":

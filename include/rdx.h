@@ -176,6 +176,36 @@ int rdx_set_logits_rules(rdx_ctx* ctx, const rdx_logits_rules* rules);
 typedef struct rdx_sampling { int do_sample; float temperature; int top_k; float top_p; uint64_t seed; } rdx_sampling;
 int rdx_set_sampling(rdx_ctx* ctx, const rdx_sampling* s);
 
+/* Generation log-probs: for every (row, step) of a conversation, how sure the selection was of the token the step wrote to out_tokens[row][step]. Opt-in; with
+ * the option off every launch and every output bit is that of a context that never had it.
+ * Let x be the step's scores row as the selection kernel left it, over columns 0 .. vocab - 1 only: the raw lm_head logits for plain greedy, the row processed
+ * in place under rdx_set_logits_rules, the warped row under rdx_set_sampling -- what HF's .scores holds, so that `chosen` is what
+ * compute_transition_scores(..., normalize_logits=True) computes. With m = max x, S = sum exp(float(x_i) - m), in fp32 and never rounded to the model dtype
+ * (the formula of the scoring pass below):
+ *   chosen              = (float(x_tok) - m) - log(S)
+ *   top_ids[0 .. n)     the n columns with the largest x in descending order, lowest index on ties; the order is taken on the model-dtype values, which are
+ *                       exact. -inf entries (banned or dropped columns) follow once the finite ones run out, with log-prob -inf. NaN columns never enter;
+ *                       a slot without a candidate holds (-1, 0.0f)
+ *   top_lp[0 .. n)      their log-probs by the same formula
+ * One launch of logprob_step_k (csrc/logprob.hip), one workgroup per row, rides behind the selection launch of the prompt's token-0 call, of every
+ * single-step call and of the captured step; every reduction runs in a fixed order that does not depend on where the row lies: the same row gives the same
+ * bits with and without a scores buffer, eager or replayed. A step at or beyond max_new writes nothing. Entries of steps that have not run read
+ * (0.0f, -1, 0.0f); a prefill resets the rows it starts. A row that has emitted EOS keeps getting entries, for the pad token the step's tail writes
+ * (radialog_amd's Python layer masks everything behind a row's first EOS to (0.0, -1, 0.0)).
+ * rdx_set_logprobs: top_n = -1 switches the option off, 0 .. RDX_MAX_TOP_LOGPROBS on (0: the chosen token only) for the NEXT prefill / generate / decode-step /
+ * append calls; it is part of the step graph's key. Returns -1 with a message for a top_n outside that range, before rdx_finalize_weights, for a vocabulary
+ * whose row does not fit the kernel's LDS (or above 65536 columns), and inside a row session ("rdx_rows_end first"). The first call allocates context-owned buffers (chosen
+ * float [max_batch][max_len], top_ids int32 and top_lp float [max_batch][max_len][8]) whose addresses never change; without a caller buffer the lm_head writes
+ * its rows into the context's own, as under rules. While the option is on, rdx_beam_search (beams return sequence scores) and rdx_rows_begin (a moved row's
+ * entries would have to move with it) return -1 with a message naming "logprobs". fp8 / int4 / coded weights and the fp8 KV cache need nothing special.
+ * rdx_get_logprobs drains the stream and copies the current conversation's entries to HOST memory: chosen_host float [batch][n_steps], top_ids_host int32 and
+ * top_lp_host float [batch][n_steps][top_n] (both nullable). Returns -1 while the option is off or when batch / n_steps exceed the conversation's rows /
+ * max_new.
+ * Not built: row sessions, beams, log-probs of the raw logits while rules or warpers are on, the row's entropy. */
+#define RDX_MAX_TOP_LOGPROBS 8
+int rdx_set_logprobs(rdx_ctx* ctx, int top_n);
+int rdx_get_logprobs(rdx_ctx* ctx, int batch, int n_steps, float* chosen_host, int32_t* top_ids_host, float* top_lp_host);
+
 /* Scoring given tokens: LlamaForCausalLM.forward(input_ids, attention_mask, labels=) of the reference (modeling_llama_imgemb.py:705-793) -- the logits of
  * every position and what its shifted cross-entropy is made of -- from ONE pass over the prompt's kernels (no decode steps).
  *   ids / mask / qformer_embs  device pointers as for the prefill call: the left-padded prompt, the mask (NULL -> ids != 0), the image splice

@@ -67,6 +67,14 @@ int rdx_select_test(rdx_ctx* ctx, void* logits_inout, int B, int vocab, const in
  * top1_out int32 [M] (device). Works on any context (no weights involved). */
 int rdx_score_rows_test(rdx_ctx* ctx, const void* logits, int M, int vocab, int ld, const int32_t* target, float* logprob_out, int32_t* top1_out);
 
+/* logprob_step_k alone (logprob.hip: the generation log-probs of include/rdx.h) on caller data, all device pointers. Row b (b < B) describes step =
+ * d_step[b] - 1: its scores row lies at logits + step * step_stride + b * row_stride ELEMENTS (model dtype; any 2-byte alignment: rows may start at odd
+ * elements; columns >= vocab are not looked at), its token is tokens[b * max_new + step]. chosen_out float [B][out_ld], top_ids_out int32 and top_lp_out
+ * float [B][out_ld][8] (out_ld >= max_new): entry [b][step] is written (of the top arrays the first top_n slots), nothing else is; a row whose step is outside
+ * [0, max_new) writes nothing. Works on any context (no weights involved). */
+int rdx_logprob_step_test(rdx_ctx* ctx, const void* logits, long long row_stride, long long step_stride, const int32_t* d_step, const int32_t* tokens, int B,
+                          int vocab, int max_new, int top_n, float* chosen_out, int32_t* top_ids_out, float* top_lp_out, int out_ld);
+
 /* launch_decode_attention alone (attn.hip, attn_body.h: one new token per row -- LoRA-B add, rotate-half RoPE, in-place KV append, attention over the cache), on
  * caller data: hidden = 128 heads, qkv_ld = 3 hidden + 2 lora_r rounded up to 16. qkv [B][qkv_ld] (q | k | v | LoRA-A of q [8] | of v [8]), lbq / lbv [hidden][8]
  * (lora_r 8; else ignored), EITHER cur_rope [B][2][128] (cos | sin row of each row's position) OR cos_t / sin_t [max_pos][128] with pos [B]; slot [B] (the

@@ -19,6 +19,7 @@ HOOKS_PATH = os.environ.get("RDX_HOOKS_PATH") or os.path.join(HERE, "librdx_hook
 RDX_DTYPE_F16, RDX_DTYPE_BF16 = 0, 1
 RDX_W_GEMM, RDX_W_TENSOR, RDX_W_F32, RDX_W_GEMM_FP8, RDX_W_GEMM_W4 = 0, 1, 2, 3, 4
 RDX_SRC_F32, RDX_SRC_F16, RDX_SRC_BF16 = 0, 1, 2
+RDX_MAX_TOP_LOGPROBS = 8
 
 
 class RdxLibraryError(RuntimeError):
@@ -83,6 +84,8 @@ SYMBOLS = {
     "rdx_score": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "rdx_set_logits_rules": (C.c_int, [_P, C.POINTER(RdxLogitsRules)]),
     "rdx_set_sampling": (C.c_int, [_P, C.POINTER(RdxSampling)]),
+    "rdx_set_logprobs": (C.c_int, [_P, C.c_int]),
+    "rdx_get_logprobs": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_prefill_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rdx_generate_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
                                       C.POINTER(C.c_int), C.c_int]),
@@ -142,6 +145,7 @@ DEC_HOOK_SYMBOLS = {
     "rdx_rmsnorm_test": (C.c_int, [_P, _P, _P, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong, _P, C.c_int]),
     "rdx_select_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, _P]),
     "rdx_score_rows_test": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rdx_logprob_step_test": (C.c_int, [_P, _P, C.c_longlong, C.c_longlong, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int]),
     "rdx_sample_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, C.POINTER(RdxSampling), _P]),
     "rdx_sample_u24_host": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rdx_decode_attn_test": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _F, _P, _P, _P, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_longlong,

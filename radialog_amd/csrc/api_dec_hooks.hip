@@ -317,6 +317,21 @@ extern "C" int rdx_score_rows_test(rdx_ctx* c, const void* logits, int M, int vo
     return finish(c);
 }
 
+extern "C" int rdx_logprob_step_test(rdx_ctx* c, const void* logits, long long row_stride, long long step_stride, const int32_t* d_step, const int32_t* tokens,
+                                     int B, int vocab, int max_new, int top_n, float* chosen_out, int32_t* top_ids_out, float* top_lp_out, int out_ld) {
+    if (!c || !logits || !d_step || !tokens || !chosen_out || !top_ids_out || !top_lp_out || B <= 0 || max_new <= 0 || out_ld < max_new || row_stride < 0 || step_stride < 0)
+        return fail(c, -1, "rdx_logprob_step_test: bad arguments");
+    if (top_n < 0 || top_n > RDX_MAX_TOP_LOGPROBS) return fail(c, -1, "rdx_logprob_step_test: top_n %d outside [0, %d]", top_n, RDX_MAX_TOP_LOGPROBS);
+    if (((uintptr_t)logits & 1) || !logprob_step_supported(vocab)) return fail(c, -1, "rdx_logprob_step_test: a row of vocab %d does not fit the LDS of logprob_step_k", vocab);
+    HIPCHK(c, hipSetDevice(c->device));
+    LogprobArgs a;
+    a.logits = logits; a.row_stride = (long)row_stride; a.step_stride = (long)step_stride; a.d_step = d_step; a.tokens = tokens;
+    a.B = B; a.max_new = max_new; a.vocab = vocab; a.top_n = top_n;
+    a.chosen = chosen_out; a.top_ids = top_ids_out; a.top_lp = top_lp_out; a.out_ld = out_ld;
+    launch_logprob_step(c->cfg.dtype, a, c->stream);
+    return finish(c);
+}
+
 namespace {
 
 // the dims both attention hooks build: hidden = 128 heads, the QKV row as the engine lays it out (api.hip: wqkv.Npad)

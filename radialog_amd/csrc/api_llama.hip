@@ -35,7 +35,8 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
                                int advance, int row0 = 0, int32_t* tokens = nullptr) {
     const rdx_config& f = c->cfg;
     // logits rules: the row select_step_k processes must exist, so without a caller buffer the lm_head writes into the context's own
-    if ((c->rules_on || c->sampling.do_sample) && !logits) { logits = c->rule_logits; out_step = nullptr; }
+    // (generation log-probs likewise: logprob_step_k reads the row)
+    if ((c->rules_on || c->sampling.do_sample || c->logprobs >= 0) && !logits) { logits = c->rule_logits; out_step = nullptr; }
     auto lm = [&](GemmArgs a) { a.X = x; a.out = logits; a.out_step = out_step; a.out_step_stride = step_stride; return a; };
     switch (decode_family(c, B)) {
     case DEC_UNSUPPORTED: c->unsupported = k_need_blk; return;
@@ -64,16 +65,87 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
         t.x_next = (char*)c->dx + (size_t)row0 * f.hidden * 2; t.cur_rope = (char*)c->d_cur_rope + (size_t)row0 * 512;
     }
     if (tokens) t.out_tokens = tokens;
-    if (!c->rules_on && !c->sampling.do_sample) { launch_greedy_step(f.dtype, c->part_val, c->part_idx, c->n_vtiles, B, t, c->stream); return; }
+    // generation log-probs: behind whichever selection ran, on the row it left and the token its tail wrote (d_step is already advanced: the kernel takes d_step - 1)
+    auto logprobs = [&] {
+        if (c->logprobs < 0) return;
+        LogprobArgs la;
+        la.logits = logits; la.row_stride = f.vocab; la.step_stride = out_step ? step_stride : 0;
+        la.d_step = c->d_step; la.tokens = c->cur_tokens; la.B = B; la.max_new = c->cur_max_new; la.vocab = f.vocab; la.top_n = c->logprobs;
+        la.chosen = c->lp_chosen; la.top_ids = c->lp_top_ids; la.top_lp = c->lp_top_lp; la.out_ld = f.max_len;
+        launch_logprob_step(f.dtype, la, c->stream);
+    };
+    if (!c->rules_on && !c->sampling.do_sample) { launch_greedy_step(f.dtype, c->part_val, c->part_idx, c->n_vtiles, B, t, c->stream); logprobs(); return; }
     // the row at the address the lm_head just wrote (a captured step with scores: both offset it by the step count, read from d_step before the tail advances it)
     if (c->rules_on) { t.hist = c->d_hist; t.hist_len = c->d_hist_len; t.hist_ld = f.max_len; }
     SelectArgs sa;
     sa.logits = logits; sa.step_stride = out_step ? step_stride : 0; sa.n_gen = c->d_step;
     sa.penalty = c->rules.repetition_penalty; sa.ngram = c->rules.no_repeat_ngram_size; sa.min_new = c->rules.min_new_tokens; sa.sel_out = nullptr;
-    if (!c->sampling.do_sample) { launch_select_step(f.dtype, sa, t, B, c->stream); return; }
+    if (!c->sampling.do_sample) { launch_select_step(f.dtype, sa, t, B, c->stream); logprobs(); return; }
     // sampled: the draw index of row b is d_step[b] too (0 for the token the prefill selects)
     const SampleArgs sp = {c->sampling.temperature, c->sampling.top_k, c->sampling.top_p, c->d_seed};
     launch_sample_step(f.dtype, sa, sp, t, B, c->stream);
+    logprobs();
+}
+
+// an unwritten entry reads (0.0f, -1, 0.0f): rows [0, B) of the three buffers, in stream order in front of the prompt
+static int logprobs_reset(rdx_ctx* c, int B) {
+    if (c->logprobs < 0) return 0;
+    const size_t n = (size_t)B * c->cfg.max_len;
+    HIPCHK(c, hipMemsetAsync(c->lp_chosen, 0, n * sizeof(float), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->lp_top_ids, 0xff, n * RDX_MAX_TOP_LOGPROBS * sizeof(int), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->lp_top_lp, 0, n * RDX_MAX_TOP_LOGPROBS * sizeof(float), c->stream));
+    return 0;
+}
+
+extern "C" int rdx_set_logprobs(rdx_ctx* c, int top_n) {
+    if (!c) return -1;
+    if (top_n == -1) { c->logprobs = -1; return 0; }
+    if (top_n < 0 || top_n > RDX_MAX_TOP_LOGPROBS) return fail(c, -1, "rdx_set_logprobs: top_n %d of the logprobs outside [0, %d] (-1 = off)", top_n, RDX_MAX_TOP_LOGPROBS);
+    if (int src = rows_refuse(c, "rdx_set_logprobs")) return src;
+    if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_set_logprobs: llama weights not finalized");
+    const rdx_config& f = c->cfg;
+    if (!logprob_step_supported(f.vocab)) return fail(c, -1, "rdx_set_logprobs: a row of vocab %d does not fit the LDS of logprob_step_k", f.vocab);
+    HIPCHK(c, hipSetDevice(c->device));
+    // each buffer on its own: a call that failed half way leaves the option as it was, and the next one allocates what is still missing
+    const size_t n = (size_t)f.max_batch * f.max_len;
+    const bool fresh = !c->lp_chosen || !c->lp_top_ids || !c->lp_top_lp;
+    if (!c->rule_logits) ALLOC(c, c->rule_logits, (size_t)f.max_batch * f.vocab * 2);
+    if (!c->lp_chosen) ALLOC(c, c->lp_chosen, n * sizeof(float));
+    if (!c->lp_top_ids) ALLOC(c, c->lp_top_ids, n * RDX_MAX_TOP_LOGPROBS * sizeof(int));
+    if (!c->lp_top_lp) ALLOC(c, c->lp_top_lp, n * RDX_MAX_TOP_LOGPROBS * sizeof(float));
+    const int was = c->logprobs;
+    c->logprobs = top_n;
+    if (fresh) {        // steps that have not run read (0.0f, -1, 0.0f) from the first call on
+        if (int rc = logprobs_reset(c, f.max_batch)) { c->logprobs = was; return rc; }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return 0;
+}
+
+extern "C" int rdx_get_logprobs(rdx_ctx* c, int batch, int n_steps, float* chosen_host, int32_t* top_ids_host, float* top_lp_host) {
+    if (!c) return -1;
+    if (c->logprobs < 0) return fail(c, -1, "rdx_get_logprobs: the logprobs option is off; rdx_set_logprobs first");
+    if (!chosen_host || batch <= 0 || batch > c->cur_B || n_steps <= 0 || n_steps > c->cur_max_new)
+        return fail(c, -1, "rdx_get_logprobs: batch %d / n_steps %d outside the conversation's logprobs (%d rows, %d steps)", batch, n_steps, c->cur_B, c->cur_max_new);
+    const rdx_config& f = c->cfg;
+    const int K = RDX_MAX_TOP_LOGPROBS, n = c->logprobs;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, hipMemcpy2D(chosen_host, (size_t)n_steps * sizeof(float), c->lp_chosen, (size_t)f.max_len * sizeof(float), (size_t)n_steps * sizeof(float), batch,
+                          hipMemcpyDeviceToHost));
+    // [batch][n_steps][8] of the device rows, compacted to [batch][n_steps][top_n] on the host
+    const size_t rowb = (size_t)n_steps * K;
+    if (top_ids_host && n > 0) {
+        std::vector<int32_t> tmp(rowb * batch);
+        HIPCHK(c, hipMemcpy2D(tmp.data(), rowb * sizeof(int32_t), c->lp_top_ids, (size_t)f.max_len * K * sizeof(int32_t), rowb * sizeof(int32_t), batch, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < (size_t)batch * n_steps; ++i) for (int k = 0; k < n; ++k) top_ids_host[i * n + k] = tmp[i * K + k];
+    }
+    if (top_lp_host && n > 0) {
+        std::vector<float> tmp(rowb * batch);
+        HIPCHK(c, hipMemcpy2D(tmp.data(), rowb * sizeof(float), c->lp_top_lp, (size_t)f.max_len * K * sizeof(float), rowb * sizeof(float), batch, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < (size_t)batch * n_steps; ++i) for (int k = 0; k < n; ++k) top_lp_host[i * n + k] = tmp[i * K + k];
+    }
+    return 0;
 }
 
 static const rdx_sampling k_sampling_off = {0, 1.0f, 0, 1.0f, 0};
@@ -282,6 +354,7 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
     if (rc) return rc;
     c->cur_B = B; c->cur_T = keep + T; c->cur_max_new = max_new; c->cur_eos = eos_id; c->cur_pad = pad_id; c->cur_tokens = out_tokens;
     c->cur_steps = 1;
+    if (int lrc = logprobs_reset(c, B)) return lrc;
     prompt_layers(c, ids, mask, B, T, qformer_embs, keep, pad_id, c->rules_on);
     return prompt_token0(c, B, T, logits);
 }
@@ -608,6 +681,7 @@ int build_graph(rdx_ctx* c, void* scores, bool fixed) {
     k.B = c->cur_B; k.max_new = c->cur_max_new; k.eos = c->cur_eos; k.pad = c->cur_pad; k.tokens = c->cur_tokens; k.scores = scores; k.fixed = fixed;
     k.rules = c->rules;
     k.sampling = c->sampling;
+    k.logprobs = c->logprobs;
     if (int rrc = rules_need_prefill(c, "decode step graph")) return rrc;
     if (c->graph && k == c->gkey) return 0;
     if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }
@@ -731,6 +805,7 @@ extern "C" int rdx_beam_search(rdx_ctx* c, const int32_t* ids, const int32_t* ma
     if (int krc = kv8_refuse(c, "rdx_beam_search", "the beam reorder moves model-dtype cache rows")) return krc;
     if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_beam_search: llama weights not finalized");
     const rdx_config& f = c->cfg;
+    if (c->logprobs >= 0) return fail(c, -1, "rdx_beam_search: not available while the logprobs option is on (beams return sequence scores); rdx_set_logprobs(ctx, -1) first");
     if (c->sampling.do_sample) return fail(c, -1, "rdx_beam_search: not available while sampling is on (beam-sample is not built); rdx_set_sampling(ctx, NULL) first");
     if (c->rules_on) return fail(c, -1, "rdx_beam_search: not available under logits rules (beam search applies them to log-softmax scores and reorders histories); rdx_set_logits_rules(ctx, NULL) first");
     const int rows = groups * num_beams;

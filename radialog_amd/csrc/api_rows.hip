@@ -35,6 +35,7 @@ extern "C" int rdx_rows_begin(rdx_ctx* c, int rows, int stage, int cap, int eos_
     const rdx_config& f = c->cfg;
     if (c->rules_on) return fail(c, -1, "rdx_rows_begin: not available under logits rules (a moved row's token history would have to move too); rdx_set_logits_rules(ctx, NULL) first");
     if (c->sampling.do_sample) return fail(c, -1, "rdx_rows_begin: not available while sampling is on (a moved row's draw index would have to move too); rdx_set_sampling(ctx, NULL) first");
+    if (c->logprobs >= 0) return fail(c, -1, "rdx_rows_begin: not available while the logprobs option is on (a moved row's entries would have to move too); rdx_set_logprobs(ctx, -1) first");
     if (rows < 1 || stage < 1 || rows + stage > f.max_batch || rows + stage > ROWLIST_MAX)
         return fail(c, -1, "rdx_rows_begin: rows (%d) + stage (%d) must be >= 1 each and fit max_batch %d", rows, stage, f.max_batch);
     if (cap < 1 || cap >= f.max_len || cap >= f.max_pos) return fail(c, -1, "rdx_rows_begin: cap %d outside [1, max_len %d / max_position_embeddings %d)", cap, f.max_len, f.max_pos);

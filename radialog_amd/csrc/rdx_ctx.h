@@ -58,8 +58,9 @@ struct GraphKey {
     bool fixed = false;             // logits always to `scores` itself (beam search) instead of scores + step * stride
     rdx_logits_rules rules = {1.0f, 0, 0};      // the captured step selects through select_step_k unless neutral
     rdx_sampling sampling = {0, 1.0f, 0, 1.0f, 0};      // do_sample: through sample_step_k, t / k / p its arguments; the seed is no part of the key (a device word)
+    int logprobs = -1;              // rdx_set_logprobs: >= 0: logprob_step_k rides behind the selection with this top_n
     bool operator==(const GraphKey& o) const {
-        return B == o.B && max_new == o.max_new && eos == o.eos && pad == o.pad && tokens == o.tokens && scores == o.scores && fixed == o.fixed &&
+        return logprobs == o.logprobs && B == o.B && max_new == o.max_new && eos == o.eos && pad == o.pad && tokens == o.tokens && scores == o.scores && fixed == o.fixed &&
                rules.repetition_penalty == o.rules.repetition_penalty && rules.no_repeat_ngram_size == o.rules.no_repeat_ngram_size &&
                rules.min_new_tokens == o.rules.min_new_tokens && sampling.do_sample == o.sampling.do_sample &&
                sampling.temperature == o.sampling.temperature && sampling.top_k == o.sampling.top_k && sampling.top_p == o.sampling.top_p;
@@ -150,6 +151,11 @@ struct rdx_ctx {
     // ---- sampled decoding (rdx_set_sampling): do_sample == 0 = off; on: the step selects through sample_step_k (elem.hip), rules included ----
     rdx_sampling sampling = {0, 1.0f, 0, 1.0f, 0};
     unsigned long long* d_seed = nullptr;           // the seed word sample_step_k reads (rewritten in stream order by every rdx_set_sampling call)
+
+    // ---- generation log-probs (rdx_set_logprobs): -1 = off; 0 .. 8 = on with that many alternatives: logprob_step_k (logprob.hip) behind every selection ----
+    int logprobs = -1;
+    float* lp_chosen = nullptr;                     // [max_batch][max_len]: entry [row][step] of the current conversation
+    int* lp_top_ids = nullptr; float* lp_top_lp = nullptr;      // [max_batch][max_len][RDX_MAX_TOP_LOGPROBS]; allocated once, so a captured graph keeps its pointers
 
     // ---- scoring pass (rdx_score), sized on first use ----
     int score_chunk = 2048;                         // logits rows per lm_head launch (rdx_set_option("score_chunk", rows); 0 = all rows at once): profiles/r11_score.md

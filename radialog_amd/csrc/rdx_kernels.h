@@ -366,6 +366,20 @@ void launch_gather_rows(int dtype, const void* x, const int* rows, void* out, in
 void launch_score_scatter(const float* lp, const int* t1, const int* dst, float* logprob, int* top1, int n, hipStream_t s);   // logprob[dst[i]] = lp[i] (top1 likewise, nullable); dst < 0: skipped
 void launch_logits_out(int dtype, const void* ws, long ld, const int* dst, void* out, int vocab, int n, hipStream_t s);       // out[dst[i]][0 .. vocab) = ws[i][0 .. vocab)
 
+// Generation log-probs (logprob.hip). logprob_step_k: one workgroup per batch row behind the step's selection launch. Row b describes step = d_step[b] - 1 (the
+// tail has advanced it): the scores row at logits + step * step_stride + b * row_stride elements (model dtype, columns 0 .. vocab - 1) and the token
+// tokens[b * max_new + step]. chosen [B][out_ld] float, top_ids / top_lp [B][out_ld][8]: entry [b][step] gets the token's log-prob and the top_n (0 .. 8)
+// largest columns (descending, lowest index on ties) with theirs; a step outside [0, max_new) writes nothing (out_ld >= max_new).
+struct LogprobArgs {
+    const void* logits; long row_stride, step_stride;
+    const int* d_step; const int* tokens;
+    int B, max_new, vocab, top_n;
+    float* chosen; int* top_ids; float* top_lp; long out_ld;
+};
+inline size_t logprob_step_lds(int vocab) { return (size_t)((vocab + 7) / 8) * 16; }      // dynamic LDS: the row in whole 8-element groups
+bool logprob_step_supported(int vocab);
+void launch_logprob_step(int dtype, const LogprobArgs& a, hipStream_t s);
+
 // beam search (beam.hip)
 #define RDX_MAX_BEAMS 8
 void launch_beam_topk(int dtype, const void* logits, const float* beam_scores, int groups, int beams, int vocab, float* cand_score,

@@ -83,6 +83,42 @@ class Sampling:
         return cls(*sampling)
 
 
+def mask_logprobs_after_eos(tokens, eos_id, chosen, top_ids, top_lp):
+    """What the Python layer returns for generation log-probs: everything BEHIND a row's first EOS (the pad tokens the step's tail writes for a finished
+    row) reads (0.0, -1, 0.0); the EOS entry itself stays. tokens int [B, n], chosen [B, n], top_ids / top_lp [B, n, k]. New tensors; eos_id < 0: copies."""
+    tokens = torch.as_tensor(tokens)
+    B, n = chosen.shape
+    done = torch.zeros(B, n, dtype=torch.bool)
+    if eos_id is not None and eos_id >= 0 and n > 1:
+        hit = (tokens[:, :n].cpu() == eos_id).to(torch.int64)
+        done[:, 1:] = hit.cumsum(dim=1)[:, :-1] > 0
+    chosen, top_ids, top_lp = chosen.clone(), top_ids.clone(), top_lp.clone()
+    chosen[done] = 0.0
+    top_ids[done] = -1
+    top_lp[done] = 0.0
+    return chosen, top_ids, top_lp
+
+
+def mean_token_logprob(tokens, eos_id, chosen):
+    """float64 [B]: the mean log-prob of each row's generated tokens up to and including its first EOS (all n without one): a report's confidence."""
+    tokens = torch.as_tensor(tokens)
+    B, n = chosen.shape
+    live = torch.ones(B, n, dtype=torch.bool)
+    if eos_id is not None and eos_id >= 0 and n > 1:
+        live[:, 1:] = (tokens[:, :n].cpu() == eos_id).to(torch.int64).cumsum(dim=1)[:, :-1] == 0
+    c = torch.where(live, chosen.double(), torch.zeros(B, n, dtype=torch.float64))
+    return c.sum(dim=1) / live.sum(dim=1).clamp(min=1)
+
+
+def check_top_logprobs(n, what="logprobs"):
+    """None (off) or an int in 0 .. RDX_MAX_TOP_LOGPROBS; anything else is a ValueError naming `what`."""
+    if n is None:
+        return None
+    if isinstance(n, bool) or not isinstance(n, int) or not 0 <= n <= _lib.RDX_MAX_TOP_LOGPROBS:
+        raise ValueError(f"{what} must be None or an int in 0 .. {_lib.RDX_MAX_TOP_LOGPROBS} (the number of top alternatives per step), got {n!r}")
+    return n
+
+
 class RdxEngine:
     def __init__(self, cfg: RaDialogCfg, dtype: str = "bf16", device: int = 0, max_batch: int = 1, max_len: int = 512,
                  lora: bool = True, vision: bool = True, llama: bool = True, classifier: bool = False,
@@ -137,6 +173,7 @@ class RdxEngine:
             self.set_option("kv_fp8", 1)
         self._rules = LogitsRules()                  # what the context holds (set_logits_rules is the one place that changes it)
         self._sampling = None                        # likewise (set_sampling); None = greedy
+        self._logprobs = None                        # likewise (set_logprobs); None = off, else the number of top alternatives
 
     # ------------------------------------------------------------------------------------------------------------
     def close(self):
@@ -241,6 +278,54 @@ class RdxEngine:
         self._sampling = sm
         return sm
 
+    def set_logprobs(self, top_n=None) -> Optional[int]:
+        """rdx_set_logprobs: generation log-probs of the next prefill / generate / decode_step calls; None = off, 0 .. 8 = the chosen token's log-prob and
+        that many top alternatives per step (read back with get_logprobs)."""
+        n = check_top_logprobs(top_n)
+        check(self.ctx, self.lib.rdx_set_logprobs(self.ctx, -1 if n is None else n), "rdx_set_logprobs")
+        self._logprobs = n
+        return n
+
+    def get_logprobs(self, batch: int, n_steps: int, tokens=None, eos_id: int = -1):
+        """rdx_get_logprobs: (chosen float32 [batch, n_steps], top_ids int32 [batch, n_steps, k], top_lp float32 [batch, n_steps, k]) of the current
+        conversation, on the host, as the device holds them (a finished row's later entries describe the pad token). With `tokens` int [batch, >= n_steps]
+        and eos_id >= 0: masked behind each row's first EOS (mask_logprobs_after_eos)."""
+        k = self._logprobs
+        if k is None:
+            raise ValueError("get_logprobs: the logprobs option is off (set_logprobs, or logprobs= of generate / prefill)")
+        chosen = torch.zeros(batch, n_steps, dtype=torch.float32)
+        top_ids = torch.full((batch, n_steps, k), -1, dtype=torch.int32)
+        top_lp = torch.zeros(batch, n_steps, k, dtype=torch.float32)
+        check(self.ctx, self.lib.rdx_get_logprobs(self.ctx, batch, n_steps, C.c_void_p(chosen.data_ptr()), C.c_void_p(top_ids.data_ptr()) if k else None,
+                                                  C.c_void_p(top_lp.data_ptr()) if k else None), "rdx_get_logprobs")
+        if tokens is not None:
+            return mask_logprobs_after_eos(tokens, eos_id, chosen, top_ids, top_lp)
+        return chosen, top_ids, top_lp
+
+    def logprob_step_test(self, logits, d_step, tokens, vocab, top_n, row_stride=None, step_stride=0, out_ld=None, offset=0, guard_rows=2):
+        """logprob_step_k alone (rdx_logprob_step_test). logits: a model-dtype tensor of any shape, read flat from element `offset` on: row b of step s lies at
+        offset + s * step_stride + b * row_stride; d_step int [B] (the ADVANCED step counts: row b describes step d_step[b] - 1), tokens int [B, max_new].
+        Returns (chosen float32 [B + guard_rows, out_ld], top_ids int32 [.., out_ld, 8], top_lp float32 [.., out_ld, 8]), pre-filled with canaries
+        (NaN, -7, NaN) that only the entries the kernel writes replace; the guard rows lie behind the launch's last row."""
+        B, max_new = tokens.shape
+        x = logits.to(self.device, self.tdtype).contiguous().view(-1)
+        ds = d_step.to(self.device, torch.int32).contiguous()
+        tk = tokens.to(self.device, torch.int32).contiguous()
+        rs = int(vocab if row_stride is None else row_stride)
+        ld = int(max_new if out_ld is None else out_ld)
+        # every row the kernel can address lies inside the tensor (a step outside [0, max_new) reads nothing)
+        last_step = min(max(int(ds.max()) - 1, 0), max_new - 1)
+        reach = int(offset) + last_step * int(step_stride) + (B - 1) * rs + int(vocab)
+        if ds.numel() != B or offset < 0 or reach > x.numel():
+            raise ValueError(f"logprob_step_test: d_step [B]; the last row ends at element {reach} of {x.numel()}")
+        chosen = torch.full((B + guard_rows, ld), float("nan"), dtype=torch.float32, device=self.device)
+        top_ids = torch.full((B + guard_rows, ld, 8), -7, dtype=torch.int32, device=self.device)
+        top_lp = torch.full((B + guard_rows, ld, 8), float("nan"), dtype=torch.float32, device=self.device)
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_logprob_step_test(self.ctx, C.c_void_p(x.data_ptr() + 2 * int(offset)), rs, int(step_stride), _ptr(ds), _ptr(tk), B, int(vocab),
+                                                       max_new, int(top_n), _ptr(chosen), _ptr(top_ids), _ptr(top_lp), ld), "rdx_logprob_step_test")
+        return chosen, top_ids, top_lp
+
     def sample_test(self, logits, n_generated, sampling, rules=None, hist=None, hist_len=None, eos_id=-1):
         """sample_step_k alone (rdx_sample_test): logits [B, V] model dtype, n_generated int [B] (the draw indices), sampling a Sampling or tuple; rules with
         hist int [B, ld] and hist_len int [B] as in select_test. Returns (processed logits [B, V], tokens int32 [B]); the caller's tensors stay."""
@@ -301,8 +386,11 @@ class RdxEngine:
 
     def generate(self, ids: torch.Tensor, qformer_embs: Optional[torch.Tensor], max_new: int, eos_id: int = 2,
                  pad_id: int = 0, mask: Optional[torch.Tensor] = None, output_scores: bool = False, use_graph: bool = True,
-                 reuse_prefix: bool = False, logits_rules=None, sampling=None):
+                 reuse_prefix: bool = False, logits_rules=None, sampling=None, logprobs: Optional[int] = None):
         """Greedy (sampling=None) or sampled generation. Returns (tokens int32[B,n_steps], scores [n_steps,B,V] model dtype or None, n_steps).
+        logprobs: None, or 0 .. 8: a FOURTH element (chosen float32 [B, n_steps], top_ids int32 [B, n_steps, k], top_lp float32 [B, n_steps, k]) on the host --
+        the log-prob of every generated token under the scores row it was chosen from (processed / warped under rules / sampling: HF's
+        compute_transition_scores(normalize_logits=True)) and the k largest columns of that row with theirs; (0.0, -1, 0.0) behind a row's first EOS.
         reuse_prefix: multi-turn conversations -- keep the KV rows of the token prefix this prompt shares with the previous
         reuse_prefix call and prefill only the rest (rdx_generate_append); outputs are those of the full prompt.
         logits_rules: LogitsRules or (repetition_penalty, no_repeat_ngram_size, min_new_tokens); the scores are then the processed ones
@@ -314,6 +402,7 @@ class RdxEngine:
         self.set_sampling(sampling)
         if self.set_logits_rules(logits_rules).active:
             reuse_prefix = False
+        self.set_logprobs(logprobs)
         ids32 = ids.to(device=self.device, dtype=torch.int32).contiguous()
         m32 = None if mask is None else mask.to(device=self.device, dtype=torch.int32).contiguous()
         qf = None if qformer_embs is None else qformer_embs.to(device=self.device, dtype=torch.float32).contiguous()
@@ -347,6 +436,8 @@ class RdxEngine:
                           "qf": None if qf is None else qf.clone()}
         else:
             self._conv = None
+        if logprobs is not None:
+            return toks, scores, n.value, self.get_logprobs(B, n.value, tokens=toks[:, : n.value], eos_id=eos_id)
         return toks, scores, n.value
 
     def beam_search(self, ids: torch.Tensor, qformer_embs: Optional[torch.Tensor], num_beams: int, max_new: int, eos_id: int = 2,
@@ -361,6 +452,7 @@ class RdxEngine:
         ids32, m32, qf = rep(ids, torch.int32), rep(mask, torch.int32), rep(qformer_embs, torch.float32)
         self.set_logits_rules(None)                  # rules are a greedy-search feature; a call that left some behind must not make this one fail
         self.set_sampling(None)                      # likewise: beam-sample is not built
+        self.set_logprobs(None)                      # likewise: beams return sequence scores
         toks = torch.zeros(B, max_new, dtype=torch.int32)
         lens = torch.zeros(B, dtype=torch.int32)
         seq_scores = torch.zeros(B, dtype=torch.float32)
@@ -374,11 +466,13 @@ class RdxEngine:
               "rdx_beam_search")
         return toks, lens, seq_scores, (None if sc is None else sc[: n.value]), n.value
 
-    def prefill(self, ids, qformer_embs, max_new, eos_id=2, pad_id=0, mask=None, want_logits=True, logits_rules=None, sampling=None):
-        """The prompt and token 0. logits_rules and sampling (as in generate) stay in force for the decode_step calls behind this prefill."""
+    def prefill(self, ids, qformer_embs, max_new, eos_id=2, pad_id=0, mask=None, want_logits=True, logits_rules=None, sampling=None, logprobs: Optional[int] = None):
+        """The prompt and token 0. logits_rules, sampling and logprobs (as in generate) stay in force for the decode_step calls behind this prefill; the
+        log-probs of the steps run so far: get_logprobs(B, steps)."""
         B, T = ids.shape
         self.set_sampling(sampling)
         self.set_logits_rules(logits_rules)
+        self.set_logprobs(logprobs)
         ids32 = ids.to(device=self.device, dtype=torch.int32).contiguous()
         m32 = None if mask is None else mask.to(device=self.device, dtype=torch.int32).contiguous()
         qf = None if qformer_embs is None else qformer_embs.to(device=self.device, dtype=torch.float32).contiguous()
@@ -392,11 +486,14 @@ class RdxEngine:
         self.sync()
         return toks, logits
 
-    def decode_step(self, want_logits=True, input_ids: Optional[torch.Tensor] = None, logits_rules=None, sampling=None):
+    def decode_step(self, want_logits=True, input_ids: Optional[torch.Tensor] = None, logits_rules=None, sampling=None, logprobs: Optional[int] = None):
         """One decode step on the token the previous step selected, or on caller-supplied `input_ids` int[B] (rdx_decode_step_ids).
         logits_rules: None keeps the rules the context holds (those of the prefill, unless a generate / beam_search call came in between); rules
-        cannot be switched on behind a prefill that ran without any. sampling: None keeps what the context holds, too."""
+        cannot be switched on behind a prefill that ran without any. sampling: None keeps what the context holds, too, and so does logprobs (an int
+        switches the option on from this step on, or changes its top-n; earlier steps keep what they wrote)."""
         ids32, m32, qf, toks = self._keep["prefill"]
+        if logprobs is not None and check_top_logprobs(logprobs) != self._logprobs:
+            self.set_logprobs(logprobs)
         if sampling is not None and Sampling.of(sampling) != self._sampling:
             self.set_sampling(sampling)
         if logits_rules is not None and LogitsRules.of(logits_rules) != self._rules:
@@ -416,9 +513,10 @@ class RdxEngine:
 
     def row_session(self, rows: int, stage: int, cap: int, eos_id: int = 2, pad_id: int = 0, use_graph: bool = True) -> "RowSession":
         """Open a row session (rdx_rows_begin): `rows` live rows refilled one by one through `stage` staging rows, `cap` tokens per request at most.
-        Greedy search only: logits rules and sampling are switched off first. Close it (or leave the `with` block) before any other decoder call."""
+        Greedy search only: logits rules, sampling and generation log-probs are switched off first. Close it (or leave the `with` block) before any other decoder call."""
         self.set_sampling(None)
         self.set_logits_rules(None)
+        self.set_logprobs(None)
         self._conv = None                            # the KV cache is overwritten
         return RowSession(self, rows, stage, cap, eos_id, pad_id, use_graph)
 

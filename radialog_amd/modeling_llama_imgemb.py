@@ -31,7 +31,7 @@ EMB_TRAIN_PKL = "pretraining/embs/stage1_pt_instruct_blip_origlr_img448_embeddin
 
 
 class GenerateOutput(SimpleNamespace):
-    """`.sequences`, `.scores` like transformers' GreedySearchDecoderOnlyOutput."""
+    """`.sequences`, `.scores` like transformers' GreedySearchDecoderOnlyOutput; with generate(output_logprobs=True) also `.token_logprobs` and `.top_logprobs`."""
 
 
 class _BaseModel:
@@ -222,8 +222,13 @@ class LlamaForCausalLM:
                  qformer_embs: Optional[torch.Tensor] = None, eos_token_id: Optional[int] = None,
                  pad_token_id: Optional[int] = None, length_penalty: float = 1.0, early_stopping: bool = False,
                  repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-                 temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None, **_unused):
-        """do_sample=True on a model with `enable_sampling = True` set on it (the way `reuse_prefix_kv` is set): transformers' `sample` with its
+                 temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None,
+                 output_logprobs: bool = False, top_logprobs: int = 0, **_unused):
+        """output_logprobs=True (with return_dict_in_generate; no reference counterpart): the output gains `.token_logprobs` float32 [B, n], the log-prob of
+        every generated token under the scores row it was chosen from (what compute_transition_scores(sequences, scores, normalize_logits=True) gives, without
+        the [n][B][V] scores), and `.top_logprobs` = (ids int32 [B, n, k], logprobs float32 [B, n, k]), the k = top_logprobs (0 .. 8) likeliest tokens of
+        each step; entries behind a row's EOS read (0.0, -1, 0.0). Greedy search and sampling only: num_beams > 1 raises ValueError.
+        do_sample=True on a model with `enable_sampling = True` set on it (the way `reuse_prefix_kv` is set): transformers' `sample` with its
         temperature / top_k / top_p warpers (top_k=50 is GenerationConfig's default), drawn from a counter RNG: `seed`, or, when None, 63 bits
         from torch's default CPU generator, so that torch.manual_seed(s) in front of two calls makes them equal. A model without the switch
         refuses do_sample=True with NotImplementedError, as it always has: every reference call site decodes deterministically, and a caller
@@ -234,7 +239,13 @@ class LlamaForCausalLM:
                                       "`model.enable_sampling = True` to let generate(do_sample=True) sample")
         if num_beams < 1:
             raise ValueError("`num_beams` has to be an integer strictly greater than 0")
-        from .engine import LogitsRules
+        from .engine import LogitsRules, check_top_logprobs
+        if not output_logprobs and top_logprobs:
+            raise ValueError("top_logprobs needs output_logprobs=True")
+        logprobs = check_top_logprobs(top_logprobs, "top_logprobs (generation logprobs)") if output_logprobs else None
+        if logprobs is not None and num_beams > 1:
+            raise ValueError("output_logprobs / top_logprobs apply to num_beams=1 only: per-step logprobs of beams are not built (beam search returns "
+                             "sequences_scores)")
         sampling = _sampling_of(do_sample, num_beams, temperature, top_k, top_p, seed, _unused)        # ValueError before an engine exists
         # transformers builds RepetitionPenaltyLogitsProcessor, which takes a float only, when the value differs from 1.0: 1 (int) is "off" there too
         if not isinstance(repetition_penalty, float) and not (isinstance(repetition_penalty, numbers.Real) and repetition_penalty == 1):
@@ -262,10 +273,11 @@ class LlamaForCausalLM:
         # multi-turn chats (demo.py:277-305 re-sends the whole conversation every turn): with `reuse_prefix_kv` set on the model
         # the KV rows of the token prefix shared with the previous call are kept and only the new turn is prefilled (not under an
         # active logits rule: the token history is not carried across calls, the full prompt is prefilled)
-        toks, scores, n = self._engine.generate(input_ids, embs, max_new=max_new_tokens, eos_id=eos, pad_id=pad,
-                                                mask=attention_mask, output_scores=output_scores,
-                                                reuse_prefix=bool(getattr(self, "reuse_prefix_kv", False)) and attention_mask is None,
-                                                logits_rules=rules, sampling=sampling)
+        lp_kw = {} if logprobs is None else {"logprobs": logprobs}
+        toks, scores, n, *lp = self._engine.generate(input_ids, embs, max_new=max_new_tokens, eos_id=eos, pad_id=pad,
+                                                     mask=attention_mask, output_scores=output_scores,
+                                                     reuse_prefix=bool(getattr(self, "reuse_prefix_kv", False)) and attention_mask is None,
+                                                     logits_rules=rules, sampling=sampling, **lp_kw)
         toks = toks[:, :n].to(torch.int64)
         # HF stops as soon as every row has emitted EOS; the engine polls every 4th step (api_llama.hip decode_loop), so trim the all-pad tail
         if eos >= 0 and n > 0:
@@ -278,18 +290,22 @@ class LlamaForCausalLM:
             return seq
         # fresh tensors like HF's: the engine reuses its score buffer on the next call
         sc = tuple(scores[i].clone() for i in range(n)) if output_scores else None
-        return GenerateOutput(sequences=seq, scores=sc)
+        if logprobs is None:
+            return GenerateOutput(sequences=seq, scores=sc)
+        chosen, top_ids, top_lp = lp[0]
+        return GenerateOutput(sequences=seq, scores=sc, token_logprobs=chosen[:, :n], top_logprobs=(top_ids[:, :n], top_lp[:, :n]))
 
     @torch.no_grad()
     def generate_many(self, input_ids: List[torch.Tensor], dicom: Optional[List[str]] = None, qformer_embs: Optional[torch.Tensor] = None,
                       max_new_tokens=20, rows: Optional[int] = None, stage: Optional[int] = None, num_beams: int = 1, do_sample: bool = False,
                       repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-                      eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None) -> List[torch.Tensor]:
+                      eos_token_id: Optional[int] = None, pad_token_id: Optional[int] = None, output_logprobs: bool = False,
+                      top_logprobs: int = 0) -> List[torch.Tensor]:
         """Greedy generation of many prompts of different lengths through a queue (no reference counterpart; RdxEngine.generate_queue): `rows` rows decode
         at a time (default: max_batch less the staging rows) and a row whose report has ended takes the next waiting prompt. input_ids: a list of 1-D
         prompts, unpadded; dicom / qformer_embs ([N, 32, qformer_dim]) as in generate; max_new_tokens: one int or one per prompt. Returns one 1-D int64
         sequence per prompt, in order: the prompt, then what was generated up to and including EOS or up to the prompt's max_new_tokens.
-        Greedy search only: num_beams > 1, do_sample and active logits rules raise ValueError."""
+        Greedy search only: num_beams > 1, do_sample, active logits rules and output_logprobs / top_logprobs raise ValueError."""
         from .engine import LogitsRules, QUEUE_STAGE
         if self.kv_fp8:
             raise ValueError("kv_fp8: generate_many is not built on the fp8 KV cache (a row session moves model-dtype cache rows)")
@@ -297,6 +313,8 @@ class LlamaForCausalLM:
             raise ValueError("generate_many runs greedy search only (num_beams=1): beams in a row session are not built")
         if do_sample:
             raise ValueError("generate_many runs greedy search only: sampling in a row session is not built")
+        if output_logprobs or top_logprobs:
+            raise ValueError("generate_many: generation logprobs in a row session are not built (a moved row's entries would have to move with it)")
         if LogitsRules(repetition_penalty, no_repeat_ngram_size, min_new_tokens).active:
             raise ValueError("generate_many: repetition_penalty / no_repeat_ngram_size / min_new_tokens in a row session are not built")
         prompts = [torch.as_tensor(p).reshape(-1) for p in input_ids]

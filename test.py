@@ -63,6 +63,8 @@ def main(argv=None):
     p.add_argument("--do_sample", action="store_true", help="sample the report instead of decoding greedily (top_k 50, top_p 1.0, as transformers' defaults)")
     p.add_argument("--temperature", type=float, default=1.0, help="with --do_sample: divide the logits by this (1.0 = off)")
     p.add_argument("--seed", type=int, default=None, help="with --do_sample: the sampler's seed (default: drawn from torch's CPU generator)")
+    p.add_argument("--logprobs", type=int, default=None, metavar="N", help="report the mean token log-prob of every report (and keep the N = 0 .. 8 likeliest "
+                   "tokens of every step); greedy / sampled search only")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     p.add_argument("--synthetic", action="store_true", help="deterministic random-init weights (no checkpoints reachable offline)")
     p.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: decoder GEMMs in OCP e4m3 on the fp8 MFMA (weights_fp8=True)")
@@ -94,6 +96,8 @@ def main(argv=None):
     beams = max(args.num_beams, 1)
     if args.kv_fp8 and (beams > 1 or args.queue_rows > 0):
         p.error("--kv_fp8 runs greedy / sampled search only: beam search and the row queue are not built on the fp8 KV cache")
+    if args.logprobs is not None and (beams > 1 or args.queue_rows > 0 or not 0 <= args.logprobs <= 8):
+        p.error("--logprobs N (0 .. 8) runs greedy / sampled search only: per-step logprobs of beams and of the row queue are not built")
     queue_stage = 0
     if args.queue_rows > 0:
         if beams > 1 or args.do_sample or args.repetition_penalty != 1.0 or args.no_repeat_ngram_size or args.min_new_tokens:
@@ -112,7 +116,7 @@ def main(argv=None):
         images = synth.synth_images(len(dicoms), 448, seed=1000 + lo)
         lang_model.model.blip_embeddings.update(dump_embeddings(images, dicoms, dtype=args.dtype, device=local, synthetic=args.synthetic))
 
-    all_preds, all_ids, preds_history = [], [], []
+    all_preds, all_ids, preds_history, mean_lp = [], [], [], []
     if args.queue_rows > 0:
         # opt-in: every study's prompt waits in one queue; rows that finish early are refilled instead of decoding pads to the batch's longest report
         texts = []
@@ -145,7 +149,11 @@ def main(argv=None):
         out = lang_model.generate(input_ids=input_ids, dicom=batch if args.use_embs else None, return_dict_in_generate=True,
                                   output_scores=True, max_new_tokens=args.max_new_tokens, num_beams=args.num_beams,
                                   repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
-                                  min_new_tokens=args.min_new_tokens, do_sample=args.do_sample, temperature=args.temperature, seed=args.seed)
+                                  min_new_tokens=args.min_new_tokens, do_sample=args.do_sample, temperature=args.temperature, seed=args.seed,
+                                  output_logprobs=args.logprobs is not None, top_logprobs=args.logprobs or 0)
+        if args.logprobs is not None:
+            from radialog_amd.engine import mean_token_logprob
+            mean_lp.extend(mean_token_logprob(out.sequences[:, input_ids.shape[1]:], lang_model.config.eos_token_id, out.token_logprobs).tolist())
         preds = tok.batch_decode(out.sequences, skip_special_tokens=True)
         preds_history.extend(preds)
         all_preds.extend([q.split("ASSISTANT:")[1] if "ASSISTANT:" in q else q for q in preds])
@@ -181,6 +189,9 @@ def main(argv=None):
             print(f"rank {rank}: findings QA label matrix {oh.shape}, positives {int(oh.sum())}")
     if rank == 0:
         print(f"generated {ids.shape[0]} reports x {ids.shape[1]} token slots on {world} GPU(s); first: {all_preds[0][:120]!r}")
+    if args.logprobs is not None:
+        res["mean_logprob"] = mean_lp
+        print(f"rank {rank}: mean token log-prob per report: " + " ".join(f"{v:.3f}" for v in mean_lp))
     res.update({"ids": ids.cpu(), "preds": all_preds, "dicoms": dicoms, "batch_size": args.batch_size})
     lang_model.close()
     return res
