@@ -241,6 +241,17 @@ std::string S(const char* fmt, ...) {
 }
 }  // namespace
 
+std::vector<StreamW> stream_weights(rdx_ctx* c) {
+    std::vector<StreamW> ws;
+    if (!c->cfg.enable_llama) return ws;
+    ws.push_back({UNIT_LM_HEAD, 0, &c->lm_head});
+    for (int l = 0; l < (int)c->ll.size(); ++l) {
+        LlamaLayer& L = c->ll[l];
+        ws.push_back({UNIT_QKV, l, &L.wqkv}); ws.push_back({UNIT_O, l, &L.wo}); ws.push_back({UNIT_GATE_UP, l, &L.wgu}); ws.push_back({UNIT_DOWN, l, &L.wdown});
+    }
+    return ws;
+}
+
 extern "C" int rdx_finalize_weights(rdx_ctx* c) {
     if (!c) return -1;
     if (c->finalized) return fail(c, -1, "rdx_finalize_weights: already finalized");
@@ -272,32 +283,22 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
             }
         }
         if (R.rc) return R.rc;
-        // int4 streams (RDX_W_GEMM_W4) are read by the gate/up, down_proj and QKV units of the batch <= 2 step and of the 3-16-row step; o_proj streams the
-        // packed bytes of its dequantised weight (inside the fused attention launch, xrow16_k), and nothing else has an int4 kernel: those streams are dropped
-        for (int l = 0; l < f.layers; ++l) { dfree(c, c->ll[l].wo.w4); dfree(c, c->ll[l].wo.w4h); }
-        dfree(c, c->lm_head.w4); dfree(c, c->lm_head.w4h);
-        // Coded bf16 copies (rdx_common.h WcChunk) of what the batch <= 2 step streams outside the fused attention launch: every gate/up and down_proj,
-        // the QKV of layers 1.. (the chained launch's second role) and the lm_head. Layer 0's stand-alone QKV measured no lower coded and stays raw. Encoded from the PACKED buffers, which stay (prefill, batch >= 3 and the tiles the code cannot express read them).
-        // The dispatch rule of the coded path, first half (the second is coded_unit / step_chained): bf16, NOT the fp8-weight mode, both K multiples of
-        // the coded chunk, and a context whose step can run the batch <= 2 chained family at all.
+        // Which copies a weight keeps follows from who streams them (api_dispatch.hip stream_wants, the one table): an int4 stream (RDX_W_GEMM_W4) that no
+        // family's unit reads is dropped, and a weight whose coded bf16 copy (rdx_common.h WcChunk) some family reads gets one, unless it holds an int4 stream.
+        // Encoded from the PACKED buffers, which stay (prefill, batch >= 3 and the tiles the code cannot express read them). The coded format itself needs
+        // bf16, NOT the fp8-weight mode, both K multiples of the coded chunk, and a context whose step can run the batch <= 2 chained family at all.
         const bool fp8_mode = fp8_weights(c->ll[0].wqkv) || fp8_weights(c->ll[0].wgu) || fp8_weights(c->lm_head);
         LlamaDims probe = {}; probe.hidden = H; probe.heads = f.heads; probe.head_dim = 128;
-        if (f.dtype == DT_BF16 && !fp8_mode && H % WC_CHUNK_K == 0 && I % WC_CHUNK_K == 0 && chain_supported(probe, I, 1)) {
-            auto encode = [&](GemmW& W) -> int {
-                if (!W.w || W.wc || W.w4) return 0;       // (a weight with an int4 stream gets no coded copy)
-                ALLOC(c, W.wc, wc_bytes(W.Npad, W.K));
-                ALLOC(c, W.wch, wc_hdr_words(W.Npad) * sizeof(unsigned));       // header words, then dense words
-                launch_encode_wc(W.w, W.wc, W.wch, W.Npad, W.K, c->stream);
-                return 0;
-            };
-            if (int erc = encode(c->lm_head)) return erc;
-            for (int l = 0; l < f.layers; ++l) {
-                if (l > 0) if (int erc = encode(c->ll[l].wqkv)) return erc;
-                if (int erc = encode(c->ll[l].wgu)) return erc;
-                if (int erc = encode(c->ll[l].wdown)) return erc;
-            }
-            HIPCHK(c, hipStreamSynchronize(c->stream));
+        const bool coded_ok = f.dtype == DT_BF16 && !fp8_mode && H % WC_CHUNK_K == 0 && I % WC_CHUNK_K == 0 && chain_supported(probe, I, 1);
+        for (const StreamW& sw : stream_weights(c)) {
+            GemmW& W = *sw.W;
+            if (!stream_wanted(sw.u, sw.layer, WS_W4)) { dfree(c, W.w4); dfree(c, W.w4h); }
+            if (!coded_ok || !stream_wanted(sw.u, sw.layer, WS_CODED) || !W.w || W.wc || W.w4) continue;
+            ALLOC(c, W.wc, wc_bytes(W.Npad, W.K));
+            ALLOC(c, W.wch, wc_hdr_words(W.Npad) * sizeof(unsigned));       // header words, then dense words
+            launch_encode_wc(W.w, W.wc, W.wch, W.Npad, W.K, c->stream);
         }
+        HIPCHK(c, hipStreamSynchronize(c->stream));
         c->ld.hidden = H; c->ld.heads = f.heads; c->ld.head_dim = 128; c->ld.qkv_ld = c->ll[0].wqkv.Npad;
         c->ld.lora_r = f.lora_r; c->ld.lora_scale = f.lora_scale; c->ld.max_len = f.max_len; c->ld.max_pos = f.max_pos;
         c->ld.k_perm = (getenv("RDX_KPERM") ? atoi(getenv("RDX_KPERM")) : (f.max_batch * f.heads <= 256)) ? 1 : 0;

@@ -81,12 +81,11 @@ extern "C" int rdx_gemv_trace(rdx_ctx* c, int what, int layer, long long* host, 
     const size_t bytes = (size_t)max_tiles * 8 * sizeof(long long);
     HIPCHK(c, hipMalloc(&dtr, bytes));
     HIPCHK(c, hipMemsetAsync(dtr, 0, bytes, c->stream));
-    GemmArgs a = unit_args(c, &L, what == 1 ? UNIT_GATE_UP : what == 2 ? UNIT_QKV : UNIT_DOWN, B);
+    const DecUnit u = what == 1 ? UNIT_GATE_UP : what == 2 ? UNIT_QKV : UNIT_DOWN;
+    GemmArgs a = decode_family(c, B) == DEC_CHAINED ? chained_unit(c, &L, u, B) : unit_args(c, &L, u, B);      // the step's builder: with the copy the chained family streams
     if (what != 1 && what != 2) { a.out = c->dqkv; a.resid = nullptr; a.ldr = 0; }      // down_proj alone: into a scratch buffer, no residual (dx stays as it is)
     if ((a.N + 15) / 16 > max_tiles) { hipFree(dtr); return fail(c, -1, "rdx_gemv_trace: need room for %d tiles", (a.N + 15) / 16); }
     a.trace = dtr;
-    if (what == 1) a = coded_unit(c, a, L.wgu, B);                    // as the step launches them: on the coded bf16 copy where it streams one
-    if (what == 1 || what == 2) a = w4_unit(c, a, what == 1 ? L.wgu : L.wqkv, B);      // ... or on the int4 stream
     skinny(c, a, what == 1 ? EPI_SILU_MUL : EPI_NONE);
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipMemcpy(host, dtr, bytes, hipMemcpyDeviceToHost);

@@ -532,14 +532,10 @@ extern "C" int rdx_wcode_dense_words(rdx_ctx* c, int unit, int layer, uint32_t* 
     if (!c || !c->finalized) return fail(c, -1, "rdx_wcode_dense_words: a finalized context is needed");
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    std::vector<const GemmW*> ws;
-    if (c->cfg.enable_llama) {
-        ws.push_back(&c->lm_head);
-        for (const LlamaLayer& L : c->ll) { ws.push_back(&L.wqkv); ws.push_back(&L.wgu); ws.push_back(&L.wdown); }
-    }
     if (dense_total) {
         *dense_total = 0;
-        for (const GemmW* W : ws) {
+        for (const StreamW& sw : stream_weights(c)) {
+            const GemmW* W = sw.W;
             if (!W->wc || !W->wch) continue;
             const int nt = W->Npad / 16;
             std::vector<unsigned> d(nt);
@@ -563,13 +559,9 @@ extern "C" int rdx_wcode_stats(rdx_ctx* c, long long* out) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     out[0] = out[1] = out[2] = 0;
-    out[3] = c->n_wc_gemv; out[4] = c->n_wc_chain;
-    std::vector<const GemmW*> ws;
-    if (c->cfg.enable_llama) {
-        ws.push_back(&c->lm_head);
-        for (const LlamaLayer& L : c->ll) { ws.push_back(&L.wqkv); ws.push_back(&L.wo); ws.push_back(&L.wgu); ws.push_back(&L.wdown); }
-    }
-    for (const GemmW* W : ws) {
+    out[3] = c->n_stream[rdx_ctx::WK_GEMV][WS_CODED]; out[4] = c->n_stream[rdx_ctx::WK_CHAIN][WS_CODED];
+    for (const StreamW& sw : stream_weights(c)) {
+        const GemmW* W = sw.W;
         if (!W->wc || !W->wch) continue;
         const int nt = W->Npad / 16;
         std::vector<unsigned> h(nt);
@@ -604,7 +596,7 @@ extern "C" int rdx_w4_test(rdx_ctx* c, const float* W, int N, int K, void* wprim
 
 extern "C" int rdx_w4_rows_stats(rdx_ctx* c, long long out[2]) {
     if (!c || !out || !c->finalized) return fail(c, -1, "rdx_w4_rows_stats: a finalized context and an output are needed");
-    out[0] = c->n_w4_xstat16; out[1] = c->n_w4_xrow16;
+    out[0] = c->n_stream[rdx_ctx::WK_XSTAT16][WS_W4]; out[1] = c->n_stream[rdx_ctx::WK_XROW16][WS_W4];
     return 0;
 }
 
@@ -613,18 +605,17 @@ extern "C" int rdx_w4_stats(rdx_ctx* c, long long* out) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     out[0] = out[1] = out[2] = 0;
-    out[3] = c->n_w4_gemv; out[4] = c->n_w4_chain;
-    if (!c->cfg.enable_llama) return 0;
-    for (const LlamaLayer& L : c->ll)
-        for (const GemmW* W : {&L.wqkv, &L.wo, &L.wgu, &L.wdown}) {
-            if (!W->w4 || !W->w4h) continue;
-            const int nt = W->Npad / 16;
-            std::vector<unsigned> h(nt);
-            HIPCHK(c, hipMemcpy(h.data(), W->w4h, (size_t)nt * sizeof(unsigned), hipMemcpyDeviceToHost));
-            long long raw = 0;
-            for (unsigned v : h) raw += (v >> 8) & 1u;
-            out[0] += nt - raw; out[1] += raw;
-            out[2] += (long long)w4_bytes(W->Npad, W->K) + (long long)nt * 4;
-        }
+    out[3] = c->n_stream[rdx_ctx::WK_GEMV][WS_W4]; out[4] = c->n_stream[rdx_ctx::WK_CHAIN][WS_W4];
+    for (const StreamW& sw : stream_weights(c)) {
+        const GemmW* W = sw.W;
+        if (!W->w4 || !W->w4h) continue;
+        const int nt = W->Npad / 16;
+        std::vector<unsigned> h(nt);
+        HIPCHK(c, hipMemcpy(h.data(), W->w4h, (size_t)nt * sizeof(unsigned), hipMemcpyDeviceToHost));
+        long long raw = 0;
+        for (unsigned v : h) raw += (v >> 8) & 1u;
+        out[0] += nt - raw; out[1] += raw;
+        out[2] += (long long)w4_bytes(W->Npad, W->K) + (long long)nt * 4;
+    }
     return 0;
 }

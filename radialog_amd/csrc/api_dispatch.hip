@@ -42,31 +42,68 @@ GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     return a;
 }
 
-// The coded bf16 copy of a unit's weight (GemmW::wc) instead of the raw packed one: only where the step runs the batch <= 2 chained family, the option is
-// on and the copy exists (bf16, model-dtype weights: api.hip rdx_finalize_weights). Everything else -- and every tile flagged in the header -- reads a.W.
-GemmArgs coded_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B) {
-    if (c->wcode && W.wc && W.wch && decode_family(c, B) == DEC_CHAINED) { a.WC = W.wc; a.wchdr = W.wch; }
+// ---- which copy of a weight each unit streams (rdx_ctx.h): THE table. The copies a family reads for a unit of a layer where the weight holds them, int4
+// before coded; every other family and unit -- and every tile a copy's header flags -- reads the packed W. ----
+static unsigned stream_wants(DecFamily fam, DecUnit u, int layer) {
+    constexpr unsigned C = 1u << WS_CODED, Q = 1u << WS_W4;
+    //                                  QKV    o_proj  gate/up  down_proj  lm_head (of a decode step; not quantised)
+    static const unsigned chained[5] = {Q | C, 0,      Q | C,   Q | C,     C};        // batch <= 2; o_proj: hidden under the attention of the fused launch
+    static const unsigned xs16[5]    = {Q,     0,      Q,       Q,         0};        // 3-16 rows: xstat16_w4_k / xrow16_w4_k
+    // layer 0's QKV is the family's stand-alone launch (18.0 / 18.5 us raw, 18.7 / 18.6 coded: never coded); QKV of layers 1.. and down_proj: the chained launch
+    if (fam == DEC_CHAINED) return u == UNIT_QKV && layer == 0 ? Q : chained[u];
+    return fam == DEC_XS16 ? xs16[u] : 0;
+}
+// the table names copy s (coded or int4), its option is on (bf16 only) and W holds it
+static bool can_stream(rdx_ctx* c, DecFamily fam, DecUnit u, int layer, const GemmW& W, WStream s) {
+    if (!(stream_wants(fam, u, layer) >> s & 1) || c->cfg.dtype != DT_BF16) return false;
+    return s == WS_W4 ? c->w4 && W.w4 && W.w4h : c->wcode && W.wc && W.wch;
+}
+WStream unit_stream(rdx_ctx* c, DecFamily fam, DecUnit u, int layer, const GemmW& W) {
+    return can_stream(c, fam, u, layer, W, WS_W4) ? WS_W4 : can_stream(c, fam, u, layer, W, WS_CODED) ? WS_CODED : WS_RAW;
+}
+bool stream_wanted(DecUnit u, int layer, WStream s) {
+    return ((stream_wants(DEC_CHAINED, u, layer) | stream_wants(DEC_XS16, u, layer)) >> s & 1) != 0;       // (the families with a row in the table)
+}
+
+static const GemmW& unit_weight(rdx_ctx* c, const LlamaLayer* L, DecUnit u) { return u == UNIT_QKV ? L->wqkv : u == UNIT_O ? L->wo : u == UNIT_GATE_UP ? L->wgu : u == UNIT_DOWN ? L->wdown : c->lm_head; }
+// a stand-alone launch of unit u with the copy of its weight that family fam streams (QKV: the table's layer-0 entry, whichever layer's weight it is)
+static GemmArgs with_stream(rdx_ctx* c, DecFamily fam, GemmArgs a, const LlamaLayer* L, DecUnit u) {
+    const GemmW& W = unit_weight(c, L, u);
+    const WStream s = unit_stream(c, fam, u, 0, W);
+    if (s == WS_W4) { a.W4 = W.w4; a.w4hdr = W.w4h; }
+    if (s == WS_CODED) { a.WC = W.wc; a.wchdr = W.wch; }
     return a;
 }
 
-// The int4 stream of a unit's weight (GemmW::w4, RDX_W_GEMM_W4) instead of the packed bf16 copy of its dequantised values: the same rule.
-GemmArgs w4_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B) {
-    if (c->w4 && W.w4 && W.w4h && decode_family(c, B) == DEC_CHAINED) { a.W4 = W.w4; a.w4hdr = W.w4h; }
-    return a;
-}
-
-// ... and where the step runs the 3-16-row family in bf16: QKV, gate/up (xstat16_w4_k) and down_proj (xrow16_w4_k) take the int4 kernel when the
-// arguments carry the stream and the kernel's own predicate accepts them (api_llama.hip step_xs16); o_proj has no stream (rdx_finalize_weights)
-GemmArgs w4_rows_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B) {
-    if (c->w4 && c->cfg.dtype == DT_BF16 && W.w4 && W.w4h && decode_family(c, B) == DEC_XS16) { a.W4 = W.w4; a.w4hdr = W.w4h; }
-    return a;
+GemmArgs chained_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
+    return u == UNIT_DOWN ? unit_args(c, L, u, B) : with_stream(c, DEC_CHAINED, unit_args(c, L, u, B), L, u);       // (down_proj's entry is its role in chain_args)
 }
 
 GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
     GemmArgs a = unit_args(c, L, u, B);
     if (u == UNIT_GATE_UP) a.out_packed = ACT_BLK32;
     if (u == UNIT_O || u == UNIT_DOWN) a.xpacked = ACT_BLK32;
-    return a;
+    return with_stream(c, DEC_XS16, a, L, u);
+}
+
+ChainArgs chain_args(rdx_ctx* c, int l, int B) {
+    const rdx_config& f = c->cfg;
+    const LlamaLayer &L0 = c->ll[0], &L = c->ll[l];
+    const LlamaLayer* Ln = l + 1 < f.layers ? &c->ll[l + 1] : nullptr;      // the last launch has no QKV role
+    ChainArgs ca; memset(&ca, 0, sizeof(ca));
+    ca.hidden = f.hidden; ca.inter = f.inter; ca.qkv_n = L0.wqkv.Npad; ca.qkv_ld = c->ld.qkv_ld; ca.B = B; ca.eps = f.rms_eps; ca.layer = l;
+    ca.dx = c->dx; ca.dqkv = c->dqkv; ca.dgu = c->dgu; ca.ctr = c->d_cctr; ca.err = c->d_err; ca.naps = c->chain_naps;
+    ca.w8 = (L0.wqkv.w8 && L0.wdown.w8 && f.hidden % 64 == 0 && f.inter % 64 == 0) ? 1 : 0;       // fp8 weights: the chained roles stream the e4m3 bytes too
+    ca.wdown = L.wdown.w; ca.wdown8 = L.wdown.w8; ca.sdown = L.wdown.scale;
+    if (Ln) { ca.wqkv = Ln->wqkv.w; ca.wqkv8 = Ln->wqkv.w8; ca.sqkv = Ln->wqkv.scale; ca.attn_norm = Ln->attn_norm; }
+    // one copy per launch: int4 if both roles' weights hold a stream (decode_chain_w4_k), else coded if both hold a copy (decode_chain_wc_k), else the
+    // packed weights; never beside the fp8 bytes. (The coded pointers travel whenever the copies exist, as they always have: wc = 0 reads none of them.)
+    auto both = [&](WStream t) { return can_stream(c, DEC_CHAINED, UNIT_DOWN, l, L.wdown, t) && (!Ln || can_stream(c, DEC_CHAINED, UNIT_QKV, l + 1, Ln->wqkv, t)); };
+    ca.wc = ca.w8 ? WS_RAW : both(WS_W4) ? WS_W4 : both(WS_CODED) ? WS_CODED : WS_RAW;
+    const bool q = ca.wc == WS_W4;
+    ca.cdown = q ? L.wdown.w4 : L.wdown.wc; ca.hdown = q ? L.wdown.w4h : L.wdown.wch;
+    if (Ln) { ca.cqkv = q ? Ln->wqkv.w4 : Ln->wqkv.wc; ca.hqkv = q ? Ln->wqkv.w4h : Ln->wqkv.wch; }
+    return ca;
 }
 
 GemmArgs blk_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
@@ -148,7 +185,7 @@ PromptPlan prompt_plan(rdx_ctx* c, int B, int T) {
 GemmArgs prompt_unit(rdx_ctx* c, const PromptPlan& p, const LlamaLayer* L, DecUnit u) {
     const rdx_config& f = c->cfg;
     const int H = f.hidden;
-    const GemmW& W = u == UNIT_QKV ? L->wqkv : u == UNIT_O ? L->wo : u == UNIT_GATE_UP ? L->wgu : L->wdown;
+    const GemmW& W = unit_weight(c, L, u);
     GemmArgs a;
     switch (u) {
     case UNIT_QKV: a = gargs(c->pxn, H, W, nullptr, c->pqkv, c->ld.qkv_ld, p.M); a.N = W.Npad; break;
@@ -236,9 +273,22 @@ void skinny(rdx_ctx* c, GemmArgs a, int epi) {
             return;
         }
     }
-    if (skinny_w4_supported(c->cfg.dtype, a, epi) && !xstat32_supported(a, epi)) ++c->n_w4_gemv;
-    else if (skinny_wc_supported(c->cfg.dtype, a, epi) && !xstat32_supported(a, epi)) ++c->n_wc_gemv;       // launch_skinny_gemm's own choice, counted for the tests
-    launch_skinny_gemm(c->cfg.dtype, a, epi, c->stream);
+    ++c->n_stream[rdx_ctx::WK_GEMV][launch_skinny_gemm(c->cfg.dtype, a, epi, c->stream)];       // the launcher's own choice, counted
+}
+
+void launch_chain(rdx_ctx* c, int l, int B) {
+    ChainArgs ca = chain_args(c, l, B);
+    ca.trace = l == c->chain_trace_layer ? c->chain_trace : nullptr;
+    ++c->n_stream[rdx_ctx::WK_CHAIN][ca.wc];
+    launch_decode_chain(c->cfg.dtype, ca, l + 1 < c->cfg.layers, c->stream);
+}
+
+void launch_xs16(rdx_ctx* c, const GemmArgs& a, int epi) {
+    const int dt = c->cfg.dtype;
+    const bool row = epi == EPI_RESID, w4 = row ? xrow16_w4_supported(dt, a) : xstat16_w4_supported(dt, a, epi);
+    ++c->n_stream[row ? rdx_ctx::WK_XROW16 : rdx_ctx::WK_XSTAT16][w4 ? WS_W4 : WS_RAW];
+    if (row) { if (w4) launch_xrow16_w4(a, c->stream); else launch_xrow16(dt, a, c->stream); }
+    else { if (w4) launch_xstat16_w4(a, epi, c->stream); else launch_xstat16(dt, a, epi, c->stream); }
 }
 
 int take_unsupported(rdx_ctx* c) {

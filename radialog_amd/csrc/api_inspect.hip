@@ -114,33 +114,26 @@ extern "C" int rdx_time(rdx_ctx* c, int what, int iters, float* ms_host) {
         const bool resid_unit = u == UNIT_O || u == UNIT_DOWN;
         // batch 3-16 decodes on xs16.hip (norm-prologue xstat16_k, un-split xrow16_k): time THOSE kernels, not the 32-row family the step never launches there
         x16 = proj && fam == DEC_XS16;
-        GemmArgs pn;
-        bool hoisted = false;
+        GemmArgs pn; bool hoisted = false;
         if (proj && !x16 && !resid_unit) { pn = skinny_prenorm(c, unit_args(c, &c->ll[0], u, B), epi); hoisted = !pn.norm_w; }
         HIPCHK(c, hipEventRecord(e0, c->stream));
         for (int i = 0; i < iters; ++i) {
             for (int l = 0; l < (what == 5 ? 1 : f.layers); ++l, ++launches) {
                 const int li = same_layer ? 0 : l;
                 const LlamaLayer* L = &c->ll[li];
-                if (what == 6) {        // decode attention at the current slot (re-appends the same KV row: idempotent)
-                    run_decode_attention(c, dec_attn_args(c, li), li, B);
-                } else if (x16) {
-                    GemmArgs a = xs16_unit(c, L, u, B);
-                    if (resid_unit) { a.out = c->dqkv; launch_xrow16(dt, a, c->stream); }
-                    else launch_xstat16(dt, a, epi, c->stream);
-                } else if (resid_unit) {
-                    GemmArgs a = unit_args(c, L, u, B);
-                    a.out = c->dqkv; a.resid = nullptr; a.ldr = 0;
+                if (what == 6) { run_decode_attention(c, dec_attn_args(c, li), li, B); continue; }       // at the current slot (re-appends the same KV row: idempotent)
+                // the builder of the step's family (with the copy of the weight that family streams) into the step's choose-and-count launchers
+                GemmArgs a = fam == DEC_CHAINED ? chained_unit(c, L, u, B) : x16 ? xs16_unit(c, L, u, B) : unit_args(c, L, u, B);
+                if (resid_unit) a.out = c->dqkv;
+                if (x16) launch_xs16(c, a, resid_unit ? EPI_RESID : epi);
+                else if (resid_unit) {
+                    a.resid = nullptr; a.ldr = 0;
                     const bool split = u == UNIT_O ? B >= xs_min_rows() && c->kslab && xsplit32_groups(ksplit_args(a)) : down_split_ok(c, *L, B);
                     if (split) launch_xsplit32(dt, ksplit_args(a), c->kslab, c->stream);
                     else skinny(c, a, EPI_NONE);
-                } else {
-                    GemmArgs a = unit_args(c, L, u, B);
-                    // as the step launches them: on the coded bf16 copy where it streams one (batch <= 2 chained family, "wcode" on)
-                    if (u != UNIT_QKV) a = coded_unit(c, a, u == UNIT_GATE_UP ? L->wgu : c->lm_head, B);      // (layer 0's stand-alone QKV is raw in the step)
-                    if (u == UNIT_QKV || u == UNIT_GATE_UP) a = w4_unit(c, a, u == UNIT_QKV ? L->wqkv : L->wgu, B);            // ... or on the int4 stream ("w4" on)
+                } else {        // (a hoisted RMSNorm leaves skinny() nothing to put in front)
                     if (hoisted) { a = prenormed(c, a); a.xpacked = pn.xpacked; a.xscale = pn.xscale; a.xgroups = pn.xgroups; }
-                    launch_skinny_gemm(dt, a, epi, c->stream);
+                    skinny(c, a, epi);
                 }
             }
         }
@@ -151,5 +144,5 @@ extern "C" int rdx_time(rdx_ctx* c, int what, int iters, float* ms_host) {
     HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
     hipEventDestroy(e0); hipEventDestroy(e1);
     *ms_host = ms / (float)launches;
-    return x16 ? take_unsupported(c) : 0;
+    return take_unsupported(c);
 }

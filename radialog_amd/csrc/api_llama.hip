@@ -38,19 +38,16 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
     // (generation log-probs likewise: logprob_step_k reads the row)
     if ((c->rules_on || c->sampling.do_sample || c->logprobs >= 0) && !logits) { logits = c->rule_logits; out_step = nullptr; }
     auto lm = [&](GemmArgs a) { a.X = x; a.out = logits; a.out_step = out_step; a.out_step_stride = step_stride; return a; };
-    switch (decode_family(c, B)) {
+    switch (const DecFamily fam = decode_family(c, B); fam) {
     case DEC_UNSUPPORTED: c->unsupported = k_need_blk; return;
     // 33-128 rows: final RMSNorm into the fragment-packed row tiles (after the last layer it also folds in the K-split down_proj's slabs), lm_head in row blocks
     case DEC_BLK: launch_xstat_blk(f.dtype, norm_in_front(c, lm(blk_unit(c, nullptr, UNIT_LM_HEAD, B))), EPI_LOGITS, c->stream); break;
     case DEC_BLK8: launch_xstat_blk8(f.dtype, norm_in_front(c, lm(blk8_unit(c, nullptr, UNIT_LM_HEAD, B))), EPI_LOGITS, c->stream); break;
     case DEC_XS16:       // batch 3-16 decode: the final RMSNorm is the kernel's prologue (the prompt's last rows, in datt, go the generic way)
-        if (x == c->dx) { launch_xstat16(f.dtype, lm(xs16_unit(c, nullptr, UNIT_LM_HEAD, B)), EPI_LOGITS, c->stream); break; }
+        if (x == c->dx) { launch_xs16(c, lm(xs16_unit(c, nullptr, UNIT_LM_HEAD, B)), EPI_LOGITS); break; }
         [[fallthrough]];
-    default: {
-        GemmArgs a = lm(unit_args(c, nullptr, UNIT_LM_HEAD, B));
-        if (advance) a = coded_unit(c, a, c->lm_head, B);       // a decode step of the batch <= 2 family: the coded bf16 copy (the prompt's last rows: the raw one)
-        skinny(c, a, EPI_LOGITS);
-    }
+    default:       // the prompt's last rows are no decode step: the unit's base form, whichever family the batch decodes on
+        skinny(c, lm(advance && fam == DEC_CHAINED ? chained_unit(c, nullptr, UNIT_LM_HEAD, B) : unit_args(c, nullptr, UNIT_LM_HEAD, B)), EPI_LOGITS);
     }
     StepTail t = {};
     t.eos_id = c->cur_eos; t.pad_id = c->cur_pad; t.max_new = c->cur_max_new; t.out_tokens = c->cur_tokens; t.unfinished = c->d_unf;
@@ -511,27 +508,18 @@ static void step_blk8(rdx_ctx* c, int B) {
 }
 
 // batch 3-16 (xs16.hip): five launches per layer -- QKV with the RMSNorm as its prologue, attention (output fragment-packed), o_proj with the
-// residual epilogue, gate/up with the RMSNorm prologue (SwiGLU output fragment-packed), down_proj with the residual epilogue
-// int4 group-quantised weights (RDX_W_GEMM_W4, "w4" on, bf16): QKV, gate/up and down_proj stream their int4 copies (w4_rows_unit: xstat16_w4_k /
-// xrow16_w4_k, the same output bits); o_proj streams the packed bytes of its dequantised weight, the lm_head is not quantised
+// residual epilogue, gate/up with the RMSNorm prologue (SwiGLU output fragment-packed), down_proj with the residual epilogue. Which units stream an int4 copy:
+// the table (api_dispatch.hip stream_wants) through xs16_unit; launch_xs16 takes the int4 kernel where the arguments carry one.
 static void step_xs16(rdx_ctx* c, int B) {
-    const int dt = c->cfg.dtype;
-    hipStream_t s = c->stream;
-    auto xstat = [&](const GemmArgs& a, int epi) {
-        if (xstat16_w4_supported(dt, a, epi)) { ++c->n_w4_xstat16; launch_xstat16_w4(a, epi, s); }
-        else launch_xstat16(dt, a, epi, s);
-    };
     for (int l = 0; l < c->cfg.layers; ++l) {
         const LlamaLayer* L = &c->ll[l];
-        xstat(w4_rows_unit(c, xs16_unit(c, L, UNIT_QKV, B), L->wqkv, B), EPI_NONE);
+        launch_xs16(c, xs16_unit(c, L, UNIT_QKV, B), EPI_NONE);
         DecAttnArgs at = dec_attn_args(c, l);
         at.out_packed = ACT_BLK32;
         run_decode_attention(c, at, l, B);
-        launch_xrow16(dt, xs16_unit(c, L, UNIT_O, B), s);
-        xstat(w4_rows_unit(c, xs16_unit(c, L, UNIT_GATE_UP, B), L->wgu, B), EPI_SILU_MUL);
-        const GemmArgs dn = w4_rows_unit(c, xs16_unit(c, L, UNIT_DOWN, B), L->wdown, B);
-        if (xrow16_w4_supported(dt, dn)) { ++c->n_w4_xrow16; launch_xrow16_w4(dn, s); }
-        else launch_xrow16(dt, dn, s);
+        launch_xs16(c, xs16_unit(c, L, UNIT_O, B), EPI_RESID);
+        launch_xs16(c, xs16_unit(c, L, UNIT_GATE_UP, B), EPI_SILU_MUL);
+        launch_xs16(c, xs16_unit(c, L, UNIT_DOWN, B), EPI_RESID);
     }
 }
 
@@ -577,46 +565,15 @@ static void step_generic(rdx_ctx* c, int B) {
 // batch <= 2: QKV of layer 0 and every gate/up stand-alone, attention + o_proj fused, down(l) -> QKV(l+1) chained inside one launch by the fence-free hand-off.
 // The hand-off counter shards of the chained launches are cleared by greedy_step_k at the end of the previous step (and of the prefill): a memset node at the
 // head of the step graph was observed to race with the first producers. The fused launch's tagged granules need no clearing: step_tail bumps their epoch. evs: an event pair around every chained launch (rdx_time 7).
+// Which copy of its weight each launch streams: the table (api_dispatch.hip stream_wants) through chained_unit and chain_args.
 static void step_chained(rdx_ctx* c, int B, std::vector<hipEvent_t>* evs) {
-    const rdx_config& f = c->cfg;
-    hipStream_t s = c->stream;
-    ChainArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.hidden = f.hidden; ca.inter = f.inter; ca.qkv_n = c->ll[0].wqkv.Npad; ca.qkv_ld = c->ld.qkv_ld; ca.B = B; ca.eps = f.rms_eps;
-    ca.dx = c->dx; ca.dqkv = c->dqkv; ca.dgu = c->dgu; ca.ctr = c->d_cctr; ca.err = c->d_err; ca.naps = c->chain_naps;
-    const LlamaLayer& L0 = c->ll[0];        // fp8 weights: the chained roles stream the e4m3 bytes too
-    ca.w8 = (L0.wqkv.w8 && L0.wdown.w8 && f.hidden % 64 == 0 && f.inter % 64 == 0) ? 1 : 0;
-    auto mark = [&] { if (evs) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, s); evs->push_back(e); } };
-    // gate/up and the lm_head stream the coded bf16 copies of their weights where those exist (coded_unit), the chained launch likewise (ca.wc);
-    // layer 0's QKV (one launch per step, three workgroups per CU: 18.0 / 18.5 us raw, 18.7 / 18.6 coded) and o_proj stay raw
-    // int4 group-quantised weights (RDX_W_GEMM_W4, "w4" on): layer 0's QKV, gate/up and both roles of the chained launch stream their int4 copies
-    // (w4_unit, ca.wc = 2); o_proj streams the packed bytes of its dequantised weight, the lm_head is not quantised
-    skinny(c, w4_unit(c, unit_args(c, &L0, UNIT_QKV, B), L0.wqkv, B), EPI_NONE);
-    for (int l = 0; l < f.layers; ++l) {
+    auto mark = [&] { if (evs) { hipEvent_t e; hipEventCreate(&e); hipEventRecord(e, c->stream); evs->push_back(e); } };
+    skinny(c, chained_unit(c, &c->ll[0], UNIT_QKV, B), EPI_NONE);
+    for (int l = 0; l < c->cfg.layers; ++l) {
         attn_oproj(c, l, B);
-        skinny(c, w4_unit(c, coded_unit(c, unit_args(c, &c->ll[l], UNIT_GATE_UP, B), c->ll[l].wgu, B), c->ll[l].wgu, B), EPI_SILU_MUL);
+        skinny(c, chained_unit(c, &c->ll[l], UNIT_GATE_UP, B), EPI_SILU_MUL);
         mark();
-        ca.layer = l;
-        {       // the layer's pointers by value: down_proj of l, norm + QKV of l + 1 (the last launch has no QKV role)
-            const LlamaLayer& L = c->ll[l];
-            const LlamaLayer* Ln = l + 1 < f.layers ? &c->ll[l + 1] : nullptr;
-            ca.wdown = L.wdown.w; ca.wdown8 = L.wdown.w8; ca.sdown = L.wdown.scale;
-            ca.wqkv = Ln ? Ln->wqkv.w : nullptr; ca.wqkv8 = Ln ? Ln->wqkv.w8 : nullptr; ca.sqkv = Ln ? Ln->wqkv.scale : nullptr;
-            ca.attn_norm = Ln ? Ln->attn_norm : nullptr;
-            // coded bf16 copies of both roles' weights ("wcode" on, not the fp8 stream): decode_chain_wc_k
-            ca.wc = (c->wcode && !ca.w8 && L.wdown.wc && L.wdown.wch && (!Ln || (Ln->wqkv.wc && Ln->wqkv.wch))) ? 1 : 0;
-            ca.cdown = L.wdown.wc; ca.hdown = L.wdown.wch;
-            ca.cqkv = Ln ? Ln->wqkv.wc : nullptr; ca.hqkv = Ln ? Ln->wqkv.wch : nullptr;
-            if (c->w4 && !ca.w8 && f.dtype == DT_BF16 && L.wdown.w4 && L.wdown.w4h && (!Ln || (Ln->wqkv.w4 && Ln->wqkv.w4h))) {       // decode_chain_w4_k
-                ca.wc = 2;
-                ca.cdown = L.wdown.w4; ca.hdown = L.wdown.w4h;
-                ca.cqkv = Ln ? Ln->wqkv.w4 : nullptr; ca.hqkv = Ln ? Ln->wqkv.w4h : nullptr;
-                ++c->n_w4_chain;
-            } else
-            if (ca.wc && f.dtype == DT_BF16) ++c->n_wc_chain;
-        }
-        ca.trace = l == c->chain_trace_layer ? c->chain_trace : nullptr;
-        launch_decode_chain(f.dtype, ca, l + 1 < f.layers, s);
+        launch_chain(c, l, B);
         mark();
     }
 }

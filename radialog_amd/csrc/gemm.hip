@@ -383,16 +383,16 @@ static void launch_skinny_T(const GemmArgs& a, int epi, hipStream_t s) {
     }
 }
 
-void launch_skinny_gemm(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
+WStream launch_skinny_gemm(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
     // (fp8 weights: only with the e4m3 activation block, ACT_BLK64_E4M3 -- the batch >= 3 rule of the fp8 scheme; callers go through skinny())
-    if (xstat32_supported(a, epi) && (!(a.W8 && a.wscale) || (a.xpacked == ACT_BLK64_E4M3 && a.xscale))) { launch_xstat32(dtype, a, epi, s); return; }
+    if (xstat32_supported(a, epi) && (!(a.W8 && a.wscale) || (a.xpacked == ACT_BLK64_E4M3 && a.xscale))) { launch_xstat32(dtype, a, epi, s); return WS_RAW; }
     if (skinny_w4_supported(dtype, a, epi)) {       // int4 weights: likewise
         const bool norm = a.norm_w != nullptr;
         const int waves = skinny_lds_waves(a);
         if (waves == 16) { if (norm) launch_skinny_w4<true, 16>(a, epi, s); else launch_skinny_w4<false, 16>(a, epi, s); }
         else if (waves == 4) { if (norm) launch_skinny_w4<true, 4>(a, epi, s); else launch_skinny_w4<false, 4>(a, epi, s); }
         else { if (norm) launch_skinny_w4<true, 8>(a, epi, s); else launch_skinny_w4<false, 8>(a, epi, s); }
-        return;
+        return WS_W4;
     }
     if (skinny_wc_supported(dtype, a, epi)) {       // coded weights: the wave counts of launch_skinny_T (the K split is part of the sums)
         const bool norm = a.norm_w != nullptr;
@@ -400,9 +400,10 @@ void launch_skinny_gemm(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
         if (waves == 16) { if (norm) launch_skinny_wc<true, 16>(a, epi, s); else launch_skinny_wc<false, 16>(a, epi, s); }
         else if (waves == 4) { if (norm) launch_skinny_wc<true, 4>(a, epi, s); else launch_skinny_wc<false, 4>(a, epi, s); }
         else { if (norm) launch_skinny_wc<true, 8>(a, epi, s); else launch_skinny_wc<false, 8>(a, epi, s); }
-        return;
+        return WS_CODED;
     }
     RDX_DISPATCH_T(dtype, T, launch_skinny_T<T>(a, epi, s));
+    return WS_RAW;
 }
 
 // ------------------------------------------------------------------------------------------------------------------

@@ -123,9 +123,10 @@ struct rdx_ctx {
     bool w4 = true;                  // ... their int4 stream (GemmW::w4) where the weight has one, and so do QKV, gate/up and down_proj of the 3-16-row family; rdx_set_option("w4", 0): the packed bf16 bytes of W' (same bits)
     int* w4_bad = nullptr;           // device flag of the int4 quantiser: the weight held an Inf / NaN
     bool has_fp8_w = false, has_w4_w = false;     // kinds of GEMM weights set so far (RDX_W_GEMM_FP8 and RDX_W_GEMM_W4 do not mix)
-    long long n_w4_gemv = 0, n_w4_chain = 0;      // launches of skinny_gemm_w4_k / decode_chain_w4_k (a captured graph counts once): rdx_w4_stats
-    long long n_w4_xstat16 = 0, n_w4_xrow16 = 0;  // launches of xstat16_w4_k / xrow16_w4_k by the 3-16-row step (likewise): rdx_w4_rows_stats
-    long long n_wc_gemv = 0, n_wc_chain = 0;      // launches of skinny_gemm_wc_k / decode_chain_wc_k issued by this context (a captured graph counts once): rdx_wcode_stats
+    // launches this context issued, by kernel and by the copy it streamed, counted where the choice is made (api_dispatch.hip skinny / launch_chain /
+    // launch_xs16; a captured graph counts once). The coded and int4 columns are what rdx_wcode_stats, rdx_w4_stats and rdx_w4_rows_stats report.
+    enum WKernel { WK_GEMV, WK_CHAIN, WK_XSTAT16, WK_XROW16, WK_COUNT };
+    long long n_stream[WK_COUNT][3] = {};         // [kernel][WStream]
     int chain_naps = 1;             // poll back-off of the chained launch (x s_sleep(8) between polls)
     long long* chain_trace = nullptr; int chain_trace_layer = -1;     // rdx_gemv_trace(7): device timeline buffer of ONE chained launch of the next step
     long long* ao_trace = nullptr; int ao_trace_layer = -1;           // rdx_gemv_trace(8): the same for ONE fused attention + o_proj launch
@@ -239,11 +240,25 @@ DecAttnArgs dec_attn_args(rdx_ctx* c, int layer);                               
 // a unit in its base form: row-major activations, the RMSNorm in front of QKV / gate-up / lm_head as the kernel's prologue (norm_w), the residual of o_proj /
 // down_proj as its epilogue. L may be null for UNIT_LM_HEAD, whose callers set X (when not dx), out and out_step.
 GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);
-// ... and in the layout of a family (what its probe checks IS what its step function launches):
-GemmArgs coded_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B);         // batch <= 2 chained family, "wcode" on: the GEMV streams W's coded bf16 copy
-GemmArgs w4_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B);            // ... "w4" on: W's int4 stream, where it has one
-GemmArgs w4_rows_unit(rdx_ctx* c, GemmArgs a, const GemmW& W, int B);       // 3-16-row family, bf16, "w4" on: likewise (xstat16_w4_k / xrow16_w4_k)
+// Which copy of a unit's weight a family streams (WStream, rdx_kernels.h): ONE table, stream_wants in api_dispatch.hip ("Which copy of
+// a weight each unit streams"). unit_stream: the table's entry for (family, unit, layer), narrowed to what the options ("w4", "wcode"; bf16 only) allow and W
+// holds. Of the chained family, UNIT_DOWN and UNIT_QKV of layers >= 1 are the two roles of the chained launch (chain_args), UNIT_QKV of layer 0 the
+// stand-alone launch. The table says what a family wants; whether a kernel takes the arguments stays with its own *_supported predicate.
+WStream unit_stream(rdx_ctx* c, DecFamily fam, DecUnit u, int layer, const GemmW& W);
+bool stream_wanted(DecUnit u, int layer, WStream s);      // some family's entry for (unit, layer) names s: what rdx_finalize_weights keeps and encodes
+struct StreamW { DecUnit u; int layer; GemmW* W; };
+std::vector<StreamW> stream_weights(rdx_ctx* c);           // (api.hip) every decoder weight that can hold a stream: the lm_head, then each layer's four projections
+// ... and in the layout of a family, with the copy that family streams attached (what its probe checks IS what its step function, the timers and the trace
+// hooks launch). A family's builder is for code that has decided the family: it does not ask decode_family.
+// the chained family's stand-alone launches: layer 0's QKV (the timers run that launch on every layer's weight), gate/up and the step's lm_head; o_proj (in
+// the fused launch) and down_proj (a role of the chained launch) have none and come back in their base form
+GemmArgs chained_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);
 GemmArgs xs16_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);      // one row tile: gate/up writes, o_proj / down_proj read the fragment-packed block
+ChainArgs chain_args(rdx_ctx* c, int l, int B);           // the chained launch of layer l: down_proj(l), norm + QKV(l + 1) (none behind the last layer), their stream
+// The launches that choose between copies of a weight choose once and count what they chose (rdx_ctx::n_stream), for the step, the timers and the trace hooks:
+// skinny() (launch_skinny_gemm's choice: the raw, coded or int4 GEMV, or xstat32_k) and
+void launch_chain(rdx_ctx* c, int l, int B);                                // launch_decode_chain on chain_args (+ the trace pointer of rdx_gemv_trace 7)
+void launch_xs16(rdx_ctx* c, const GemmArgs& a, int epi);                   // xstat16_k (norm-prologue units) / xrow16_k (EPI_RESID), or their int4 forms
 GemmArgs blk_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);       // row blocks: fragment-packed row tiles of 16 in and (gate/up) out
 GemmArgs blk8_unit(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B);      // ... fp8 weights: e4m3 blocks + xscale in; 64-deep model-dtype blocks into the K-split o_proj / down_proj
 GemmArgs ksplit_args(GemmArgs a);                  // o_proj / down_proj K-split at 3-32 rows: X is the fragment-packed 32-row block (fp8 weights: 64-deep)

@@ -58,6 +58,8 @@ struct GemmArgs {
     // packed bf16 bytes from W). W is the packed bf16 copy of the dequantised weight W': the same bits, four times the bytes. Null: not streamed.
     const void* W4; const unsigned* w4hdr;
 };
+// which of these copies a launch streams: W, WC or W4 (the values double as ChainArgs::wc)
+enum WStream { WS_RAW = 0, WS_CODED = 1, WS_W4 = 2 };
 
 // int4 group-quantised weights (radialog_amd/w4.py): groups of 128 k of one row, per (tile, 128 k) one chunk of 1 KiB of nibbles + 16 bf16 scales
 constexpr int W4_CHUNK_K = 128, W4_CHUNK_BYTES = 64 * 16 + 16 * 2;
@@ -132,9 +134,10 @@ void launch_pack_weight(int dtype, const float* src, void* dst, int N, int K, in
 // dequantised weights in the model dtype, standard fragment order (K % 64 == 0)
 void launch_pack_weight_fp8(int dtype, const float* src, void* dst8, float* scale, void* dst, int N, int K, int Npad, hipStream_t s);
 // skinny GEMM. A fused RMSNorm (a.norm_w != null) is only honoured when skinny_fits_lds(M, K); otherwise the caller
-// must normalise first (launch_rmsnorm) and pass norm_w = null.
+// must normalise first (launch_rmsnorm) and pass norm_w = null. Returns the copy the kernel it chose streams: WS_W4 (skinny_gemm_w4_k) or WS_CODED
+// (skinny_gemm_wc_k) where the arguments carry that copy and its predicate accepts them, else WS_RAW (the GEMV on W / W8, or xstat32_k).
 bool skinny_fits_lds(int M, int K);
-void launch_skinny_gemm(int dtype, const GemmArgs& a, int epi, hipStream_t s);
+WStream launch_skinny_gemm(int dtype, const GemmArgs& a, int epi, hipStream_t s);
 bool xstat32_supported(const GemmArgs& a, int epi);
 void launch_xstat32(int dtype, const GemmArgs& a, int epi, hipStream_t s);
 // K-split activation-stationary GEMM for the 256-tile projections at 16 < M <= 32: fp32 partial slabs [groups][32][N], combined

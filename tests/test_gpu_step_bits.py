@@ -12,6 +12,9 @@ down_proj) and its fp8 form (40 and 128 rows), and the small config, whose width
 behind a stand-alone RMSNorm). The prompts' prefill variants (wstat / row-block kernels at 72 rows, the K-split prompt down_proj, the tile
 GEMMs above 384 rows, gemm8) ride along in the same digests.
 
+The cases on an int4 engine ("weights_w4", with and without the "w4" option), plain bf16 at 2 rows and "wcode=0" were recorded the same way, on the
+commit before the choice of which copy of a weight each unit streams moved into one table (csrc/api_dispatch.hip stream_wants): host code again.
+
 (The commit the digests come from read RDX_BLK_DOWN once per PROCESS, in a function-local static: there the RDX_BLK_DOWN=0 case had to be
 recorded by a run of its own.)"""
 import hashlib
@@ -34,7 +37,8 @@ T_PROMPT, N_NEW = 72, 8
 ENV_SWITCHES = ("RDX_FUSE_AO", "RDX_CHAIN", "RDX_BLK_DOWN")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "step_bits.json")
 
-# (widths, batch, dtype, fp8 weights, setting): setting = "default", an environment switch "NAME=0" read at rdx_create, or an option "name=0"
+# (widths, batch, dtype, fp8 weights, setting): setting = "default", an environment switch "NAME=0" read at rdx_create, an option "name=0", or
+# "weights_w4" (an int4 engine, RdxEngine(weights_w4=True)), alone or with an option behind a comma
 CASES = [("prod2", 1, "bf16", False, "default"), ("prod2", 1, "f16", False, "default"),
          ("prod2", 1, "bf16", False, "RDX_FUSE_AO=0"), ("prod2", 1, "bf16", False, "RDX_CHAIN=0"), ("prod2", 1, "bf16", False, "prompt_blk=0"),
          ("prod2", 2, "bf16", True, "default"),
@@ -46,7 +50,13 @@ CASES = [("prod2", 1, "bf16", False, "default"), ("prod2", 1, "f16", False, "def
          ("prod2", 33, "bf16", False, "RDX_BLK_DOWN=0"),
          ("prod2", 40, "bf16", True, "default"), ("prod2", 128, "bf16", True, "default"),
          ("small", 1, "bf16", False, "default"), ("small", 1, "f16", False, "default"),
-         ("small", 4, "bf16", False, "default"), ("small", 18, "bf16", False, "default")]
+         ("small", 4, "bf16", False, "default"), ("small", 18, "bf16", False, "default"),
+         # which copy of a weight each unit streams (api_dispatch.hip unit_stream): int4 in the chained family (1, 2), in xs16 (3, 16) and not beyond (17),
+         # the packed copy with "w4" off; plain bf16: the coded copies at 2 rows, the raw ones with "wcode" off
+         ("prod2", 1, "bf16", False, "weights_w4"), ("prod2", 2, "bf16", False, "weights_w4"), ("prod2", 3, "bf16", False, "weights_w4"),
+         ("prod2", 16, "bf16", False, "weights_w4"), ("prod2", 17, "bf16", False, "weights_w4"),
+         ("prod2", 1, "bf16", False, "weights_w4,w4=0"), ("prod2", 3, "bf16", False, "weights_w4,w4=0"),
+         ("prod2", 2, "bf16", False, "default"), ("prod2", 1, "bf16", False, "wcode=0")]
 
 
 def _key(which, B, dtype, fp8, setting):
@@ -60,12 +70,13 @@ def _case_digests(env, which, B, dtype, fp8, setting):
     cfg = small_cfg() if which == "small" else RaDialogCfg(llama=LlamaCfg(layers=2, qformer_dim=192))
     for name in ENV_SWITCHES:
         env.delenv(name, raising=False)
-    name, _, value = setting.partition("=")
+    _, w4, setting = setting.rpartition("weights_w4")
+    name, _, value = (setting.lstrip(",") or "default").partition("=")
     if name in ENV_SWITCHES:
         env.setenv(name, value)
-    eng = RdxEngine(cfg, dtype=dtype, device=0, max_batch=B, max_len=128, lora=True, vision=False, weights_fp8=fp8)
+    eng = RdxEngine(cfg, dtype=dtype, device=0, max_batch=B, max_len=128, lora=True, vision=False, weights_fp8=fp8, weights_w4=bool(w4))
     eng.load_weights(synth_getter(cfg, eng.device, lora=True), vision=False)
-    if setting != "default" and name not in ENV_SWITCHES:
+    if name != "default" and name not in ENV_SWITCHES:
         eng.set_option(name, int(value))
     ids = synth.synth_prompt_ids(B, T_PROMPT, vocab=cfg.llama.vocab, img_offset=6, pad_rows=False, seed=33)
     if B > 1:                                  # left-pad row 1 by 5 (pad id 0), keep 32 <IMG> inside
