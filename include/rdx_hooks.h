@@ -1,5 +1,5 @@
 /* rdx_hooks.h -- kernel-test, trace and microbenchmark hooks of librdx: a SEPARATE shared library, radialog_amd/librdx_hooks.so, built from
- * radialog_amd/csrc/api_debug.hip and linked against librdx.so. None of these is on the product path (the reference has no counterpart for any
+ * radialog_amd/csrc/api_debug.hip (and api_dec_hooks.hip: rdx_dec_hooks.h; both over csrc/hook_util.h) and linked against librdx.so. None of these is on the product path (the reference has no counterpart for any
  * of them); the parity tests and the tools/ scripts drive single kernels through them. radialog_amd/_lib.py loads the library only when
  * RDX_DEBUG_HOOKS=1 is set (tests/conftest.py and the tools set it); without it the Python wrappers raise RdxLibraryError. */
 #ifndef RDX_HOOKS_H
@@ -28,22 +28,31 @@ int rdx_quant_test(rdx_ctx* ctx, const void* X, int M, int K, int groups, int mo
 #define RDX_TRACE_ATTN_OPROJ 8
 int rdx_gemv_trace(rdx_ctx* ctx, int what, int layer, long long* host, int max_tiles);
 
+/* the kernel family rdx_gemm_test runs (its `force` argument, passed as an int). The skinny codes 1 and 12 - 14 accept any N > 0 (rows are padded to whole
+ * tiles of 16, as the loader pads them); every other code needs N % 16 == 0. */
+enum rdx_gemm_force {
+    RDX_GEMM_DISPATCH = 0,       /* production dispatch: M <= 32 -> skinny, else LDS-DMA GEMM when K % 64 == 0, else tiled */
+    RDX_GEMM_SKINNY = 1,         /* skinny */
+    RDX_GEMM_TILED = 2,          /* tiled_gemm_k */
+    RDX_GEMM_LDS_DMA = 3,        /* gemm_dma_k */
+    RDX_GEMM_SKINNY_FP8 = 4,     /* skinny with fp8 (e4m3 + per-row scale) weights, held as the engine holds them (e4m3 bytes + scales only): batch >= 3 shapes multiply fp8 x fp8 */
+    RDX_GEMM_KSPLIT = 5,         /* the batch 3-32 K-split path (epi 3 only: pack X, xsplit32_k, slab combine + residual) */
+    RDX_GEMM_KSPLIT_FP8 = 6,     /* 5 with fp8 weights, held as in 4 */
+    RDX_GEMM_WSGEMM = 7,         /* the encoder's many-row kernel wsgemm_k (K % 64 == 0, epi 0-3 / 6; RDX_WS_CFG=A..E forces a tile shape) */
+    RDX_GEMM_WSTAT = 8,          /* the single prompt's weight-stationary kernel wstat_k (K = 4096 / 11008, epi 0 / 3 / 4: the rows are RMS-normalised or just re-laid into the
+                                    fragment-packed order (ACT_TILES32) by launch_rmsnorm, then streamed past the register-resident weights) */
+    RDX_GEMM_GEMM8_G1 = 9,       /* 9 / 10 / 11: the fp8 path's prefill GEMM gemm8 (e4m3 weights x e4m3 activations with 1 / 2 / 4 K groups; K % 64 == 0, epi 0 / 3 / 4) */
+    RDX_GEMM_GEMM8_G2 = 10,
+    RDX_GEMM_GEMM8_G4 = 11,
+    RDX_GEMM_SKINNY_CODED = 12,  /* the skinny GEMV on CODED bf16 weights (13 bits per weight, decoded exactly in registers: radialog_amd/wcode.py): the hook encodes the packed W
+                                    itself, as rdx_finalize_weights does for the batch <= 2 step; bf16 contexts, M <= 2, K % 128 == 0, epi 0 / 3 / 4 (the logits epilogue:
+                                    rdx_logits_test); the same bits as 1 */
+    RDX_GEMM_SKINNY_W4 = 13,     /* the skinny GEMV on int4 group-quantised weights (radialog_amd/w4.py): the hook quantises W itself, as rdx_set_weight(RDX_W_GEMM_W4) does, and
+                                    streams the nibbles; the constraints of 12, epi 0 / 3 / 4; the same bits as 1 on the dequantised weight */
+    RDX_GEMM_SKINNY_W4_RAW = 14  /* 13 with the tile of rows 16..31 left raw (not quantised: its packed bf16 bytes are streamed, as the LoRA-A tiles of a fused QKV weight are; N >= 48) */
+};
 /* one bare GEMM through the production kernels: out = epilogue(X . W^T); X/resid/norm_w/out model dtype, W [N][K] and
- * bias fp32. epi: 0 none, 1 relu, 2 gelu, 3 +resid, 4 swiglu(interleaved gate/up rows), 6 relu(+resid).
- * force: 0 = production dispatch (M <= 32 -> skinny, else LDS-DMA GEMM when K % 64 == 0, else tiled), 1 = skinny,
- * 2 = tiled_gemm_k, 3 = gemm_dma_k, 4 = skinny with fp8 (e4m3 + per-row scale) weights, 5 = the batch 3-32 K-split path (epi 3 only:
- * pack X, xsplit32_k, slab combine + residual), 6 = 5 with fp8 weights, 7 = the encoder's many-row kernel wsgemm_k (K % 64 == 0, epi 0-3 / 6;
- * RDX_WS_CFG=A..E forces a tile shape), 8 = the single prompt's weight-stationary kernel wstat_k (K = 4096 / 11008, epi 0 / 3 / 4: the rows are
- * RMS-normalised or just re-laid into the fragment-packed order (ACT_TILES32) by launch_rmsnorm, then streamed past the register-resident weights),
- * 9 / 10 / 11 = the fp8 path's prefill GEMM gemm8 (e4m3 weights x e4m3 activations with 1 / 2 / 4 K groups; K % 64 == 0, epi 0 / 3 / 4).
- * force 4 / 6 hold the fp8 weights as the engine does (e4m3 bytes + scales only): batch >= 3 shapes multiply fp8 x fp8.
- * 12 = the skinny GEMV on CODED bf16 weights (13 bits per weight, decoded exactly in registers: radialog_amd/wcode.py): the hook encodes the packed W
- * itself, as rdx_finalize_weights does for the batch <= 2 step; bf16 contexts, M <= 2, K % 128 == 0, epi 0 / 3 / 4 (the logits epilogue: rdx_logits_test); the same bits as force 1.
- * 13 = the skinny GEMV on int4 group-quantised weights (radialog_amd/w4.py): the hook quantises W itself, as rdx_set_weight(RDX_W_GEMM_W4) does, and streams
- * the nibbles; the constraints of force 12, epi 0 / 3 / 4; the same bits as force 1 on the dequantised weight. 14 = the same with the tile of rows 16..31
- * left raw (not quantised: its packed bf16 bytes are streamed, as the LoRA-A tiles of a fused QKV weight are; N >= 48).
- * force 1 and 12 - 14 accept any N > 0 (rows are padded to whole tiles of 16, as the loader pads them); every other force needs N % 16 == 0.
- * Test / benchmark hook. */
+ * bias fp32. epi: 0 none, 1 relu, 2 gelu, 3 +resid, 4 swiglu(interleaved gate/up rows), 6 relu(+resid). force: an rdx_gemm_force. Test / benchmark hook. */
 int rdx_gemm_test(rdx_ctx* ctx, const void* X, const float* W, const float* bias, const void* resid, void* out, int M, int N,
                   int K, int epi, const void* norm_w, float eps, int force);
 

@@ -12,7 +12,7 @@ OUT_HOOKS = os.path.join(HERE, "librdx_hooks.so")
 SOURCES = ["gemm.hip", "xstat32.hip", "xs16.hip", "gemm_dma.hip", "gemm8.hip", "attn.hip", "flash.hip", "chain.hip", "elem.hip", "score.hip", "logprob.hip", "beam.hip", "rows.hip", "conv1x1.hip", "wsgemm.hip", "stem.hip", "wstat.hip", "pconv.hip",
            "api.hip", "api_dispatch.hip", "api_encode.hip", "api_llama.hip", "api_comm.hip", "api_inspect.hip", "api_transform.hip", "api_rows.hip"]
 HOOK_SOURCES = ["api_debug.hip", "api_dec_hooks.hip"]
-HEADERS = ["rdx_common.h", "rdx_kernels.h", "rdx_ctx.h", "skinny_body.h", "attn_body.h", "handoff.h", "philox.h", os.path.join("..", "..", "include", "rdx.h"),
+HEADERS = ["rdx_common.h", "rdx_kernels.h", "rdx_ctx.h", "skinny_body.h", "attn_body.h", "handoff.h", "philox.h", "hook_util.h", os.path.join("..", "..", "include", "rdx.h"),
            os.path.join("..", "..", "include", "rdx_hooks.h"), os.path.join("..", "..", "include", "rdx_enc_hooks.h"), os.path.join("..", "..", "include", "rdx_dec_hooks.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result"]
 # Kernarg preloading, for the units that hold the kernels of the batch-1/2 decode step only (skinny_gemm_k; decode_chain_k, attn_oproj16_k): the command

@@ -2,55 +2,18 @@
 // (include/rdx_dec_hooks.h; tests/test_gpu_decoder_gemms.py, tests/test_gpu_rmsnorm.py, tests/test_gpu_decode_attn.py). Every hook packs the caller's fp32 weight with the production packer, allocates its own temporaries (the test
 // engines have no decoder: c->kslab / c->dxs / c->dxn do not exist), asks the production *_supported predicate BEFORE anything is launched on the
 // caller's outputs, and calls the production launch_* functions unchanged. Temporaries the kernels only partly write are filled with 0xff bytes
-// (NaN in both model dtypes and in fp32) first.
-#include <cmath>
-
-#include "rdx_ctx.h"
+// (NaN in both model dtypes and in fp32) first. The temporaries are a DevBufs, the weight forms and the common ending (finish) come from hook_util.h.
+#include "hook_util.h"
 #include "philox.h"
 #include "../../include/rdx_dec_hooks.h"
 
 namespace {
-
-struct DevBufs {       // device temporaries of one hook call, freed on every return path
-    std::vector<void*> p;
-    ~DevBufs() { for (void* q : p) hipFree(q); }
-    void* get(size_t bytes) {
-        void* q = nullptr;
-        if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
-        p.push_back(q);
-        return q;
-    }
-};
-
-// the per-tile argmax partials of EPI_LOGITS reduced with the kernels' tie rule (lowest index), as rdx_logits_test does
-int reduce_partials(rdx_ctx* c, const GemmArgs& a, int32_t* argmax_host) {
-    const int nt = (a.N + 15) / 16;
-    std::vector<float> pv((size_t)a.M * nt);
-    std::vector<int> pi((size_t)a.M * nt);
-    HIPCHK(c, hipMemcpy(pv.data(), a.part_val, pv.size() * 4, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(pi.data(), a.part_idx, pi.size() * 4, hipMemcpyDeviceToHost));
-    for (int m = 0; m < a.M; ++m) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int t = 0; t < nt; ++t) {
-            const float v = pv[(size_t)m * nt + t]; const int ix = pi[(size_t)m * nt + t];
-            if (v > bv || (v == bv && ix < bi)) { bv = v; bi = ix; }
-        }
-        argmax_host[m] = bi;
-    }
-    return 0;
-}
 
 bool epi_args_ok(int epi, int N, int n_valid, int ldo, int out_packed, const void* resid, const int32_t* argmax_host) {
     if (epi == EPI_LOGITS && (!argmax_host || n_valid <= 0 || n_valid > N)) return false;
     if (epi == EPI_RESID && !resid) return false;
     if (epi == EPI_SILU_MUL && out_packed != ACT_ROWS) return true;
     return ldo >= (epi == EPI_SILU_MUL ? N / 2 : N);
-}
-
-int finish(rdx_ctx* c) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    return take_unsupported(c);       // a norm combination without a kernel (run_rmsnorm)
 }
 
 // the hooks' RMSNorm / re-layout launches: no slabs unless given
@@ -77,7 +40,7 @@ extern "C" int rdx_xstat16_test(rdx_ctx* c, const void* X, const void* norm_w, f
     a.norm_w = norm_w; a.eps = eps; a.out_packed = (ActLayout)out_packed;
     if (epi == EPI_LOGITS) { a.n_valid = n_valid; a.part_val = pv; a.part_idx = pi; }
     if (!xstat16_supported(a, epi)) return fail(c, -1, "rdx_xstat16_test: %d x %d (epilogue %d) is not a shape of xstat16_k", M, N, epi);
-    launch_pack_weight(c->cfg.dtype, W, w.w, N, K, N, nullptr, c->stream);
+    pack_w(c, W, w);
     launch_xstat16(c->cfg.dtype, a, epi, c->stream);
     if (int rc = finish(c)) return rc;
     return epi == EPI_LOGITS ? reduce_partials(c, a, argmax_host) : 0;
@@ -94,30 +57,11 @@ extern "C" int rdx_xrow16_test(rdx_ctx* c, const void* X, int x_packed, const fl
     GemmArgs a = gargs(x_packed ? X : xp, K, w, nullptr, out, ldo, M);
     a.resid = resid; a.ldr = N; a.xpacked = ACT_BLK32;
     if (!xrow16_supported(a)) return fail(c, -1, "rdx_xrow16_test: %d x %d x %d is not a shape of xrow16_k", M, N, K);
-    launch_pack_weight(c->cfg.dtype, W, w.w, N, K, N, nullptr, c->stream);
+    pack_w(c, W, w);
     if (!x_packed) run_rmsnorm(c, nargs(X, nullptr, xp, nullptr, M, K, 0.f, ACT_BLK32, 0));      // w = null: re-layout only
     launch_xrow16(c->cfg.dtype, a, c->stream);
     return finish(c);
 }
-
-namespace {
-
-// W fp32 [N][K] quantised as rdx_set_weight(RDX_W_GEMM_W4) does it (launch_quant_w4; the tiles of rows [raw_lo, raw_hi) raw): w.w = the packed copy of W',
-// w.w4 / w.w4h = the stream and its header words. Returns 0, -2 (out of memory) or -1 (an Inf / NaN in W), after a synchronisation.
-int quant_w4_for_test(rdx_ctx* c, DevBufs& b, const float* W, GemmW& w, int raw_lo, int raw_hi) {
-    w.w = b.get((size_t)w.Npad * w.K * 2);
-    w.w4 = b.get(w4_bytes(w.Npad, w.K));
-    w.w4h = (unsigned*)b.get((size_t)(w.Npad / 16) * sizeof(unsigned));
-    int* badf = (int*)b.get(sizeof(int));
-    if (!w.w || !w.w4 || !w.w4h || !badf) return -2;
-    hipMemsetAsync(badf, 0, sizeof(int), c->stream);
-    launch_quant_w4(W, w.w, w.w4, w.w4h, badf, w.N, w.K, w.Npad, raw_lo, raw_hi, c->stream);
-    int bad = 0;
-    if (hipMemcpyAsync(&bad, badf, sizeof(int), hipMemcpyDeviceToHost, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return -1;
-    return bad ? -1 : 0;
-}
-
-}  // namespace
 
 extern "C" int rdx_xstat16_w4_test(rdx_ctx* c, const void* X, const void* norm_w, float eps, const float* W, int M, int N, int epi, void* out, int ldo,
                                    int out_packed, int raw_lo) {
@@ -183,7 +127,7 @@ extern "C" int rdx_xstat_blk_test(rdx_ctx* c, const void* X, const void* norm_w,
     if (epi == EPI_RESID) { a.resid = resid; a.ldr = N; }
     if (epi == EPI_LOGITS) { a.n_valid = n_valid; a.part_val = pv; a.part_idx = pi; }
     if (!xstat_blk_supported(a, epi)) return fail(c, -1, "rdx_xstat_blk_test: %d x %d (epilogue %d) is not a shape of the row-block xstat32_k", M, N, epi);
-    launch_pack_weight(c->cfg.dtype, W, w.w, N, K, N, nullptr, c->stream);
+    pack_w(c, W, w);
     HIPCHK(c, hipMemsetAsync(xp, 0xff, xpb, c->stream));
     run_rmsnorm(c, nargs(X, norm_w, xp, nullptr, M, K, eps, ACT_TILES32, mtl));
     launch_xstat_blk(c->cfg.dtype, a, epi, c->stream);
@@ -209,7 +153,7 @@ extern "C" int rdx_xsplit_blk_test(rdx_ctx* c, const void* X, const float* W, vo
     GemmArgs a = gargs(xp, K, w, nullptr, nullptr, N, M);
     a.xpacked = ACT_TILES32; a.mtiles = mtl;
     if (!xsplit_blk_supported(a)) return fail(c, -1, "rdx_xsplit_blk_test: %d x %d is not a shape of the row-block xsplit32_k", M, N);
-    launch_pack_weight(c->cfg.dtype, W, w.w, N, K, N, nullptr, c->stream);
+    pack_w(c, W, w);
     HIPCHK(c, hipMemsetAsync(xp, 0xff, xpb, c->stream));
     HIPCHK(c, hipMemsetAsync(slab, 0xff, sb, c->stream));
     run_rmsnorm(c, nargs(X, nullptr, xp, nullptr, M, K, eps, ACT_TILES32, mtl));       // w = null: re-layout only
@@ -240,7 +184,7 @@ extern "C" int rdx_xstat_blk8_test(rdx_ctx* c, const void* X, const void* norm_w
     a.xpacked = ACT_BLK64_E4M3; a.xscale = xs; a.xgroups = 1; a.mtiles = mtl; a.out_packed = (ActLayout)out_packed;
     if (epi == EPI_LOGITS) { a.n_valid = n_valid; a.part_val = pv; a.part_idx = pi; }
     if (!xstat_blk8_supported(a, epi)) return fail(c, -1, "rdx_xstat_blk8_test: %d x %d (epilogue %d) is not a shape of the fp8 row-block xstat32_k", M, N, epi);
-    launch_pack_weight_fp8(c->cfg.dtype, W, w.w8, w.scale, nullptr, N, K, N, c->stream);
+    pack_w8(c, W, w);
     run_rmsnorm(c, nargs(X, norm_w, x8, xs, M, K, eps, ACT_BLK64_E4M3, mtl));
     launch_xstat_blk8(c->cfg.dtype, a, epi, c->stream);
     if (x8_out) HIPCHK(c, hipMemcpyAsync(x8_out, x8, x8b, hipMemcpyDeviceToDevice, c->stream));
@@ -271,7 +215,7 @@ extern "C" int rdx_xsplit_blk8_test(rdx_ctx* c, const void* X, const float* W, v
     const size_t sb = (size_t)groups * 32 * NB * N * 4;
     float* slab = (float*)b.get(sb);
     if (!slab) return fail(c, -2, "rdx_xsplit_blk8_test: out of device memory");
-    launch_pack_weight_fp8(c->cfg.dtype, W, w.w8, w.scale, nullptr, N, K, N, c->stream);
+    pack_w8(c, W, w);
     HIPCHK(c, hipMemsetAsync(slab, 0xff, sb, c->stream));
     for (int blk = 0; blk < NB; ++blk)      // every 32-row block in the 64-deep order of the fp8 kernels, rows past M zero: the re-layout launch of rdx_gemm_test's fp8 K-split mode
         run_rmsnorm(c, nargs((const char*)X + (size_t)blk * 32 * K * 2, nullptr, xp + (size_t)blk * 32 * K * 2, nullptr, std::min(32, M - 32 * blk), K, eps, ACT_BLK64, 0));
@@ -522,8 +466,7 @@ extern "C" int rdx_wcode_dense_test(rdx_ctx* c, const float* W, int N, int K, ui
     if (!packed || !planes || !words) return fail(c, -2, "rdx_wcode_dense_test: out of device memory");
     launch_pack_weight(c->cfg.dtype, W, packed, N, K, npad, nullptr, c->stream);
     launch_encode_wc(packed, planes, words, npad, K, c->stream);
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
+    if (int rc = finish(c)) return rc;
     HIPCHK(c, hipMemcpy(dense_host, words + nt, (size_t)nt * sizeof(unsigned), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -578,8 +521,9 @@ extern "C" int rdx_w4_test(rdx_ctx* c, const float* W, int N, int K, void* wprim
     if (c->cfg.dtype != DT_BF16 || K % W4_CHUNK_K) return fail(c, -8, "rdx_w4_test: int4 weights need a bf16 context and K %% 128 == 0");
     HIPCHK(c, hipSetDevice(c->device));
     const int npad = (N + 15) / 16 * 16;
-    char* tmp = nullptr;        // header words + the quantiser's non-finite flag
-    HIPCHK(c, hipMalloc((void**)&tmp, (size_t)(npad / 16) * sizeof(unsigned) + sizeof(int)));
+    DevBufs b;
+    char* tmp = (char*)b.get((size_t)(npad / 16) * sizeof(unsigned) + sizeof(int));        // header words + the quantiser's non-finite flag
+    if (!tmp) return fail(c, -2, "rdx_w4_test: out of device memory");
     int* badf = (int*)(tmp + (size_t)(npad / 16) * sizeof(unsigned));
     hipMemsetAsync(badf, 0, sizeof(int), c->stream);
     launch_quant_w4(W, wprime_out, stream_out, (unsigned*)tmp, badf, N, K, npad, npad, npad, c->stream);
@@ -587,9 +531,7 @@ extern "C" int rdx_w4_test(rdx_ctx* c, const float* W, int N, int K, void* wprim
     hipMemcpy2DAsync(scales_out, 32, (const char*)stream_out + 1024, W4_CHUNK_BYTES, 32, (size_t)(npad / 16) * (K / W4_CHUNK_K), hipMemcpyDeviceToDevice, c->stream);
     int bad = 0;
     hipMemcpyAsync(&bad, badf, sizeof(int), hipMemcpyDeviceToHost, c->stream);
-    const int rc = finish(c);
-    hipFree(tmp);
-    if (rc) return rc;
+    if (int rc = finish(c)) return rc;
     if (bad) return fail(c, -1, "rdx_w4_test: the weight holds an Inf or a NaN");
     return 0;
 }
