@@ -326,15 +326,12 @@ long long rdx_kv_bytes(rdx_ctx* ctx);
  *   At batch >= 3 the RMSNorm in front of QKV / gate-up / lm_head is a launch of its own: it runs once, outside the timed region, and
  *   units 1, 2, 5 time the GEMM launches alone. */
 int rdx_time(rdx_ctx* ctx, int what, int iters, float* ms_host);
-/* test / experiment switches of one context (defaults come from the environment at rdx_create): "flash_min" = 64-query workgroups from which the
- * batched prefill attention takes the flash-style kernel (0 never, 1 always; RDX_FLASH_MIN, default 512), "pconv" = the image encoder on
- * fragment-packed activations (1, default) or on the row-major kernels of rounds 1-3 (0; RDX_PCONV), "xs16" = batch 3-16 decode on the one-row-tile
- * family of xs16.hip (1, default) or on the 32-row family (0; RDX_XS16), "prompt_blk" = one prompt's K = 4096 projections on 32-row blocks (1, default) or on
- * the weight-stationary kernel (0; RDX_PBLK), "wcode" = the batch <= 2 decode step of a bf16 context streams the 13-bit coded copies of its gate/up, down_proj,
- * QKV and lm_head weights (1, default) or the raw packed ones (0); the results are the same bits either way, a captured step graph is dropped (no
- * environment variable), "w4" = likewise for RDX_W_GEMM_W4 weights: the batch <= 2 step streams the int4 copies of gate/up, down_proj and QKV (1, default) or
- * the packed bytes of their dequantised values (0); the same bits, a captured step graph is dropped, "score_chunk" = logits rows per lm_head launch of the scoring pass (default 2048, the fastest of 128 / 512 / 2048 / all on 3382 rows: profiles/r11_score.md; 0 = all rows of a call at once; negative values
- * return -1), "kv_fp8" = the decoder's KV cache as an fp8 storage format (0, default: the model dtype; 1: OCP e4m3 codes with one power-of-two exponent
+/* The runtime switches of one context. Every switch is one row of one table (radialog_amd/csrc/api_options.hip; for the caller: INTEGRATION.md "Runtime
+ * switches": option, environment variable, default, when settable, what it selects). Its environment variable is read once, at rdx_create; after that only
+ * rdx_set_option changes it, for this context. A boolean stores value != 0; any other value outside its row's range, an unknown name, and a row that
+ * rdx_finalize_weights allocates by ("kv_fp8", "kperm") set after that call return -1 with a message and change nothing. Where a captured step graph holds
+ * the old choice it is dropped. No reference counterpart.
+ * "kv_fp8" = the decoder's KV cache as an fp8 storage format (0, default: the model dtype; 1: OCP e4m3 codes with one power-of-two exponent
  * byte per cache row of 128 values, radialog_amd/kv8.py). Valid only BEFORE rdx_finalize_weights, which then allocates codes, exponents and one layer of
  * staging rows instead of the 2-byte caches (afterwards: -1 with a message). A stored row IS its dequantised value x' = code 2^e, exactly a value of the
  * model dtype: decode attention over the fp8 cache gives the bits it gives over a model-dtype cache holding x'. The prompt's own attention sees its
@@ -342,10 +339,13 @@ int rdx_time(rdx_ctx* ctx, int what, int iters, float* ms_host);
  * unquantised and is stored quantised. Rows 1-2 run the generic kernel family (no fused attention + o_proj, no chained launch). Not built on an fp8
  * cache, -1 with a message naming "kv_fp8": rdx_prefill_append / rdx_generate_append (the kept prefix is not held in the model dtype), rdx_beam_search,
  * rdx_rows_begin. Without the option every launch and every output bit is unchanged.
- * Unknown names return -1. No reference counterpart.
  * At batch 3-16 on the xs16 family rdx_time units 1-5 time THOSE kernels (the RMSNorm is their prologue); max_batch > 32 needs the Vicuna-7B widths
  * (hidden 4096, inter 11008): rdx_finalize_weights refuses other models with more than 32 rows. */
 int rdx_set_option(rdx_ctx* ctx, const char* name, int value);
+/* what is in force: the value of switch `name` as stored ("kperm" stays -1 where rdx_finalize_weights chose) */
+int rdx_get_option(rdx_ctx* ctx, const char* name, int* value);
+/* the table's option names in order; NULL past the end */
+const char* rdx_option_name(int index);
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,8 @@ SYMBOLS = {
     "rdx_hidden_read": (C.c_int, [_P, _P]),
     "rdx_time": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "rdx_set_option": (C.c_int, [_P, C.c_char_p, C.c_int]),
+    "rdx_get_option": (C.c_int, [_P, C.c_char_p, C.POINTER(C.c_int)]),
+    "rdx_option_name": (C.c_char_p, [C.c_int]),
 }
 
 # include/rdx_hooks.h: every symbol of librdx_hooks.so

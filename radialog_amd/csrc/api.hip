@@ -60,18 +60,11 @@ extern "C" int rdx_create(rdx_ctx** out, int device_id, const rdx_config* cfg) {
     rdx_ctx* c = new rdx_ctx();
     c->cfg = *cfg;
     c->device = device_id;
-    if (const char* e = getenv("RDX_FUSE_AO")) c->fuse_attn_oproj = atoi(e) != 0;
-    if (const char* e = getenv("RDX_CHAIN")) c->chain_mlp = atoi(e) != 0;
+    if (options_from_env(c)) { const std::string msg = c->err; delete c; return fail(nullptr, -1, "rdx_create: %s", msg.c_str()); }      // the one read of the environment (api_options.hip)
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) {
         delete c;
         return fail(nullptr, -2, "rdx_create: cannot create stream on device %d", device_id);
     }
-    { const char* e = getenv("RDX_FLASH_MIN"); if (e) c->flash_min = atoi(e); }
-    { const char* e = getenv("RDX_XS16"); if (e) c->xs16 = atoi(e) != 0; }
-    { const char* e = getenv("RDX_PBLK"); if (e) c->prompt_blk = atoi(e) != 0; }
-    { const char* e = getenv("RDX_BLK_DOWN"); c->blk_down = !(e && atoi(e) == 0); }
-    { const char* e = getenv("RDX_PCONV_KSPLIT"); c->pconv_noks = e && atoi(e) == 0; }
-    { const char* e = getenv("RDX_PCONV"); c->trunk_packed = !(e && atoi(e) == 0); }      // read once (A/B legs of the tests set it before rdx_create)
     if (hipMalloc(&c->zero16, 64) == hipSuccess) { hipMemset(c->zero16, 0, 64); c->allocs.push_back(c->zero16); } else c->zero16 = nullptr;
     c->gemm_ws_floats = (size_t)16 << 20;          // 64 MiB of fp32 split-K slabs
     if (hipMalloc((void**)&c->gemm_ws, c->gemm_ws_floats * sizeof(float)) != hipSuccess) { c->gemm_ws = nullptr; c->gemm_ws_floats = 0; }
@@ -301,18 +294,18 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->ld.hidden = H; c->ld.heads = f.heads; c->ld.head_dim = 128; c->ld.qkv_ld = c->ll[0].wqkv.Npad;
         c->ld.lora_r = f.lora_r; c->ld.lora_scale = f.lora_scale; c->ld.max_len = f.max_len; c->ld.max_pos = f.max_pos;
-        c->ld.k_perm = (getenv("RDX_KPERM") ? atoi(getenv("RDX_KPERM")) : (f.max_batch * f.heads <= 256)) ? 1 : 0;
+        c->ld.k_perm = (c->sw.kperm >= 0 ? c->sw.kperm : (f.max_batch * f.heads <= 256)) ? 1 : 0;
         const int B = f.max_batch;
         c->kv_layer_elems = (size_t)B * f.heads * f.max_len * 128;
-        c->ld.kv_fp8 = c->kv_fp8 ? 1 : 0;
+        c->ld.kv_fp8 = c->sw.kv_fp8 ? 1 : 0;
         // fp8 KV cache: one code byte per element, one exponent byte per row of 128, and the prompt's rows of ONE layer in the model dtype
-        const size_t kvb = c->kv_layer_elems * f.layers * (c->kv_fp8 ? 1 : 2), kxb = c->kv_fp8 ? c->kv_layer_elems / 128 * f.layers : 0;
+        const size_t kvb = c->kv_layer_elems * f.layers * (c->sw.kv_fp8 ? 1 : 2), kxb = c->sw.kv_fp8 ? c->kv_layer_elems / 128 * f.layers : 0;
         ALLOC(c, c->kcache, kvb);
         ALLOC(c, c->vcache, kvb);
         // zero-initialised: decode attention multiplies never-written rows by P = 0 (any finite value is fine, NaN bits are not)
         HIPCHK(c, hipMemset(c->kcache, 0, kvb));
         HIPCHK(c, hipMemset(c->vcache, 0, kvb));
-        if (c->kv_fp8) {
+        if (c->sw.kv_fp8) {
             ALLOC(c, c->kexp, kxb); ALLOC(c, c->vexp, kxb);
             HIPCHK(c, hipMemset(c->kexp, 0, kxb));
             HIPCHK(c, hipMemset(c->vexp, 0, kxb));
@@ -432,41 +425,4 @@ extern "C" int rdx_finalize_weights(rdx_ctx* c) {
     if (R.rc) return R.rc;
     c->finalized = true;
     return 0;
-}
-
-// Test / experiment switches of one context (read from the environment once, at rdx_create): "flash_min" = workgroups from which the batched
-// prefill attention takes flash_prefill_k (0 = never, 1 = always; RDX_FLASH_MIN), "pconv" = the encoder on fragment-packed activations (RDX_PCONV),
-// "xs16" = batch 3-16 decode on the one-row-tile family (RDX_XS16), "prompt_blk" = one prompt's K = 4096 projections on 32-row blocks (RDX_PBLK),
-// "wcode" = the batch <= 2 step streams the coded bf16 weights (no environment variable: on unless switched off here), "w4" = ... the int4 streams.
-extern "C" int rdx_set_option(rdx_ctx* c, const char* name, int value) {
-    if (!c || !name) return -1;
-    if (!strcmp(name, "flash_min")) { c->flash_min = value; return 0; }
-    if (!strcmp(name, "pconv")) { c->trunk_packed = value != 0; return 0; }
-    if (!strcmp(name, "prompt_blk")) { c->prompt_blk = value != 0; return 0; }
-    if (!strcmp(name, "xs16")) {          // batch 3-16 decode family (xs16.hip) on / off; a captured step graph of the other family is dropped
-        c->xs16 = value != 0;
-        if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; c->gkey = GraphKey(); }
-        return 0;
-    }
-    if (!strcmp(name, "w4")) {            // likewise for int4 group-quantised weights: their int4 streams (on) or the packed bytes of their dequantised values; same bits
-        c->w4 = value != 0;
-        if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; c->gkey = GraphKey(); }
-        return 0;
-    }
-    if (!strcmp(name, "wcode")) {         // the batch <= 2 step's GEMVs and chained launches on the coded bf16 weights (on) or on the raw packed ones (the A/B leg); same bits either way
-        c->wcode = value != 0;
-        if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; c->gkey = GraphKey(); }
-        return 0;
-    }
-    if (!strcmp(name, "kv_fp8")) {        // the decoder's KV cache as e4m3 codes + one power-of-two exponent per row (radialog_amd/kv8.py): decides what rdx_finalize_weights allocates
-        if (c->finalized) return fail(c, -1, "rdx_set_option: kv_fp8 decides what rdx_finalize_weights allocates; set it before that call");
-        c->kv_fp8 = value != 0;
-        return 0;
-    }
-    if (!strcmp(name, "score_chunk")) {   // rdx_score: logits rows per lm_head launch (0 = all rows of a call at once)
-        if (value < 0) return fail(c, -1, "rdx_set_option: score_chunk %d is negative (0 = all rows at once)", value);
-        c->score_chunk = value;
-        return 0;
-    }
-    return fail(c, -1, "rdx_set_option: unknown option '%s'", name);
 }

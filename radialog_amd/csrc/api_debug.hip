@@ -52,7 +52,7 @@ extern "C" int rdx_gemv_trace(rdx_ctx* c, int what, int layer, long long* host, 
         if (layer < 0 || layer >= f.layers) return fail(c, -1, "rdx_gemv_trace(%d): layer %d of %d", what, layer, f.layers);
         if (c->cur_T + c->cur_steps + 1 > f.max_len || c->cur_T + c->cur_steps + 1 > f.max_pos)       // as rdx_time(7): bounded by the KV cache, not by max_new
             return fail(c, -1, "rdx_gemv_trace(%d): no room for one more decode step in the KV cache", what);
-        const bool fused = c->fuse_attn_oproj && attn_oproj16_supported(c->ld, c->ll[layer].wo.N, c->ll[layer].wo.K, B);
+        const bool fused = c->sw.fuse_ao && attn_oproj16_supported(c->ld, c->ll[layer].wo.N, c->ll[layer].wo.K, B);
         if (what == 8 && !fused)
             return fail(c, -1, "rdx_gemv_trace(8): the fused attention + o_proj launch is not active in this configuration (batch > 2, RDX_FUSE_AO=0)");
         const int wgs = what == 7 ? H / 16 + ((c->ll[0].wqkv.Npad + 15) / 16 + 3) / 4      // down_proj tiles + QKV workgroups of 4 tiles
@@ -165,7 +165,7 @@ extern "C" int rdx_conv_test(rdx_ctx* c, const void* X, const float* W, const fl
         if (need_res) launch_pack_rows(dt, resid, Cout, rp, M, Cout, c->stream);
         pa.X = xp; pa.W = buf; pa.bias = bias; pa.resid = need_res ? rp : nullptr; pa.out = path == 2 ? out : (void*)op; pa.zero16 = c->zero16;
         pa.Hin = H; pa.Win = H; pa.Cin = Cin; pa.Hout = Ho; pa.Wout = Ho; pa.N = Cout; pa.M = M; pa.mt_in = mt_in; pa.mt_out = mt_out; pa.ldo = Cout;
-        pa.no_ksplit = c->pconv_noks;
+        pa.no_ksplit = !c->sw.pconv_ksplit;
         if (const char* e = getenv("RDX_PCONV_TILE")) {            // "MxN" or "MxNkS": forced register tile (tools/pconv_check.py)
             if (e[0] >= '1' && e[0] <= '8' && e[1] == 'x' && (e[2] == '2' || e[2] == '4')) {
                 pa.tile_m = e[0] - '0'; pa.tile_n = e[2] - '0';
@@ -250,7 +250,7 @@ struct GemmCall {       // one rdx_gemm_test call: its arguments, its device tem
         return true;
     }
     GemmArgs args() const {       // row-major X, the RMSNorm (norm_w) as the kernel's prologue
-        GemmArgs a = gargs(X, K, w, bias, out, epi == EPI_SILU_MUL ? N / 2 : N, M);
+        GemmArgs a = with_switches(c, gargs(X, K, w, bias, out, epi == EPI_SILU_MUL ? N / 2 : N, M));
         a.resid = resid; a.ldr = N; a.norm_w = norm_w; a.eps = eps;
         return a;
     }
@@ -353,7 +353,7 @@ int gemm_rows(GemmCall& g, bool try_dma, bool may_tile) {
     return finish(c);
 }
 
-// the encoder's many-row kernel (wsgemm.hip), tile shape via RDX_WS_CFG
+// the encoder's many-row kernel (wsgemm.hip), tile shape by the context's switch "ws_cfg"
 int gemm_wsgemm(GemmCall& g) {
     rdx_ctx* c = g.c;
     if (g.N % 16) return g.bad_shape();
@@ -361,7 +361,7 @@ int gemm_wsgemm(GemmCall& g) {
     if (!g.packed()) return g.oom();
     GemmArgs a = g.args();
     a.norm_w = nullptr;
-    launch_wsgemm(c->cfg.dtype, a, ConvGeom{}, g.epi, c->zero16, c->stream);
+    launch_wsgemm(c->cfg.dtype, a, ConvGeom{}, g.epi, c->zero16, c->sw.ws_cfg, c->stream);
     return finish(c);
 }
 
@@ -579,7 +579,7 @@ extern "C" int rdx_attn_test(rdx_ctx* c, const void* Q, const void* K, const voi
     a.o_bs = strides[9]; a.o_ts = strides[10]; a.o_hs = strides[11];
     a.B = B; a.H = H; a.Tq = Tq; a.Tk = Tk; a.causal = causal;
     a.key_mask = key_mask; a.km_bs = key_mask ? (long)km_bs : 0;
-    a.flash_min = kernel == 0 ? c->flash_min : (kernel == 2 ? 1 : 0);
+    a.flash_min = kernel == 0 ? c->sw.flash_min : (kernel == 2 ? 1 : 0);
     if (kernel == 2 && !flash_prefill_supported(D, a))
         return fail(c, -1, "rdx_attn_test: flash_prefill_k does not take this call (D 128, causal, key mask, 8-element strides)");
     const long M = (long)B * Tq;

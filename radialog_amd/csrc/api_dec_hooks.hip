@@ -122,7 +122,7 @@ extern "C" int rdx_xstat_blk_test(rdx_ctx* c, const void* X, const void* norm_w,
     float* pv = (float*)b.get((size_t)M * nt * 4);
     int* pi = (int*)b.get((size_t)M * nt * 4);
     if (!w.w || !xp || !pv || !pi) return fail(c, -2, "rdx_xstat_blk_test: out of device memory");
-    GemmArgs a = gargs(xp, K, w, nullptr, out, ldo, M);
+    GemmArgs a = with_switches(c, gargs(xp, K, w, nullptr, out, ldo, M));
     a.xpacked = ACT_TILES32; a.mtiles = mtl; a.out_packed = (ActLayout)out_packed;
     if (epi == EPI_RESID) { a.resid = resid; a.ldr = N; }
     if (epi == EPI_LOGITS) { a.n_valid = n_valid; a.part_val = pv; a.part_idx = pi; }
@@ -150,7 +150,7 @@ extern "C" int rdx_xsplit_blk_test(rdx_ctx* c, const void* X, const float* W, vo
     void* xp = b.get(xpb);
     float* slab = (float*)b.get(sb);
     if (!w.w || !xp || !slab) return fail(c, -2, "rdx_xsplit_blk_test: out of device memory");
-    GemmArgs a = gargs(xp, K, w, nullptr, nullptr, N, M);
+    GemmArgs a = with_switches(c, gargs(xp, K, w, nullptr, nullptr, N, M));
     a.xpacked = ACT_TILES32; a.mtiles = mtl;
     if (!xsplit_blk_supported(a)) return fail(c, -1, "rdx_xsplit_blk_test: %d x %d is not a shape of the row-block xsplit32_k", M, N);
     pack_w(c, W, w);
@@ -180,7 +180,7 @@ extern "C" int rdx_xstat_blk8_test(rdx_ctx* c, const void* X, const void* norm_w
     float* pv = (float*)b.get((size_t)M * nt * 4);
     int* pi = (int*)b.get((size_t)M * nt * 4);
     if (!w.w8 || !w.scale || !x8 || !xs || !pv || !pi) return fail(c, -2, "rdx_xstat_blk8_test: out of device memory");
-    GemmArgs a = gargs(x8, K, w, nullptr, out, ldo, M);
+    GemmArgs a = with_switches(c, gargs(x8, K, w, nullptr, out, ldo, M));
     a.xpacked = ACT_BLK64_E4M3; a.xscale = xs; a.xgroups = 1; a.mtiles = mtl; a.out_packed = (ActLayout)out_packed;
     if (epi == EPI_LOGITS) { a.n_valid = n_valid; a.part_val = pv; a.part_idx = pi; }
     if (!xstat_blk8_supported(a, epi)) return fail(c, -1, "rdx_xstat_blk8_test: %d x %d (epilogue %d) is not a shape of the fp8 row-block xstat32_k", M, N, epi);
@@ -208,7 +208,7 @@ extern "C" int rdx_xsplit_blk8_test(rdx_ctx* c, const void* X, const float* W, v
     w.scale = (float*)b.get((size_t)N * 4);
     char* xp = (char*)b.get(xpb);
     if (!w.w8 || !w.scale || !xp) return fail(c, -2, "rdx_xsplit_blk8_test: out of device memory");
-    GemmArgs a = gargs(xp, K, w, nullptr, nullptr, N, M);
+    GemmArgs a = with_switches(c, gargs(xp, K, w, nullptr, nullptr, N, M));
     a.xpacked = ACT_BLK64; a.mtiles = mtl;
     const int groups = xsplit_blk8_groups(a);
     if (!groups) return fail(c, -1, "rdx_xsplit_blk8_test: %d x %d x %d is not a shape of the fp8 row-block xsplit32_k", M, N, K);
@@ -329,8 +329,8 @@ int decode_attn_hook(rdx_ctx* c, const char* who, int heads, int B, int max_len,
     a.qkv = qkv; a.lbq = lbq; a.lbv = lbv; a.cos_t = cos_t; a.sin_t = sin_t; a.cur_rope = cur_rope; a.pos = pos; a.slot_b = slot; a.key_mask = key_mask;
     a.kcache = kcache; a.vcache = vcache; a.out = out; a.out_packed = (ActLayout)out_packed; a.out_mt = out_mt;
     HIPCHK(c, hipMemsetAsync(out, 0xff, (size_t)out_bytes, c->stream));
-    if (kexp) { a.d.kv_fp8 = 1; launch_decode_attention_kv8(c->cfg.dtype, a, kexp, vexp, B, c->stream); }
-    else launch_decode_attention(c->cfg.dtype, a, B, c->stream);
+    if (kexp) { a.d.kv_fp8 = 1; launch_decode_attention_kv8(c->cfg.dtype, a, kexp, vexp, B, attn_sw(c), c->stream); }
+    else launch_decode_attention(c->cfg.dtype, a, B, attn_sw(c), c->stream);
     return finish(c);
 }
 
@@ -366,7 +366,7 @@ extern "C" int rdx_kv8_quant_test(rdx_ctx* c, int heads, int B, int T, int stage
 // logical model-dtype rows [B][heads][max_len][128] into a PLAIN context's cache of one layer (K in the order the context keeps it)
 extern "C" int rdx_kv_write_test(rdx_ctx* c, int layer, int which, const void* src) {
     if (!c || !c->finalized || !c->cfg.enable_llama || !src || layer < 0 || layer >= c->cfg.layers) return fail(c, -1, "rdx_kv_write_test: bad arguments");
-    if (c->kv_fp8) return fail(c, -1, "rdx_kv_write_test: a plain (model-dtype) KV cache is needed, this context's is fp8 (kv_fp8)");
+    if (c->sw.kv_fp8) return fail(c, -1, "rdx_kv_write_test: a plain (model-dtype) KV cache is needed, this context's is fp8 (kv_fp8)");
     HIPCHK(c, hipSetDevice(c->device));
     const size_t bytes = c->kv_layer_elems * 2;
     if (which || !c->ld.k_perm) {

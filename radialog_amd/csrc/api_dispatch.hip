@@ -21,8 +21,8 @@ DecAttnArgs dec_attn_args(rdx_ctx* c, int layer) {
 }
 
 void run_decode_attention(rdx_ctx* c, const DecAttnArgs& at, int layer, int B) {
-    if (c->kv_fp8) launch_decode_attention_kv8(c->cfg.dtype, at, kvx_ptr(c, c->kexp, layer), kvx_ptr(c, c->vexp, layer), B, c->stream);
-    else launch_decode_attention(c->cfg.dtype, at, B, c->stream);
+    if (c->sw.kv_fp8) launch_decode_attention_kv8(c->cfg.dtype, at, kvx_ptr(c, c->kexp, layer), kvx_ptr(c, c->vexp, layer), B, attn_sw(c), c->stream);
+    else launch_decode_attention(c->cfg.dtype, at, B, attn_sw(c), c->stream);
 }
 
 GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
@@ -39,7 +39,7 @@ GemmArgs unit_args(rdx_ctx* c, const LlamaLayer* L, DecUnit u, int B) {
         a.N = c->lm_head.Npad; a.n_valid = f.vocab; a.norm_w = c->final_norm; a.part_val = c->part_val; a.part_idx = c->part_idx;
     }
     if (a.norm_w) a.eps = f.rms_eps;
-    return a;
+    return with_switches(c, a);
 }
 
 // ---- which copy of a weight each unit streams (rdx_ctx.h): THE table. The copies a family reads for a unit of a layer where the weight holds them, int4
@@ -56,7 +56,7 @@ static unsigned stream_wants(DecFamily fam, DecUnit u, int layer) {
 // the table names copy s (coded or int4), its option is on (bf16 only) and W holds it
 static bool can_stream(rdx_ctx* c, DecFamily fam, DecUnit u, int layer, const GemmW& W, WStream s) {
     if (!(stream_wants(fam, u, layer) >> s & 1) || c->cfg.dtype != DT_BF16) return false;
-    return s == WS_W4 ? c->w4 && W.w4 && W.w4h : c->wcode && W.wc && W.wch;
+    return s == WS_W4 ? c->sw.w4 && W.w4 && W.w4h : c->sw.wcode && W.wc && W.wch;
 }
 WStream unit_stream(rdx_ctx* c, DecFamily fam, DecUnit u, int layer, const GemmW& W) {
     return can_stream(c, fam, u, layer, W, WS_W4) ? WS_W4 : can_stream(c, fam, u, layer, W, WS_CODED) ? WS_CODED : WS_RAW;
@@ -148,7 +148,7 @@ GemmArgs norm_in_front(rdx_ctx* c, GemmArgs a) {
 DecFamily decode_family(rdx_ctx* c, int B) {
     if (B > 32) return !blk64_ok(c, B) ? DEC_UNSUPPORTED : blk64_fp8(c) ? DEC_BLK8 : DEC_BLK;
     // batch <= 2: down(l) -> QKV(l+1) chained inside one launch by the fence-free hand-off, attention + o_proj in the fused launch
-    if (c->chain_mlp && c->fuse_attn_oproj && chain_supported(c->ld, c->cfg.inter, B) && attn_oproj16_supported(c->ld, c->cfg.hidden, c->cfg.hidden, B))
+    if (c->sw.chain && c->sw.fuse_ao && chain_supported(c->ld, c->cfg.inter, B) && attn_oproj16_supported(c->ld, c->cfg.hidden, c->cfg.hidden, B))
         return DEC_CHAINED;
     return xs16_ok(c, B) ? DEC_XS16 : DEC_GENERIC;
 }
@@ -173,12 +173,12 @@ PromptPlan prompt_plan(rdx_ctx* c, int B, int T) {
     // up to 192 rows the K = 4096 projections run activation-stationary in row blocks of 32 whose workgroups share an XCD's L2
     // (xstat32_k<.., BLK>: the weights cross each CU once per row block instead of the activations once per 32 columns); down_proj
     // (K = 11008) and longer prompts keep the weight-stationary kernel
-    p.blk = c->prompt_blk && xstat_blk_supported(qkv, EPI_NONE) && xstat_blk_supported(prompt_unit(c, p, L, UNIT_O), EPI_RESID) &&
+    p.blk = c->sw.prompt_blk && xstat_blk_supported(qkv, EPI_NONE) && xstat_blk_supported(prompt_unit(c, p, L, UNIT_O), EPI_RESID) &&
             xstat_blk_supported(prompt_unit(c, p, L, UNIT_GATE_UP), EPI_SILU_MUL);
     // down_proj of a prompt of <= 128 rows (<= 4 row blocks: 160 rows measured 55.9 us against wstat_k 49.5; 64 rows 3.96 -> 3.69 ms per prefill) K-split over
     // 4 workgroups per tile into fp32 slabs (xsplit32_k<.., BLK>), combined (+ residual) by the next layer's RMSNorm -- after the last layer by one more norm
     // launch whose packed output nobody reads
-    p.down_split = c->prompt_blk && p.M <= 128 && xsplit_blk_supported(down);
+    p.down_split = c->sw.prompt_blk && p.M <= 128 && xsplit_blk_supported(down);
     return p;
 }
 
@@ -199,7 +199,7 @@ GemmArgs prompt_unit(rdx_ctx* c, const PromptPlan& p, const LlamaLayer* L, DecUn
     case PROMPT_FP8:        // gemm8 over the e4m3 rows in pxq and whole weight tiles; the rows' scales: 1 K group behind an RMSNorm, 2 for o_proj, 4 for down_proj
         a.X = c->pxq; a.N = W.Npad; a.xscale = c->pxs; a.xgroups = u == UNIT_O ? 2 : u == UNIT_DOWN ? 4 : 1; a.ldr = H;
     }
-    return a;
+    return with_switches(c, a);
 }
 
 void prompt_norm(rdx_ctx* c, const PromptPlan& p, const void* w, int pend) {
@@ -216,7 +216,7 @@ void prompt_attention(rdx_ctx* c, const PromptPlan& p, int l, int B, int T, int 
     // where the layer's new K / V rows land (behind the kept slots) and what the attention reads: cache rows row0 .. of layer l ...
     LlamaDims d = c->ld;
     void *K = nullptr, *V = nullptr;
-    if (!c->kv_fp8) {
+    if (!c->sw.kv_fp8) {
         const size_t kv_row = (size_t)row0 * f.heads * f.max_len * 128 * 2;
         K = (char*)kv_ptr(c, c->kcache, l) + kv_row; V = (char*)kv_ptr(c, c->vcache, l) + kv_row;
     } else {
@@ -234,10 +234,10 @@ void prompt_attention(rdx_ctx* c, const PromptPlan& p, int l, int B, int T, int 
     at.k_bs = at.v_bs = (long)f.heads * d.max_len * 128; at.k_ts = at.v_ts = 128; at.k_hs = at.v_hs = (long)d.max_len * 128;
     at.O = c->patt; at.o_bs = (long)T * H; at.o_ts = H; at.o_hs = 128;
     at.B = B; at.H = f.heads; at.Tq = T; at.Tk = keep + T; at.causal = 1; at.k_perm = d.k_perm; at.km_bs = f.max_len;
-    at.flash_min = c->flash_min;
+    at.flash_min = c->sw.flash_min;
     at.o_packed_mt = p.family == PROMPT_TILES ? p.mtiles : 0;
     launch_attention(f.dtype, 128, at, s);
-    if (c->kv_fp8)
+    if (c->sw.kv_fp8)
         launch_kv8_quant_rows(f.dtype, K, V, d.max_len, kv_ptr(c, c->kcache, l), kvx_ptr(c, c->kexp, l), kv_ptr(c, c->vcache, l), kvx_ptr(c, c->vexp, l),
                               (size_t)B * f.heads, f.max_len, T, 0, s);
 }
@@ -260,7 +260,7 @@ GemmArgs skinny_prenorm(rdx_ctx* c, GemmArgs a, int epi) {
 }
 
 void skinny(rdx_ctx* c, GemmArgs a, int epi) {
-    a = skinny_prenorm(c, a, epi);
+    a = skinny_prenorm(c, with_switches(c, a), epi);
     if (!a.W && a.W8) {
         // fp8-only weights: the kernels that read e4m3 are the batch <= 2 GEMV with LDS-staged activations (expanded in registers) and, from
         // batch 3, the activation-stationary fp8 x fp8 kernel (K = 4096, many tiles). Anything else has no kernel in this mode.
@@ -308,8 +308,7 @@ bool down_split_ok(rdx_ctx* c, const LlamaLayer& L, int B) {
 
 // A K-split projection (o_proj, down_proj at batch 3-32): its fp32 slabs stay pending for the stand-alone RMSNorm of the
 // projection that follows (norm_in_front), which adds them, rounds and applies the residual.
-// (fp8 weights: W8A16 since round 6 -- the e4m3 weight fragments are expanded in registers and multiply the producer's model-dtype activation
-// fragments; RDX_FP8_SPLIT_A8=1 is the earlier form whose workgroups quantise their K range of the activations: xstat32.hip fp8_split_a8)
+// (fp8 weights: W8A16 -- the e4m3 weight fragments are expanded in registers and multiply the producer's model-dtype activation fragments)
 void launch_ksplit(rdx_ctx* c, const GemmArgs& a) {
     launch_xsplit32(c->cfg.dtype, a, c->kslab, c->stream);
     c->pend_groups = xsplit32_groups(a);
@@ -323,7 +322,7 @@ void launch_down(rdx_ctx* c, const LlamaLayer& L, int B, bool split) {
 
 // 33-128 rows (round 5; VERDICT r4 "missing" 3): the decoder's rows as NB = ceil(rows / 32) blocks of 32. Every K = 4096 projection runs activation-stationary per block,
 // the two block workgroups of a tile walker on one XCD (xstat32_k<.., BLK>: a weight fragment comes from HBM once, from that L2 once more); o_proj is
-// un-split (final rows: no slabs), down_proj (K = 11008) K-split into fp32 slabs (or, RDX_BLK_DOWN=0, on the prompt's weight-stationary kernel); the RMSNorms write the
+// un-split (final rows: no slabs), down_proj (K = 11008) K-split into fp32 slabs (or, "blk_down" off, on the prompt's weight-stationary kernel); the RMSNorms write the
 // fragment-packed [k / 32][row tiles][lane][8] the consumers read. fp8 weights (blk64_fp8) take the 32-row fp8 kernels per row block instead.
 bool blk64_fp8(rdx_ctx* c) { return !c->ll.empty() && fp8_weights(c->ll[0].wqkv); }
 
@@ -332,7 +331,7 @@ bool blk64_ok(rdx_ctx* c, int B) {
     const LlamaLayer* L = &c->ll[0];
     if (blk64_fp8(c)) {
         // fp8 weights (round 5): the 32-row fp8 kernels per row block -- e4m3 blocks + xscale for QKV / gate-up / lm_head (fp8 x fp8); o_proj and down_proj K-split
-        // over model-dtype activation blocks (xsplit32_k<.., BLK>: W8A16 since round 6, xstat32.hip fp8_split_a8), slabs combined by the next RMSNorm
+        // over model-dtype activation blocks (xsplit32_k<.., BLK>: W8A16), slabs combined by the next RMSNorm
         return c->kslab && c->dxs && xstat_blk8_supported(prenormed(c, blk8_unit(c, L, UNIT_QKV, B)), EPI_NONE) && xsplit_blk8_groups(blk8_unit(c, L, UNIT_O, B)) == 2 &&
                xstat_blk8_supported(prenormed(c, blk8_unit(c, L, UNIT_GATE_UP, B)), EPI_SILU_MUL) && xsplit_blk8_groups(blk8_unit(c, L, UNIT_DOWN, B)) == 4 &&
                xstat_blk8_supported(prenormed(c, blk8_unit(c, L, UNIT_LM_HEAD, B)), EPI_LOGITS);
@@ -343,7 +342,7 @@ bool blk64_ok(rdx_ctx* c, int B) {
 }
 
 bool xs16_ok(rdx_ctx* c, int B) {
-    if (!c->xs16 || !xs16_rows_ok(B) || c->ll.empty()) return false;
+    if (!c->sw.xs16 || !xs16_rows_ok(B) || c->ll.empty()) return false;
     const LlamaLayer* L = &c->ll[0];
     return xstat16_supported(xs16_unit(c, L, UNIT_QKV, B), EPI_NONE) && xstat16_supported(xs16_unit(c, L, UNIT_GATE_UP, B), EPI_SILU_MUL) &&
            xstat16_supported(xs16_unit(c, L, UNIT_LM_HEAD, B), EPI_LOGITS) && xrow16_supported(xs16_unit(c, L, UNIT_O, B)) && xrow16_supported(xs16_unit(c, L, UNIT_DOWN, B));
@@ -355,7 +354,7 @@ void run_gemm(rdx_ctx* c, GemmArgs a, int epi) {
     memset(&cg, 0, sizeof(cg));
     if (a.M <= 32) skinny(c, a, epi == EPI_RESID_RELU ? EPI_RESID : epi);
     else if (c->ws_ok && c->zero16 && wsgemm_supported(a, cg, epi))
-        launch_wsgemm(c->cfg.dtype, a, cg, epi, c->zero16, c->stream);       // the encoder's short-K residual GEMMs
+        launch_wsgemm(c->cfg.dtype, a, cg, epi, c->zero16, c->sw.ws_cfg, c->stream);       // the encoder's short-K residual GEMMs
     else if (gemm_dma_supported(a)) launch_gemm_dma(c->cfg.dtype, a, epi, c->gemm_ws, c->gemm_ws_floats, c->stream);
     else launch_tiled_gemm(c->cfg.dtype, a, cg, epi, c->stream);
 }
@@ -378,7 +377,7 @@ void conv_gemm(rdx_ctx* c, const void* X, const GemmW& W, const float* bias, con
     if (KH == 1 && KW == 1 && stride == 1 && pad == 0) cg.mode = 0;
     // memory-bound 1x1 convolutions (K <= 256, tens of thousands of rows): weight-stationary streaming kernel
     if (conv1x1_stream_supported(a, cg, epi)) { launch_conv1x1_stream(c->cfg.dtype, a, cg, epi, c->stream); return; }
-    if (c->ws_ok && c->zero16 && wsgemm_supported(a, cg, epi)) { launch_wsgemm(c->cfg.dtype, a, cg, epi, c->zero16, c->stream); return; }
+    if (c->ws_ok && c->zero16 && wsgemm_supported(a, cg, epi)) { launch_wsgemm(c->cfg.dtype, a, cg, epi, c->zero16, c->sw.ws_cfg, c->stream); return; }
     // 1x1 stride-1 convolutions are plain GEMMs; everything else needs the gather path of the tiled kernel
     if (cg.mode == 0 && gemm_dma_supported(a)) launch_gemm_dma(c->cfg.dtype, a, epi, c->gemm_ws, c->gemm_ws_floats, c->stream);
     else if (c->zero16 && !resid && gemm_dma_conv_supported(a, cg, epi)) launch_gemm_dma_conv(c->cfg.dtype, a, cg, epi, c->zero16, c->gemm_ws, c->gemm_ws_floats, c->stream);

@@ -80,7 +80,7 @@ static int encode_impl(rdx_ctx* c, const float* image, const float* previous, in
     // barriers; packed [C / 32][pixels / 16][64][8]) whenever every convolution of it has a packed kernel -- the stem writes the packed
     // layout, the last Bottleneck writes row-major NHWC for the GEMMs behind it. RDX_PCONV=0 keeps the row-major kernels of rounds 1-3
     // (the A/B leg of tests/test_gpu_fullsize.py).
-    bool packed = c->zero16 && c->trunk_packed && stem_pool_supported(f.v_stem) && f.v_stem % 32 == 0;
+    bool packed = c->zero16 && c->sw.pconv && stem_pool_supported(f.v_stem) && f.v_stem % 32 == 0;
     if (packed) {
         int Ch = f.v_stem;
         for (const VBlock& vb : c->vb) {
@@ -97,7 +97,7 @@ static int encode_impl(rdx_ctx* c, const float* image, const float* previous, in
     auto pgemm_rows = [&](const void* X, int K, const GemmW& W, const float* bias, const void* resid, void* out, int rows, int epi, bool rowout) {
         PConvArgs a; memset(&a, 0, sizeof(a));
         a.X = X; a.W = W.w; a.bias = bias; a.resid = resid; a.out = out; a.zero16 = c->zero16;
-        a.Hin = a.Win = a.Hout = a.Wout = 1; a.Cin = K; a.N = W.N; a.M = rows; a.mt_in = a.mt_out = mtiles(rows); a.ldo = W.N; a.no_ksplit = c->pconv_noks;
+        a.Hin = a.Win = a.Hout = a.Wout = 1; a.Cin = K; a.N = W.N; a.M = rows; a.mt_in = a.mt_out = mtiles(rows); a.ldo = W.N; a.no_ksplit = !c->sw.pconv_ksplit;
         if (!launch_pconv(dt, a, 1, 1, epi, rowout, s)) c->unsupported = "pconv: a 1 x 1 stride-1 convolution whose input and output row tilings differ";
     };
     if (stem_pool_supported(f.v_stem)) {
@@ -115,7 +115,7 @@ static int encode_impl(rdx_ctx* c, const float* image, const float* previous, in
         PConvArgs a; memset(&a, 0, sizeof(a));
         a.X = X; a.W = W.w; a.bias = bias; a.resid = resid; a.out = out; a.zero16 = c->zero16;
         a.Hin = Hin; a.Win = Hin; a.Cin = Cin; a.Hout = Hout; a.Wout = Hout; a.N = W.N;
-        a.M = B * Hout * Hout; a.mt_in = mtiles((long)B * Hin * Hin); a.mt_out = mtiles(a.M); a.ldo = W.N; a.no_ksplit = c->pconv_noks;
+        a.M = B * Hout * Hout; a.mt_in = mtiles((long)B * Hin * Hin); a.mt_out = mtiles(a.M); a.ldo = W.N; a.no_ksplit = !c->sw.pconv_ksplit;
         if (!launch_pconv(dt, a, taps, stride, epi, rowout, s)) c->unsupported = "pconv: a 1 x 1 stride-1 convolution whose input and output row tilings differ";
     };
     for (const VBlock& vb : c->vb) {
@@ -203,13 +203,13 @@ static int encode_impl(rdx_ctx* c, const float* image, const float* previous, in
     // registers, the workgroup's waves splitting K; the 1024-row GEMMs of a batch of 32 had 48-192 LDS-staged tiles with 12-48 serial 0.7-us
     // k-steps each, one image's 32 rows ran on the GEMV family): the LayerNorms and the attention output write the packed layout, only
     // Q / K / V stay row-major for the attention kernel.
-    bool qpacked = c->trunk_packed && c->zero16 && NQ % 16 == 0 && layernorm_packed_supported(H) && H % 32 == 0 && f.q_inter % 32 == 0;
+    bool qpacked = c->sw.pconv && c->zero16 && NQ % 16 == 0 && layernorm_packed_supported(H) && H % 32 == 0 && f.q_inter % 32 == 0;
     if (qpacked) {
         const int mt = M / 16;
         auto pgemm = [&](const void* X, int K, const GemmW& W, const float* bias, const void* resid, void* out, int epi, bool rowout) {
             PConvArgs a; memset(&a, 0, sizeof(a));
             a.X = X; a.W = W.w; a.bias = bias; a.resid = resid; a.out = out; a.zero16 = c->zero16;
-            a.Hin = a.Win = a.Hout = a.Wout = 1; a.Cin = K; a.N = W.N; a.M = M; a.mt_in = mt; a.mt_out = mt; a.ldo = W.N; a.no_ksplit = c->pconv_noks;
+            a.Hin = a.Win = a.Hout = a.Wout = 1; a.Cin = K; a.N = W.N; a.M = M; a.mt_in = mt; a.mt_out = mt; a.ldo = W.N; a.no_ksplit = !c->sw.pconv_ksplit;
             if (!launch_pconv(dt, a, 1, 1, epi, rowout, s)) c->unsupported = "pconv: a 1 x 1 stride-1 convolution whose input and output row tilings differ";
         };
         auto attn = [&](const void* Q, long q_ts, const void* K_, const void* V_, long kv_bs, long kv_ts, int Tk) {

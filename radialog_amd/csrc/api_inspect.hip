@@ -9,7 +9,7 @@
 extern "C" int rdx_kv_read(rdx_ctx* c, int layer, int which, void* dst) {
     if (!c || !c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_kv_read: no llama state");
     if (layer < 0 || layer >= c->cfg.layers || !dst) return fail(c, -1, "rdx_kv_read: bad arguments");
-    if (c->kv_fp8) {        // the stored values x' = code 2^e in the model dtype, logical order
+    if (c->sw.kv_fp8) {        // the stored values x' = code 2^e in the model dtype, logical order
         launch_kv8_read(c->cfg.dtype, kv_ptr(c, which ? c->vcache : c->kcache, layer), kvx_ptr(c, which ? c->vexp : c->kexp, layer), which ? 0 : 1,
                         c->kv_layer_elems / ((size_t)c->cfg.max_len * 128), c->cfg.max_len, nullptr, dst, c->stream);
         return 0;
@@ -21,7 +21,7 @@ extern "C" int rdx_kv_read(rdx_ctx* c, int layer, int which, void* dst) {
 
 extern "C" int rdx_kv_read_codes(rdx_ctx* c, int layer, int which, void* codes, void* exps) {
     if (!c || !c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_kv_read_codes: no llama state");
-    if (!c->kv_fp8) return fail(c, -1, "rdx_kv_read_codes: the context's KV cache is not fp8 (rdx_set_option kv_fp8)");
+    if (!c->sw.kv_fp8) return fail(c, -1, "rdx_kv_read_codes: the context's KV cache is not fp8 (rdx_set_option kv_fp8)");
     if (layer < 0 || layer >= c->cfg.layers || !codes || !exps) return fail(c, -1, "rdx_kv_read_codes: bad arguments");
     launch_kv8_read(c->cfg.dtype, kv_ptr(c, which ? c->vcache : c->kcache, layer), nullptr, which ? 0 : 1, c->kv_layer_elems / ((size_t)c->cfg.max_len * 128),
                     c->cfg.max_len, codes, nullptr, c->stream);

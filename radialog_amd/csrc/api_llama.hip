@@ -54,7 +54,7 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
     t.pos = advance ? c->d_pos : nullptr; t.slot_b = advance ? c->d_slot : nullptr; t.step_b = c->d_step;
     t.embed = c->embed; t.vocab = f.vocab; t.x_next = c->dx; t.H = f.hidden; t.pos_ro = c->d_pos; t.cos_t = c->rope_cos; t.sin_t = c->rope_sin;
     t.cur_rope = c->d_cur_rope;
-    t.ctr_zero = c->chain_mlp ? c->d_ctr : nullptr;
+    t.ctr_zero = c->sw.chain ? c->d_ctr : nullptr;
     t.n_zero = (int)chain_ctr_ints(f.layers);
     t.epoch = c->d_epoch;
     if (row0) {       // (advance == 0: pos / slot_b are null)
@@ -211,7 +211,7 @@ static int rules_need_prefill(rdx_ctx* c, const char* who) {
 // What the prompt path refuses, decided from the arguments and the context alone. Its entry points ask before their first effect: before the workspace
 // grows, before cur_* / hist_ready change and before the first launch, so that a refused call leaves the conversation it would have replaced as it was.
 static int prompt_refuse(rdx_ctx* c, int B, int keep, int row0) {
-    if (c->kv_fp8 && (keep > 0 || row0 > 0)) return fail(c, -1, "the prompt path on the fp8 KV cache (kv_fp8) starts at slot 0 of row 0");
+    if (c->sw.kv_fp8 && (keep > 0 || row0 > 0)) return fail(c, -1, "the prompt path on the fp8 KV cache (kv_fp8) starts at slot 0 of row 0");
     if (B > 32 && !blk64_ok(c, B)) return fail(c, -8, "rdx_prefill: more than 32 rows per context need the Vicuna-7B widths (hidden 4096, inter 11008: the row-block decode family)");
     return 0;
 }
@@ -431,7 +431,7 @@ extern "C" int rdx_score(rdx_ctx* c, const int32_t* ids, const int32_t* mask, in
             dst.push_back(scored ? b * T + t + 1 : -1); ldst.push_back(logits ? b * T + t : -1);
         }
     const size_t n = rows.size();
-    const size_t chunk = c->score_chunk > 0 ? std::min<size_t>((size_t)c->score_chunk, n) : n;
+    const size_t chunk = c->sw.score_chunk > 0 ? std::min<size_t>((size_t)c->sw.score_chunk, n) : n;
     if (int prc = n ? prompt_refuse(c, B, 0, 0) : 0) return prc;       // (nothing scored: no prompt runs)
     int rc = ensure_prefill_ws(c, (size_t)B * T);
     if (rc) return rc;
@@ -484,7 +484,7 @@ static void step_blk(rdx_ctx* c, int B) {
         // down_proj: K-split over 4 workgroups per tile into fp32 slabs, combined (+ residual) by the next RMSNorm (xsplit32_k<.., BLK>: 21 us against
         // 29.5 us for the prompt's weight-stationary kernel at 64 rows); RDX_BLK_DOWN=0: wstat_k, the A/B leg
         const GemmArgs d = blk_unit(c, L, UNIT_DOWN, B);
-        if (c->blk_down && xsplit_blk_supported(d)) { launch_xsplit_blk(dt, d, c->kslab, s); c->pend_groups = 4; }
+        if (c->sw.blk_down && xsplit_blk_supported(d)) { launch_xsplit_blk(dt, d, c->kslab, s); c->pend_groups = 4; }
         else launch_wstat(dt, d, EPI_RESID, s);
     }
 }
@@ -529,7 +529,7 @@ static void attn_oproj(rdx_ctx* c, int l, int B) {
     const LlamaLayer& L = c->ll[l];
     DecAttnArgs at = dec_attn_args(c, l);
     const GemmArgs ao = unit_args(c, &L, UNIT_O, B);
-    if (c->fuse_attn_oproj && attn_oproj16_supported(c->ld, L.wo.N, L.wo.K, B)) {
+    if (c->sw.fuse_ao && attn_oproj16_supported(c->ld, L.wo.N, L.wo.K, B)) {
         at.trace = l == c->ao_trace_layer ? c->ao_trace : nullptr;
         at.out = c->d_gran; at.epoch = c->d_epoch; at.layers = c->cfg.layers; at.layer = l;      // tagged granules instead of datt (handoff.h)
         GemmArgs ag = ao;
@@ -692,8 +692,8 @@ static int decode_loop(rdx_ctx* c, int B, int max_new, int eos_id, void* scores,
             if (rc) return rc;
         }
         // EOS poll: a 4-byte-per-row copy + stream sync every 4th step (round 4: every 16th -- up to 15 wasted 3.9-ms steps per finished
-        // batch); the sync costs one launch-queue drain (~20 us) per 4 steps of 2.6-3.9 ms. RDX_EOS_POLL overrides (tools/eos_time.py)
-        static const int check_every = [] { const char* e = getenv("RDX_EOS_POLL"); const int v = e ? atoi(e) : 4; return v > 0 ? v : 4; }();
+        // batch); the sync costs one launch-queue drain (~20 us) per 4 steps of 2.6-3.9 ms. The switch "eos_poll" overrides (tools/eos_time.py)
+        const int check_every = c->sw.eos_poll > 0 ? c->sw.eos_poll : 4;
         while (done < max_new) {
             if (use_graph) {
                 HIPCHK(c, hipGraphLaunch(c->graph, c->stream));
@@ -804,7 +804,7 @@ extern "C" int rdx_beam_search(rdx_ctx* c, const int32_t* ids, const int32_t* ma
     std::vector<BeamHyps> hyps(groups);
     for (BeamHyps& h : hyps) { h.num_beams = num_beams; h.length_penalty = length_penalty; h.early_stopping = early_stopping; }
     std::vector<char> done(groups, 0);
-    const bool full_copy = getenv("RDX_BEAM_FULLCOPY") && atoi(getenv("RDX_BEAM_FULLCOPY"));     // tests: move every generated position (A/B leg)
+    const bool full_copy = c->sw.beam_fullcopy != 0;     // tests: move every generated position (A/B leg)
     int cur_len = T, steps = 0;
     for (int step = 0; step < max_new; ++step) {
         HIPCHK(c, hipMemcpyAsync(c->bm_scores, beam_scores.data(), rows * sizeof(float), hipMemcpyHostToDevice, s));

@@ -394,18 +394,15 @@ __global__ __launch_bounds__(WAVES * 64, (WAVES == 16 ? 1 : 4)) void decode_atte
 }
 
 // which build a launch of heads x B pairs takes (both caches): 16, 8 or 4 waves
-static int decode_attention_waves(const DecAttnArgs& a, int B) {
-    const char* tp_env = getenv("RDX_ATT_TP");                       // tests: 1 forces the throughput variant, 2 the 8-wave one (re-read per launch: the tests flip it between engines)
-    const int force_tp = tp_env ? atoi(tp_env) : 0;
-    static const bool att_mid = !(getenv("RDX_ATT_MID") && atoi(getenv("RDX_ATT_MID")) == 0);      // A/B switch, read once
-    if (a.d.heads * B <= 256 && !force_tp) return DA_WAVES;
-    if (force_tp == 2 || (a.d.heads * B <= 512 && !force_tp && att_mid)) return DA_WAVES_MID;
+static int decode_attention_waves(const DecAttnArgs& a, int B, DecAttnSw sw) {
+    if (a.d.heads * B <= 256 && !sw.att_tp) return DA_WAVES;
+    if (sw.att_tp == 2 || (a.d.heads * B <= 512 && !sw.att_tp && sw.att_mid)) return DA_WAVES_MID;
     return DA_WAVES_TP;
 }
 
-void launch_decode_attention_kv8(int dtype, const DecAttnArgs& a, signed char* kexp, signed char* vexp, int B, hipStream_t s) {
+void launch_decode_attention_kv8(int dtype, const DecAttnArgs& a, signed char* kexp, signed char* vexp, int B, DecAttnSw sw, hipStream_t s) {
     dim3 grid(a.d.heads, B);
-    const int waves = decode_attention_waves(a, B);
+    const int waves = decode_attention_waves(a, B, sw);
     const size_t smem = decode_attention_smem_floats(waves, a.d.max_len) * sizeof(float);
     if (waves == DA_WAVES) {
         RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((decode_attention_kv8_k<T, DA_WAVES>), grid, dim3(DA_WAVES * 64), smem, s, a, kexp, vexp));
@@ -472,14 +469,14 @@ void launch_kv8_read(int dtype, const void* codes, const signed char* exps, int 
                                                 max_len, total8, (unsigned char*)codes_out, (T*)t_out));
 }
 
-void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, hipStream_t s) {
+void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, DecAttnSw sw, hipStream_t s) {
     dim3 grid(a.d.heads, B);
-    const int waves = decode_attention_waves(a, B);
+    const int waves = decode_attention_waves(a, B, sw);
     if (waves == DA_WAVES) {
         const size_t smem = decode_attention_smem_floats(DA_WAVES, a.d.max_len) * sizeof(float);
         RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((decode_attention_k<T, DA_WAVES>), grid, dim3(DA_WAVES * 64), smem, s, a));
     } else if (waves == DA_WAVES_MID) {
-        // 9-16 rows at 32 heads (round 5; RDX_ATT_MID=0: the 4-wave form, the A/B leg; RDX_ATT_TP=2: forced, tests): batch 12 3.162 -> 3.098 ms per step, 16: 3.222 -> 3.178
+        // 9-16 rows at 32 heads (round 5; att_mid 0: the 4-wave form, the A/B leg; att_tp 2: forced, tests): batch 12 3.162 -> 3.098 ms per step, 16: 3.222 -> 3.178
         const size_t smem = decode_attention_smem_floats(DA_WAVES_MID, a.d.max_len) * sizeof(float);
         RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((decode_attention_k<T, DA_WAVES_MID>), grid, dim3(DA_WAVES_MID * 64), smem, s, a));
     } else {

@@ -234,7 +234,7 @@ __global__ __launch_bounds__(FL_WAVES * 64, 4) void flash_prefill_k(AttnArgs a) 
 }
 
 bool flash_prefill_supported(int head_dim, const AttnArgs& a) {
-    const int min_wgs = a.flash_min;                           // rdx_ctx::flash_min: RDX_FLASH_MIN at rdx_create (default 512), rdx_set_option("flash_min") in tests
+    const int min_wgs = a.flash_min;                           // the context's switch "flash_min" (default 512)
     const long wgs = (long)((a.Tq + FL_QB - 1) / FL_QB) * a.H * a.B;
     return min_wgs > 0 && head_dim == FL_D && a.causal && wgs >= min_wgs && (a.v_ts & 7) == 0 && (a.q_ts & 7) == 0 && (a.k_perm || (a.k_ts & 7) == 0) &&
            a.key_mask && (a.km_bs & 3) == 0;

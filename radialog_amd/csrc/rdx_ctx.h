@@ -67,8 +67,16 @@ struct GraphKey {
     }
 };
 
+// The runtime switches of one context, one int each (a bool holds 0 / 1). What each selects, its environment variable, default, range and when it may be
+// set stand in ONE table: api_options.hip. The environment is read once, at rdx_create; after that only rdx_set_option changes a value.
+struct Switches {
+    int fuse_ao, chain, flash_min, xs16, prompt_blk, blk_down, pconv, pconv_ksplit, kperm, wcode, w4, kv_fp8, score_chunk;
+    int att_tp, att_mid, xdup, ws_cfg, beam_fullcopy, eos_poll;
+};
+
 struct rdx_ctx {
     rdx_config cfg;
+    Switches sw = {};                // defaults and the environment: options_from_env (api_options.hip), called by rdx_create
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -87,10 +95,9 @@ struct rdx_ctx {
     LlamaDims ld;
     void *kcache = nullptr, *vcache = nullptr;     // [layers][B][heads][max_len][D]
     size_t kv_layer_elems = 0;
-    // fp8 KV cache (rdx_set_option("kv_fp8", 1) before rdx_finalize_weights; the format: radialog_amd/kv8.py): kcache / vcache then hold the e4m3 codes, one BYTE
+    // fp8 KV cache (sw.kv_fp8; the format: radialog_amd/kv8.py): kcache / vcache then hold the e4m3 codes, one BYTE
     // per element (K in the kperm8 order of rdx_common.h, V row-major), kexp / vexp the row exponents [layers][B][heads][max_len]; kv_kstage / kv_vstage:
     // the prompt's K / V rows of ONE layer in the model dtype, [B][heads][ceil16(T)][128] row-major -- what the prompt's own attention reads
-    bool kv_fp8 = false;
     signed char *kexp = nullptr, *vexp = nullptr;
     void *kv_kstage = nullptr, *kv_vstage = nullptr;
     size_t kv_alloc_bytes = 0;                     // bytes of the KV allocation (caches, exponents; the staging buffer is not part of it): rdx_kv_bytes
@@ -111,16 +118,6 @@ struct rdx_ctx {
     int cur_steps = 0;               // tokens selected since the last prefill (1 after it): bounds rdx_decode_step
     int32_t* cur_tokens = nullptr;
     hipGraphExec_t graph = nullptr;
-    bool fuse_attn_oproj = true;     // RDX_FUSE_AO=0 (tests): attention and o_proj as separate launches. Default where supported (batch <= 2):
-                                     // ONE 16-wave launch with a fence-free hand-off (chain.hip: attn_oproj16_k)
-    bool chain_mlp = true;           // RDX_CHAIN=0 (tests): one kernel per unit. Default at batch <= 2: down(l) -> QKV(l+1) as one chained
-                                     // launch, one workgroup per CU (chain.hip: decode_chain_k)
-    bool xs16 = true;                // batch 3-16 decode on the one-row-tile family (xs16.hip: norm-prologue projections + un-split o_proj / down, 5 launches
-                                     // per layer); RDX_XS16=0 at create / rdx_set_option("xs16", 0): the 32-row family of xstat32.hip (7 launches; A/B leg of the tests)
-    bool prompt_blk = true;          // one prompt's K = 4096 projections on xstat32_k<.., BLK> (RDX_PBLK=0 / rdx_set_option("prompt_blk", 0): wstat_k, the A/B leg)
-    bool blk_down = true;            // 33-128 rows, model-dtype weights: down_proj K-split into fp32 slabs (xsplit32_k<.., BLK>); RDX_BLK_DOWN=0 at create: wstat_k, the A/B leg
-    bool wcode = true;               // batch <= 2 chained family, bf16: gate/up, down_proj, QKV and the lm_head stream their coded copy (GemmW::wc); rdx_set_option("wcode", 0): the raw one
-    bool w4 = true;                  // ... their int4 stream (GemmW::w4) where the weight has one, and so do QKV, gate/up and down_proj of the 3-16-row family; rdx_set_option("w4", 0): the packed bf16 bytes of W' (same bits)
     int* w4_bad = nullptr;           // device flag of the int4 quantiser: the weight held an Inf / NaN
     bool has_fp8_w = false, has_w4_w = false;     // kinds of GEMM weights set so far (RDX_W_GEMM_FP8 and RDX_W_GEMM_W4 do not mix)
     // launches this context issued, by kernel and by the copy it streamed, counted where the choice is made (api_dispatch.hip skinny / launch_chain /
@@ -137,9 +134,6 @@ struct rdx_ctx {
     int* d_cctr = nullptr;
     int *d_ctr = nullptr, *d_err = nullptr;   // hand-off counters of the chained launches (= d_cctr), sticky error flag
     void* d_gran = nullptr; int *d_hint = nullptr, *d_epoch = nullptr;   // fused attention + o_proj launch: tagged-granule buffer [2][hidden] x 4 B, hint words, step epoch (handoff.h)
-    int flash_min = 512;             // batched causal prefill attention: flash_prefill_k from this many workgroups (RDX_FLASH_MIN at create / rdx_set_option)
-    bool pconv_noks = false;         // RDX_PCONV_KSPLIT=0 at create: pconv_k never splits K inside a workgroup (A/B)
-    bool trunk_packed = true;        // the ResNet trunk (and the Q-Former GEMMs) on fragment-packed activations (pconv.hip); RDX_PCONV=0 at create: the row-major kernels
     bool ws_ok = false;              // set while the image encoder runs: its many-row GEMMs / convolutions may take wsgemm_k
     float* gemm_ws = nullptr; size_t gemm_ws_floats = 0;      // split-K slabs of gemm_dma_k
     GraphKey gkey;
@@ -159,7 +153,6 @@ struct rdx_ctx {
     int* lp_top_ids = nullptr; float* lp_top_lp = nullptr;      // [max_batch][max_len][RDX_MAX_TOP_LOGPROBS]; allocated once, so a captured graph keeps its pointers
 
     // ---- scoring pass (rdx_score), sized on first use ----
-    int score_chunk = 2048;                         // logits rows per lm_head launch (rdx_set_option("score_chunk", rows); 0 = all rows at once): profiles/r11_score.md
     void *sc_x = nullptr, *sc_xn = nullptr;         // [rows][hidden]: the gathered residual rows and their final RMSNorm
     void* sc_logits = nullptr;                      // [chunk rows][lm_head.Npad]: the one chunk of logits the library ever holds
     int* sc_idx = nullptr;                          // rows[n] | target[n] | dst[n] | ldst[n]: the host-built index lists of one call
@@ -203,6 +196,8 @@ struct rdx_ctx {
 
 int fail(rdx_ctx* c, int code, const char* fmt, ...);
 const char* create_error();
+int options_from_env(rdx_ctx* c);      // (api_options.hip) every switch to its default or its environment variable's value; nonzero: a value out of range, c->err says which
+inline DecAttnSw attn_sw(const rdx_ctx* c) { return DecAttnSw{c->sw.att_tp, c->sw.att_mid}; }
 
 #define HIPCHK(c, call)                                                                         \
     do {                                                                                        \
@@ -227,6 +222,8 @@ inline void dfree(rdx_ctx* c, P*& p) {
 
 // ---- host-side GEMM dispatch (api_dispatch.hip) ----
 GemmArgs gargs(const void* X, int ldx, const GemmW& W, const float* bias, void* out, int ldo, int M);
+// the switches that travel in the arguments: every GemmArgs that may reach xstat32_k / xsplit32_k passes here (the decode and prompt unit builders, skinny(), the hooks that launch those kernels)
+inline GemmArgs with_switches(const rdx_ctx* c, GemmArgs a) { a.xdup_off = c->sw.xdup ? 0 : 1; return a; }
 GemmArgs skinny_prenorm(rdx_ctx* c, GemmArgs a, int epi);
 void skinny(rdx_ctx* c, GemmArgs a, int epi);
 void launch_ksplit(rdx_ctx* c, const GemmArgs& a);
@@ -301,13 +298,13 @@ inline bool fp8_weights(const GemmW& W) { return W.w8 && W.scale && !W.w; }     
 int take_unsupported(rdx_ctx* c);     // nonzero (and rdx_last_error set) when a launch since the last call had no kernel for its shape
 
 // ---- decoder (api_llama.hip) ----
-inline void* kv_ptr(rdx_ctx* c, void* base, int layer) { return (char*)base + (size_t)layer * c->kv_layer_elems * (c->kv_fp8 ? 1 : 2); }
+inline void* kv_ptr(rdx_ctx* c, void* base, int layer) { return (char*)base + (size_t)layer * c->kv_layer_elems * (c->sw.kv_fp8 ? 1 : 2); }
 inline signed char* kvx_ptr(rdx_ctx* c, signed char* base, int layer) { return base + (size_t)layer * (c->kv_layer_elems / 128); }      // fp8 KV cache: a layer's row exponents
 // decode attention of one layer on whichever cache the context holds (at from dec_attn_args)
 void run_decode_attention(rdx_ctx* c, const DecAttnArgs& at, int layer, int B);
 // every entry point that needs the cached rows in the model dtype refuses on an fp8 KV cache (-1, a message naming "kv_fp8")
 inline int kv8_refuse(rdx_ctx* c, const char* who, const char* why) {
-    return c->kv_fp8 ? fail(c, -1, "%s: not built for the fp8 KV cache (kv_fp8): %s", who, why) : 0;
+    return c->sw.kv_fp8 ? fail(c, -1, "%s: not built for the fp8 KV cache (kv_fp8): %s", who, why) : 0;
 }
 int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep,
                  int max_new, int eos_id, int pad_id, int32_t* out_tokens, void* logits);

@@ -46,7 +46,7 @@ struct GemmArgs {
     ActLayout out_packed;            // EPI_SILU_MUL: the order the output is written in (see ActLayout)
     ActLayout xpacked;               // the order X is in (see ActLayout)
     int mtiles;                      // row tiles of 16 of the packed orders
-    int xdup_off;                    // experiments (RDX_XDUP=0): padding rows of a 32-row block load their own (zero / stale) lines instead of re-reading real rows
+    int xdup_off;                    // the context's switch "xdup" off (set by the argument builders): padding rows of a 32-row block load their own (zero / stale) lines instead of re-reading real rows
     // fp8 activations (W8A8: gemm8.hip, xstat32_k<.., A8>): X holds e4m3 bytes, xscale[row][xgroups] their absmax / 448 scales over `xgroups`
     // equal K ranges (1 behind an RMSNorm, 2 o_proj, 4 down_proj); see ActLayout
     const float* xscale; int xgroups;
@@ -97,7 +97,7 @@ struct PConvArgs {
     int mt_in, mt_out;               // 16-row tiles of the packed input / output tensors
     int ldo;                         // row stride (elements) when the output is written row-major
     int clog;                        // log2(Cin / 32), filled by launch_pconv
-    int no_ksplit;                   // experiments: never let a workgroup's waves split K (rdx_ctx::pconv_noks, RDX_PCONV_KSPLIT=0 at create)
+    int no_ksplit;                   // experiments: never let a workgroup's waves split K (the switch "pconv_ksplit" off)
     int tile_m, tile_n, tile_k;      // experiments: forced register tile (MTW x NTW, K split over tile_k waves; 0 = pick; tools/pconv_check.py)
 };
 
@@ -192,7 +192,7 @@ void launch_xstat_blk8(int dtype, const GemmArgs& a, int epi, hipStream_t s);
 int xsplit_blk8_groups(const GemmArgs& a);
 void launch_xsplit_blk8(int dtype, const GemmArgs& a, float* slab, hipStream_t s);
 bool wsgemm_supported(const GemmArgs& a, const ConvGeom& cg, int epi);
-void launch_wsgemm(int dtype, const GemmArgs& a, const ConvGeom& cg, int epi, const void* zero16, hipStream_t s);
+void launch_wsgemm(int dtype, const GemmArgs& a, const ConvGeom& cg, int epi, const void* zero16, int ws_cfg, hipStream_t s);      // ws_cfg: the context's switch (0 = by shape, 1..5 = tile shapes A..E)
 
 // fragment-packed convolution (pconv.hip): taps 1 | 9 (3 x 3 pad 1), stride 1 | 2, epilogues NONE / RELU / RESID_RELU; rowout = row-major output
 bool pconv_supported(const PConvArgs& a, int taps, int stride, int epi);
@@ -236,11 +236,13 @@ struct DecAttnArgs {
     const int* epoch = nullptr;
     int layers = 0, layer = 0;
 };
-void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, hipStream_t s);
+// host only, beside the arguments: the context's switches "att_tp" (1 forces the 4-wave throughput build, 2 the 8-wave one) and "att_mid" (api_options.hip)
+struct DecAttnSw { int att_tp = 0, att_mid = 1; };
+void launch_decode_attention(int dtype, const DecAttnArgs& a, int B, DecAttnSw sw, hipStream_t s);
 // fp8 KV cache (the format: radialog_amd/kv8.py; device side: rdx_common.h "kv8"). a.kcache / a.vcache are the code slabs [B][heads][max_len][128] bytes (K in
 // the kperm8 order, V row-major; a.d.k_perm is not looked at), kexp / vexp the row exponents [B][heads][max_len]. Same variants and output bits as
 // launch_decode_attention on a T cache holding the stored values.
-void launch_decode_attention_kv8(int dtype, const DecAttnArgs& a, signed char* kexp, signed char* vexp, int B, hipStream_t s);
+void launch_decode_attention_kv8(int dtype, const DecAttnArgs& a, signed char* kexp, signed char* vexp, int B, DecAttnSw sw, hipStream_t s);
 // staged T rows [slabs][stage_len][128] (row-major K and V) -> codes and exponents of cache positions [slot0, slot0 + T) of every slab
 void launch_kv8_quant_rows(int dtype, const void* kstage, const void* vstage, int stage_len, void* kcodes, signed char* kexp, void* vcodes, signed char* vexp,
                            size_t slabs, int max_len, int T, int slot0, hipStream_t s);

@@ -248,11 +248,10 @@ static void launch_ws_cfg(const GemmArgs& a, const ConvGeom& cg, const void* zer
 }
 
 template <typename T, int EPI, bool CONV>
-static void launch_ws_epi(const GemmArgs& a, const ConvGeom& cg, const void* zero16, hipStream_t s) {
-    const char* e = getenv("RDX_WS_CFG");                        // tests: force a tile shape A .. E
+static void launch_ws_epi(const GemmArgs& a, const ConvGeom& cg, const void* zero16, int ws_cfg, hipStream_t s) {
     const int wgA = ((a.M + 511) / 512) * ((a.N + 127) / 128), wgB = ((a.M + 127) / 128) * ((a.N + 127) / 128);
     char cfg = a.N <= 64 ? 'D' : (wgA >= 200 ? 'A' : (wgB >= 160 ? 'B' : 'C'));
-    if (e && *e >= 'A' && *e <= 'E') cfg = *e;
+    if (ws_cfg >= 1 && ws_cfg <= 5) cfg = (char)('A' + ws_cfg - 1);       // tests: a forced tile shape A .. E
     // (the implicit-GEMM address state of a convolution does not fit next to 128 accumulators: its large tile is 256 rows, E)
     if (CONV && cfg == 'A') cfg = 'E';
     if (cfg == 'D') launch_ws_cfg<T, EPI, 4, 4, 8, CONV>(a, cg, zero16, s);          // N <= 64: 512 rows x 64 columns
@@ -263,21 +262,21 @@ static void launch_ws_epi(const GemmArgs& a, const ConvGeom& cg, const void* zer
 }
 
 template <typename T, bool CONV>
-static void launch_ws_T(const GemmArgs& a, const ConvGeom& cg, int epi, const void* zero16, hipStream_t s) {
+static void launch_ws_T(const GemmArgs& a, const ConvGeom& cg, int epi, const void* zero16, int ws_cfg, hipStream_t s) {
     switch (epi) {
-        case EPI_NONE: launch_ws_epi<T, EPI_NONE, CONV>(a, cg, zero16, s); break;
-        case EPI_RELU: launch_ws_epi<T, EPI_RELU, CONV>(a, cg, zero16, s); break;
-        case EPI_GELU: launch_ws_epi<T, EPI_GELU, CONV>(a, cg, zero16, s); break;
-        case EPI_RESID: launch_ws_epi<T, EPI_RESID, CONV>(a, cg, zero16, s); break;
-        case EPI_RESID_RELU: launch_ws_epi<T, EPI_RESID_RELU, CONV>(a, cg, zero16, s); break;
+        case EPI_NONE: launch_ws_epi<T, EPI_NONE, CONV>(a, cg, zero16, ws_cfg, s); break;
+        case EPI_RELU: launch_ws_epi<T, EPI_RELU, CONV>(a, cg, zero16, ws_cfg, s); break;
+        case EPI_GELU: launch_ws_epi<T, EPI_GELU, CONV>(a, cg, zero16, ws_cfg, s); break;
+        case EPI_RESID: launch_ws_epi<T, EPI_RESID, CONV>(a, cg, zero16, ws_cfg, s); break;
+        case EPI_RESID_RELU: launch_ws_epi<T, EPI_RESID_RELU, CONV>(a, cg, zero16, ws_cfg, s); break;
         default: break;
     }
 }
 
-void launch_wsgemm(int dtype, const GemmArgs& a, const ConvGeom& cg, int epi, const void* zero16, hipStream_t s) {
+void launch_wsgemm(int dtype, const GemmArgs& a, const ConvGeom& cg, int epi, const void* zero16, int ws_cfg, hipStream_t s) {
     RDX_DISPATCH_T(dtype, T, {
-        if (cg.mode == 1) launch_ws_T<T, true>(a, cg, epi, zero16, s);
-        else launch_ws_T<T, false>(a, cg, epi, zero16, s);
+        if (cg.mode == 1) launch_ws_T<T, true>(a, cg, epi, zero16, ws_cfg, s);
+        else launch_ws_T<T, false>(a, cg, epi, zero16, ws_cfg, s);
     });
 }
 

@@ -266,14 +266,13 @@ __global__ __launch_bounds__(XS_THREADS) void xstat32_k(GemmArgs a) {
 // (A variant that ran that RMSNorm as a tail of this launch -- write-through slabs, arrival counter, workgroups 0..31 finishing one
 // row each -- was measured 1.2 us slower per norm than the 5-us launch it replaced and made low-index workgroups wait on all others,
 // against the liveness rule of handoff.h; removed in round 2.)
-// A8 (with W8): the workgroup quantises ITS K range of the (model-dtype, fragment-packed) activations to e4m3 at start-up -- one absmax / 448
-// scale per row over the range (cross-wave maximum through LDS) -- and multiplies fp8 x fp8; the partial carries wscale[n] * that scale. The
-// ranges of the KGN groups are the `xgroups` K groups of the fp8 scheme (gemm8.hip; whole 128-deep blocks): o_proj 2, down_proj 4.
+// W8 is W8A16: the e4m3 weight fragments are expanded to the model dtype in registers (exact) and multiply the producer's model-dtype fragments as they are.
+// (The fp8 x fp8 form of rounds 3-5, whose workgroups quantised their K range of the activations at start-up, cost ~3 us of a 9.6-us o_proj and was the less
+// accurate of the two: profiles/r06_fp8_variants.md; removed.)
 // BLK (round 5, 33-128 decoder rows): the rows in blocks of 32, the row-block workgroups of a (tile slot, K group) pair on one XCD like xstat32_k<.., BLK>;
 // X is the fragment-packed [k / 32][mtiles][lane][8], the slabs are [KGN][16 mtiles][N].
-template <typename T, int KC, int KGN, bool W8, int TPI, bool A8 = false, bool BLK = false>
+template <typename T, int KC, int KGN, bool W8, int TPI, bool BLK = false>
 __global__ __launch_bounds__(XS_THREADS) void xsplit32_k(GemmArgs a, float* __restrict__ slab) {
-    static_assert(!A8 || W8, "fp8 activations go with fp8 weights");
     constexpr int SLOTS = XS_WAVES * KGN, CPW = (KC + SLOTS - 1) / SLOTS, FPL = W8 ? 2 : 1;   // fragments (MFMAs per row tile) per load
     extern __shared__ __attribute__((aligned(16))) unsigned char smx[];
     float* red = reinterpret_cast<float*>(smx);       // [2 bufs][TPI][8 waves][2 mt][256]
@@ -295,14 +294,7 @@ __global__ __launch_bounds__(XS_THREADS) void xsplit32_k(GemmArgs a, float* __re
 #define XS_T(i) do { if (trc) trc[i] = (long long)__builtin_amdgcn_s_memrealtime(); } while (0)
     XS_T(0);
     const int slot = kg * XS_WAVES + wa;
-    int c0 = (KC * slot) / SLOTS, cnt = (KC * (slot + 1)) / SLOTS - c0;      // wave-uniform
-    if (A8) {
-        // fp8 x fp8: the K range of group kg is the scheme's quantisation group -- whole 128-deep blocks [NB kg / KGN, NB (kg + 1) / KGN), NB = K / 128
-        // (gemm8.hip) -- split evenly over the 8 waves (KC counts 64-deep chunks here)
-        const int gs = 2 * (((KC >> 1) * kg) / KGN), ge = 2 * (((KC >> 1) * (kg + 1)) / KGN);
-        c0 = gs + ((ge - gs) * wa) / XS_WAVES;
-        cnt = gs + ((ge - gs) * (wa + 1)) / XS_WAVES - c0;
-    }
+    const int c0 = (KC * slot) / SLOTS, cnt = (KC * (slot + 1)) / SLOTS - c0;      // wave-uniform
     const u4* wbase = reinterpret_cast<const u4*>(W8 ? a.W8 : a.W) + (size_t)c0 * 64;
     auto tile_ptr = [&](int t) { return wbase + (size_t)min(t, ntiles - 1) * KC * 64; };
 
@@ -336,43 +328,6 @@ __global__ __launch_bounds__(XS_THREADS) void xsplit32_k(GemmArgs a, float* __re
 
     const int e_mt = threadIdx.x >> 8, e_idx = threadIdx.x & 255, e_m = (BLK ? 32 * mb : 0) + e_mt * 16 + (e_idx >> 4), e_nl = e_idx & 15;
     float* sl = slab + ((size_t)kg * (BLK ? (W8 ? 32 * ((a.mtiles + 1) >> 1) : 16 * a.mtiles) : 32) + e_m) * a.N;       // slab plane: the padded row count
-    u4 xq[2][A8 ? CPW : 1];
-    float e_xs = 1.f;
-    if (A8) {
-        // row maxima over this workgroup's K range: lane -> its 4 lane groups (same row, other k) -> the 8 waves through LDS (`red` is free here)
-        float* rowmax = red;                       // [8 waves][32 rows]
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            float am = 0.f;
-#pragma unroll
-            for (int j = 0; j < CPW * FPL; ++j) am = fmaxf(am, amax8<T>(as_vec8<T>(xf[mt][j])));
-            am = fmaxf(am, __shfl_xor(am, 16, 64));
-            am = fmaxf(am, __shfl_xor(am, 32, 64));
-            if (g == 0) rowmax[wa * 32 + mt * 16 + r] = am;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int mt = 0; mt < 2; ++mt) {
-            float am = 0.f;
-#pragma unroll
-            for (int i = 0; i < XS_WAVES; ++i) am = fmaxf(am, rowmax[i * 32 + mt * 16 + r]);
-            float sc, inv;
-            fp8_scale(am, sc, inv);
-#pragma unroll
-            for (int j = 0; j < CPW; ++j) {
-                const u2 lo = quant8<T>(as_vec8<T>(xf[mt][2 * j]), inv), hi = quant8<T>(as_vec8<T>(xf[mt][2 * j + 1]), inv);
-                xq[mt][j] = (u4){lo.x, lo.y, hi.x, hi.y};
-            }
-        }
-        {
-            float am = 0.f;
-#pragma unroll
-            for (int i = 0; i < XS_WAVES; ++i) am = fmaxf(am, rowmax[i * 32 + e_mt * 16 + (e_idx >> 4)]);       // this thread's row WITHIN the block
-            float inv;
-            fp8_scale(am, e_xs, inv);
-        }
-        __syncthreads();                           // rowmax is read before the first trip's partials overwrite `red`
-    }
 
     auto trip = [&](int it, auto pf_tag) {
         constexpr bool PF = decltype(pf_tag)::value;
@@ -388,10 +343,7 @@ __global__ __launch_bounds__(XS_THREADS) void xsplit32_k(GemmArgs a, float* __re
 #pragma unroll
             for (int j = 0; j < CPW; ++j) {
                 const u4 wv = ring[q][j];
-                if (A8) {
-                    acc[q][0] = xs_mfma8(wv, xq[0][A8 ? j : 0], acc[q][0]);
-                    acc[q][1] = xs_mfma8(wv, xq[1][A8 ? j : 0], acc[q][1]);
-                } else if (W8) {
+                if (W8) {
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const u4 wd = dequant8<T>(h ? wv.z : wv.x, h ? wv.w : wv.y);
@@ -422,7 +374,7 @@ __global__ __launch_bounds__(XS_THREADS) void xsplit32_k(GemmArgs a, float* __re
 #pragma unroll
             for (int i = 0; i < XS_WAVES; ++i) v += rb[((q * XS_WAVES + i) * 2 + e_mt) * 256 + e_idx];
             const int tl = it * TPI + q, n = (ts + tl * nts) * 16 + e_nl;
-            if (tl < ntl && e_m < a.M && n < a.N) sl[n] = v * e_sc[q] * e_xs;
+            if (tl < ntl && e_m < a.M && n < a.N) sl[n] = v * e_sc[q];
         }
     };
     if (nit > 1) {
@@ -435,23 +387,6 @@ __global__ __launch_bounds__(XS_THREADS) void xsplit32_k(GemmArgs a, float* __re
     XS_T(5);
     if (trc) { trc[6] = nit; trc[7] = (long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (31 << 11)); }
 #undef XS_T
-}
-
-// Round 6: the K-split projections of the fp8 configuration's DECODE (o_proj, down_proj at 3-128 rows) multiply W8A16 -- the e4m3 weight fragments expanded to the model
-// dtype in registers (exact), the producer's model-dtype activation fragments as they are. Their fp8 x fp8 form (rounds 3-5; RDX_FP8_SPLIT_A8=1: the A/B leg) had every one
-// of the 256 workgroups load its K range of the model-dtype activations anyway, reduce the row maxima across its waves through LDS (two barriers) and convert -- ~3 us of a
-// 9.6-us o_proj whose weight stream is 16.8 MB -- and it is the less accurate of the two (profiles/r06_fp8_variants.md). The prefill and the activation-stationary
-// projections (QKV, gate/up, lm_head: their e4m3 rows come out of the RMSNorm launch for free) stay fp8 x fp8.
-static bool fp8_split_a8() {
-    static const bool a8 = getenv("RDX_FP8_SPLIT_A8") && atoi(getenv("RDX_FP8_SPLIT_A8")) == 1;
-    return a8;
-}
-
-// RDX_XDUP=0 (A/B leg): the padding rows of a 32-row block load their own lines
-static GemmArgs xs_env(GemmArgs a) {
-    static const bool off = getenv("RDX_XDUP") && atoi(getenv("RDX_XDUP")) == 0;
-    a.xdup_off = off ? 1 : 0;
-    return a;
 }
 
 // smallest row count (batch) that takes the activation-stationary / K-split kernels; below it the GEMV family of skinny_body.h
@@ -471,36 +406,32 @@ int xsplit32_groups(const GemmArgs& a) {
     return 0;
 }
 
-void launch_xsplit32(int dtype, const GemmArgs& a_in, float* slab, hipStream_t s) {
-    const GemmArgs a = xs_env(a_in);
+void launch_xsplit32(int dtype, const GemmArgs& a, float* slab, hipStream_t s) {
     const int kgn = xsplit32_groups(a);
     const int nt = (a.N + 15) / 16;
-    const bool w8 = a.W8 && a.wscale;                        // fp8 weights: fp8 x fp8, every K-group workgroup quantises its range of the activations
+    const bool w8 = a.W8 && a.wscale;                        // fp8 weights: W8A16
     const size_t smem = (size_t)2 * (w8 ? 2 : 1) * XS_WAVES * 2 * 256 * 4;
     RDX_DISPATCH_T(dtype, T, {
         if (kgn == 4) {
             const int nts = std::min(nt, 256 / 4);
-            if (w8 && fp8_split_a8()) hipLaunchKernelGGL((xsplit32_k<T, 172, 4, true, 2, true>), dim3(nts * 4), dim3(XS_THREADS), smem, s, a, slab);
-            else if (w8) hipLaunchKernelGGL((xsplit32_k<T, 172, 4, true, 2, false>), dim3(nts * 4), dim3(XS_THREADS), smem, s, a, slab);
+            if (w8) hipLaunchKernelGGL((xsplit32_k<T, 172, 4, true, 2>), dim3(nts * 4), dim3(XS_THREADS), smem, s, a, slab);
             else hipLaunchKernelGGL((xsplit32_k<T, 344, 4, false, 1>), dim3(nts * 4), dim3(XS_THREADS), smem, s, a, slab);
         } else if (kgn == 2) {
             const int nts = std::min(nt, 256 / 2);
-            if (w8 && fp8_split_a8()) hipLaunchKernelGGL((xsplit32_k<T, 64, 2, true, 2, true>), dim3(nts * 2), dim3(XS_THREADS), smem, s, a, slab);
-            else if (w8) hipLaunchKernelGGL((xsplit32_k<T, 64, 2, true, 2, false>), dim3(nts * 2), dim3(XS_THREADS), smem, s, a, slab);
+            if (w8) hipLaunchKernelGGL((xsplit32_k<T, 64, 2, true, 2>), dim3(nts * 2), dim3(XS_THREADS), smem, s, a, slab);
             else hipLaunchKernelGGL((xsplit32_k<T, 128, 2, false, 1>), dim3(nts * 2), dim3(XS_THREADS), smem, s, a, slab);
         }
     });
 }
 
-// fp8 x fp8 on row blocks (33-128 rows, round 5): X = per-block 32-row layouts at a block stride -- xstat: e4m3 blocks (ACT_BLK64_E4M3) + xscale[rows];
-// xsplit: model-dtype 64-deep blocks (ACT_BLK64), each K-group workgroup quantises its range; slabs [groups][32 NB][N]
+// fp8 weights on row blocks (33-128 rows, round 5): X = per-block 32-row layouts at a block stride -- xstat (fp8 x fp8): e4m3 blocks (ACT_BLK64_E4M3) + xscale[rows];
+// xsplit (W8A16): model-dtype 64-deep blocks (ACT_BLK64); slabs [groups][32 NB][N]
 bool xstat_blk8_supported(const GemmArgs& a, int epi) {
     return a.xpacked == ACT_BLK64_E4M3 && a.xscale && a.mtiles >= 3 && a.mtiles <= 8 && a.M <= a.mtiles * 16 && a.K == XS_K && a.W8 && a.wscale && !a.norm_w && !a.bias &&
            (epi == EPI_NONE || epi == EPI_SILU_MUL || epi == EPI_LOGITS) && (a.out_packed == ACT_ROWS || (a.out_packed == ACT_BLK64 && epi == EPI_SILU_MUL)) && (a.N + 15) / 16 >= 128;
 }
 
-void launch_xstat_blk8(int dtype, const GemmArgs& a_in, int epi, hipStream_t s) {
-    const GemmArgs a = xs_env(a_in);
+void launch_xstat_blk8(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
     const size_t smem = (size_t)2 * 2 * XS_WAVES * 2 * 256 * 4;
     RDX_DISPATCH_T(dtype, T, {
         if (epi == EPI_NONE) hipLaunchKernelGGL((xstat32_k<T, EPI_NONE, true, true, true>), dim3(256), dim3(XS_THREADS), smem, s, a);
@@ -514,17 +445,11 @@ int xsplit_blk8_groups(const GemmArgs& a) {
     return a.K == 11008 ? 4 : a.K == 4096 ? 2 : 0;
 }
 
-void launch_xsplit_blk8(int dtype, const GemmArgs& a_in, float* slab, hipStream_t s) {
-    const GemmArgs a = xs_env(a_in);
+void launch_xsplit_blk8(int dtype, const GemmArgs& a, float* slab, hipStream_t s) {
     const size_t smem = (size_t)2 * 2 * XS_WAVES * 2 * 256 * 4;
     RDX_DISPATCH_T(dtype, T, {
-        if (fp8_split_a8()) {
-            if (a.K == 11008) hipLaunchKernelGGL((xsplit32_k<T, 172, 4, true, 2, true, true>), dim3(256), dim3(XS_THREADS), smem, s, a, slab);
-            else hipLaunchKernelGGL((xsplit32_k<T, 64, 2, true, 2, true, true>), dim3(256), dim3(XS_THREADS), smem, s, a, slab);
-        } else {
-            if (a.K == 11008) hipLaunchKernelGGL((xsplit32_k<T, 172, 4, true, 2, false, true>), dim3(256), dim3(XS_THREADS), smem, s, a, slab);
-            else hipLaunchKernelGGL((xsplit32_k<T, 64, 2, true, 2, false, true>), dim3(256), dim3(XS_THREADS), smem, s, a, slab);
-        }
+        if (a.K == 11008) hipLaunchKernelGGL((xsplit32_k<T, 172, 4, true, 2, true>), dim3(256), dim3(XS_THREADS), smem, s, a, slab);
+        else hipLaunchKernelGGL((xsplit32_k<T, 64, 2, true, 2, true>), dim3(256), dim3(XS_THREADS), smem, s, a, slab);
     });
 }
 
@@ -533,10 +458,9 @@ bool xsplit_blk_supported(const GemmArgs& a) {
            (a.N + 15) / 16 >= 128 && (a.N + 15) / 16 <= 512;
 }
 
-void launch_xsplit_blk(int dtype, const GemmArgs& a_in, float* slab, hipStream_t s) {
-    const GemmArgs a = xs_env(a_in);
+void launch_xsplit_blk(int dtype, const GemmArgs& a, float* slab, hipStream_t s) {
     const size_t smem = (size_t)2 * XS_WAVES * 2 * 256 * 4;
-    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((xsplit32_k<T, 344, 4, false, 1, false, true>), dim3(256), dim3(XS_THREADS), smem, s, a, slab));
+    RDX_DISPATCH_T(dtype, T, hipLaunchKernelGGL((xsplit32_k<T, 344, 4, false, 1, true>), dim3(256), dim3(XS_THREADS), smem, s, a, slab));
 }
 
 bool xstat32_supported(const GemmArgs& a, int epi) {
@@ -574,8 +498,7 @@ bool xstat_blk_supported(const GemmArgs& a, int epi) {
            (a.N + 15) / 16 >= 128;
 }
 
-void launch_xstat_blk(int dtype, const GemmArgs& a_in, int epi, hipStream_t s) {
-    const GemmArgs a = xs_env(a_in);
+void launch_xstat_blk(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
     const size_t smem = (size_t)2 * XS_WAVES * 2 * 256 * 4;
     RDX_DISPATCH_T(dtype, T, {
         if (epi == EPI_NONE) hipLaunchKernelGGL((xstat32_k<T, EPI_NONE, false, false, true>), dim3(256), dim3(XS_THREADS), smem, s, a);
@@ -585,8 +508,7 @@ void launch_xstat_blk(int dtype, const GemmArgs& a_in, int epi, hipStream_t s) {
     });
 }
 
-void launch_xstat32(int dtype, const GemmArgs& a_in, int epi, hipStream_t s) {
-    const GemmArgs a = xs_env(a_in);
+void launch_xstat32(int dtype, const GemmArgs& a, int epi, hipStream_t s) {
     const bool w8 = a.W8 && a.wscale;        // fp8 weights: the activations are the RMSNorm's e4m3 block (ACT_BLK64_E4M3; launch_skinny_gemm checks)
     RDX_DISPATCH_T(dtype, T, {
         if (w8) launch_xstat32_t<T, true, true>(a, epi, s);

@@ -639,9 +639,23 @@ class RdxEngine:
         return out8, sc
 
     def set_option(self, name: str, value: int):
-        """rdx_set_option: "flash_min" (batched prefill attention kernel choice), "pconv" (packed / row-major encoder kernels), "xs16", "prompt_blk",
-        "wcode" (the batch <= 2 step streams the coded bf16 weights: on by default; 0 = the raw packed ones, same bits), "w4" (likewise for the int4 streams of a weights_w4 engine, which QKV, gate/up and down_proj stream at 1-16 rows), "score_chunk" (logits rows per lm_head launch of score(); default 2048, 0 = all at once)."""
+        """rdx_set_option: one runtime switch of this engine (the table: INTEGRATION.md "Runtime switches"; option_names() lists them). The environment is read
+        once, when the engine is created; afterwards only this call changes a switch. Raises RdxError for an unknown name, a value out of range, or a switch that
+        load_weights allocates by ("kv_fp8", "kperm") once the weights are loaded."""
         check(self.ctx, self.lib.rdx_set_option(self.ctx, name.encode(), int(value)), "rdx_set_option")
+
+    def get_option(self, name: str) -> int:
+        """rdx_get_option: the value of a switch as this engine holds it."""
+        v = C.c_int(0)
+        check(self.ctx, self.lib.rdx_get_option(self.ctx, name.encode(), C.byref(v)), "rdx_get_option")
+        return v.value
+
+    def option_names(self) -> list:
+        """rdx_option_name: every switch the library has, in table order."""
+        names = []
+        while (n := self.lib.rdx_option_name(len(names))) is not None:
+            names.append(n.decode())
+        return names
 
     def conv_test(self, x, w, bias=None, resid=None, ksize=1, stride=1, epi=0, path=0, iters=0):
         """One NHWC convolution (rdx_conv_test): x [B,H,H,Cin] model dtype, w [Cout, ksize*ksize*Cin] fp32 in the (kh, kw, c) K order;

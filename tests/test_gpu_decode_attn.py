@@ -9,7 +9,7 @@ negative factor), the kernels may store +0. The compiler forms T(x cos) as v_fma
 that instruction is the compiler's choice. The two zeros are the same number to everything that reads the cache (a product with either is a zero, and a sum's
 value does not depend on the sign of a zero term), so the RoPE outputs (K rows, qout) are compared as numbers: every non-zero bit pattern identical, a zero
 where the restatement has a zero. Everything else, the untouched cache rows included, is compared as bits.
-heads = 2 throughout; the variant is the launcher's choice, by RDX_ATT_TP as in the whole-model tests."""
+heads = 2 throughout; the variant is the launcher's choice, by the option "att_tp" (RDX_ATT_TP in the whole-model tests)."""
 import pytest
 import torch
 
@@ -33,11 +33,8 @@ def eng(request):
     e.close()
 
 
-def _variant(monkeypatch, variant):
-    if variant:
-        monkeypatch.setenv("RDX_ATT_TP", str(variant))
-    else:
-        monkeypatch.delenv("RDX_ATT_TP", raising=False)
+def _variant(eng, variant):
+    eng.set_option("att_tp", variant)                                    # the engine is shared: 0, the launcher's own choice, is set too
 
 
 def _bits(t):
@@ -93,11 +90,11 @@ def _check(eng, case, r, res, k_perm, what):
 
 @pytest.mark.parametrize("k_perm", [0, 1])
 @pytest.mark.parametrize("variant", list(A.VARIANTS))
-def test_contexts_on_either_side_of_every_boundary(eng, monkeypatch, variant, k_perm):
+def test_contexts_on_either_side_of_every_boundary(eng, variant, k_perm):
     """_dec_attn.edge_groups: per launch the three contexts around one boundary (1 / 2 / 15 and 1535 at max_len 1536 included), per context the hot position
     last cached, first live, just inside the boundary and the new token; rows of different slots in one launch, one left-padded, one with its hot position
     masked out."""
-    _variant(monkeypatch, variant)
+    _variant(eng, variant)
     worst = 0.0
     for gi, group in enumerate(A.edge_groups(variant)):
         case = A.edge_case(eng.dt, group, 100 * variant + gi, lora=bool(gi & 1))
@@ -109,10 +106,10 @@ def test_contexts_on_either_side_of_every_boundary(eng, monkeypatch, variant, k_
 
 
 @pytest.mark.parametrize("variant", list(A.VARIANTS))
-def test_every_cached_position_is_the_hot_one_once(eng, monkeypatch, variant):
+def test_every_cached_position_is_the_hot_one_once(eng, variant):
     """One context per variant beyond the register window and into the second tail trip (1000, 700, 300): 16 pairs a launch, the hot positions 16 i .. 16 i + 15
     in launch i, no position left out. K in the order production pairs with the variant (fragment order with the 16-wave build)."""
-    _variant(monkeypatch, variant)
+    _variant(eng, variant)
     ctx, k_perm = A.SWEEP_CTX[variant], int(variant == 0)
     worst, seen = 0.0, set()
     for i in range(A.sweep_launches(ctx)):
@@ -127,10 +124,10 @@ def test_every_cached_position_is_the_hot_one_once(eng, monkeypatch, variant):
 
 
 @pytest.mark.parametrize("variant", list(A.VARIANTS))
-def test_in_place_append_with_and_without_lora_from_either_rope_source(eng, monkeypatch, variant):
+def test_in_place_append_with_and_without_lora_from_either_rope_source(eng, variant):
     """lora_r 0 and 8; the cos / sin row from cur_rope and from the tables through pos: the same bits either way, and the restatement's (_check: the slot row
     of K and V exact, every other byte of both caches unchanged)."""
-    _variant(monkeypatch, variant)
+    _variant(eng, variant)
     group = A.EDGES[variant][1]
     for lora in (False, True):
         for k_perm in (0, 1):
@@ -151,10 +148,10 @@ def _unpack(layout, body, held, dt):
 
 
 @pytest.mark.parametrize("variant", list(A.VARIANTS))
-def test_packed_outputs_equal_the_row_major_one(eng, monkeypatch, variant):
+def test_packed_outputs_equal_the_row_major_one(eng, variant):
     """ACT_TILES32 (out_mt 3) and ACT_BLK64 (its second 32-row block) at 40 rows, ACT_BLK32 at 20: un-permuted with the helpers of _dec_gemm.py they are the
     row-major output bit for bit; rows the launch does not have and everything past the layout's extent stay 0xff."""
-    _variant(monkeypatch, variant)
+    _variant(eng, variant)
     for B, legs in ((40, ((TILES32, 3, 48), (BLK64, 0, 64))), (20, ((BLK32, 0, 32),))):
         slots = [1 + (7 * b) % 50 for b in range(B)]
         hot = [[(3 * b) % (slots[b] + 1), (5 * b + 1) % (slots[b] + 1)] for b in range(B)]
@@ -227,19 +224,19 @@ def _prompt(eng, B, T, slot0, k_perm, lora, seed):
 
 
 @pytest.mark.parametrize("k_perm", [0, 1])
-def test_prompt_write_then_a_decode_step(eng, monkeypatch, k_perm):
+def test_prompt_write_then_a_decode_step(eng, k_perm):
     """rdx_rope_kv_test below 2048 tokens (one token per workgroup) and above (tpb = 5 at 3 x 701: T is no multiple of it), from slot 0 and appended behind 19
     cached rows: qout and the written rows exact, every other cache byte untouched; then decode attention over the cache the kernel wrote."""
-    _variant(monkeypatch, 0)
+    _variant(eng, 0)
     worst = 0.0
     for B, T, slot0, lora in ((2, 37, 0, True), (2, 37, 19, False), (3, 701, 0, False), (3, 701, 19, True)):
         worst = max(worst, _prompt(eng, B, T, slot0, k_perm, lora, 40 + T + slot0))
     print(f"prompt write + decode step {eng.dt} k_perm {k_perm}: worst {worst:.3f} x the bar")
 
 
-def test_refusals_leave_everything_untouched(eng, monkeypatch):
+def test_refusals_leave_everything_untouched(eng):
     """Every item of the two refusal lists: an error, output all 0xff, caches bit for bit the input."""
-    _variant(monkeypatch, 0)
+    _variant(eng, 0)
     dt = eng.dt
 
     def refused(case, what, **kw):

@@ -75,7 +75,7 @@ CASES = [
     (32, 8192, 11008, 3, False, 5),
 ]
 # the encoder's many-row kernel (wsgemm.hip, force=7): weight slice in an LDS ring, activations direct to registers. Every tile shape
-# (RDX_WS_CFG), every epilogue, ragged M / N, one k-stage and many
+# (the option "ws_cfg"), every epilogue, ragged M / N, one k-stage and many
 WS_CASES = [(cfg_, M, N, K, epi) for cfg_ in "ABCDE" for (M, N, K, epi) in
             [(700, 272, 64, 0), (1025, 128, 576, 1), (513, 768, 768, 3), (2048, 96, 1408, 2), (1300, 2064, 256, 6)]]
 WS_CASES += [("", 1024, 768, 768, 3), ("", 6272, 2048, 512, 6)]        # production shapes it is dispatched for (Q-Former o_proj at batch 32, layer4 c3), default tile choice
@@ -96,11 +96,8 @@ def test_wstat_matches_fp32(eng, M, N, K, epi, norm):
 
 
 @pytest.mark.parametrize("cfg_,M,N,K,epi", WS_CASES)
-def test_wsgemm_matches_fp32(eng, cfg_, M, N, K, epi, monkeypatch):
-    if cfg_:
-        monkeypatch.setenv("RDX_WS_CFG", cfg_)
-    else:
-        monkeypatch.delenv("RDX_WS_CFG", raising=False)
+def test_wsgemm_matches_fp32(eng, cfg_, M, N, K, epi):
+    eng.set_option("ws_cfg", " ABCDE".index(cfg_) if cfg_ else 0)         # the engine is shared: 0, the launcher's own choice, is set too
     test_gemm_matches_fp32(eng, M, N, K, epi, False, 7)
 
 

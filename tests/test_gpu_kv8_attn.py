@@ -9,7 +9,7 @@ Per launch:
       either sign, as tests/test_gpu_decode_attn.py allows for the zeros of the kernels' RoPE;
   (d) every other code and exponent byte is unchanged;
   (e) 0xff guard bytes behind the output, both code buffers and both exponent buffers hold.
-heads = 2; the variant is the launcher's choice, by RDX_ATT_TP as in the whole-model tests. The kv8 builds keep their twins' row sweeps and register windows,
+heads = 2; the variant is the launcher's choice, by the option "att_tp" (RDX_ATT_TP in the whole-model tests). The kv8 builds keep their twins' row sweeps and register windows,
 so the boundaries are _dec_attn.EDGES."""
 import pytest
 import torch
@@ -36,11 +36,8 @@ def eng(request):
     e.close()
 
 
-def _variant(monkeypatch, variant):
-    if variant:
-        monkeypatch.setenv("RDX_ATT_TP", str(variant))
-    else:
-        monkeypatch.delenv("RDX_ATT_TP", raising=False)
+def _variant(eng, variant):
+    eng.set_option("att_tp", variant)                                    # the engine is shared: 0, the launcher's own choice, is set too
 
 
 def _rope(case, tables):
@@ -100,10 +97,10 @@ def _check(eng, case, r, res, what, out_bytes=None):
 
 
 @pytest.mark.parametrize("variant", list(A.VARIANTS))
-def test_contexts_on_either_side_of_every_boundary(eng, monkeypatch, variant):
+def test_contexts_on_either_side_of_every_boundary(eng, variant):
     """_dec_attn.edge_groups (1 / 2 / 15, 15 / 16 / 17, the variant's row sweep, half window, window and tail trips, 1535 at max_len 1536): rows of different
     slots in one launch, one left-padded, one with its hot position masked out; LoRA on in every other launch."""
-    _variant(monkeypatch, variant)
+    _variant(eng, variant)
     worst = 0.0
     for gi, group in enumerate(A.edge_groups(variant)):
         case = K8.edge_case(eng.dt, group, 100 * variant + gi, lora=bool(gi & 1))
@@ -115,9 +112,9 @@ def test_contexts_on_either_side_of_every_boundary(eng, monkeypatch, variant):
 
 
 @pytest.mark.parametrize("variant", list(A.VARIANTS))
-def test_every_cached_position_is_the_hot_one_once(eng, monkeypatch, variant):
+def test_every_cached_position_is_the_hot_one_once(eng, variant):
     """One context per variant beyond the register window and into the second tail trip (1000, 700, 300): the hot positions 16 i .. 16 i + 15 in launch i."""
-    _variant(monkeypatch, variant)
+    _variant(eng, variant)
     ctx = A.SWEEP_CTX[variant]
     worst, seen = 0.0, set()
     for i in range(A.sweep_launches(ctx)):
@@ -132,9 +129,9 @@ def test_every_cached_position_is_the_hot_one_once(eng, monkeypatch, variant):
 
 
 @pytest.mark.parametrize("variant", list(A.VARIANTS))
-def test_append_with_and_without_lora_from_either_rope_source(eng, monkeypatch, variant):
+def test_append_with_and_without_lora_from_either_rope_source(eng, variant):
     """lora_r 0 and 8; the cos / sin row from cur_rope and from the tables through pos: the same bits either way."""
-    _variant(monkeypatch, variant)
+    _variant(eng, variant)
     group = A.EDGES[variant][1]
     for lora in (False, True):
         case = K8.edge_case(eng.dt, group, 300 + variant, lora=lora)
@@ -144,10 +141,10 @@ def test_append_with_and_without_lora_from_either_rope_source(eng, monkeypatch, 
 
 
 @pytest.mark.parametrize("variant", list(A.VARIANTS))
-def test_packed_outputs_equal_the_row_major_one(eng, monkeypatch, variant):
+def test_packed_outputs_equal_the_row_major_one(eng, variant):
     """ACT_TILES32 (out_mt 3) and ACT_BLK64 (its second 32-row block) at 40 rows, ACT_BLK32 at 20 rows: the shared output stage. Un-permuted they are the
     row-major output bit for bit; rows the launch does not have and everything past the layout's extent stay 0xff."""
-    _variant(monkeypatch, variant)
+    _variant(eng, variant)
     for B, legs in ((40, ((TILES32, 3, 48), (BLK64, 0, 64))), (20, ((BLK32, 0, 32),))):
         case = K8.packed_case(eng.dt, B, 900 + B)
         r = case.ref()
@@ -167,9 +164,9 @@ def test_packed_outputs_equal_the_row_major_one(eng, monkeypatch, variant):
             assert bool((u[B:].contiguous().view(torch.uint8) == 0xff).all()), f"{what}: rows the launch does not have were written"
 
 
-def test_refusals_leave_everything_untouched(eng, monkeypatch):
+def test_refusals_leave_everything_untouched(eng):
     """The refusal list of rdx_decode_attn_test holds for the kv8 hook: an error, output all 0xff, codes and exponents the input bytes."""
-    _variant(monkeypatch, 0)
+    _variant(eng, 0)
     case = K8.packed_case(eng.dt, 2, 5)
     st = K8.stored(case)
 

@@ -1,6 +1,6 @@
 """The engine on the fp8 KV cache (RdxEngine(kv_fp8=True); the format: radialog_amd/kv8.py). kv8 is a storage format: engine A (kv_fp8) must compute, bit for
 bit, what a plain twin B computes on a cache that holds A's stored values -- the same weights, dtype and sizes, created under RDX_FUSE_AO=0 so that at 1-2
-rows both run the generic family (A never runs the fused attention + o_proj launch), and launched under the same RDX_ATT_TP.
+rows both run the generic family (A never runs the fused attention + o_proj launch), and launched under the same "att_tp".
 
   prompt      A's logits and token 0 are B's bits (the prompt's own attention reads its unquantised K / V), and A's codes and exponents of every layer are
               kv8.quant of the rows B's prompt wrote, byte for byte;
@@ -57,11 +57,11 @@ def _inputs(cfg, B, seed=43):
     return ids, qf
 
 
-def _variant(monkeypatch, tp):
-    if tp:
-        monkeypatch.setenv("RDX_ATT_TP", str(tp))
-    else:
-        monkeypatch.delenv("RDX_ATT_TP", raising=False)
+def _variant(monkeypatch, tp, *engines):
+    """The live engines take the variant as their option "att_tp" (0 too: they are shared); engines created from here on find no RDX_ATT_TP."""
+    monkeypatch.delenv("RDX_ATT_TP", raising=False)
+    for e in engines:
+        e.set_option("att_tp", tp)
 
 
 def _bits(t):
@@ -109,13 +109,13 @@ def _twin_run(cfg, a, b, B, steps, what):
 @pytest.mark.parametrize("B", [1, 3, 12, 17])
 def test_steps_equal_the_plain_twin_on_the_stored_values(pair, monkeypatch, B, tp):
     cfg, a, b = pair
-    _variant(monkeypatch, tp)
+    _variant(monkeypatch, tp, a, b)
     _twin_run(cfg, a, b, B, STEPS, f"{a.dtype}, {B} rows, RDX_ATT_TP {tp}")
 
 
 def test_generate_with_and_without_the_graph_and_the_flag_is_not_ignored(pair, monkeypatch):
     cfg, a, b = pair
-    _variant(monkeypatch, 0)
+    _variant(monkeypatch, 0, a, b)
     ids, qf = _inputs(cfg, 3)
     out = []
     for use_graph in (False, True):
@@ -132,7 +132,7 @@ def test_generate_with_and_without_the_graph_and_the_flag_is_not_ignored(pair, m
 def test_score_bytes_and_refusals(pair, monkeypatch):
     from radialog_amd._lib import RdxError
     cfg, a, b = pair
-    _variant(monkeypatch, 0)
+    _variant(monkeypatch, 0, a, b)
     ids, qf = _inputs(cfg, 3)
     labels = ids.clone()
     labels[:, :40] = -100

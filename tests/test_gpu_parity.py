@@ -428,7 +428,7 @@ def test_batch_3_16_decode_families_agree_and_match_oracle(B):
 
 def test_fp8_row_blocks_equal_the_32_row_kernels_row_by_row():
     """fp8 weights at 33-128 rows run the 32-row fp8 kernels once per 32-row block (xstat32_k<.., A8, BLK> fp8 x fp8 behind rmsnorm4096_k into e4m3 blocks (ACT_BLK64_E4M3); the K-split
-    o_proj / down_proj xsplit32_k<.., BLK> W8A16 since round 6, xstat32.hip fp8_split_a8): a row's arithmetic -- its own e4m3 scales, the K groups of o_proj /
+    o_proj / down_proj xsplit32_k<.., BLK> W8A16, the only form since the fp8 x fp8 K-split leg was removed): a row's arithmetic -- its own e4m3 scales, the K groups of o_proj /
     down_proj, every accumulation order -- is what the 32-row family computes for that row.
     So 40 rows in one pass (a full block + a ragged one) must reproduce, BIT FOR BIT, the tokens and logits of rows 0-31 and of rows 8-39 run as two
     32-row calls on the same engine (production width, two layers, hipGraph step; 32 rows each so that both sides take the same decode-attention

@@ -1,6 +1,6 @@
 """Beam search at the 7B shape: python tools/beam_time.py [groups] [beams] [max_new]  -- time per forward with the
-suffix-only _reorder_cache against the move-everything A/B leg (RDX_BEAM_FULLCOPY=1)."""
-import os, sys, time, torch
+suffix-only _reorder_cache against the move-everything A/B leg (the option "beam_fullcopy")."""
+import sys, time, torch
 from radialog_amd import synth
 from radialog_amd.config import full_cfg
 from radialog_amd.engine import RdxEngine, synth_getter
@@ -15,7 +15,7 @@ ids = synth.synth_prompt_ids(G, T, vocab=cfg.llama.vocab, pad_rows=True, seed=7)
 qf = synth.synth("u.qf", (G, 32, cfg.llama.qformer_dim), -1.0, 1.0)
 res = {}
 for full in ("1", "0"):
-    os.environ["RDX_BEAM_FULLCOPY"] = full
+    eng.set_option("beam_fullcopy", int(full))
     eng.beam_search(ids, qf, K, 8, eos_id=-1)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
