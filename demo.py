@@ -14,6 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from radialog_amd import synth                                              # noqa: E402
+from radialog_amd.config import PROMPT_LOOKUP_DEFAULT                      # noqa: E402
 from radialog_amd.blip2_qformer import Config, tasks                        # noqa: E402
 from radialog_amd.chexpert_model import CHEXPERT_COLS, ChexpertClassifier   # noqa: E402
 from radialog_amd.modeling_llama_imgemb import LlamaForCausalLM, PeftModelForCausalLM   # noqa: E402
@@ -37,6 +38,8 @@ def parse_args(argv=None):
     p.add_argument("--no_repeat_ngram_size", type=int, default=0, help="greedy decode: no n-gram of this size occurs twice (0 = off)")
     p.add_argument("--min_new_tokens", type=int, default=0, help="greedy decode: no EOS before this many generated tokens (0 = off)")
     p.add_argument("--logprobs", type=int, default=None, metavar="N", help="print the report's mean token log-prob (and keep the N = 0 .. 8 likeliest tokens of every step)")
+    p.add_argument("--prompt_lookup", type=int, nargs="?", const=PROMPT_LOOKUP_DEFAULT, default=0, metavar="N",
+                   help=f"verify up to N tokens per forward, drafted from the conversation itself (prompt-lookup decoding; without a number: {PROMPT_LOOKUP_DEFAULT})")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     p.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: decoder GEMMs in OCP e4m3 on the fp8 MFMA (weights_fp8=True)")
     p.add_argument("--kv_fp8", action="store_true", help="the decoder's KV cache as e4m3 codes + one exponent byte per row (kv_fp8=True): half the cache bytes; "
@@ -122,9 +125,12 @@ def main(argv=None):
     pred, out = get_response(blip_model, lang_model, tok, new_conversation(), image, findings, args.max_new_tokens,
                              repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram_size,
                              min_new_tokens=args.min_new_tokens,
-                             **({} if args.logprobs is None else {"output_logprobs": True, "top_logprobs": args.logprobs}))
+                             **({} if args.logprobs is None else {"output_logprobs": True, "top_logprobs": args.logprobs}),
+                             **({"prompt_lookup_num_tokens": args.prompt_lookup} if args.prompt_lookup else {}))
     print(f"generated {out.sequences.shape[1]} ids, {len(out.scores)} steps")
     print("ASSISTANT:", pred[:400])
+    if args.prompt_lookup:
+        print("prompt lookup:", out.lookup_stats)
     res = {"findings": findings, "prediction": pred, "sequences": out.sequences.cpu(), "n_scores": len(out.scores)}
     if args.logprobs is not None:
         from radialog_amd.engine import mean_token_logprob

@@ -240,6 +240,40 @@ int rdx_prefill_append(rdx_ctx* ctx, const int32_t* ids_tail, int batch, int T_t
 int rdx_generate_append(rdx_ctx* ctx, const int32_t* ids_tail, int batch, int T_tail, int keep_len, int max_new, int eos_id,
                         int pad_id, int32_t* out_tokens, void* scores, int* n_steps_host, int use_graph);
 
+/* Prompt-lookup decoding (transformers' generate(prompt_lookup_num_tokens=, max_matching_ngram_size=)): batch 1, greedy. Where the answer copies text that
+ * already stands in the sequence (a corrected report, a quoted document), several tokens per weight stream are nearly free: propose the tokens that followed
+ * the same n-gram earlier, run them through the decoder in ONE pass of the append path's <= 32-row kernels, keep the longest prefix the model agrees with.
+ * Opt-in; with the option off no launch, no graph key and no output bit changes, and every other call ignores the option.
+ * The draft rule. H = corpus | prompt ids as passed | every emitted token. For n = ngram_max down to ngram_min: among the starts j with H[j .. j+n) equal to
+ * the last n tokens of H and j + n < len(H), the largest; the draft is H[j+n .. min(j+n+draft_len, len(H))). The first n with a match wins; no match, no
+ * draft. A draft is clipped so that a pass never emits beyond max_new (d <= max_new - emitted - 1) and never writes a cache slot at or beyond T + max_new.
+ * Every forward: d == 0 is the captured batch-1 step; d > 0 one verify pass over [last emitted token, draft_1 .. draft_d] at slots L .. L + d behind the L
+ * kept ones (the layer loop of rdx_prefill_append), the final RMSNorm and the lm_head over the d + 1 rows. Row j's argmax (lowest index on ties, real
+ * vocabulary columns only) is compared with draft_{j+1}: with a accepted drafts the pass emits draft_1 .. draft_a and argmax_a; an EOS among them ends the
+ * emission and the call, pads follow. The next slot is L + a + 1; the rejected slots behind it are overwritten before anything reads them.
+ * One launch of lookup_accept_k (csrc/lookup.hip) behind the lm_head of either kind of forward does all of that on the device; the host reads 8 bytes per
+ * forward (the next d and the finished flag, the next slot) for its launch shapes: one small copy and one sync per forward.
+ * The contract is NOT bit identity with rdx_generate: a pass runs the prompt kernels, a plain step the chained batch-1 kernels, and their logits differ in
+ * rounding, which can flip a near-tie. What holds: (1) tokens[i] is the lowest-index argmax of scores[i], exactly; (2) scores[i] are the model's logits on the
+ * call's own emitted prefix, within the project's parity bar; (3) given the emitted tokens, drafts and accepted counts follow the rule above exactly;
+ * (4) a call in which no draft is ever found gives rdx_generate's tokens and scores bit for bit.
+ *   rdx_set_lookup  draft_len in [1, 15], ngram_max in [1, 8], ngram_min in [1, ngram_max]; NULL or draft_len == 0 switches the option off.
+ *   corpus       nullable HOST int32[n_corpus], n_corpus >= 0: extra token ids searched in front of the prompt (copied into a context-owned buffer)
+ *   scores       nullable device buffer, model dtype [max_new][vocab]: for every emitted token the logits row it was chosen from
+ *   n_tokens_host tokens emitted (EOS included); stats_host int[3] = {verify passes, tokens drafted, tokens accepted}
+ *   trace_host   nullable int[trace_cap][2]: (drafted, accepted) of every forward behind the prompt in order; a plain step records (0, 0)
+ * The call leaves an ordinary conversation of n_tokens steps behind: rdx_decode_step* and rdx_generate_append continue it.
+ * Returns -1 with a message, the previous conversation untouched, for: the option off; batch != 1; logits rules, sampling or logprobs on; inside a row session;
+ * the fp8 KV cache ("kv_fp8": the kept prefix is not held in the model dtype); an fp8-weight context (the all-row lm_head of a pass has no quantisation
+ * convention below batch 3, as for rdx_score); T + max_new beyond max_len / max_position_embeddings. int4 and coded weights work: the plain steps stream
+ * them, the passes multiply the packed W' / W, the same weights.
+ * Not built: batch > 1, sampling (speculative sampling), logits rules, beams, row sessions, a draft model, a captured pass, a split-key verify attention. */
+typedef struct rdx_lookup { int draft_len; int ngram_max; int ngram_min; } rdx_lookup;
+int rdx_set_lookup(rdx_ctx* ctx, const rdx_lookup* lookup);
+int rdx_generate_lookup(rdx_ctx* ctx, const int32_t* ids, const int32_t* mask, int batch, int T, const float* qformer_embs, const int32_t* corpus_host, int n_corpus,
+                        int max_new, int eos_id, int pad_id, int32_t* out_tokens, void* scores, int* n_tokens_host, int* stats_host, int* trace_host,
+                        int trace_cap);
+
 /* LlamaForCausalLM.generate(..., num_beams = k > 1) (test.py:467,:629 pass `num_beams=args.num_beams`): transformers 4.28.1
  * GenerationMixin.beam_search driven by BeamSearchScorer (length_penalty 1.0, early_stopping False, one returned hypothesis per
  * prompt by default) over the same forward, with `_reorder_cache` (modeling_llama_imgemb.py:838-843) between steps.

@@ -62,6 +62,19 @@ int rdx_rmsnorm_test(rdx_ctx* ctx, void* x, const void* norm_w, float eps, int r
 int rdx_select_test(rdx_ctx* ctx, void* logits_inout, int B, int vocab, const int32_t* hist, const int32_t* hist_len, const int32_t* n_generated, int ld,
                     const rdx_logits_rules* rules, int eos_id, int32_t* tokens_out);
 
+/* lookup_accept_k alone (lookup.hip: what follows the lm_head of a forward of rdx_generate_lookup, see include/rdx.h) on caller data, all device pointers
+ * unless said otherwise. part_val / part_idx [d + 1][n_tiles]: the rows' argmax partials; tail int32[16]: [last token, draft_1 .. draft_d] in, the next
+ * forward's ids out; corpus int32[n_corpus] (nullable); draft_len (0: never draft) / ngram_max / ngram_min / slot_end: the call's constants; hist int32[hist_ld]:
+ * the history, appended to; state int32[5] = {step, slot, position, unfinished, history length}, advanced in place (advance == 0: the token-0 form, which
+ * leaves slot and position alone and records no forward); out_tokens int32[max_new]; logits [d + 1][vocab] / scores [max_new][vocab] model dtype, nullable;
+ * status int32[4] (word 2, the forward count, is read: zero it first); trace int32[trace_cap][2] nullable; pos_ids int32[16]. vocab, the embedding and the
+ * RoPE tables are those of the (finalized) context, and the kernel writes the context's own next-input row and cos | sin row: run a new prefill before
+ * decoding on that context again. Refused before the launch: sizes out of range, a state that would leave the caller's arrays or the RoPE tables. */
+int rdx_lookup_accept_test(rdx_ctx* ctx, const float* part_val, const int32_t* part_idx, int n_tiles, int d, int32_t* tail, const int32_t* corpus, int n_corpus,
+                           int draft_len, int ngram_max, int ngram_min, int slot_end, int32_t* hist, int hist_ld, int32_t* state, int advance, int eos_id,
+                           int pad_id, int max_new, int32_t* out_tokens, const void* logits, void* scores, int32_t* status, int32_t* trace, int trace_cap,
+                           int32_t* pos_ids);
+
 /* score_rows_k alone (score.hip: the kernel of the scoring pass, see include/rdx.h): logits [M][ld] model dtype (device, 16-byte aligned; ld a multiple of 8,
  * >= vocab: columns vocab .. ld - 1 are pad columns that must not be looked at), target int32 [M] (device; -100 = row not scored), logprob_out float [M],
  * top1_out int32 [M] (device). Works on any context (no weights involved). */

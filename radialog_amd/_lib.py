@@ -40,6 +40,11 @@ class RdxSampling(C.Structure):
     _fields_ = [("do_sample", C.c_int), ("temperature", C.c_float), ("top_k", C.c_int), ("top_p", C.c_float), ("seed", C.c_uint64)]
 
 
+class RdxLookup(C.Structure):
+    """rdx_lookup (include/rdx.h): draft_len 0 = off."""
+    _fields_ = [("draft_len", C.c_int), ("ngram_max", C.c_int), ("ngram_min", C.c_int)]
+
+
 class RdxConfig(C.Structure):
     _fields_ = [
         ("dtype", C.c_int),
@@ -89,6 +94,9 @@ SYMBOLS = {
     "rdx_prefill_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rdx_generate_append": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P,
                                       C.POINTER(C.c_int), C.c_int]),
+    "rdx_set_lookup": (C.c_int, [_P, C.POINTER(RdxLookup)]),
+    # corpus_host / n_tokens_host / stats_host / trace_host are HOST int32 arrays
+    "rdx_generate_lookup": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_int), _P, _P, C.c_int]),
     "rdx_beam_search": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P, _P, _P,
                                   C.POINTER(C.c_int)]),
     # row sessions (continuous batching): rows_host / unfinished_host / steps_host are HOST int32 arrays
@@ -146,6 +154,8 @@ DEC_HOOK_SYMBOLS = {
     "rdx_xsplit_blk8_test": (C.c_int, [_P, _P, _P, _P, _P, _F, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_rmsnorm_test": (C.c_int, [_P, _P, _P, _F, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_longlong, _P, C.c_int]),
     "rdx_select_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, _P]),
+    "rdx_lookup_accept_test": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, _P, _P, _P, _P, _P, C.c_int, _P]),
     "rdx_score_rows_test": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdx_logprob_step_test": (C.c_int, [_P, _P, C.c_longlong, C.c_longlong, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int]),
     "rdx_sample_test": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.POINTER(RdxLogitsRules), C.c_int, C.POINTER(RdxSampling), _P]),

@@ -9,8 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librdx.so")
 OUT_HOOKS = os.path.join(HERE, "librdx_hooks.so")
-SOURCES = ["gemm.hip", "xstat32.hip", "xs16.hip", "gemm_dma.hip", "gemm8.hip", "attn.hip", "flash.hip", "chain.hip", "elem.hip", "score.hip", "logprob.hip", "beam.hip", "rows.hip", "conv1x1.hip", "wsgemm.hip", "stem.hip", "wstat.hip", "pconv.hip",
-           "api.hip", "api_options.hip", "api_dispatch.hip", "api_encode.hip", "api_llama.hip", "api_comm.hip", "api_inspect.hip", "api_transform.hip", "api_rows.hip"]
+SOURCES = ["gemm.hip", "xstat32.hip", "xs16.hip", "gemm_dma.hip", "gemm8.hip", "attn.hip", "flash.hip", "chain.hip", "elem.hip", "score.hip", "logprob.hip", "lookup.hip", "beam.hip", "rows.hip", "conv1x1.hip", "wsgemm.hip", "stem.hip", "wstat.hip", "pconv.hip",
+           "api.hip", "api_options.hip", "api_dispatch.hip", "api_encode.hip", "api_llama.hip", "api_comm.hip", "api_inspect.hip", "api_transform.hip", "api_rows.hip", "api_lookup.hip"]
 HOOK_SOURCES = ["api_debug.hip", "api_dec_hooks.hip"]
 HEADERS = ["rdx_common.h", "rdx_kernels.h", "rdx_ctx.h", "skinny_body.h", "attn_body.h", "handoff.h", "philox.h", "hook_util.h", os.path.join("..", "..", "include", "rdx.h"),
            os.path.join("..", "..", "include", "rdx_hooks.h"), os.path.join("..", "..", "include", "rdx_enc_hooks.h"), os.path.join("..", "..", "include", "rdx_dec_hooks.h")]

@@ -124,6 +124,11 @@ def small_classifier_cfg() -> RaDialogCfg:
                        cls=ClsCfg(hidden=96, classes=14, pool=2))
 
 
+# `--prompt_lookup` without a number (test.py, demo.py): the draft length with the lowest ms per emitted token on a corpus corrupted at every 4th token
+# (profiles/r20_lookup.md, table (b))
+PROMPT_LOOKUP_DEFAULT = 3
+
+
 def small_cfg() -> RaDialogCfg:
     """Reduced shapes for parity tests the CPU oracle finishes in seconds. Head dims stay at the
     real 128 (Llama) / 64 (Q-Former) so the same kernel instantiations are exercised."""

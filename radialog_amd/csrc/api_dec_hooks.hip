@@ -276,6 +276,44 @@ extern "C" int rdx_logprob_step_test(rdx_ctx* c, const void* logits, long long r
     return finish(c);
 }
 
+extern "C" int rdx_lookup_accept_test(rdx_ctx* c, const float* part_val, const int32_t* part_idx, int n_tiles, int d, int32_t* tail, const int32_t* corpus,
+                                      int n_corpus, int draft_len, int ngram_max, int ngram_min, int slot_end, int32_t* hist, int hist_ld, int32_t* state,
+                                      int advance, int eos_id, int pad_id, int max_new, int32_t* out_tokens, const void* logits, void* scores, int32_t* status,
+                                      int32_t* trace, int trace_cap, int32_t* pos_ids) {
+    if (!c || !part_val || !part_idx || !tail || !hist || !state || !out_tokens || !status || !pos_ids || n_tiles <= 0 || hist_ld <= 0 || max_new <= 0 ||
+        n_corpus < 0 || (n_corpus && !corpus) || trace_cap < 0)
+        return fail(c, -1, "rdx_lookup_accept_test: bad arguments");
+    if (!c->finalized || !c->cfg.enable_llama) return fail(c, -1, "rdx_lookup_accept_test: needs a finalized llama context (the embedding and RoPE tables are its own)");
+    if (d < 0 || d > LOOKUP_MAX_DRAFT || draft_len < 0 || draft_len > LOOKUP_MAX_DRAFT || ngram_max < 1 || ngram_max > LOOKUP_MAX_NGRAM || ngram_min < 1 || ngram_min > ngram_max)
+        return fail(c, -1, "rdx_lookup_accept_test: d / draft_len outside [0, %d] or n-gram sizes outside 1 <= min <= max <= %d", LOOKUP_MAX_DRAFT, LOOKUP_MAX_NGRAM);
+    HIPCHK(c, hipSetDevice(c->device));
+    // refused before anything is written: a state that would carry a store or a table read out of the caller's arrays
+    int st[5], fwd = 0;
+    HIPCHK(c, hipMemcpy(st, state, sizeof(st), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&fwd, status + LKS_FWD, sizeof(int), hipMemcpyDeviceToHost));
+    if (st[0] < 0 || st[2] < 0 || st[2] + LOOKUP_MAX_DRAFT + 1 >= c->cfg.max_pos || st[4] < 0 || st[4] > hist_ld || fwd < 0)
+        return fail(c, -1, "rdx_lookup_accept_test: state (step %d, position %d, history %d of %d) outside the caller's arrays / the RoPE tables", st[0], st[2], st[4], hist_ld);
+    DevBufs bufs;
+    int* par = (int*)bufs.get(LKP_INTS * sizeof(int));
+    int* img = (int*)bufs.get(sizeof(int));
+    int* one = (int*)bufs.get(sizeof(int));      // stands in for a null corpus
+    if (!par || !img || !one) return fail(c, -2, "rdx_lookup_accept_test: out of device memory");
+    const int ph[LKP_INTS] = {n_corpus, draft_len, ngram_max, ngram_min, slot_end};
+    HIPCHK(c, hipMemcpy(par, ph, sizeof(ph), hipMemcpyHostToDevice));
+    const rdx_config& f = c->cfg;
+    StepTail t = {};
+    t.eos_id = eos_id; t.pad_id = pad_id; t.max_new = max_new; t.out_tokens = out_tokens;
+    t.step_b = state; t.unfinished = state + 3; t.hist_len = state + 4; t.hist = hist; t.hist_ld = hist_ld;
+    t.pos_ro = state + 2; t.pos = advance ? state + 2 : nullptr; t.slot_b = advance ? state + 1 : nullptr;
+    t.embed = c->embed; t.vocab = f.vocab; t.x_next = c->dx; t.H = f.hidden; t.cos_t = c->rope_cos; t.sin_t = c->rope_sin; t.cur_rope = c->d_cur_rope;
+    LookupArgs a;
+    a.part_val = part_val; a.part_idx = part_idx; a.n_tiles = n_tiles; a.d = d; a.logits = logits; a.scores = scores;
+    a.tail = tail; a.slot = state + 1; a.pos_ids = pos_ids; a.img_pos = img; a.status = status; a.trace = trace; a.trace_cap = trace_cap;
+    a.par = par; a.corpus = corpus ? corpus : one;
+    launch_lookup_accept(f.dtype, a, t, c->stream);
+    return finish(c);
+}
+
 namespace {
 
 // the dims both attention hooks build: hidden = 128 heads, the QKV row as the engine lays it out (api.hip: wqkv.Npad)

@@ -29,6 +29,20 @@ static int ensure_prefill_ws(rdx_ctx* c, size_t rows) {
 
 static const char* const k_need_blk = "more than 32 decoder rows need hidden 4096 / inter 11008 (the row-block family)";
 
+// the tail of a selection on the conversation's rows from base 0 (rdx_kernels.h StepTail); advance == 0: the prompt's token-0 call
+StepTail step_tail_args(rdx_ctx* c, int advance) {
+    const rdx_config& f = c->cfg;
+    StepTail t = {};
+    t.eos_id = c->cur_eos; t.pad_id = c->cur_pad; t.max_new = c->cur_max_new; t.out_tokens = c->cur_tokens; t.unfinished = c->d_unf;
+    t.pos = advance ? c->d_pos : nullptr; t.slot_b = advance ? c->d_slot : nullptr; t.step_b = c->d_step;
+    t.embed = c->embed; t.vocab = f.vocab; t.x_next = c->dx; t.H = f.hidden; t.pos_ro = c->d_pos; t.cos_t = c->rope_cos; t.sin_t = c->rope_sin;
+    t.cur_rope = c->d_cur_rope;
+    t.ctr_zero = c->sw.chain ? c->d_ctr : nullptr;
+    t.n_zero = (int)chain_ctr_ints(f.layers);
+    t.epoch = c->d_epoch;
+    return t;
+}
+
 // row0 / tokens (a row session's refill, never under rules or sampling): the selected rows are rows row0 .. row0 + B - 1 of the per-row decode state, and
 // token 0 of row r goes to tokens[r * max_new] instead of the conversation's out_tokens. x, the logits and the argmax partials stay B-row scratch at base 0.
 static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, const int* out_step, long step_stride,
@@ -49,14 +63,9 @@ static void lm_head_and_greedy(rdx_ctx* c, const void* x, int B, void* logits, c
     default:       // the prompt's last rows are no decode step: the unit's base form, whichever family the batch decodes on
         skinny(c, lm(advance && fam == DEC_CHAINED ? chained_unit(c, nullptr, UNIT_LM_HEAD, B) : unit_args(c, nullptr, UNIT_LM_HEAD, B)), EPI_LOGITS);
     }
-    StepTail t = {};
-    t.eos_id = c->cur_eos; t.pad_id = c->cur_pad; t.max_new = c->cur_max_new; t.out_tokens = c->cur_tokens; t.unfinished = c->d_unf;
-    t.pos = advance ? c->d_pos : nullptr; t.slot_b = advance ? c->d_slot : nullptr; t.step_b = c->d_step;
-    t.embed = c->embed; t.vocab = f.vocab; t.x_next = c->dx; t.H = f.hidden; t.pos_ro = c->d_pos; t.cos_t = c->rope_cos; t.sin_t = c->rope_sin;
-    t.cur_rope = c->d_cur_rope;
-    t.ctr_zero = c->sw.chain ? c->d_ctr : nullptr;
-    t.n_zero = (int)chain_ctr_ints(f.layers);
-    t.epoch = c->d_epoch;
+    StepTail t = step_tail_args(c, advance);
+    // prompt-lookup decoding (api_lookup.hip): inside rdx_generate_lookup the selection behind every lm_head is lookup_accept_k, here on the one row of a plain forward
+    if (c->lk_run) { lookup_accept(c, t, 0, c->part_val, c->part_idx, nullptr); return; }
     if (row0) {       // (advance == 0: pos / slot_b are null)
         t.unfinished += row0; t.step_b += row0; t.pos_ro += row0;
         t.x_next = (char*)c->dx + (size_t)row0 * f.hidden * 2; t.cur_rope = (char*)c->d_cur_rope + (size_t)row0 * 512;
@@ -282,6 +291,19 @@ static void prompt_fp8(rdx_ctx* c, const PromptPlan& p, int B, int T, int keep, 
     }
 }
 
+// the embedding rows (+ image splice) of B x T tokens into px, then the layer loop of the prompt's kernel family behind `keep` kept slots. The position ids
+// (d_pos_ids), the image positions and the key mask are the caller's: prompt_layers prepares them, a verify pass of api_lookup.hip finds them on the device.
+void prompt_embed_layers(rdx_ctx* c, const int32_t* ids, int B, int T, int keep, bool splice, int row0) {
+    const rdx_config& f = c->cfg;
+    launch_embed_splice(f.dtype, ids, c->d_img_pos, c->embed, f.vocab, c->pimg, 32, c->px, B, T, f.hidden, splice ? 1 : 0, c->stream);
+    const PromptPlan p = prompt_plan(c, B, T);
+    switch (p.family) {
+    case PROMPT_ROWS: prompt_rows(c, p, B, T, keep, row0); break;
+    case PROMPT_TILES: prompt_tiles(c, p, B, T, keep, row0); break;
+    case PROMPT_FP8: prompt_fp8(c, p, B, T, keep, row0); break;
+    }
+}
+
 // The prompt through every layer: the residual stream of all B x T positions ends in c->px (row-major [B T][hidden]), K / V in the cache behind `keep` kept
 // slots (keep > 0: `T` further tokens of a cached conversation, no image splice), the per-row decode state (d_pos / d_slot / d_step / d_unf, the key mask) is
 // that of a prompt of T tokens. What the callers do with px is theirs: the prefill gathers the last row of each prompt for token 0, the scoring pass the rows
@@ -307,13 +329,7 @@ static void prompt_layers(rdx_ctx* c, const int32_t* ids, const int32_t* mask, i
         launch_from_f32(dt, qformer_embs, c->pqe, (size_t)B * 32 * f.qformer_dim, s);
         run_gemm(c, gargs(c->pqe, f.qformer_dim, c->img_proj_w, c->img_proj_b, c->pimg, H, B * 32), EPI_NONE);
     }
-    launch_embed_splice(dt, ids, c->d_img_pos, c->embed, f.vocab, c->pimg, 32, c->px, B, T, H, qformer_embs ? 1 : 0, s);
-    const PromptPlan p = prompt_plan(c, B, T);
-    switch (p.family) {
-    case PROMPT_ROWS: prompt_rows(c, p, B, T, keep, row0); break;
-    case PROMPT_TILES: prompt_tiles(c, p, B, T, keep, row0); break;
-    case PROMPT_FP8: prompt_fp8(c, p, B, T, keep, row0); break;
-    }
+    prompt_embed_layers(c, ids, B, T, keep, qformer_embs != nullptr, row0);
 }
 
 // token 0 of B prompts whose layers have run: the last row of each (datt doubles as the [B][H] last-position buffer) through the lm_head and the selection
@@ -352,7 +368,7 @@ int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int
     c->cur_B = B; c->cur_T = keep + T; c->cur_max_new = max_new; c->cur_eos = eos_id; c->cur_pad = pad_id; c->cur_tokens = out_tokens;
     c->cur_steps = 1;
     if (int lrc = logprobs_reset(c, B)) return lrc;
-    prompt_layers(c, ids, mask, B, T, qformer_embs, keep, pad_id, c->rules_on);
+    prompt_layers(c, ids, mask, B, T, qformer_embs, keep, pad_id, c->rules_on || c->lk_run);       // (the draft rule searches the history too)
     return prompt_token0(c, B, T, logits);
 }
 
@@ -639,6 +655,7 @@ int build_graph(rdx_ctx* c, void* scores, bool fixed) {
     k.rules = c->rules;
     k.sampling = c->sampling;
     k.logprobs = c->logprobs;
+    k.lookup = c->lk_run ? c->lk_corpus : nullptr;
     if (int rrc = rules_need_prefill(c, "decode step graph")) return rrc;
     if (c->graph && k == c->gkey) return 0;
     if (c->graph) { hipGraphExecDestroy(c->graph); c->graph = nullptr; }

@@ -59,8 +59,9 @@ struct GraphKey {
     rdx_logits_rules rules = {1.0f, 0, 0};      // the captured step selects through select_step_k unless neutral
     rdx_sampling sampling = {0, 1.0f, 0, 1.0f, 0};      // do_sample: through sample_step_k, t / k / p its arguments; the seed is no part of the key (a device word)
     int logprobs = -1;              // rdx_set_logprobs: >= 0: logprob_step_k rides behind the selection with this top_n
+    const void* lookup = nullptr;   // rdx_generate_lookup's plain step: the context's corpus buffer (never null there); the selection is lookup_accept_k
     bool operator==(const GraphKey& o) const {
-        return logprobs == o.logprobs && B == o.B && max_new == o.max_new && eos == o.eos && pad == o.pad && tokens == o.tokens && scores == o.scores && fixed == o.fixed &&
+        return lookup == o.lookup && logprobs == o.logprobs && B == o.B && max_new == o.max_new && eos == o.eos && pad == o.pad && tokens == o.tokens && scores == o.scores && fixed == o.fixed &&
                rules.repetition_penalty == o.rules.repetition_penalty && rules.no_repeat_ngram_size == o.rules.no_repeat_ngram_size &&
                rules.min_new_tokens == o.rules.min_new_tokens && sampling.do_sample == o.sampling.do_sample &&
                sampling.temperature == o.sampling.temperature && sampling.top_k == o.sampling.top_k && sampling.top_p == o.sampling.top_p;
@@ -151,6 +152,16 @@ struct rdx_ctx {
     int logprobs = -1;
     float* lp_chosen = nullptr;                     // [max_batch][max_len]: entry [row][step] of the current conversation
     int* lp_top_ids = nullptr; float* lp_top_lp = nullptr;      // [max_batch][max_len][RDX_MAX_TOP_LOGPROBS]; allocated once, so a captured graph keeps its pointers
+
+    // ---- prompt-lookup decoding (rdx_set_lookup / rdx_generate_lookup, api_lookup.hip; kernel: lookup.hip); the buffers exist from the first rdx_set_lookup on ----
+    rdx_lookup lookup = {0, 0, 0};                  // draft_len 0 = off
+    bool lk_run = false;                            // inside rdx_generate_lookup: lm_head_and_greedy selects through lookup_accept_k, the prefill starts the history
+    int *lk_tail = nullptr, *lk_status = nullptr, *lk_trace = nullptr, *lk_par = nullptr;      // rdx_kernels.h LookupArgs
+    int* lk_corpus = nullptr; size_t lk_corpus_cap = 0;      // the caller's corpus, grown on demand
+    float* lk_part_val = nullptr; int* lk_part_idx = nullptr;      // argmax partials [16][n_vtiles] of a verify pass
+    void* lk_logits = nullptr;                      // [16][vocab]: a verify pass's logits rows when the caller wants scores
+    void* lk_scores = nullptr;                      // the running call's scores buffer
+    int lk_par_host[LKP_INTS] = {};                 // source of the asynchronous copy into lk_par
 
     // ---- scoring pass (rdx_score), sized on first use ----
     void *sc_x = nullptr, *sc_xn = nullptr;         // [rows][hidden]: the gathered residual rows and their final RMSNorm
@@ -308,6 +319,10 @@ inline int kv8_refuse(rdx_ctx* c, const char* who, const char* why) {
 }
 int prefill_impl(rdx_ctx* c, const int32_t* ids, const int32_t* mask, int B, int T, const float* qformer_embs, int keep,
                  int max_new, int eos_id, int pad_id, int32_t* out_tokens, void* logits);
+StepTail step_tail_args(rdx_ctx* c, int advance);
+void prompt_embed_layers(rdx_ctx* c, const int32_t* ids, int B, int T, int keep, bool splice, int row0);
+// (api_lookup.hip) lookup_accept_k behind a forward of d + 1 rows whose argmax partials are pv / pi; logits: the rows of a verify pass (null: written in place)
+void lookup_accept(rdx_ctx* c, StepTail t, int d, const float* pv, const int* pi, const void* logits);
 // evs (timing only, eager launches): a pair of events recorded around every chained down(l) -> QKV(l+1) launch of this step
 bool decode_step_launch(rdx_ctx* c, void* logits, const int* out_step, long step_stride, std::vector<hipEvent_t>* evs = nullptr);
 int build_graph(rdx_ctx* c, void* scores, bool fixed = false);

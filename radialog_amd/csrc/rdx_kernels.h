@@ -362,6 +362,28 @@ void launch_sample_step(int dtype, const SelectArgs& a, const SampleArgs& sp, co
 void launch_hist_init(const int* ids, int B, int T, int* hist, int* hist_len, int ld, hipStream_t s);
 void launch_hist_set_last(const int* ids, int* hist, const int* hist_len, int ld, int B, hipStream_t s);
 
+// Prompt-lookup decoding (lookup.hip; the rules: include/rdx.h rdx_generate_lookup). lookup_accept_k: ONE workgroup, one sequence, behind the lm_head of a
+// forward over d + 1 rows [last emitted token, draft_1 .. draft_d] (d == 0: the plain step, or the prompt's token-0 call with t.pos / t.slot_b null). It reduces
+// the rows' argmax partials, accepts the longest draft prefix the model agrees with, emits a + 1 tokens through the EOS / pad rule (out_tokens, the history,
+// `scores` rows from the pass's `logits`), advances the decode state of row 0 as a + 1 plain steps would have (step_tail's fields of t; t.hist is required),
+// finds the next draft and leaves the next forward's inputs: tail ids, their position ids, and the status words the host reads.
+constexpr int LOOKUP_MAX_DRAFT = 15, LOOKUP_MAX_NGRAM = 8;
+// par (device, int[5]): the call's constants
+enum { LKP_NCORPUS = 0, LKP_DRAFT_LEN = 1, LKP_NGRAM_MAX = 2, LKP_NGRAM_MIN = 3, LKP_SLOT_END = 4, LKP_INTS = 5 };
+// status (device, int[4]): what the host copies after every forward ([0], [1]: 8 bytes) and what the kernel keeps for itself
+enum { LKS_NEXT = 0 /* next d | finished << 8 */, LKS_SLOT = 1 /* cache slot of the next forward's first row */, LKS_FWD = 2 /* forwards so far */, LKS_INTS = 4 };
+struct LookupArgs {
+    const float* part_val; const int* part_idx; int n_tiles;     // [d + 1][n_tiles]
+    int d;                                  // drafts this forward verified; they are tail[1 .. d]
+    const void* logits; void* scores;       // the pass's rows [d + 1][vocab] -> scores[step + j][vocab] (both nullable; d == 0: the lm_head wrote the row in place)
+    int* tail;                              // [LOOKUP_MAX_DRAFT + 1]: this forward's input ids in, the next forward's out
+    const int* slot;                        // row 0's cache slot (t.slot_b where the forward advances it; the token-0 call only reads it)
+    int* pos_ids; int* img_pos;             // the next pass's position ids [d' + 1] and its (unused) image position
+    int* status; int* trace; int trace_cap; // trace [trace_cap][2] = (drafted, accepted) of forward status[LKS_FWD] (nullable; the token-0 call records nothing)
+    const int* par; const int* corpus;      // corpus [par[LKP_NCORPUS]]
+};
+void launch_lookup_accept(int dtype, const LookupArgs& a, const StepTail& t, hipStream_t s);
+
 // Scoring given tokens (score.hip). score_rows_k: one workgroup per row of logits [M][ld] (model dtype; ld % 8 == 0, base 16-byte aligned), over columns
 // 0 .. vocab - 1 only: logprob[r] = (x_target - max) - log(sum exp(x - max)) in fp32, top1[r] = argmax (lowest index on ties); target -100: (0.0f, -1).
 inline size_t score_rows_lds(int vocab) { return (size_t)((vocab + 7) / 8) * 16; }      // dynamic LDS: the row

@@ -16,7 +16,7 @@ sklearn metrics around them are not on the path. With `lang_model.reuse_prefix_k
 token prefix a call shares with the previous one (rdx_generate_append) instead of re-running the whole conversation."""
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -78,21 +78,28 @@ def get_chexpert_prompts_all(preds_history: List[str], col_names: Sequence[str])
     return preds_history
 
 
-def _generate(lang_model, tok, texts, dicom, max_new_tokens, num_beams=1):
+def _generate(lang_model, tok, texts, dicom, max_new_tokens, num_beams=1, prompt_lookup=0, stats=None):
     ids = tok.batch_encode_plus(list(texts), return_tensors="pt", padding=True)["input_ids"]
+    kw = {"prompt_lookup_num_tokens": prompt_lookup} if prompt_lookup else {}
     out = lang_model.generate(input_ids=ids, return_dict_in_generate=True, output_scores=True, max_new_tokens=max_new_tokens,
-                              dicom=dicom, num_beams=num_beams)
+                              dicom=dicom, num_beams=num_beams, **kw)
+    if stats is not None and prompt_lookup:
+        for k in ("passes", "drafted", "accepted", "forwards"):
+            stats[k] = stats.get(k, 0) + out.lookup_stats[k]
     return tok.batch_decode(out.sequences, skip_special_tokens=True)
 
 
-def run_correction(lang_model, tok, correction_prompts: List[str], dicoms=None, num_beams: int = 1, max_new_tokens: int = 256) -> List[str]:
-    """test.py:440-500: batch 1; studies whose prompt says KEEP_OLD keep their first report (test.py:483-486)."""
+def run_correction(lang_model, tok, correction_prompts: List[str], dicoms=None, num_beams: int = 1, max_new_tokens: int = 256, prompt_lookup: int = 0,
+                   lookup_stats: Optional[dict] = None) -> List[str]:
+    """test.py:440-500: batch 1; studies whose prompt says KEEP_OLD keep their first report (test.py:483-486).
+    prompt_lookup=N (0 = off; greedy search only): the report to correct stands in the prompt and the answer copies most of it, so every forward verifies up to
+    N tokens drafted from the sequence itself (generate(prompt_lookup_num_tokens=N)); lookup_stats, a dict, accumulates passes / drafted / accepted / forwards."""
     preds = []
     for i, prompt in enumerate(correction_prompts):
         if "KEEP_OLD" in prompt:
             preds.append(prompt.split("ASSISTANT:")[-2].split("</s>")[0].strip())
             continue
-        full = _generate(lang_model, tok, [prompt], None if dicoms is None else [dicoms[i]], max_new_tokens, num_beams)
+        full = _generate(lang_model, tok, [prompt], None if dicoms is None else [dicoms[i]], max_new_tokens, num_beams, prompt_lookup, lookup_stats)
         preds.append(full[0].split("ASSISTANT:")[-1].strip())
     return preds
 

@@ -83,6 +83,36 @@ class Sampling:
         return cls(*sampling)
 
 
+@dataclass(frozen=True)
+class Lookup:
+    """Prompt-lookup decoding (rdx_lookup, include/rdx.h): drafts of up to `draft_len` tokens (1 .. 15) that followed the most recent earlier occurrence of the
+    sequence's last n tokens, n from `ngram_max` (<= 8) down to `ngram_min` (>= 1). Raises ValueError on what the library refuses."""
+    draft_len: int = 8
+    ngram_max: int = 3
+    ngram_min: int = 1
+
+    def __post_init__(self):
+        for name in ("draft_len", "ngram_max", "ngram_min"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, numbers.Integral):
+                raise ValueError(f"`{name}` has to be an integer, but is {v!r}")
+        if not 1 <= self.draft_len <= 15:
+            raise ValueError(f"`draft_len` has to be in 1 .. 15, but is {self.draft_len}")
+        if not 1 <= self.ngram_max <= 8:
+            raise ValueError(f"`ngram_max` has to be in 1 .. 8, but is {self.ngram_max}")
+        if not 1 <= self.ngram_min <= self.ngram_max:
+            raise ValueError(f"`ngram_min` has to be in 1 .. ngram_max ({self.ngram_max}), but is {self.ngram_min}")
+
+    @classmethod
+    def of(cls, lookup) -> "Lookup":
+        """A Lookup, an int (the draft length) or a (draft_len, ngram_max, ngram_min) tuple."""
+        if isinstance(lookup, cls):
+            return lookup
+        if isinstance(lookup, numbers.Integral) and not isinstance(lookup, bool):
+            return cls(draft_len=int(lookup))
+        return cls(*lookup)
+
+
 def mask_logprobs_after_eos(tokens, eos_id, chosen, top_ids, top_lp):
     """What the Python layer returns for generation log-probs: everything BEHIND a row's first EOS (the pad tokens the step's tail writes for a finished
     row) reads (0.0, -1, 0.0); the EOS entry itself stays. tokens int [B, n], chosen [B, n], top_ids / top_lp [B, n, k]. New tensors; eos_id < 0: copies."""
@@ -439,6 +469,82 @@ class RdxEngine:
         if logprobs is not None:
             return toks, scores, n.value, self.get_logprobs(B, n.value, tokens=toks[:, : n.value], eos_id=eos_id)
         return toks, scores, n.value
+
+    def set_lookup(self, lookup=None) -> Optional[Lookup]:
+        """rdx_set_lookup: the draft rule of the next generate_lookup calls; None = off. No other call looks at the option."""
+        lk = None if lookup is None else Lookup.of(lookup)
+        c = None if lk is None else _lib.RdxLookup(int(lk.draft_len), int(lk.ngram_max), int(lk.ngram_min))
+        check(self.ctx, self.lib.rdx_set_lookup(self.ctx, None if c is None else C.byref(c)), "rdx_set_lookup")
+        return lk
+
+    def generate_lookup(self, ids: torch.Tensor, qformer_embs: Optional[torch.Tensor], max_new: int, eos_id: int = 2, pad_id: int = 0,
+                        mask: Optional[torch.Tensor] = None, lookup=Lookup(), corpus=None, output_scores: bool = False):
+        """Batch-1 greedy generation with prompt-lookup drafts (rdx_generate_lookup). ids int [1, T]; corpus: optional int sequence of further token ids
+        to search for drafts, in front of the prompt. Returns (tokens int32 [1, max_new], scores [n, 1, V] model dtype or None, n,
+        stats = {"passes", "drafted", "accepted", "forwards"}, trace int32 [forwards, 2] = (drafted, accepted) per forward behind the prompt).
+        The tokens are greedy under the returned scores; they need not equal generate()'s (a pass and a plain step round differently). Rules, sampling
+        and logprobs a previous call left on the context are switched off first, as beam_search does."""
+        B, T = ids.shape
+        lk = Lookup.of(lookup)
+        self.set_logits_rules(None)
+        self.set_sampling(None)
+        self.set_logprobs(None)
+        self.set_lookup(lk)
+        ids32 = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        m32 = None if mask is None else mask.to(device=self.device, dtype=torch.int32).contiguous()
+        qf = None if qformer_embs is None else qformer_embs.to(device=self.device, dtype=torch.float32).contiguous()
+        cp = None if corpus is None else torch.as_tensor(corpus).to(device="cpu", dtype=torch.int32).contiguous().view(-1)
+        toks = torch.full((B, max_new), pad_id, dtype=torch.int32, device=self.device)
+        scores = torch.zeros(max_new, B, self.cfg.llama.vocab, dtype=self.tdtype, device=self.device) if output_scores else None
+        cap = max(int(max_new), 1)
+        trace = torch.full((cap, 2), -1, dtype=torch.int32)      # the call writes one row per forward
+        stats = (C.c_int * 3)()
+        n = C.c_int(0)
+        self._keep["prefill"] = (ids32, m32, qf, toks)        # decode_step continues the conversation the call leaves behind
+        self._conv = None
+        torch.cuda.synchronize(self.device)
+        check(self.ctx, self.lib.rdx_generate_lookup(self.ctx, _ptr(ids32), _ptr(m32), B, T, _ptr(qf), None if cp is None or cp.numel() == 0 else C.c_void_p(cp.data_ptr()),
+                                                     0 if cp is None else cp.numel(), max_new, eos_id, pad_id, _ptr(toks), _ptr(scores), C.byref(n), stats,
+                                                     C.c_void_p(trace.data_ptr()), cap), "rdx_generate_lookup")
+        if mask is None:      # what the cache now holds, for a generate(reuse_prefix=True) behind this call
+            self._conv = {"seq": torch.cat([ids.cpu().to(torch.int64), toks[:, :max(n.value - 1, 0)].cpu().to(torch.int64)], dim=1),
+                          "qf": None if qf is None else qf.clone()}
+        trace = trace[: int((trace[:, 0] >= 0).sum())]
+        stats = {"passes": stats[0], "drafted": stats[1], "accepted": stats[2], "forwards": trace.shape[0]}
+        return toks, (None if scores is None else scores[: n.value]), n.value, stats, trace
+
+    def lookup_accept_test(self, part_val, part_idx, d, tail, hist, hist_len, state, lookup, corpus=None, slot_end=1 << 30, advance=True, eos_id=-1, pad_id=0,
+                           max_new=64, logits=None, fwd=0):
+        """lookup_accept_k alone (rdx_lookup_accept_test). part_val float [d + 1, n_tiles], part_idx int [d + 1, n_tiles]; tail: [last token, drafts ..];
+        hist int [hist_ld] with hist_len entries; state (step, slot, position, unfinished); lookup a Lookup. Returns a dict of host tensors: out_tokens
+        [max_new] (-7 where not written), tail [16], hist, state [5], status [4], trace [8, 2], pos_ids [16], scores [max_new, V] or None."""
+        lk = Lookup.of(lookup)
+        dev = self.device
+        pv = part_val.to(dev, torch.float32).contiguous()
+        pi = part_idx.to(dev, torch.int32).contiguous()
+        if pv.shape != pi.shape or pv.shape[0] != d + 1:
+            raise ValueError("lookup_accept_test: part_val / part_idx [d + 1, n_tiles]")
+        tl = torch.full((16,), -7, dtype=torch.int32)
+        tl[: len(tail)] = torch.as_tensor(tail, dtype=torch.int32)
+        tl = tl.to(dev)
+        h = torch.as_tensor(hist, dtype=torch.int32).to(dev).contiguous()
+        st = torch.tensor(list(state) + [int(hist_len)], dtype=torch.int32, device=dev)
+        cp = None if corpus is None or len(corpus) == 0 else torch.as_tensor(corpus, dtype=torch.int32).to(dev).contiguous()
+        out = torch.full((max_new,), -7, dtype=torch.int32, device=dev)
+        status = torch.tensor([-7, -7, int(fwd), 0], dtype=torch.int32, device=dev)
+        trace = torch.full((8, 2), -7, dtype=torch.int32, device=dev)
+        pos_ids = torch.full((16,), -7, dtype=torch.int32, device=dev)
+        lg = None if logits is None else logits.to(dev, self.tdtype).contiguous()
+        sc = None if logits is None else torch.zeros(max_new, self.cfg.llama.vocab, dtype=self.tdtype, device=dev)
+        if st.numel() != 5 or len(tail) != d + 1 or (lg is not None and tuple(lg.shape) != (d + 1, self.cfg.llama.vocab)):
+            raise ValueError("lookup_accept_test: state of 4 ints, tail of d + 1 ids, logits [d + 1, vocab]")
+        torch.cuda.synchronize(dev)
+        check(self.ctx, self.lib.rdx_lookup_accept_test(self.ctx, _ptr(pv), _ptr(pi), pv.shape[1], int(d), _ptr(tl), _ptr(cp), 0 if cp is None else cp.numel(),
+                                                        lk.draft_len, lk.ngram_max, lk.ngram_min, int(slot_end), _ptr(h), h.numel(), _ptr(st), int(bool(advance)),
+                                                        int(eos_id), int(pad_id), int(max_new), _ptr(out), _ptr(lg), _ptr(sc), _ptr(status), _ptr(trace), 8,
+                                                        _ptr(pos_ids)), "rdx_lookup_accept_test")
+        return {"out_tokens": out.cpu(), "tail": tl.cpu(), "hist": h.cpu(), "state": st.cpu(), "status": status.cpu(), "trace": trace.cpu(),
+                "pos_ids": pos_ids.cpu(), "scores": None if sc is None else sc.cpu()}
 
     def beam_search(self, ids: torch.Tensor, qformer_embs: Optional[torch.Tensor], num_beams: int, max_new: int, eos_id: int = 2,
                     pad_id: int = 0, mask: Optional[torch.Tensor] = None, length_penalty: float = 1.0, early_stopping: bool = False,

@@ -31,7 +31,8 @@ EMB_TRAIN_PKL = "pretraining/embs/stage1_pt_instruct_blip_origlr_img448_embeddin
 
 
 class GenerateOutput(SimpleNamespace):
-    """`.sequences`, `.scores` like transformers' GreedySearchDecoderOnlyOutput; with generate(output_logprobs=True) also `.token_logprobs` and `.top_logprobs`."""
+    """`.sequences`, `.scores` like transformers' GreedySearchDecoderOnlyOutput; with generate(output_logprobs=True) also `.token_logprobs` and `.top_logprobs`,
+    with generate(prompt_lookup_num_tokens=N) `.lookup_stats` = {"passes", "drafted", "accepted", "forwards"}."""
 
 
 class _BaseModel:
@@ -223,8 +224,14 @@ class LlamaForCausalLM:
                  pad_token_id: Optional[int] = None, length_penalty: float = 1.0, early_stopping: bool = False,
                  repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
                  temperature: float = 1.0, top_k: int = 50, top_p: float = 1.0, seed: Optional[int] = None,
-                 output_logprobs: bool = False, top_logprobs: int = 0, **_unused):
-        """output_logprobs=True (with return_dict_in_generate; no reference counterpart): the output gains `.token_logprobs` float32 [B, n], the log-prob of
+                 output_logprobs: bool = False, top_logprobs: int = 0, prompt_lookup_num_tokens: Optional[int] = None,
+                 max_matching_ngram_size: Optional[int] = None, lookup_corpus=None, **_unused):
+        """prompt_lookup_num_tokens=N (transformers' name; None or 0 = off) with max_matching_ngram_size=M (default 3) and lookup_corpus= (token ids of a
+        document the answer is expected to quote): batch-1 greedy search whose forwards verify up to N tokens copied from the sequence itself
+        (engine.generate_lookup; include/rdx.h rdx_generate_lookup). The tokens are greedy under the returned scores, which are the model's within the parity
+        bar; they are NOT guaranteed to equal a plain call's (a verify pass and a plain step round differently). The output gains `.lookup_stats`.
+        ValueError for what the library refuses: batch > 1, num_beams > 1, do_sample, active logits rules, output_logprobs, kv_fp8, fp8 weights.
+        output_logprobs=True (with return_dict_in_generate; no reference counterpart): the output gains `.token_logprobs` float32 [B, n], the log-prob of
         every generated token under the scores row it was chosen from (what compute_transition_scores(sequences, scores, normalize_logits=True) gives, without
         the [n][B][V] scores), and `.top_logprobs` = (ids int32 [B, n, k], logprobs float32 [B, n, k]), the k = top_logprobs (0 .. 8) likeliest tokens of
         each step; entries behind a row's EOS read (0.0, -1, 0.0). Greedy search and sampling only: num_beams > 1 raises ValueError.
@@ -261,6 +268,7 @@ class LlamaForCausalLM:
         if input_ids.dim() != 2:
             raise ValueError("You have to specify decoder_input_ids of shape [batch, seq]")
         B, T = input_ids.shape
+        lookup = self._lookup_of(prompt_lookup_num_tokens, max_matching_ngram_size, lookup_corpus, B, num_beams, do_sample, rules.active, logprobs is not None)
         eos = self.config.eos_token_id if eos_token_id is None else eos_token_id
         pad = self.config.pad_token_id if pad_token_id is None else pad_token_id
         embs = self._image_embs(B, dicom, use_img, qformer_embs)
@@ -273,6 +281,13 @@ class LlamaForCausalLM:
         # multi-turn chats (demo.py:277-305 re-sends the whole conversation every turn): with `reuse_prefix_kv` set on the model
         # the KV rows of the token prefix shared with the previous call are kept and only the new turn is prefilled (not under an
         # active logits rule: the token history is not carried across calls, the full prompt is prefilled)
+        if lookup is not None:
+            toks, scores, n, stats, _trace = self._engine.generate_lookup(input_ids, embs, max_new=max_new_tokens, eos_id=eos, pad_id=pad, mask=attention_mask,
+                                                                          lookup=lookup, corpus=lookup_corpus, output_scores=output_scores)
+            seq = torch.cat([input_ids.to(toks.device), toks[:, :n].to(torch.int64)], dim=1)
+            if not return_dict_in_generate:
+                return seq
+            return GenerateOutput(sequences=seq, scores=tuple(scores[i].clone() for i in range(n)) if output_scores else None, lookup_stats=stats)
         lp_kw = {} if logprobs is None else {"logprobs": logprobs}
         toks, scores, n, *lp = self._engine.generate(input_ids, embs, max_new=max_new_tokens, eos_id=eos, pad_id=pad,
                                                      mask=attention_mask, output_scores=output_scores,
@@ -294,6 +309,25 @@ class LlamaForCausalLM:
             return GenerateOutput(sequences=seq, scores=sc)
         chosen, top_ids, top_lp = lp[0]
         return GenerateOutput(sequences=seq, scores=sc, token_logprobs=chosen[:, :n], top_logprobs=(top_ids[:, :n], top_lp[:, :n]))
+
+    def _lookup_of(self, num_tokens, ngram, corpus, B, num_beams, do_sample, rules_active, logprobs):
+        """generate()'s prompt-lookup arguments as an engine.Lookup, or None when they are neutral (the existing path). ValueError, before an engine
+        exists, for what rdx_generate_lookup refuses."""
+        from .engine import Lookup
+        if num_tokens is None or (not isinstance(num_tokens, bool) and num_tokens == 0):
+            if ngram is not None or corpus is not None:
+                raise ValueError("max_matching_ngram_size / lookup_corpus need prompt_lookup_num_tokens")
+            return None
+        lookup = Lookup(draft_len=num_tokens, ngram_max=3 if ngram is None else ngram, ngram_min=1)        # ValueError on values out of range
+        why = ("batch > 1 (prompt-lookup decoding is built for batch 1)" if B != 1 else "num_beams > 1 (beams are not built)" if num_beams > 1 else
+               "do_sample (speculative sampling is not built)" if do_sample else
+               "repetition_penalty / no_repeat_ngram_size / min_new_tokens (logits rules are not built)" if rules_active else
+               "output_logprobs (generation logprobs are not built)" if logprobs else
+               "kv_fp8 (the kept prefix is not held in the model dtype)" if self.kv_fp8 else
+               "weights_fp8 (the all-row lm_head of a verify pass has no fp8 convention)" if self.weights_fp8 else None)
+        if why:
+            raise ValueError(f"prompt_lookup_num_tokens does not go with {why}")
+        return lookup
 
     @torch.no_grad()
     def generate_many(self, input_ids: List[torch.Tensor], dicom: Optional[List[str]] = None, qformer_embs: Optional[torch.Tensor] = None,

@@ -16,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from radialog_amd import synth                                              # noqa: E402
+from radialog_amd.config import PROMPT_LOOKUP_DEFAULT                      # noqa: E402
 from radialog_amd.embed_dump import dump_embeddings                         # noqa: E402
 from radialog_amd.modeling_llama_imgemb import LlamaForCausalLM, PeftModelForCausalLM   # noqa: E402
 from radialog_amd.prompter import new_conversation, report_prompt          # noqa: E402
@@ -65,6 +66,9 @@ def main(argv=None):
     p.add_argument("--seed", type=int, default=None, help="with --do_sample: the sampler's seed (default: drawn from torch's CPU generator)")
     p.add_argument("--logprobs", type=int, default=None, metavar="N", help="report the mean token log-prob of every report (and keep the N = 0 .. 8 likeliest "
                    "tokens of every step); greedy / sampled search only")
+    p.add_argument("--prompt_lookup", type=int, nargs="?", const=PROMPT_LOOKUP_DEFAULT, default=0, metavar="N",
+                   help="with --do_corr (greedy, num_beams 1): verify up to N tokens per forward, drafted from the prompt and the answer so far "
+                        f"(prompt-lookup decoding; without a number: {PROMPT_LOOKUP_DEFAULT})")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f16"])
     p.add_argument("--synthetic", action="store_true", help="deterministic random-init weights (no checkpoints reachable offline)")
     p.add_argument("--fp8", action="store_true", help="BASELINE configs[4]: decoder GEMMs in OCP e4m3 on the fp8 MFMA (weights_fp8=True)")
@@ -175,8 +179,13 @@ def main(argv=None):
         dc = dicoms if args.use_embs else None
         if args.do_corr:
             P, L = rng.integers(0, 2, (len(dicoms), 14)), rng.integers(0, 2, (len(dicoms), 14))
-            corr = D.run_correction(lang_model, tok, D.get_correction_prompts(list(preds_history), CHEXPERT_COLS, P, L), dc, args.num_beams)
+            lk_stats = {}
+            corr = D.run_correction(lang_model, tok, D.get_correction_prompts(list(preds_history), CHEXPERT_COLS, P, L), dc, args.num_beams,
+                                    prompt_lookup=args.prompt_lookup, lookup_stats=lk_stats)
             res["corrected"] = corr
+            if args.prompt_lookup:
+                print(f"rank {rank}: prompt lookup accepted {lk_stats.get('accepted', 0)} / {lk_stats.get('drafted', 0)} drafted tokens in "
+                      f"{lk_stats.get('passes', 0)} passes of {lk_stats.get('forwards', 0)} forwards")
             print(f"rank {rank}: {len(corr)} corrected reports; first: {corr[0][:80]!r}")
         if args.do_cp_bin_qa:
             yn = D.run_binary_qa(lang_model, tok, D.get_chexpert_prompts_bin(list(preds_history), CHEXPERT_COLS), CHEXPERT_COLS, dc)
